@@ -11,7 +11,11 @@ Workload: BASELINE.json configs[1] — the stompy_pro stand-in (synth_stompy_pro
 environments PER GPU (weak scaling: configs[2] is 8 x 4096), fp32.  Inputs are synthetic and resident in
 HBM (the environment state itself); weights are random-init.  Rank 0 prints ONE JSON line.
 
-The line also carries
+A plain run sets up, warms up, times the K steps and prints the line (`value`, `ms_per_step`, `sanity`, ...; `roofline` and
+`cpu_baseline` null).  --dump-outputs DIR also writes what the last timed step computed as DIR/<name>.npy (dump_outputs); the inputs
+are seeded, so two builds run with the same arguments can be compared array for array.
+
+With --full the line also carries
   roofline     : the dominant kernel (`fused_mlp_kernel`, the row-local forward + backward of one minibatch on the
                  f32 matrix cores) timed live with HIP events on a hipGraph replay of 50 launches, algorithmic
                  FLOPs per launch / average duration against the dense f32 MFMA peak (157.3 TFLOP/s,
@@ -91,11 +95,46 @@ def parse() -> argparse.Namespace:
     ap.add_argument("--config", default="stompy_pro")
     ap.add_argument("--set", action="append", default=[], metavar="KEY=VALUE", help="config override (dot-list), e.g. training.mlp_dtype=bf16")
     ap.add_argument("--no-graph", action="store_true")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-probe", action="store_true", help="do not run the stand-alone row-pass probe (profiling runs: the rocprofv3 summary of the "
+    ap.add_argument("--full", action="store_true", help="also measure what the headline figure does not need: the row-pass roofline probe and the "
+                    "committed profile summaries (`roofline`), the CPU baseline (`cpu_baseline`), and with several ranks the flag latency "
+                    "(`config.t_link_us`) and the replica checksum (`config.replicas_identical`)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baseline")
+    ap.add_argument("--no-probe", action="store_true", help="with --full: do not run the stand-alone row-pass probe (profiling runs: the rocprofv3 summary of the "
                     "update then contains the update's launches of the kernel only; the line's `roofline` is null)")
     ap.add_argument("--cpu-baseline-envs", type=int, default=4096)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one computed as DIR/<name>.npy")
     return ap.parse_args()
+
+
+DUMP_LIMIT_BYTES = 63 << 20  # (64 MB in all with the .npy headers and env_index.npy)
+
+
+def dump_outputs(tr, out_dir) -> dict:
+    """--dump-outputs: what a caller of `Trainer.update()` receives after the last timed step - the parameters, the minibatch losses [E, M, 4],
+    the rollout's trajectory (`Trainer.traj()`; observations without their padding columns) and `rollout_stats()` - one DIR/<name>.npy per
+    array, float32, or float64 where the engine hands out float64.  If that comes to more than 64 MB, the per-environment arrays are cut to
+    a fixed, seeded sample of environments (`env_index.npy` lists them).  Returns {name: shape}."""
+    import numpy as np
+
+    out = {"params": tr.params_flat(), "losses": tr.losses()}
+    st = tr.rollout_stats()
+    out["rollout_stats"] = np.array([st[k] for k in ("mean_reward", "done_fraction", "episodes", "mean_episode_return", "mean_episode_length")], np.float64)
+    per_env = {k: v.detach().cpu().numpy() for k, v in tr.traj().items()}
+    per_env["obs"] = per_env["obs"][..., :tr.O]
+    out = {k: v.astype(np.float64 if v.dtype == np.float64 else np.float32) for k, v in {**out, **per_env}.items()}
+    total = sum(v.nbytes for v in out.values())
+    if total > DUMP_LIMIT_BYTES:
+        fixed = sum(out[k].nbytes for k in out if k not in per_env)
+        keep = max(1, int((DUMP_LIMIT_BYTES - fixed) * tr.N // (total - fixed)))
+        idx = np.sort(np.random.default_rng(0).choice(tr.N, keep, replace=False))
+        for k in per_env:  # the environment axis: 0 for last_val [N], 1 for the [T(+1), N, ...] arrays
+            out[k] = np.take(out[k], idx, axis=0 if k == "last_val" else 1)
+        out["env_index"] = idx.astype(np.float64)
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    for k, v in out.items():
+        np.save(d / f"{k}.npy", np.ascontiguousarray(v))
+    return {k: list(v.shape) for k, v in out.items()}
 
 
 def rowpass_probe(tr, launches: int = 64, replays: int = 4):
@@ -553,8 +592,8 @@ def main() -> None:
         if world > 1 and rank == 0:
             sys.stderr.write(f"bench.py: gradient transport: {transport}" + (f" ({tr.peer_form()})" if transport == "peer" else "") + f" - {tr.comm_note}\n")
         # the measured one-way latency of a system-scope flag between rank 0 and every peer (collective; about 1 ms per peer): the t_link of the
-        # efficiency model in DESIGN.md 7.2, for the first run on distinct GPUs to put a number where the model has an assumption
-        t_link = tr.peer_latencies() if transport == "peer" else None
+        # efficiency model in DESIGN.md 7.2, for the first run on distinct GPUs to put a number where the model has an assumption (--full)
+        t_link = tr.peer_latencies() if transport == "peer" and args.full else None
         if t_link is not None and rank == 0:
             sys.stderr.write("bench.py: one-way flag latency rank 0 <-> rank 1.." + str(world - 1) + " [us]: " + ", ".join(f"{x:.2f}" for x in t_link) + "\n")
     tr.reset()
@@ -593,9 +632,11 @@ def main() -> None:
         t = t if share else t.to(f"cuda:{local_rank}")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
-        # replicas must hold bit-identical parameters after the same updates: a checksum of the parameter bits, compared over the ranks
+    dumped = dump_outputs(tr, args.dump_outputs) if args.dump_outputs and rank == 0 else None
     if world > 1 and not indep:
         tr.check_peers()
+    # replicas must hold bit-identical parameters after the same updates: a checksum of the parameter bits, compared over the ranks (--full)
+    if world > 1 and not indep and args.full:
         import numpy as _np
         bits = tr.params_flat().view(_np.uint32).astype(_np.uint64)
         chk = torch.tensor([int(bits.sum()), int((bits * (_np.arange(bits.size, dtype=_np.uint64) % 65521 + 1)).sum() % (1 << 62))], dtype=torch.int64)
@@ -617,7 +658,7 @@ def main() -> None:
             baseline_cfg = "BASELINE configs[3]" if args.config == "stompy_pro" else baseline_cfg + ", bf16 MFMA"
         headline_shape = args.config == "stompy_pro" and args.envs_per_gpu == 4096
         roofline = None
-        if not args.no_probe:
+        if args.full and not args.no_probe:
             sec, flops, desc = rowpass_probe(tr)
             achieved = flops / sec / 1e12
             here = kernel_sources_sha()
@@ -718,8 +759,10 @@ def main() -> None:
                        "pre_warm": f"{pre_warm_s:.1f} s of unrelated device work before the {args.warmup} warm-up steps (one-time start-up stall of the device, see bench.py)"},
             "roofline": roofline,
             "sanity": {"mean_reward": stats["mean_reward"], "done_fraction": stats["done_fraction"], "mean_total_loss": float(lossm[0])},
+            "full": bool(args.full),
+            "outputs": {"dir": args.dump_outputs, "arrays": dumped} if dumped else None,
         }
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(args.config, args.set, args.cpu_baseline_envs)
             out["cpu_baseline"]["engine_over_cpu"] = out["value"] / out["cpu_baseline"]["value"] if out["cpu_baseline"]["value"] else None  # (reported, not a target: the roofline fraction is what describes the kernels)
         else:

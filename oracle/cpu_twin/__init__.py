@@ -2,7 +2,7 @@
 
 PARITY UNPINNED (oracle/physics_oracle.py).  Used by `bench.py`'s `cpu_baseline` leg and by tests/test_cpu_twin.py only; nothing under
 minppo_amd/ imports it.  The library is compiled with `-march=native`, so it is built on the machine that runs it: one file per CPU
-model (`libenv_twin.<tag>.so`, git-ignored), rebuilt when the source is newer."""
+model and set of flags (`libenv_twin.<tag>.so`, git-ignored), rebuilt when the source is newer."""
 
 from __future__ import annotations
 
@@ -17,10 +17,13 @@ import numpy as np
 
 HERE = Path(__file__).resolve().parent
 ROOT = HERE.parent.parent
+# -ffp-contract=off: no fused multiply-add that the source does not spell out, so the twin rounds alike on every x86-64 host whatever
+# -march=native offers (contracted, a host with FMA and one without take different float32 paths through the six CG iterations)
+CXXFLAGS = ["-std=c++17", "-O3", "-march=native", "-ffp-contract=off", "-fopenmp", "-fPIC", "-shared", "-Wall", "-Wno-unused-variable"]
 
 
 def _cpu_tag() -> str:
-    model = platform.processor() or ""
+    model = " ".join(CXXFLAGS) + (platform.processor() or "")
     try:
         for line in open("/proc/cpuinfo"):
             if line.startswith(("model name", "flags")):
@@ -41,8 +44,7 @@ def build(force: bool = False) -> Path:
     src = [HERE / "env_twin.cpp", ROOT / "minppo_amd" / "csrc" / "model_view.h"]
     if not force and out.exists() and all(s.stat().st_mtime <= out.stat().st_mtime for s in src):
         return out
-    cmd = ["g++", "-std=c++17", "-O3", "-march=native", "-fopenmp", "-fPIC", "-shared", "-Wall", "-Wno-unused-variable", f"-I{HERE / 'stub'}",
-           f"-I{ROOT / 'minppo_amd' / 'csrc'}", str(HERE / "env_twin.cpp"), "-o", str(out)]
+    cmd = ["g++", *CXXFLAGS, f"-I{HERE / 'stub'}", f"-I{ROOT / 'minppo_amd' / 'csrc'}", str(HERE / "env_twin.cpp"), "-o", str(out)]
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode != 0:
         raise RuntimeError("building the CPU twin failed:\n" + r.stderr[-3000:])

@@ -14,9 +14,9 @@ step() { local secs=$1; shift; timeout -k 10 "$secs" "$@"; local rc=$?; if [ $rc
 has() { case " $PARTS " in *" $1 "*) return 0;; *) return 1;; esac; }
 if has tests; then echo "=== pytest -m gpu"; step 1500 python -m pytest tests -q -m gpu > "$OUT/pytest_gpu.log" 2>&1; tail -3 "$OUT/pytest_gpu.log"; fi
 if has bench; then
-  echo "=== bench default (configs[1])"; step 900 python bench.py > "$OUT/bench_default.json" 2> "$OUT/bench_default.err"; tail -c 700 "$OUT/bench_default.json"
-  echo "=== bench bf16 (configs[3])"; step 600 python bench.py --set training.mlp_dtype=bf16 --no-cpu-baseline > "$OUT/bench_config3_bf16.json" 2>/dev/null
-  echo "=== bench stompy_full 8192 (configs[4])"; step 600 python bench.py --config stompy_full --envs-per-gpu 8192 --no-cpu-baseline > "$OUT/bench_config5_stompy_full_8192.json" 2>/dev/null
+  echo "=== bench default (configs[1])"; step 900 python bench.py --full > "$OUT/bench_default.json" 2> "$OUT/bench_default.err"; tail -c 700 "$OUT/bench_default.json"
+  echo "=== bench bf16 (configs[3])"; step 600 python bench.py --full --set training.mlp_dtype=bf16 --no-cpu-baseline > "$OUT/bench_config3_bf16.json" 2>/dev/null
+  echo "=== bench stompy_full 8192 (configs[4])"; step 600 python bench.py --full --config stompy_full --envs-per-gpu 8192 --no-cpu-baseline > "$OUT/bench_config5_stompy_full_8192.json" 2>/dev/null
   for f in bench_default bench_config3_bf16 bench_config5_stompy_full_8192; do python3 -c "import json;d=json.loads(open('$OUT/$f.json').read().strip().splitlines()[-1]);print('$f', round(d['value']/1e6,3),'M', round(d['ms_per_step'],3),'ms', round(d['roofline']['us_per_launch'],2),'us', round(d['roofline']['frac'],4))"; done
 fi
 if has stats; then

@@ -622,10 +622,10 @@ struct RuntimeModel {
   static constexpr bool kStatic = false;
   static constexpr BlobDims dims() { return BlobDims{}; }
 };
-template <int NQ, int NV, int NU, int NBODY, int NJNT, int NCON, int NLIMIT, int NPAIR, int NLEVEL, int NROOT, int NCVX = 0, int NCVXVERT = 0, int HULL = 0, int NCYL = 0>
+template <int NQ, int NV, int NU, int NBODY, int NJNT, int NCON, int NLIMIT, int NPAIR, int NLEVEL, int NROOT, int NCVX = 0, int NCVXVERT = 0, int HULL = 0, int NCYL = 0, int CPARAM = 0>
 struct StaticModel {
   static constexpr bool kStatic = true;
-  static constexpr BlobDims dims() { return BlobDims{NQ, NV, NU, NBODY, NJNT, NCON, NLIMIT, NPAIR, NLEVEL, NROOT, NCVX, NCVXVERT, HULL, NCYL}; }
+  static constexpr BlobDims dims() { return BlobDims{NQ, NV, NU, NBODY, NJNT, NCON, NLIMIT, NPAIR, NLEVEL, NROOT, NCVX, NCVXVERT, HULL, NCYL, CPARAM}; }
 };
 // MODE (EnvArgs::mode) is a template parameter too: the step kernel carries neither the probe's 17 output pointers nor its stores.
 template <class SD, int MODE>
@@ -686,6 +686,12 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerBlock) env_kernel(ModelView m
   const int npair = kDims ? kSD.npair : mv.npair, nplane = ncon - npair, ncvx = kDims ? kSD.ncvx : mv.ncvx;
   // (features that select code: constants in a model-specialised kernel - a robot without hull pairs / cylinders carries none of it)
   const bool has_hull = kDims ? kSD.hull != 0 : mv.hull_words > 0, has_cyl = kDims ? kSD.ncyl > 0 : mv.ncyl > 0;
+  // per-row contact / limit parameters (blob version 8): a model whose rows all take the model-wide values runs the code of version 7 -
+  // in a model-specialised kernel the per-row code is not even compiled in.  The section is read from global memory (CParamView).
+  const bool cp = kDims ? kSD.cparam != 0 : mv.cparam != 0;
+  const CParamView cpv = cparam_view(ncon, kDims ? kSD.nlimit : mv.nlimit, ncvx);
+  const float* cpf = reinterpret_cast<const float*>(mv.blob + mv.blob_words + mv.hull_words);
+  const int* cpi = mv.blob + mv.blob_words + mv.hull_words;
   float* cvxsel = S + P.cvxsel; float* cvxok = S + P.cvxok;
   float* xanchor = S + P.xanchor; float* xaxis = S + P.xaxis;
   float* Cw = S + P.C; float* cdofdot = S + P.cdofdot; float* cfrc = S + P.cfrc; float* J = (float*)__builtin_assume_aligned(S + P.J, 16);
@@ -852,7 +858,8 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerBlock) env_kernel(ModelView m
         const float* vt = TF(cvx_vert);
         float smax = -INFINITY;
         for (int v = v0; v < v1; ++v) smax = fmaxf(smax, h0 - dot3(nl, ld3(vt + 3 * v)));
-        const float thr = fmaxf(0.f, smax - 1e-3f);
+        // (per-row parameters: vertices within the geom's includemargin of the plane are candidates too, as MJX keeps them)
+        const float thr = cp ? fmaxf(-cpf[cpv.cvx_margin + k], smax - 1e-3f) : fmaxf(0.f, smax - 1e-3f);
         auto dm = [&](int v) { return (h0 - dot3(nl, ld3(vt + 3 * v)) > thr) ? 0.f : -1e6f; };
         int ia = v0;
         { float best = -INFINITY; for (int v = v0; v < v1; ++v) { const float x = dm(v); if (x > best) { best = x; ia = v; } } }
@@ -1420,7 +1427,7 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerBlock) env_kernel(ModelView m
       FOR_G(c, ncon) {
         u64 m = TU(body_ancdof_mask)[TI(con_bodyid)[c]];
         if (c >= nplane) m |= TU(body_ancdof_mask)[TI(pair_body)[2 * (c - nplane)]];
-        jmask[c] = condist[c] < 0.f ? m : 0ull;
+        jmask[c] = condist[c] < (cp ? cpf[cpv.con_margin + c] : 0.f) ? m : 0ull;
       }
     }
     SYNC();
@@ -1428,7 +1435,7 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerBlock) env_kernel(ModelView m
       const int jid = TI(lim_jntid)[r];
       const int qa = TI(jnt_qposadr)[jid], da = TI(jnt_dofadr)[jid];
       const float dlo = qpos[qa] - TF(jnt_range)[2 * jid], dhi = TF(jnt_range)[2 * jid + 1] - qpos[qa];
-      const float pos = fminf(dlo, dhi);
+      const float pos = cp ? fminf(dlo, dhi) - cpf[cpv.lim_margin + r] : fminf(dlo, dhi);  // (per-row: active within the joint's margin)
       const bool act = pos < 0.f;
       if (act) dlim[da] = dlo < dhi ? r + 1 : -(r + 1);
       jv[r] = act ? pos : 0.f;               // pos, parked in jv until the row parameters are built
@@ -1456,6 +1463,7 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerBlock) env_kernel(ModelView m
         const float jn = dot3(n, jp), jt1 = dot3(t1, jp), jt2 = dot3(t2, jp);
         const float mu = TF(con_friction)[3 * c];
         r4[0] = jn + mu * jt1; r4[1] = jn - mu * jt1; r4[2] = jn + mu * jt2; r4[3] = jn - mu * jt2;
+        if (cp && cpi[cpv.con_condim + c] == 1) { r4[0] = jn; r4[1] = 0.f; r4[2] = 0.f; r4[3] = 0.f; }  // frictionless: the normal row, three inert ones
       }
       return any;
     };
@@ -1475,7 +1483,7 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerBlock) env_kernel(ModelView m
     for (int item = g; item < ncon * nv; item += kGroupLanes) {  // contacts: 4 pyramid rows, (contact, dof) per item
       // (the same arithmetic as contact_rows, written out as in rounds 2 - 5: the BASELINE robots' kernels keep their instruction stream)
       const int c = item / nv, d = item - c * nv;
-      if (condist[c] < 0.f) {
+      if (condist[c] < (cp ? cpf[cpv.con_margin + c] : 0.f)) {
         // translational Jacobian of the contact point: body 2 minus body 1 (body 1 = world for a ground contact)
         V3 jp = {0.f, 0.f, 0.f};
         bool any = false;
@@ -1496,6 +1504,7 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerBlock) env_kernel(ModelView m
           const float jn = dot3(n, jp), jt1 = dot3(t1, jp), jt2 = dot3(t2, jp);
           const float mu = TF(con_friction)[3 * c];
           const int r0 = 4 * c;
+          if (cp && cpi[cpv.con_condim + c] == 1) { J[r0 * ldj + d] = jn; continue; }  // frictionless: the normal row (the other three stay zero)
           J[(r0 + 0) * ldj + d] = jn + mu * jt1;
           J[(r0 + 1) * ldj + d] = jn - mu * jt1;
           J[(r0 + 2) * ldj + d] = jn + mu * jt2;
@@ -1504,11 +1513,23 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerBlock) env_kernel(ModelView m
       }
     }
     FOR_G(c, ncon) {
-      const bool act = condist[c] < 0.f;
       const float mu = TF(con_friction)[3 * c];
       float tw = TF(body_invweight0)[2 * TI(con_bodyid)[c]];
       if (c >= nplane) tw += TF(body_invweight0)[2 * TI(pair_body)[2 * (c - nplane)]];
       const float iw = (tw + mu * mu * tw) * 2.f * mu * mu / mv.impratio;
+      if (cp) {
+        // per-row parameters: active below the slot's includemargin, pos = dist - includemargin; a frictionless (condim 1) contact has one
+        // row with the translational invweight (MJX), its three other rows are inert (J = 0, invweight 0 -> D = 0, aref = 0)
+        const float mg = cpf[cpv.con_margin + c];
+        const bool act = condist[c] < mg, fl = cpi[cpv.con_condim + c] == 1;
+        for (int k = 0; k < 4; ++k) {
+          const bool on = act && (!fl || k == 0);
+          jv[nlim + 4 * c + k] = on ? condist[c] - mg : 0.f;
+          jaref[nlim + 4 * c + k] = on ? (fl ? tw : iw) : 0.f;
+        }
+        continue;
+      }
+      const bool act = condist[c] < 0.f;
       for (int k = 0; k < 4; ++k) {
         jv[nlim + 4 * c + k] = act ? condist[c] : 0.f;
         jaref[nlim + 4 * c + k] = act ? iw : 0.f;
@@ -1583,6 +1604,18 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerBlock) env_kernel(ModelView m
       const float pos = jv[r], iw = jaref[r];
       const bool act = iw > 0.f;  // inactive rows are inert: J = 0, aref = 0, D = 0
       const bool lim = r < nlim;
+      if (cp) {  // the row's own solref / solimp: its limit's or its contact slot's
+        const int e = lim ? r : (r - nlim) >> 2;
+        const float* sr = cpf + (lim ? cpv.lim_solref : cpv.con_solref) + 2 * e;
+        const float* si = cpf + (lim ? cpv.lim_solimp : cpv.con_solimp) + 5 * e;
+        float k, b;
+        kb_params(sr, si, h, k, b);
+        const float imp = impedance(si, pos);
+        const float R = fmaxf(iw * (1.f - imp) / imp, MJ_MINVAL);
+        eD[r] = act ? 1.f / R : 0.f;
+        earef[r] = act ? -b * s - k * imp * pos : 0.f;
+        return;
+      }
       const float k = lim ? k_lim : k_con, b = lim ? b_lim : b_con;
       const float imp = impedance(lim ? TF(limit_solimp) : TF(contact_solimp), pos);
       const float R = fmaxf(iw * (1.f - imp) / imp, MJ_MINVAL);
@@ -1988,7 +2021,8 @@ static int find_spec(const BlobDims& d) {
   for (int i = 0; kSpecs[i].launch; ++i) {
     const BlobDims& s = kSpecs[i].d;
     if (s.nq == d.nq && s.nv == d.nv && s.nu == d.nu && s.nbody == d.nbody && s.njnt == d.njnt && s.ncon == d.ncon && s.nlimit == d.nlimit &&
-        s.npair == d.npair && s.nlevel == d.nlevel && s.nroot == d.nroot && s.ncvx == d.ncvx && s.ncvxvert == d.ncvxvert && s.hull == d.hull && s.ncyl == d.ncyl)
+        s.npair == d.npair && s.nlevel == d.nlevel && s.nroot == d.nroot && s.ncvx == d.ncvx && s.ncvxvert == d.ncvxvert && s.hull == d.hull && s.ncyl == d.ncyl &&
+        s.cparam == d.cparam)
       return i;
   }
   return -1;
@@ -2165,8 +2199,10 @@ extern "C" int32_t mppo_model_open(const void* host_blob, size_t nbytes, const v
   const float* wf = static_cast<const float*>(host_blob);
   if (w[0] != kBlobMagic) return fail(MPPO_EMODEL, "bad model blob magic 0x%08x", w[0]);
   if (w[1] != kBlobVersion) return fail(MPPO_EMODEL, "unsupported model blob version %u", w[1]);
-  const size_t total = w[2], hull_words = w[35];  // table part + hull section
-  if ((total + hull_words) * 4 != nbytes) return fail(MPPO_EMODEL, "model blob size mismatch: header says %zu + %zu words, got %zu bytes", total, hull_words, nbytes);
+  const size_t total = w[2], hull_words = w[35];  // table part + hull section (+ the contact-parameter section: below, once the dims are known)
+  if (wi[37] != 0 && wi[37] != 1) return fail(MPPO_EMODEL, "model blob: header word 37 (per-row contact parameters) is %d, not 0 or 1", wi[37]);
+  if ((total + hull_words) * 4 > nbytes || (wi[37] == 0 && (total + hull_words) * 4 != nbytes))
+    return fail(MPPO_EMODEL, "model blob size mismatch: header says %zu + %zu words, got %zu bytes", total, hull_words, nbytes);
   if (wi[32] != BLOB_ARRAY_COUNT) return fail(MPPO_EMODEL, "model blob has %d arrays, engine expects %d", wi[32], (int)BLOB_ARRAY_COUNT);
   mppo_model* m = new mppo_model();
   ModelView& v = m->mv;
@@ -2178,6 +2214,10 @@ extern "C" int32_t mppo_model_open(const void* host_blob, size_t nbytes, const v
   for (int d : {v.nq, v.nv, v.nu, v.nbody, v.njnt, v.ncon, v.nlimit, v.iterations, v.ls_iterations, v.nlevel, v.nroot, v.npair, v.ncvx, v.ncvxvert, wi[36]})
     if (d < 0 || d > (1 << 16)) { delete m; return fail(MPPO_EMODEL, "model blob: header dimension %d out of range", d); }
   v.nefc = v.nlimit + 4 * v.ncon;
+  v.cparam = wi[37];
+  const CParamView cpv = cparam_view(v.ncon, v.nlimit, v.ncvx);
+  if (v.cparam && (total + hull_words + (size_t)cpv.words) * 4 != nbytes)
+    return fail(MPPO_EMODEL, "model blob size mismatch: header says %zu + %zu + %d words (contact-parameter section), got %zu bytes", total, hull_words, cpv.words, nbytes);
   v.timestep = wf[16]; v.tolerance = wf[17]; v.ls_tolerance = wf[18]; v.impratio = wf[19]; v.plane_z = wf[20]; v.meaninertia = wf[21];
   auto bad = [&](const char* what) { delete m; return fail(MPPO_EMODEL, "model blob: %s", what); };
   if (v.nq < 1 || v.nv < 1 || v.nbody < 2 || v.nbody > 128 || v.nv > 64 || v.nq > 128 || v.nu < 0 || v.nu > v.nv || v.njnt < 1 ||
@@ -2186,7 +2226,7 @@ extern "C" int32_t mppo_model_open(const void* host_blob, size_t nbytes, const v
     return bad("dimension out of the supported range (nbody<=128, nv<=64)");
   if (!(v.timestep > 0.f) || !(v.meaninertia > 0.f) || !(v.impratio > 0.f)) return bad("non-positive timestep / meaninertia / impratio");
   const int32_t* dir = wi + kBlobHeaderWords;
-  BlobDims bd{v.nq, v.nv, v.nu, v.nbody, v.njnt, v.ncon, v.nlimit, v.npair, v.nlevel, v.nroot, v.ncvx, v.ncvxvert, 0, 0};
+  BlobDims bd{v.nq, v.nv, v.nu, v.nbody, v.njnt, v.ncon, v.nlimit, v.npair, v.nlevel, v.nroot, v.ncvx, v.ncvxvert, 0, 0, 0};
   const BlobOffsets canon = blob_offsets(bd);
   const size_t dir_end = kBlobHeaderWords + 2 * (size_t)BLOB_ARRAY_COUNT;
   if (dir_end > total) return bad("directory past the end");
@@ -2298,6 +2338,27 @@ extern "C" int32_t mppo_model_open(const void* host_blob, size_t nbytes, const v
     for (int l = 0; l < v.nlevel; ++l) if (la[l + 1] < la[l] || la[l + 1] > v.nbody - 1) return bad("level_adr not monotone");
     if (HI(BI_root_body)[0] != 1) return bad("body 1 must be the first tree root");
   }
+  if (v.cparam) {
+    // the contact-parameter section: condim 1 or 3, finite values, solimp inside MuJoCo's clamps (dmin / dmax / mid in [mjMINIMP, mjMAXIMP], width > 0,
+    // power >= 1), a positive time constant / damping ratio in standard form, margins finite
+    const float* cf = wf + total + hull_words;
+    const int32_t* ci = wi + total + hull_words;
+    auto fin = [](float x) { return x == x && x - x == 0.f; };
+    auto good_ref = [&](const float* r) { return fin(r[0]) && fin(r[1]) && (r[0] <= 0.f || r[1] > 0.f) && (r[0] > 0.f || r[1] <= 0.f); };
+    auto good_imp = [&](const float* i) {
+      for (int k = 0; k < 5; ++k) if (!fin(i[k])) return false;
+      return i[0] >= MJ_MINIMP && i[0] <= MJ_MAXIMP && i[1] >= MJ_MINIMP && i[1] <= MJ_MAXIMP && i[2] > 0.f && i[3] >= MJ_MINIMP && i[3] <= MJ_MAXIMP && i[4] >= 1.f;
+    };
+    for (int c = 0; c < v.ncon; ++c) {
+      if (ci[cpv.con_condim + c] != 1 && ci[cpv.con_condim + c] != 3) return bad("contact-parameter section: condim must be 1 or 3");
+      if (!good_ref(cf + cpv.con_solref + 2 * c) || !good_imp(cf + cpv.con_solimp + 5 * c) || !fin(cf[cpv.con_margin + c]))
+        return bad("contact-parameter section: a contact slot's solref / solimp / margin is not finite or outside MuJoCo's ranges");
+    }
+    for (int r = 0; r < v.nlimit; ++r)
+      if (!good_ref(cf + cpv.lim_solref + 2 * r) || !good_imp(cf + cpv.lim_solimp + 5 * r) || !fin(cf[cpv.lim_margin + r]))
+        return bad("contact-parameter section: a joint limit's solref / solimp / margin is not finite or outside MuJoCo's ranges");
+    for (int k = 0; k < v.ncvx; ++k) if (!fin(cf[cpv.cvx_margin + k])) return bad("contact-parameter section: a convex geom's margin is not finite");
+  }
   v.blob = static_cast<const int32_t*>(dev_blob);
   v.blob_words = (int)((total + 3) & ~(size_t)3);
   if ((size_t)v.blob_words != total) return bad("blob length must be a multiple of 4 words");
@@ -2305,7 +2366,7 @@ extern "C" int32_t mppo_model_open(const void* host_blob, size_t nbytes, const v
   v.obs_dim = v.nq + 2 * v.nv + (v.include_c ? 16 * (v.nbody - 1) : 0);  // env.py:246-259
   v.obs_pad = (v.obs_dim + 3) & ~3;
   v.rec_dim = v.obs_pad + ((v.nv + 2 + 3) & ~3);
-  bd.hull = v.hull_words > 0 ? 1 : 0; bd.ncyl = v.ncyl;
+  bd.hull = v.hull_words > 0 ? 1 : 0; bd.ncyl = v.ncyl; bd.cparam = v.cparam;
   m->spec = find_spec(bd);
   m->canon_words = canon.words;
   if (int32_t rc = mppo::finalize_layout(m); rc != MPPO_OK) { delete m; return rc; }
@@ -2357,9 +2418,9 @@ extern "C" int32_t mppo_model_attach_kernel(mppo_model_t* m, const void* image, 
     const char* e = getenv("MPPO_ENV_GENERIC");
     if ((e && e[0] == '1') || env_spill_override() >= 0) return MPPO_OK;  // (the switches that force the run-time-sized kernel)
   }
-  // the kernels' names spell the dimensions they were compiled for: StaticModel<nq, nv, nu, nbody, njnt, ncon, nlimit, npair, nlevel, nroot, ncvx, ncvxvert, hull, ncyl>, MODE
+  // the kernels' names spell the dimensions they were compiled for: StaticModel<nq, nv, nu, nbody, njnt, ncon, nlimit, npair, nlevel, nroot, ncvx, ncvxvert, hull, ncyl, cparam>, MODE
   const ModelView& v = m->mv;
-  const int dims[14] = {v.nq, v.nv, v.nu, v.nbody, v.njnt, v.ncon, v.nlimit, v.npair, v.nlevel, v.nroot, v.ncvx, v.ncvxvert, v.hull_words > 0 ? 1 : 0, v.ncyl};
+  const int dims[15] = {v.nq, v.nv, v.nu, v.nbody, v.njnt, v.ncon, v.nlimit, v.npair, v.nlevel, v.nroot, v.ncvx, v.ncvxvert, v.hull_words > 0 ? 1 : 0, v.ncyl, v.cparam};
   char want[256];
   int o = snprintf(want, sizeof want, "StaticModelI");
   for (int d : dims) o += snprintf(want + o, sizeof want - o, "Li%dE", d);

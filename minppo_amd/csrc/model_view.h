@@ -31,7 +31,7 @@ enum BlobF32 {
 };
 
 constexpr uint32_t kBlobMagic = 0x4D50504F;
-constexpr uint32_t kBlobVersion = 7;
+constexpr uint32_t kBlobVersion = 8;
 constexpr int kBlobHeaderWords = 64;
 constexpr int JNT_FREE = 0, JNT_HINGE = 2, JNT_SLIDE = 3;
 constexpr float MJ_MINVAL = 1e-15f, MJ_MINIMP = 0.0001f, MJ_MAXIMP = 0.9999f;
@@ -52,6 +52,7 @@ struct ModelView {
   int epw;           // environments per wave of the run-time-sized kernel: 4, or 2 / 1 for a robot whose working set would not fit LDS four at a time
   int ncyl;          // cylinders against the plane: three contact slots each (con_cvx = -2, -3, -4); run-time-sized kernel only
   int hull_words;    // the hull section behind it (0: the model has no convex geom in a geom-geom pair); read from global memory
+  int cparam;        // 1: contact / limit parameters per row - the contact-parameter section behind the hull section (CParamView); 0: model-uniform
   int o[BLOB_ARRAY_COUNT];
 };
 
@@ -59,7 +60,7 @@ struct ModelView {
 // array padded to 4 words, first array right after the directory).  mppo_model_open refuses a blob laid out differently, so a
 // kernel compiled for fixed dims may take the offsets as constants.
 struct BlobDims { int nq, nv, nu, nbody, njnt, ncon, nlimit, npair, nlevel, nroot, ncvx, ncvxvert;
-                  int hull, ncyl; };  // (hull: 1 if the model has a hull section; ncyl: its cylinders - they select code, not table sizes)
+                  int hull, ncyl, cparam; };  // (hull: 1 if the model has a hull section; ncyl: its cylinders; cparam: per-row contact parameters - they select code, not table sizes)
 struct BlobOffsets { int o[BLOB_ARRAY_COUNT]; int words; };
 __host__ __device__ constexpr inline int blob_array_len(const BlobDims& d, int k) {
   switch (k) {
@@ -126,6 +127,25 @@ __host__ __device__ constexpr inline HullView hull_view(int nhull, int nvert, in
   h.udadr = take(nhull + 1); h.udir = take(3 * nudir);
   h.words = cur;
   return h;
+}
+
+// The contact-parameter section (model.py _cparam_section, blob version 8; header word 37 = 1): per contact slot solref [2], solimp [5],
+// includemargin (margin - gap) and condim (1 | 3, an int), per joint-limit row solref [2], solimp [5] and margin, per convex geom against
+// the plane the includemargin of its four slots.  It sits behind the hull section (read from global memory: a few words per row per step);
+// offsets in words from the section's start, each array padded to 4 words.  A model whose rows all take the model-wide tables
+// (contact_solref ... limit_solimp) with no margin and condim 3 has no section: the kernel keeps the path of version 7.
+struct CParamView {
+  int con_solref, con_solimp, con_margin, con_condim, lim_solref, lim_solimp, lim_margin, cvx_margin;
+  int words;
+};
+__host__ __device__ constexpr inline CParamView cparam_view(int ncon, int nlimit, int ncvx) {
+  CParamView c{};
+  int cur = 0;
+  auto take = [&](int n) { const int o = cur; cur += (n + 3) & ~3; return o; };
+  c.con_solref = take(2 * ncon); c.con_solimp = take(5 * ncon); c.con_margin = take(ncon); c.con_condim = take(ncon);
+  c.lim_solref = take(2 * nlimit); c.lim_solimp = take(5 * nlimit); c.lim_margin = take(nlimit); c.cvx_margin = take(ncvx);
+  c.words = cur;
+  return c;
 }
 
 // Per-environment LDS layout (offsets in floats).  What is alive from one end of a step to the other sits in front; region "A" is

@@ -33,6 +33,12 @@ Subset
             <general joint gainprm biastype="none|affine" biasprm ...> (dyntype none, gaintype fixed)
   <contact><exclude body1 body2/>: no contacts between the geoms of these two bodies; <pair geom1 geom2 friction solref solimp/>: an explicit
             geom pair (or a geom with the ground plane) with a sliding friction of its own, whatever masks / kinship / excludes say
+  contact parameters: solref solimp solmix condim="1|3" margin gap on geoms and the ground plane (also through <default><geom>), solreflimit
+            solimplimit margin on joints (also through <default><joint>).  Each contact slot takes what its two geoms resolve to by MuJoCo's rules for
+            geoms of equal priority (XML reference, "Contact parameters"; model.mix_contact_params): condim the larger, friction elementwise the larger,
+            mix = solmix1 / (solmix1 + solmix2), solref mixed in standard form / elementwise minimum in direct form, solimp mixed, margin and gap
+            the larger (includemargin = margin - gap); a joint limit takes its joint's values.  Refused: priority, condim 4 / 6, a margin on a pair with
+            a box / mesh hull of another body, margin / gap / own solref on an explicit <pair>
 Contacts: geom-vs-ground-plane, and the geom pairs between bodies that MuJoCo would test (contype / conaffinity masks, same-body and
 parent-child pairs filtered, <exclude>d body pairs dropped): sphere / capsule among themselves, and a sphere or capsule against a box
 or a mesh hull of another body (MJX sphere_convex / capsule_convex); a box or mesh that the masks pair with another box or mesh is an
@@ -50,7 +56,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 
 from minppo_amd.model import (GEOM_BOX, GEOM_CAPSULE, GEOM_CYLINDER, GEOM_MESH, GEOM_SPHERE, JNT_FREE, JNT_HINGE, JNT_SLIDE, MAX_CONVEX_VERTS, ActuatorSpec, BodySpec, GeomSpec, JointSpec,
-                              ModelSpec, _normalize, _qmat, _qmul)
+                              ModelSpec, _normalize, _qmat, _qmul, mix_contact_params)
 
 logger = logging.getLogger(__name__)
 
@@ -453,6 +459,19 @@ def parse_mjcf(xml: str, name: str = "mjcf", base_dir: Optional[Path] = None) ->
     solrefs = {"limit": set(), "contact": set()}
     paired_names = {el.get(k) for sec in root.findall("contact") for el in sec.findall("pair") for k in ("geom1", "geom2")}
     free_z: List[float] = []
+    named_params: Dict[str, Dict[str, object]] = {}  # contact parameters of named geoms (and the plane): what an explicit pair is checked against
+
+    def contact_params(a: Dict[str, str], what: str) -> Dict[str, object]:
+        """A geom's (or the plane's) own contact parameters; solref / solimp None where the file gives none (the model's values apply)."""
+        condim = int(a.get("condim", "3"))
+        if condim not in (1, 3):
+            raise ValueError(f"{what}: condim {condim} (1: frictionless, or 3: pyramidal sliding friction; condim 4 / 6 are not supported)")
+        imp = _floats(a["solimp"]) if "solimp" in a else None
+        out = dict(solref=tuple(_floats(a["solref"], 2, what)) if "solref" in a else None, solimp=None if imp is None else tuple(imp + list(_MJ_SOLIMP[len(imp):])),
+                    solmix=float(a.get("solmix", "1")), condim=condim, margin=float(a.get("margin", "0")), gap=float(a.get("gap", "0")))
+        if a.get("name"):
+            named_params[a["name"]] = out
+        return out
 
     def geom_spec(a: Dict[str, str], what: str):
         """-> (kind, GeomSpec or None, inertia part or None); kind in {'plane', 'collide', 'inert'}"""
@@ -466,7 +485,7 @@ def parse_mjcf(xml: str, name: str = "mjcf", base_dir: Optional[Path] = None) ->
         size = _floats(a["size"]) if "size" in a else []
         if gtype == "plane":
             return "plane", dict(contype=contype, conaffinity=conaff, z=float(pos[2]), friction=tuple((_floats(a.get("friction", "1 0.005 0.0001")) + [0.005, 0.0001])[:3]) if "friction" in a else (1.0, 0.005, 0.0001),
-                                 quat=quat, a=a), None
+                                 quat=quat, a=a, **contact_params(a, what)), None
         if "fromto" in a:
             if gtype not in ("capsule", "cylinder", "box", "ellipsoid"):
                 raise ValueError(f"{what}: fromto on a {gtype}")
@@ -481,10 +500,6 @@ def parse_mjcf(xml: str, name: str = "mjcf", base_dir: Optional[Path] = None) ->
             mname = a.get("mesh")
             if mname not in meshes:
                 raise ValueError(f"{what}: mesh {mname!r} is not defined under <asset> (with vertex=... or an .obj / .stl file)")
-            if "margin" in a and float(a["margin"]) != 0 or "gap" in a and float(a["gap"]) != 0:
-                raise ValueError(f"{what}: contact margin / gap are not supported")
-            if int(a.get("condim", "3")) != 3:
-                raise ValueError(f"{what}: condim {a['condim']} (only 3: pyramidal sliding friction)")
             for k in ("solref", "solimp"):
                 if k in a:
                     solrefs["contact"].add((k, tuple(_floats(a[k]))))
@@ -492,7 +507,7 @@ def parse_mjcf(xml: str, name: str = "mjcf", base_dir: Optional[Path] = None) ->
             # MuJoCo re-centres a mesh on its centre of mass and principal axes and compensates in the geom's pose: the shape in the
             # body frame is unchanged, so the hull is kept in the file's own mesh frame under the geom's pos / quat as written
             gs = GeomSpec(GEOM_MESH, (), pos=tuple(pos), quat=tuple(quat), friction=fr, contype=contype, conaffinity=conaff, name=a.get("name", ""),
-                          vertices=tuple(map(tuple, convex_hull_vertices(meshes[mname], f"mesh {mname}", mesh_maxhull.get(mname, -1)))))
+                          vertices=tuple(map(tuple, convex_hull_vertices(meshes[mname], f"mesh {mname}", mesh_maxhull.get(mname, -1)))), **contact_params(a, what))
             return "collide", gs, None
         need = {"sphere": 1, "capsule": 2, "cylinder": 2, "box": 3, "ellipsoid": 3}.get(gtype)
         if need is None:
@@ -510,13 +525,9 @@ def parse_mjcf(xml: str, name: str = "mjcf", base_dir: Optional[Path] = None) ->
         for k in ("solref", "solimp"):
             if k in a:
                 solrefs["contact"].add((k, tuple(_floats(a[k]))))
-        if "margin" in a and float(a["margin"]) != 0 or "gap" in a and float(a["gap"]) != 0:
-            raise ValueError(f"{what}: contact margin / gap are not supported")
-        if int(a.get("condim", "3")) != 3:
-            raise ValueError(f"{what}: condim {a['condim']} (only 3: pyramidal sliding friction)")
         fr = tuple((_floats(a["friction"]) + [0.005, 0.0001])[:3]) if "friction" in a else (1.0, 0.005, 0.0001)
         gs = GeomSpec({"sphere": GEOM_SPHERE, "capsule": GEOM_CAPSULE, "cylinder": GEOM_CYLINDER, "box": GEOM_BOX}[gtype], tuple(size[:need]), pos=tuple(pos), quat=tuple(quat), friction=fr,
-                      contype=contype, conaffinity=conaff, name=a.get("name", ""))
+                      contype=contype, conaffinity=conaff, name=a.get("name", ""), **contact_params(a, what))
         return "collide", gs, part
 
     def walk(el: ET.Element, parent: str, childclass: Optional[str]) -> None:
@@ -583,8 +594,7 @@ def parse_mjcf(xml: str, name: str = "mjcf", base_dir: Optional[Path] = None) ->
                 for k in ("solreflimit", "solimplimit"):
                     if k in a:
                         solrefs["limit"].add((k, tuple(_floats(a[k]))))
-                if float(a.get("margin", "0")) != 0:
-                    raise ValueError(f"{what}: joint margin is not supported")
+                limp = _floats(a["solimplimit"]) if "solimplimit" in a else None
                 for k in a:
                     if k not in ("name", "type", "pos", "axis", "range", "limited", "ref", "damping", "armature", "stiffness", "solreflimit", "solimplimit",
                                  "springref", "margin", "group", "user", "actuatorfrcrange", "actuatorfrclimited"):
@@ -602,7 +612,9 @@ def parse_mjcf(xml: str, name: str = "mjcf", base_dir: Optional[Path] = None) ->
                     raise ValueError(f"{what}: actuatorfrclimited='true' without actuatorfrcrange")
                 joints.append(JointSpec(jn, jt, pos=tuple(_floats(a.get("pos", "0 0 0"), 3, what)), axis=tuple(_floats(a.get("axis", "0 0 1"), 3, what)), range=rng,
                                         damping=float(a.get("damping", "0")), armature=float(a.get("armature", "0")), stiffness=float(a.get("stiffness", "0")),
-                                        ref=comp.ang(ref) if jt == JNT_HINGE else ref, springref=comp.ang(sref) if jt == JNT_HINGE else sref, actuatorfrcrange=frc))
+                                        ref=comp.ang(ref) if jt == JNT_HINGE else ref, springref=comp.ang(sref) if jt == JNT_HINGE else sref, actuatorfrcrange=frc,
+                                        solreflimit=tuple(_floats(a["solreflimit"], 2, what)) if "solreflimit" in a else None,
+                                        solimplimit=None if limp is None else tuple(limp + list(_MJ_SOLIMP[len(limp):])), margin=float(a.get("margin", "0"))))
             elif ch.tag == "geom":
                 kind, gs, part = geom_spec(dfl.resolve("geom", ch, cc), what)
                 if kind == "plane":
@@ -718,13 +730,13 @@ def parse_mjcf(xml: str, name: str = "mjcf", base_dir: Optional[Path] = None) ->
 
     for kind, key_ref, key_imp, field_ref, field_imp in (("limit", "solreflimit", "solimplimit", "limit_solref", "limit_solimp"),
                                                          ("contact", "solref", "solimp", "contact_solref", "contact_solimp")):
+        # one value among the elements that give one: the model-wide value, as before blob version 8 (it then applies to every element of
+        # the kind, those without the attribute included); several: each element keeps its own, MuJoCo's default where it gives none
         refs = {v for k, v in solrefs[kind] if k == key_ref}
         imps = {v for k, v in solrefs[kind] if k == key_imp}
-        if len(refs) > 1 or len(imps) > 1:
-            raise ValueError(f"per-element {key_ref} / {key_imp} values differ; the engine keeps one {kind} solref / solimp per model")
-        if refs:
+        if len(refs) == 1:
             spec_kw[field_ref] = tuple(refs.pop())
-        if imps:
+        if len(imps) == 1:
             v = list(imps.pop())
             spec_kw[field_imp] = tuple(v + list(_MJ_SOLIMP[len(v):]))
     if plane is not None:
@@ -732,19 +744,20 @@ def parse_mjcf(xml: str, name: str = "mjcf", base_dir: Optional[Path] = None) ->
         spec_kw["plane_friction"] = plane["friction"]
         spec_kw["plane_contype"], spec_kw["plane_conaffinity"] = plane["contype"], plane["conaffinity"]
         spec_kw["plane_name"] = plane["a"].get("name", "")
-        for k in ("solref", "solimp"):
-            if k in plane["a"] and (k, tuple(_floats(plane["a"][k]))) not in solrefs["contact"]:
-                logger.warning("ground plane %s is ignored: contact parameters are taken from the robot's geoms (MuJoCo mixes both by solmix)", k)
+        # the plane takes part in the mixing like a geom (mix_contact_params)
+        spec_kw.update(plane_solref=plane["solref"], plane_solimp=plane["solimp"], plane_solmix=plane["solmix"], plane_condim=plane["condim"],
+                       plane_margin=plane["margin"], plane_gap=plane["gap"])
     else:
         spec_kw["has_plane"] = False
         logger.warning("MJCF has no ground plane: only geom-geom contacts will be generated")
     # <contact>: <exclude body1 body2/> removes every geom pair between two bodies (what exports use where neighbouring collision shapes overlap
     # at rest); <pair geom1 geom2 friction .../> adds a geom pair whatever masks, kinship or excludes say, with contact parameters of its OWN
-    # (MuJoCo does not look at the geoms' for an explicit pair): condim 3, no margin / gap, one sliding friction for both tangents, and the
-    # model's one contact solref / solimp - anything else is a loud error
+    # (MuJoCo does not look at the geoms' for an explicit pair): condim 1 or 3, no margin / gap, one sliding friction for both tangents, and the
+    # one contact solref / solimp its two geoms resolve to (mix_contact_params) - anything else is a loud error
     known = {b.name for b in bodies}
     excludes: List[Tuple[str, str]] = []
     pairs: List[Tuple[str, str, Optional[float]]] = []
+    pair_condim: List[int] = []
     for sec in root.findall("contact"):
         for el in sec:
             if el.tag == "pair":
@@ -757,21 +770,27 @@ def parse_mjcf(xml: str, name: str = "mjcf", base_dir: Optional[Path] = None) ->
                         raise ValueError(f"{what}: attribute {k!r} is outside the supported MJCF subset")
                 if "class" in el.attrib or "solreffriction" in el.attrib:
                     raise ValueError(f"{what}: class / solreffriction are not supported")
-                if int(el.get("condim", "3")) != 3:
-                    raise ValueError(f"{what}: condim {el.get('condim')} (only 3: pyramidal sliding friction)")
+                if int(el.get("condim", "3")) not in (1, 3):
+                    raise ValueError(f"{what}: condim {el.get('condim')} (1: frictionless, or 3: pyramidal sliding friction)")
                 if float(el.get("margin", "0")) != 0 or float(el.get("gap", "0")) != 0:
                     raise ValueError(f"{what}: contact margin / gap are not supported")
                 fr5 = (_floats(el.get("friction", "")) + [1.0, 1.0, 0.005, 0.0001, 0.0001][len(_floats(el.get("friction", ""))):])[:5] if el.get("friction") else [1.0, 1.0, 0.005, 0.0001, 0.0001]
                 if fr5[0] != fr5[1]:
                     raise ValueError(f"{what}: friction {fr5[0]} / {fr5[1]} - the two tangent directions of a contact share one coefficient here")
+                # the pair's solref / solimp must be what its two geoms resolve to (the engine takes the slot's parameters from the geoms)
                 want_ref = tuple(spec_kw.get("contact_solref", _MJ_SOLREF))
                 want_imp = tuple(spec_kw.get("contact_solimp", _MJ_SOLIMP))
+                if g1 in named_params and g2 in named_params:
+                    fill = lambda p_: dict(p_, solref=want_ref if p_["solref"] is None else p_["solref"], solimp=want_imp if p_["solimp"] is None else p_["solimp"])
+                    mixed = mix_contact_params(fill(named_params[g1]), fill(named_params[g2]))
+                    want_ref, want_imp = tuple(mixed["solref"]), tuple(mixed["solimp"])
                 got_ref = tuple(_floats(el.get("solref"))) if el.get("solref") else _MJ_SOLREF
                 got_imp = tuple(_floats(el.get("solimp")) + list(_MJ_SOLIMP[len(_floats(el.get("solimp"))):])) if el.get("solimp") else _MJ_SOLIMP
                 if tuple(got_ref) != want_ref or tuple(got_imp) != want_imp:
                     raise ValueError(f"{what}: solref / solimp {got_ref} / {got_imp} (MuJoCo's defaults where the pair gives none: a pair does not take the geoms') differ from "
-                                     f"the model's contact values {want_ref} / {want_imp}; the engine keeps one contact solref / solimp per model")
+                                     f"what its two geoms resolve to, {want_ref} / {want_imp}; the engine keeps one contact solref / solimp per slot, the geoms'")
                 pairs.append((g1, g2, float(fr5[0])))
+                pair_condim.append(int(el.get("condim", "3")))
                 continue
             if el.tag != "exclude":
                 raise ValueError(f"<contact><{el.tag}> is outside the supported MJCF subset (only <exclude body1 body2/> and <pair geom1 geom2/>)")
@@ -783,6 +802,8 @@ def parse_mjcf(xml: str, name: str = "mjcf", base_dir: Optional[Path] = None) ->
         spec_kw["contact_excludes"] = excludes
     if pairs:
         spec_kw["contact_pairs"] = pairs
+        if any(c != 3 for c in pair_condim):
+            spec_kw["contact_pair_condim"] = pair_condim
     return ModelSpec(name=name, bodies=bodies, actuators=acts, free_root_z=free_root_z, **spec_kw)
 
 
@@ -798,6 +819,22 @@ def load_mjcf(path: str) -> ModelSpec:
 
 def _fmt(v) -> str:
     return " ".join(repr(float(x)) for x in np.atleast_1d(v))
+
+
+def _contact_attrs(solref, solimp, solmix, condim, margin, gap) -> Dict[str, str]:
+    """A geom's (or the plane's) own contact parameters as MJCF attributes; condim always (the writer's <default><geom> says 3)."""
+    out = {"condim": str(int(condim))}
+    if solref is not None:
+        out["solref"] = _fmt(solref)
+    if solimp is not None:
+        out["solimp"] = _fmt(solimp)
+    if solmix != 1.0:
+        out["solmix"] = repr(float(solmix))
+    if margin != 0:
+        out["margin"] = repr(float(margin))
+    if gap != 0:
+        out["gap"] = repr(float(gap))
+    return out
 
 
 def to_mjcf(spec: ModelSpec) -> str:
@@ -817,8 +854,9 @@ def to_mjcf(spec: ModelSpec) -> str:
             ET.SubElement(asset, "mesh", name=f"{bname}_mesh{gi}", vertex=" ".join(_fmt(v) for v in g.vertices))
     world = ET.SubElement(root, "worldbody")
     if spec.has_plane:
-        ET.SubElement(world, "geom", name="floor", type="plane", size="0 0 1", pos=f"0 0 {float(spec.plane_z)!r}", friction=_fmt(spec.plane_friction),
-                      contype=str(spec.plane_contype), conaffinity=str(spec.plane_conaffinity))
+        ET.SubElement(world, "geom", name=spec.plane_name or "floor", type="plane", size="0 0 1", pos=f"0 0 {float(spec.plane_z)!r}", friction=_fmt(spec.plane_friction),
+                      contype=str(spec.plane_contype), conaffinity=str(spec.plane_conaffinity),
+                      **_contact_attrs(spec.plane_solref, spec.plane_solimp, spec.plane_solmix, spec.plane_condim, spec.plane_margin, spec.plane_gap))
     els = {"world": world}
     first_free = True
     for b in spec.bodies:
@@ -840,14 +878,20 @@ def to_mjcf(spec: ModelSpec) -> str:
                 a.update(actuatorfrcrange=_fmt(j.actuatorfrcrange), actuatorfrclimited="true")
             if j.range is not None:
                 a["range"] = _fmt(j.range)
+            if j.solreflimit is not None:
+                a["solreflimit"] = _fmt(j.solreflimit)
+            if j.solimplimit is not None:
+                a["solimplimit"] = _fmt(j.solimplimit)
+            if j.margin != 0:
+                a["margin"] = repr(float(j.margin))
             ET.SubElement(e, "joint", **a)
         for gi, g in enumerate(b.geoms):
             if g.type == GEOM_MESH:
                 ET.SubElement(e, "geom", type="mesh", mesh=f"{b.name}_mesh{gi}", pos=_fmt(g.pos), quat=_fmt(g.quat), friction=_fmt(g.friction), contype=str(g.contype),
-                              conaffinity=str(g.conaffinity), **({"name": g.name} if g.name else {}))
+                              conaffinity=str(g.conaffinity), **({"name": g.name} if g.name else {}), **_contact_attrs(g.solref, g.solimp, g.solmix, g.condim, g.margin, g.gap))
                 continue
             ET.SubElement(e, "geom", type={GEOM_SPHERE: "sphere", GEOM_CAPSULE: "capsule", GEOM_CYLINDER: "cylinder", GEOM_BOX: "box"}[g.type], size=_fmt(g.size), pos=_fmt(g.pos), quat=_fmt(g.quat), friction=_fmt(g.friction),
-                          contype=str(g.contype), conaffinity=str(g.conaffinity), **({"name": g.name} if g.name else {}))
+                          contype=str(g.contype), conaffinity=str(g.conaffinity), **({"name": g.name} if g.name else {}), **_contact_attrs(g.solref, g.solimp, g.solmix, g.condim, g.margin, g.gap))
     act = ET.SubElement(root, "actuator")
     for a in spec.actuators:
         kw = dict(joint=a.joint, gear=repr(float(a.gear)))
@@ -865,8 +909,13 @@ def to_mjcf(spec: ModelSpec) -> str:
         con = ET.SubElement(root, "contact")
         for b1, b2 in spec.contact_excludes:
             ET.SubElement(con, "exclude", body1=b1, body2=b2)
-        for g1, g2, mu in spec.contact_pairs:
-            ET.SubElement(con, "pair", geom1=g1, geom2=g2, solref=_fmt(spec.contact_solref), solimp=_fmt(spec.contact_solimp),
-                          **({} if mu is None else {"friction": _fmt([mu, mu, 0.005, 0.0001, 0.0001])}))
+        fill = lambda r, i, m: dict(solref=spec.contact_solref if r is None else r, solimp=spec.contact_solimp if i is None else i, solmix=m, condim=3, margin=0.0, gap=0.0)
+        own = {g.name: fill(g.solref, g.solimp, g.solmix) for b in spec.bodies for g in b.geoms if g.name}
+        own[spec.plane_name or "floor"] = fill(spec.plane_solref, spec.plane_solimp, spec.plane_solmix)
+        for k, (g1, g2, mu) in enumerate(spec.contact_pairs):
+            cd = spec.contact_pair_condim[k] if k < len(spec.contact_pair_condim) else 3
+            mixed = mix_contact_params(own[g1], own[g2]) if g1 in own and g2 in own else dict(solref=spec.contact_solref, solimp=spec.contact_solimp)
+            ET.SubElement(con, "pair", geom1=g1, geom2=g2, solref=_fmt(mixed["solref"]), solimp=_fmt(mixed["solimp"]),
+                          **({} if mu is None else {"friction": _fmt([mu, mu, 0.005, 0.0001, 0.0001])}), **({} if cd == 3 else {"condim": str(cd)}))
     ET.indent(root)
     return ET.tostring(root, encoding="unicode")

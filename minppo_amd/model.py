@@ -40,7 +40,7 @@ MAX_CONVEX_VERTS = 64  # hull vertices of one mesh collider (the kernel scans th
 MAX_BODIES = 128  # subtree sets are two 64-bit words per body (one up to 64 bodies); dofs: one word, 64
 
 BLOB_MAGIC = 0x4D50504F  # "MPPO"
-BLOB_VERSION = 7  # 7: hull section carries the hulls' edge directions (convex_convex: box / mesh against box / mesh); 6: dof_actfrcrange (joint actuatorfrcrange); 2: header word include_c_vals; 3: geom-geom pairs (npair, pair_body, pair_geom) and con_axis; 4: convex (mesh) geoms against the plane; 5: hull section (sphere / capsule against box / mesh)
+BLOB_VERSION = 8  # 8: per-slot / per-limit contact parameters (header word 37, a section behind the hull section); 7: hull section carries the hulls' edge directions (convex_convex: box / mesh against box / mesh); 6: dof_actfrcrange (joint actuatorfrcrange); 2: header word include_c_vals; 3: geom-geom pairs (npair, pair_body, pair_geom) and con_axis; 4: convex (mesh) geoms against the plane; 5: hull section (sphere / capsule against box / mesh)
 
 
 # ---------------------------------------------------------------------------
@@ -61,6 +61,10 @@ class JointSpec:
     ref: float = 0.0  # qpos0 for hinge/slide
     actuatorfrcrange: Optional[Tuple[float, float]] = None  # MJCF actuatorfrcrange: the total actuator force on this (hinge / slide) joint is clamped to it
     springref: Optional[float] = None  # position at which the joint spring (stiffness) is at rest: MuJoCo's qpos_spring; None = at `ref` (the built-in robots)
+    # the limit row's own parameters (MJCF solreflimit / solimplimit / margin); None: the model's limit_solref / limit_solimp
+    solreflimit: Optional[Sequence[float]] = None
+    solimplimit: Optional[Sequence[float]] = None
+    margin: float = 0.0  # the limit is active while the distance to it is below this
 
 
 @dataclass
@@ -79,6 +83,13 @@ class GeomSpec:
     # convex hull, like in MuJoCo / MJX: with the ground plane, and with the spheres and capsules of other bodies (not with boxes / meshes).
     vertices: Optional[Sequence[Sequence[float]]] = None
     name: str = ""  # (what an explicit contact pair - ModelSpec.contact_pairs - refers to)
+    # contact parameters, resolved per contact slot with the other side's (mix_contact_params): None = the model's contact_solref / solimp
+    solref: Optional[Sequence[float]] = None
+    solimp: Optional[Sequence[float]] = None
+    solmix: float = 1.0
+    condim: int = 3  # 1 (frictionless) or 3 (pyramidal sliding friction)
+    margin: float = 0.0
+    gap: float = 0.0
 
 
 @dataclass
@@ -140,6 +151,14 @@ class ModelSpec:
     # One of the two may be the ground plane (`plane_name`): the geom then gets its ground contact slots.
     contact_pairs: List[Tuple[str, str, Optional[float]]] = field(default_factory=list)
     plane_name: str = ""
+    contact_pair_condim: List[int] = field(default_factory=list)  # per contact pair (empty: 3 for all), MJCF <pair condim>
+    # the ground plane's own contact parameters (it takes part in the mixing like a geom); None = the model's contact_solref / solimp
+    plane_solref: Optional[Sequence[float]] = None
+    plane_solimp: Optional[Sequence[float]] = None
+    plane_solmix: float = 1.0
+    plane_condim: int = 3
+    plane_margin: float = 0.0
+    plane_gap: float = 0.0
 
 
 # ---------------------------------------------------------------------------
@@ -309,6 +328,40 @@ def hull_topology(verts: np.ndarray) -> Tuple[List[List[int]], np.ndarray, np.nd
     return faces, np.asarray(normals), np.asarray(edges, np.int32).reshape(-1, 2), np.asarray([[normals[edge_faces[e][0]], normals[edge_faces[e][1]]] for e in edges]).reshape(-1, 2, 3)
 
 
+def _solimp5(v: Sequence[float]) -> Tuple[float, ...]:
+    v = [float(x) for x in v]
+    return tuple(v + [0.9, 0.95, 0.001, 0.5, 2.0][len(v):])
+
+
+def mix_contact_params(p1: dict, p2: dict) -> dict:
+    """The contact parameters of a slot between two geoms of equal priority, from theirs - MuJoCo's rules (XML reference, "Contact
+    parameters"; restated from the documentation, no MuJoCo here to compare with):
+      condim: the larger; friction: elementwise maximum (done by the caller, as before);
+      mix = solmix1 / (solmix1 + solmix2) - 0.5 if both weights are below mjMINVAL, 0 / 1 if one of them is;
+      solref = mix s1 + (1 - mix) s2 when both are in standard form (first component > 0), else (direct form) the elementwise minimum;
+      solimp = mix i1 + (1 - mix) i2;  margin, gap: the larger of each; includemargin = margin - gap.
+    Where both sides carry the same value the slot takes that value itself (not a recomputed mix: the same bits).
+    p: dict(solref, solimp, solmix, condim, margin, gap); returns dict(solref, solimp, condim, margin, gap, includemargin)."""
+    w1, w2 = float(p1["solmix"]), float(p2["solmix"])
+    if w1 >= MJ_MINVAL and w2 >= MJ_MINVAL:
+        mix = w1 / (w1 + w2)
+    elif w1 < MJ_MINVAL and w2 < MJ_MINVAL:
+        mix = 0.5
+    else:
+        mix = 0.0 if w1 < MJ_MINVAL else 1.0
+    s1, s2 = tuple(map(float, p1["solref"])), tuple(map(float, p2["solref"]))
+    i1, i2 = _solimp5(p1["solimp"]), _solimp5(p2["solimp"])
+    if s1 == s2:
+        sr = s1
+    elif s1[0] > 0 and s2[0] > 0:
+        sr = tuple(mix * a + (1.0 - mix) * b for a, b in zip(s1, s2))
+    else:
+        sr = tuple(min(a, b) for a, b in zip(s1, s2))
+    si = i1 if i1 == i2 else tuple(mix * a + (1.0 - mix) * b for a, b in zip(i1, i2))
+    margin, gap = max(float(p1["margin"]), float(p2["margin"])), max(float(p1["gap"]), float(p2["gap"]))
+    return dict(solref=sr, solimp=si, condim=max(int(p1["condim"]), int(p2["condim"])), margin=margin, gap=gap, includemargin=margin - gap)
+
+
 def compile_model(spec: ModelSpec) -> CompiledModel:
     """Flattens a ModelSpec and derives the constants MuJoCo's compiler would
     (`mj_setConst`: `dof_invweight0`, `body_invweight0`, `stat.meaninertia`)."""
@@ -405,8 +458,12 @@ def compile_model(spec: ModelSpec) -> CompiledModel:
                     raise ValueError(f"body {b.name}: a mesh geom needs the (at least four) vertices of its convex hull")
                 if len(g.vertices) > MAX_CONVEX_VERTS:
                     raise ValueError(f"body {b.name}: a mesh collider with {len(g.vertices)} hull vertices (limit {MAX_CONVEX_VERTS}: decimate the collision mesh)")
+            if int(g.condim) not in (1, 3):
+                raise ValueError(f"body {b.name}: geom condim {g.condim} (1: frictionless, or 3: pyramidal sliding friction; condim 4 / 6 are not supported)")
             geoms.append((g.type, bi, list(g.pos), list(_normalize(g.quat)), size, list(g.friction), int(g.contype), int(g.conaffinity),
-                          None if g.vertices is None else np.asarray(g.vertices, np.float64).reshape(-1, 3), g.name))
+                          None if g.vertices is None else np.asarray(g.vertices, np.float64).reshape(-1, 3), g.name,
+                          dict(solref=spec.contact_solref if g.solref is None else g.solref, solimp=spec.contact_solimp if g.solimp is None else g.solimp,
+                               solmix=g.solmix, condim=int(g.condim), margin=float(g.margin), gap=float(g.gap))))
 
     njnt = len(jnt_type)
     # dof_parentid: previous dof in the same body, else last dof of the nearest ancestor with dofs
@@ -519,7 +576,16 @@ def compile_model(spec: ModelSpec) -> CompiledModel:
     geom_index = {g[9]: k for k, g in enumerate(geoms) if g[9]}
     pair_with_plane: Dict[int, Optional[float]] = {}
     pair_of_geoms: Dict[frozenset, Optional[float]] = {}
-    for n1, n2, mu in spec.contact_pairs:
+    pair_condim: Dict[object, int] = {}  # (geom index | frozenset of two) -> the pair's own condim
+    plane_par = dict(solref=spec.contact_solref if spec.plane_solref is None else spec.plane_solref,
+                     solimp=spec.contact_solimp if spec.plane_solimp is None else spec.plane_solimp, solmix=spec.plane_solmix,
+                     condim=int(spec.plane_condim), margin=float(spec.plane_margin), gap=float(spec.plane_gap))
+    if spec.has_plane and plane_par["condim"] not in (1, 3):
+        raise ValueError(f"ground plane condim {plane_par['condim']} (1 or 3; condim 4 / 6 are not supported)")
+    for pi_, (n1, n2, mu) in enumerate(spec.contact_pairs):
+        pcd = int(spec.contact_pair_condim[pi_]) if pi_ < len(spec.contact_pair_condim) else 3
+        if pcd not in (1, 3):
+            raise ValueError(f"contact pair ({n1!r}, {n2!r}): condim {pcd} (1 or 3; condim 4 / 6 are not supported)")
         for n in (n1, n2):
             if n not in geom_index and not (spec.has_plane and spec.plane_name and n == spec.plane_name):
                 raise ValueError(f"contact pair ({n1!r}, {n2!r}): unknown geom {n!r} (a pair names collision geoms of bodies, or the ground plane)")
@@ -530,17 +596,29 @@ def compile_model(spec: ModelSpec) -> CompiledModel:
             raise ValueError(f"contact pair ({n1!r}, {n2!r}): a pair needs two different geoms, at most one of them the ground plane")
         if on_plane:
             pair_with_plane[geom_index[n2 if on_plane[0] == n1 else n1]] = mu
+            pair_condim[geom_index[n2 if on_plane[0] == n1 else n1]] = pcd
         else:
             i_, j_ = geom_index[n1], geom_index[n2]
             if geoms[i_][1] == geoms[j_][1]:
                 raise ValueError(f"contact pair ({n1!r}, {n2!r}): both geoms belong to the same body")
             pair_of_geoms[frozenset((i_, j_))] = mu
-    for gk, (gt, bi, gpos, gquat, gsize, gfri, gct, gca, gverts, _gname) in enumerate(geoms):
+            pair_condim[frozenset((i_, j_))] = pcd
+
+    def slot_params(p1: dict, p2: dict, pair_key) -> dict:
+        r = mix_contact_params(p1, p2)
+        if pair_key in pair_condim:  # an explicit pair: its own condim, no margin / gap (its solref / solimp equal the geoms': mjcf.py)
+            r.update(condim=pair_condim[pair_key], margin=0.0, gap=0.0, includemargin=0.0)
+        return r
+
+    con_par: List[dict] = []
+    cvx_margin: List[float] = []
+    for gk, (gt, bi, gpos, gquat, gsize, gfri, gct, gca, gverts, _gname, gpar) in enumerate(geoms):
         if gt not in (GEOM_SPHERE, GEOM_CAPSULE, GEOM_CYLINDER, GEOM_BOX, GEOM_MESH):
             raise ValueError(f"unsupported geom type {gt}")
         if not spec.has_plane or not (_masks_match(spec.plane_contype, spec.plane_conaffinity, gct, gca) or gk in pair_with_plane):
             continue
         fri = np.maximum(np.asarray(gfri), np.asarray(spec.plane_friction))
+        spar = slot_params(gpar, plane_par, gk)
         if pair_with_plane.get(gk) is not None:
             fri = np.asarray([pair_with_plane[gk], fri[1], fri[2]])  # (an explicit pair's sliding friction is its own)
         axis_l = np.zeros(3)
@@ -559,7 +637,8 @@ def compile_model(spec: ModelSpec) -> CompiledModel:
             cvx_vadr.append(len(cvx_vert))
             for j in range(4):
                 con_bodyid.append(bi); con_lpos.append([0.0, 0.0, 0.0]); con_radius.append(0.0); con_friction.append(list(fri)); con_axis.append([0.0, 0.0, 0.0])
-                con_cvx.append(4 * k + j)
+                con_cvx.append(4 * k + j); con_par.append(spar)
+            cvx_margin.append(spar["includemargin"])
             continue
         if gt == GEOM_CYLINDER:
             # a cylinder against the plane, MJX collision_primitive.plane_cylinder: THREE slots per geom, placed every step - the rim point
@@ -569,7 +648,7 @@ def compile_model(spec: ModelSpec) -> CompiledModel:
             for j in range(3):
                 con_bodyid.append(bi); con_lpos.append(list(gpos)); con_radius.append(gsize[0]); con_friction.append(list(fri))
                 con_axis.append(list(_qrot(gquat, [0, 0, 1.0]) * gsize[1]) if j == 0 else list(_qrot(gquat, [1.0, 0, 0])) if j == 1 else [0.0, 0.0, 0.0])
-                con_cvx.append(-2 - j)
+                con_cvx.append(-2 - j); con_par.append(spar)
             continue
         if gt == GEOM_SPHERE:
             ends = [np.asarray(gpos, dtype=np.float64)]
@@ -584,6 +663,7 @@ def compile_model(spec: ModelSpec) -> CompiledModel:
             con_friction.append(list(fri))
             con_axis.append(list(axis_l))
             con_cvx.append(-1)
+            con_par.append(spar)
     nplane = len(con_bodyid)
     # ... then geom-geom pairs between different bodies, filtered as MuJoCo filters them: same weld group and parent-child weld
     # groups are skipped (mj_filterBodyPair), then the contype / conaffinity masks.  geom1 is the one with the smaller type id
@@ -618,12 +698,12 @@ def compile_model(spec: ModelSpec) -> CompiledModel:
             if GEOM_CYLINDER in (gi[0], gj[0]):
                 raise ValueError("a cylinder geom can only collide with the ground plane (MJX pairs it through signed-distance functions: not built): "
                                  "exclude it from geom-geom pairs with contype / conaffinity")
-            pair_rows.append(((gi[0], gj[0]), gi, gj, 0, mu_pair))
+            pair_rows.append(((gi[0], gj[0]), gi, gj, 0, mu_pair, key))
             if gj[0] in (GEOM_BOX, GEOM_MESH) and gi[0] == GEOM_CAPSULE:
-                pair_rows.append(((gi[0], gj[0]), gi, gj, 1, mu_pair))  # capsule_convex fills two contact slots
+                pair_rows.append(((gi[0], gj[0]), gi, gj, 1, mu_pair, key))  # capsule_convex fills two contact slots
             if gi[0] in (GEOM_BOX, GEOM_MESH):  # box / mesh against box / mesh (round 6; MJX convex_convex): a manifold of four contact slots
                 for slot_ in (1, 2, 3):
-                    pair_rows.append(((gi[0], gj[0]), gi, gj, slot_, mu_pair))
+                    pair_rows.append(((gi[0], gj[0]), gi, gj, slot_, mu_pair, key))
     pair_rows.sort(key=lambda r: r[0])  # stable: geom order inside a group, a pair's two slots next to each other
     pair_body, pair_geom = [], []
     # hull section: the convex geoms that take part in a pair, vertices / normals in the BODY frame
@@ -666,7 +746,7 @@ def compile_model(spec: ModelSpec) -> CompiledModel:
             hull_vadr.append(len(hull_vert)); hull_fadr.append(len(hull_fnormal)); hull_eadr.append(len(hull_edge))
         return hull_of[id(gx)]
 
-    for _, gi, gj, slot, mu_pair in pair_rows:
+    for _, gi, gj, slot, mu_pair, pkey in pair_rows:
         pair_body += [gi[1], gj[1]]
         hid = hull_id(gj) if gj[0] in (GEOM_BOX, GEOM_MESH) else -1
         hid1 = hull_id(gi) if gi[0] in (GEOM_BOX, GEOM_MESH) else -1
@@ -683,6 +763,12 @@ def compile_model(spec: ModelSpec) -> CompiledModel:
         con_friction.append(list(fri_pair))
         con_axis.append([0.0, 0.0, 0.0])
         con_cvx.append(-1)
+        spar = slot_params(gi[10], gj[10], pkey)
+        if spar["includemargin"] != 0.0 and (gj[0] in (GEOM_BOX, GEOM_MESH)):
+            raise ValueError(f"a contact margin ({spar['margin']!r}, gap {spar['gap']!r}) between a sphere / capsule / box / mesh and a box or mesh of another body: "
+                             "the hull colliders (sphere_convex, capsule_convex, convex_convex) keep only touching contacts here - a margin is supported "
+                             "against the ground plane and between spheres and capsules")
+        con_par.append(spar)
     npair = len(pair_rows)
     ncvx, ncvxvert = len(cvx_body), len(cvx_vert)
     ncyl = sum(1 for k in con_cvx if k == -2)
@@ -690,6 +776,24 @@ def compile_model(spec: ModelSpec) -> CompiledModel:
 
     lim_jnt = [j for j in range(njnt) if jnt_limited[j] and jnt_type[j] != JNT_FREE]
     nlimit = len(lim_jnt)
+    all_joints = [j for b in spec.bodies for j in b.joints]
+    lim_solref = [tuple(map(float, spec.limit_solref if all_joints[j].solreflimit is None else all_joints[j].solreflimit)) for j in lim_jnt]
+    lim_solimp = [_solimp5(spec.limit_solimp if all_joints[j].solimplimit is None else all_joints[j].solimplimit) for j in lim_jnt]
+    lim_margin = [float(all_joints[j].margin) for j in lim_jnt]
+    con_solref = [tuple(map(float, p["solref"])) for p in con_par]
+    con_solimp = [_solimp5(p["solimp"]) for p in con_par]
+    con_margin = [float(p["includemargin"]) for p in con_par]
+    con_condim = [int(p["condim"]) for p in con_par]
+    # uniform: every row takes the model-wide tables, no margin, condim 3 - the environment kernel's path of blob version 7, bit for bit
+    mref, mimp = tuple(map(float, spec.contact_solref)), _solimp5(spec.contact_solimp)
+    lref, limp = tuple(map(float, spec.limit_solref)), _solimp5(spec.limit_solimp)
+    cparam_uniform = (all(r == mref for r in con_solref) and all(i == mimp for i in con_solimp) and not any(con_margin) and all(c == 3 for c in con_condim)
+                      and all(r == lref for r in lim_solref) and all(i == limp for i in lim_solimp) and not any(lim_margin))
+    for what, refs_, imps_ in () if cparam_uniform else (("contact", con_solref, con_solimp), ("joint limit", lim_solref, lim_solimp)):
+        for r_, i_ in zip(refs_, imps_):  # (the ranges mppo_model_open checks: said here, where the model is still a file)
+            if (r_[0] > 0) != (r_[1] > 0) or not (0.0001 <= i_[0] <= 0.9999 and 0.0001 <= i_[1] <= 0.9999 and i_[2] > 0 and 0.0001 <= i_[3] <= 0.9999 and i_[4] >= 1):
+                raise ValueError(f"{what} solref {r_} / solimp {i_}: solref in standard (both > 0) or direct (both <= 0) form, solimp dmin / dmax / midpoint "
+                                 "in [0.0001, 0.9999], width > 0, power >= 1")
 
     t: Dict[str, np.ndarray] = {}
 
@@ -783,6 +887,16 @@ def compile_model(spec: ModelSpec) -> CompiledModel:
     put("contact_solimp", spec.contact_solimp)
     put("limit_solref", spec.limit_solref)
     put("limit_solimp", spec.limit_solimp)
+    # per contact slot / per limit row (blob version 8: the contact-parameter section, present when `cparam` is 1)
+    put("cparam", 0 if cparam_uniform else 1, np.int32)
+    put("con_solref", np.reshape(con_solref, (ncon, 2)))
+    put("con_solimp", np.reshape(con_solimp, (ncon, 5)))
+    put("con_margin", con_margin)
+    put("con_condim", con_condim, np.int32)
+    put("lim_solref", np.reshape(lim_solref, (nlimit, 2)))
+    put("lim_solimp", np.reshape(lim_solimp, (nlimit, 5)))
+    put("lim_margin", lim_margin)
+    put("cvx_margin", cvx_margin)
 
     cm = CompiledModel(spec.name, t, names, joint_names, spec.meaninertia)
     _set_const(cm)
@@ -940,7 +1054,8 @@ _BLOB_F32 = [
 ]
 _HDR_INT = ["nq", "nv", "nu", "nbody", "njnt", "ncon", "nlimit", "iterations", "ls_iterations", "nlevel", "nroot", "include_c_vals", "npair"]
 _HDR_F32 = ["timestep", "tolerance", "ls_tolerance", "impratio", "plane_z", "meaninertia"]
-_HDR_INT2 = ["ncvx", "ncvxvert", "hull_words", "ncyl"]  # words 33..: dims that arrived after the first header block was full (hull_words: length of the hull section behind the table part)
+_HDR_INT2 = ["ncvx", "ncvxvert", "hull_words", "ncyl", "cparam"]  # words 33..: dims that arrived after the first header block was full (hull_words: length of the hull section behind the table part;
+# cparam, word 37: 0 = the contact / limit parameters are model-uniform (the model-wide tables), 1 = the contact-parameter section follows the hull section)
 BLOB_HEADER_WORDS = 64  # fixed-size header; array directory follows
 
 
@@ -953,7 +1068,9 @@ def _to_blob(cm: CompiledModel, include_c_vals: bool = True) -> bytes:
     _BLOB_INT + _BLOB_F32 order, then the arrays (each padded to 4 words) - the table part: what the environment kernel copies
     into LDS.  Behind it, if the model has convex geoms in geom-geom pairs, the HULL SECTION (header word `hull_words`; read from
     global memory, a few lines per step): eight words (nhull, nvert, nface, nfidx, nedge, 0, 0, 0), then the arrays of
-    _HULL_ARRAYS in that order, each padded to 4 words.  The C side (csrc/model_view.h) mirrors this layout.
+    _HULL_ARRAYS in that order, each padded to 4 words.  Behind that, if header word 37 (`cparam`) is 1, the CONTACT-PARAMETER
+    section: the arrays of _CPARAM_ARRAYS in that order, each padded to 4 words, lengths following from ncon / nlimit / ncvx (read
+    from global memory by the kernel's per-row path).  The C side (csrc/model_view.h) mirrors this layout.
     """
     t = cm.t
     names = _BLOB_INT + _BLOB_F32
@@ -985,18 +1102,32 @@ def _to_blob(cm: CompiledModel, include_c_vals: bool = True) -> bytes:
     struct.pack_into("<i", hdr, 4 * 32, ndir)
     hull = _hull_section(t)
     for i, k in enumerate(_HDR_INT2):
-        struct.pack_into("<i", hdr, 4 * (33 + i), len(hull) // 4 if k == "hull_words" else int(t[k]))
+        struct.pack_into("<i", hdr, 4 * (33 + i), len(hull) // 4 if k == "hull_words" else int(t.get(k, 0)))
     d = bytearray()
     for off, n in dir_entries:
         d += struct.pack("<2i", off, n)
     d += b"\0" * (4 * (base - BLOB_HEADER_WORDS - 2 * ndir))
     blob = bytes(hdr) + bytes(d) + bytes(payload)
     assert len(blob) == 4 * total, (len(blob), total)
-    return blob + hull
+    return blob + hull + _cparam_section(t)
 
 
 _HULL_ARRAYS = [("hull_vadr", "<i4"), ("hull_fadr", "<i4"), ("hull_eadr", "<i4"), ("hull_face_adr", "<i4"), ("hull_fidx", "<i4"), ("hull_edge", "<i4"),
                 ("hull_vert", "<f4"), ("hull_fnormal", "<f4"), ("hull_enormal", "<f4"), ("hull_udadr", "<i4"), ("hull_udir", "<f4")]
+
+
+_CPARAM_ARRAYS = [("con_solref", "<f4"), ("con_solimp", "<f4"), ("con_margin", "<f4"), ("con_condim", "<i4"), ("lim_solref", "<f4"), ("lim_solimp", "<f4"),
+                  ("lim_margin", "<f4"), ("cvx_margin", "<f4")]
+
+
+def _cparam_section(t: Dict[str, np.ndarray]) -> bytes:
+    if not int(t.get("cparam", 0)):
+        return b""
+    out = bytearray()
+    for k, dt in _CPARAM_ARRAYS:
+        raw = np.ascontiguousarray(t[k]).reshape(-1).astype(dt).tobytes()
+        out += raw + b"\0" * ((-len(raw)) % 16)
+    return bytes(out)
 
 
 def _hull_section(t: Dict[str, np.ndarray]) -> bytes:

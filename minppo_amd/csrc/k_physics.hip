@@ -622,10 +622,11 @@ struct RuntimeModel {
   static constexpr bool kStatic = false;
   static constexpr BlobDims dims() { return BlobDims{}; }
 };
-template <int NQ, int NV, int NU, int NBODY, int NJNT, int NCON, int NLIMIT, int NPAIR, int NLEVEL, int NROOT, int NCVX = 0, int NCVXVERT = 0, int HULL = 0, int NCYL = 0, int CPARAM = 0>
+template <int NQ, int NV, int NU, int NBODY, int NJNT, int NCON, int NLIMIT, int NPAIR, int NLEVEL, int NROOT, int NCVX = 0, int NCVXVERT = 0, int HULL = 0, int NCYL = 0, int NEQ = 0,
+          int CPARAM = 0>
 struct StaticModel {
   static constexpr bool kStatic = true;
-  static constexpr BlobDims dims() { return BlobDims{NQ, NV, NU, NBODY, NJNT, NCON, NLIMIT, NPAIR, NLEVEL, NROOT, NCVX, NCVXVERT, HULL, NCYL, CPARAM}; }
+  static constexpr BlobDims dims() { return BlobDims{NQ, NV, NU, NBODY, NJNT, NCON, NLIMIT, NPAIR, NLEVEL, NROOT, NCVX, NCVXVERT, HULL, NCYL, NEQ, CPARAM}; }
 };
 // MODE (EnvArgs::mode) is a template parameter too: the step kernel carries neither the probe's 17 output pointers nor its stores.
 template <class SD, int MODE>
@@ -635,8 +636,9 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerBlock) env_kernel(ModelView m
   constexpr bool kDims = SD::kStatic;
   // fixed-size kernel, up to 32 dofs: a lane's rows / columns of the Cholesky factors live in registers (see factor_m below)
   constexpr bool kRegChol = kDims && kSD.nv <= kRegCholMaxNv;
-  constexpr int kSpill = kDims ? spill_for(kSD.nq, kSD.nv, kSD.nu, kSD.nbody, kSD.njnt, kSD.ncon, kSD.nlimit + 4 * kSD.ncon, kSD.nroot, kSD.ncvx, kRegChol, kSO.words) : 0;
-  constexpr PhysLds kSP = make_phys_lds(kSD.nq, kSD.nv, kSD.nu, kSD.nbody, kSD.njnt, kSD.ncon, kSD.nlimit + 4 * kSD.ncon, kSD.nroot, kSD.ncvx, kRegChol, kSpill);
+  constexpr int kNefc = kSD.neq + kSD.nlimit + 4 * kSD.ncon;
+  constexpr int kSpill = kDims ? spill_for(kSD.nq, kSD.nv, kSD.nu, kSD.nbody, kSD.njnt, kSD.ncon, kNefc, kSD.nroot, kSD.ncvx, kRegChol, kSO.words, kSD.neq) : 0;
+  constexpr PhysLds kSP = make_phys_lds(kSD.nq, kSD.nv, kSD.nu, kSD.nbody, kSD.njnt, kSD.ncon, kNefc, kSD.nroot, kSD.ncvx, kRegChol, kSpill, kSD.neq);
   const PhysLds P = SD::kStatic ? kSP : Prt;
   constexpr int NV = kDims ? kSD.nv : 0;
   constexpr int kDotU = dot_unroll(NV);
@@ -667,7 +669,11 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerBlock) env_kernel(ModelView m
   float* G = P.gwords > 0 ? a.scratch + (size_t)(blockIdx.x * ((int)(blockDim.x >> 6) * epw) + el) * P.gwords : nullptr;
 
   const int nq = kDims ? kSD.nq : mv.nq, nv = kDims ? kSD.nv : mv.nv, nu = kDims ? kSD.nu : mv.nu, nb = kDims ? kSD.nbody : mv.nbody, njnt = kDims ? kSD.njnt : mv.njnt,
-            ncon = kDims ? kSD.ncon : mv.ncon, nlim = kDims ? kSD.nlimit : mv.nlimit, nefc = kDims ? kSD.nlimit + 4 * kSD.ncon : mv.nefc;
+            ncon = kDims ? kSD.ncon : mv.ncon, nlim = kDims ? kSD.nlimit : mv.nlimit, nefc = kDims ? kNefc : mv.nefc;
+  // equality rows (blob version 9): kept BEHIND the inequality rows in the row arrays (rows nce .. nefc - 1; the probe reports them first,
+  // as MJX orders them); a model without any (neq = 0) runs exactly the code of version 8 - in a specialised kernel none of it is compiled in
+  const int neq = kDims ? kSD.neq : mv.neq, nce = nefc - neq;
+  const bool has_eq = kDims ? kSD.neq > 0 : mv.neq > 0;
   const int nlevel = kDims ? kSD.nlevel : mv.nlevel, nroot = kDims ? kSD.nroot : mv.nroot;
   const int ldm = P.ldm, ldj = P.ldj;
   const int nvq = (nv + 3) >> 2;  // dof quads (the global-memory matrices hold four consecutive dofs per 16-byte word)
@@ -692,6 +698,11 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerBlock) env_kernel(ModelView m
   const CParamView cpv = cparam_view(ncon, kDims ? kSD.nlimit : mv.nlimit, ncvx);
   const float* cpf = reinterpret_cast<const float*>(mv.blob + mv.blob_words + mv.hull_words);
   const int* cpi = mv.blob + mv.blob_words + mv.hull_words;
+  // the equality section (EqView), read from global memory: behind the contact-parameter section if there is one
+  const int* eqsec = cpi + (cp ? cpv.words : 0);
+  const EqView eqv = eq_view(neq, has_eq ? eqsec[0] : 0);
+  auto eq_rec = [&](int r) { return eqsec + eqv.rec + kEqRecordWords * eqsec[eqv.row + r]; };  // the record of row r's element
+  float* eqpos = S + P.eqpos;
   float* cvxsel = S + P.cvxsel; float* cvxok = S + P.cvxok;
   float* xanchor = S + P.xanchor; float* xaxis = S + P.xaxis;
   float* Cw = S + P.C; float* cdofdot = S + P.cdofdot; float* cfrc = S + P.cfrc; float* J = (float*)__builtin_assume_aligned(S + P.J, 16);
@@ -827,6 +838,19 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerBlock) env_kernel(ModelView m
       }
     }
     SYNC();
+    if (has_eq) {
+      // the world points of every connect's anchors, one copy per row (p1 of body1, p2 of body2 - the world's is its anchor itself): the
+      // poses are region A1's, gone by make_constraint
+      FOR_G(r, neq) {
+        const int* ri = eq_rec(r);
+        const float* rf = reinterpret_cast<const float*>(ri);
+        if (ri[0] == EQ_CONNECT) {
+          const int b1 = ri[1], b2 = ri[2];
+          st3(eqpos + 6 * r, add3(ld3(xpos + 3 * b1), qrot(ld4(xquat + 4 * b1), ld3(rf + 4))));
+          st3(eqpos + 6 * r + 3, add3(ld3(xpos + 3 * b2), qrot(ld4(xquat + 4 * b2), ld3(rf + 7))));
+        }
+      }
+    }
     if (MODE == 2 && valid && a.probe.xpos) FOR_G(i, nb * 3) a.probe.xpos[(size_t)env * nb * 3 + i] = xpos[i];  // (the poses are gone by the end of the step)
     PT(2);
     // ---- com_pos: centre of mass of every kinematic tree; contact candidates --------------------
@@ -1535,12 +1559,72 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerBlock) env_kernel(ModelView m
         jaref[nlim + 4 * c + k] = act ? iw : 0.f;
       }
     }
+    // equality rows: a dense row each (Je: LDS after the contact rows, or the record in global memory with the contact Jacobian).
+    // connect: jacp(p1, body1) - jacp(p2, body2), component k of the world frame; joint: +1 at dof1, -dpoly/dq2 at dof2
+    float* Je = has_eq ? (spJ ? G + P.gJe : S + P.Je) : nullptr;
+    const int ldje = spJ ? nv : ldj;
+    if (has_eq) {
+      for (int item = g; item < neq * nv; item += kGroupLanes) {
+        const int r = item / nv, d = item - r * nv;
+        const int* ri = eq_rec(r);
+        const float* rf = reinterpret_cast<const float*>(ri);
+        float v = 0.f;
+        if (ri[0] == EQ_CONNECT) {
+          const int k = r - ri[3];
+          for (int side = 0; side < 2; ++side) {
+            const int b = ri[1 + side];
+            if (b > 0 && ((TU(body_ancdof_mask)[b] >> d) & 1ull)) {
+              int rr = 0;
+              for (int q = 0; q < nroot; ++q) if (TI(root_body)[q] == TI(body_rootid)[b]) rr = q;
+              const V3 off = sub3(ld3(eqpos + 6 * r + 3 * side), ld3(rootcom + 3 * rr));
+              const V3 jb = add3(ld3(cdof + 6 * d + 3), cross3(ld3(cdof + 6 * d), off));
+              const float c = k == 0 ? jb.x : k == 1 ? jb.y : jb.z;
+              v = side == 0 ? v + c : v - c;
+            }
+          }
+        } else {
+          const int j1 = ri[1], j2 = ri[2];
+          if (d == TI(jnt_dofadr)[j1]) v = 1.f;
+          else if (j2 >= 0 && d == TI(jnt_dofadr)[j2]) {
+            const float x = qpos[TI(jnt_qposadr)[j2]] - TF(qpos0)[TI(jnt_qposadr)[j2]];
+            const float* pc = rf + 10;
+            v = -(pc[1] + x * (2.f * pc[2] + x * (3.f * pc[3] + x * 4.f * pc[4])));
+          }
+        }
+        Je[r * ldje + d] = v;
+      }
+      FOR_G(r, neq) {  // residual (pos, parked in jv) and invweight (parked in jaref)
+        const int* ri = eq_rec(r);
+        const float* rf = reinterpret_cast<const float*>(ri);
+        float pos;
+        if (ri[0] == EQ_CONNECT) {
+          const int k = r - ri[3];
+          pos = eqpos[6 * r + k] - eqpos[6 * r + 3 + k];
+        } else {
+          const int j1 = ri[1], j2 = ri[2];
+          const float* pc = rf + 10;
+          pos = qpos[TI(jnt_qposadr)[j1]] - TF(qpos0)[TI(jnt_qposadr)[j1]] - pc[0];
+          if (j2 >= 0) {
+            const float x = qpos[TI(jnt_qposadr)[j2]] - TF(qpos0)[TI(jnt_qposadr)[j2]];
+            pos -= x * (pc[1] + x * (pc[2] + x * (pc[3] + x * pc[4])));
+          }
+        }
+        jv[nce + r] = pos;
+        jaref[nce + r] = rf[22];
+      }
+    }
     if (spJ) GSYNC(); else SYNC();
     float k_lim, b_lim, k_con, b_con;
     kb_params(TF(limit_solref), TF(limit_solimp), h, k_lim, b_lim);
     kb_params(TF(contact_solref), TF(contact_solimp), h, k_con, b_con);
     // row r of the constraint Jacobian times an nv-vector / column i times an nefc-vector
     auto jrow_dot = [&](int r, const float* x) {
+      if (has_eq && r >= nce) {
+        const float* jr = Je + (r - nce) * ldje;
+        float s = 0.f;
+        for (int k = 0; k < nv; ++k) s += jr[k] * x[k];
+        return s;
+      }
       if (r < nlim) { const int da = TI(jnt_dofadr)[TI(lim_jntid)[r]]; return lim_sign(dlim[da]) * x[da]; }
       float s = 0.f;
       if (spJ) {
@@ -1564,7 +1648,7 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerBlock) env_kernel(ModelView m
       DOT_UNROLL for (int k = 0; k < nv; ++k) s += jr[k] * x[k];
       return s;
     };
-    auto jcol_dot = [&](int i, const float* f) {
+    auto jcol_dot_ineq = [&](int i, const float* f) {
       float s = 0.f;
       if (nlim > 0) { const int dl = dlim[i]; s = lim_sign(dl) * f[lim_row(dl)]; }
       if (spJ) {
@@ -1580,6 +1664,11 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerBlock) env_kernel(ModelView m
       }
       const int nc4 = 4 * ncon;
       DOT_UNROLL for (int r = 0; r < nc4; ++r) s += J[r * ldj + i] * f[nlim + r];
+      return s;
+    };
+    auto jcol_dot = [&](int i, const float* f) {
+      float s = jcol_dot_ineq(i, f);
+      if (has_eq) for (int e = 0; e < neq; ++e) s += Je[e * ldje + i] * f[nce + e];
       return s;
     };
     auto mrow_dot = [&](int i, const float* x) {
@@ -1602,6 +1691,21 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerBlock) env_kernel(ModelView m
     };
     auto row_params = [&](int r, float s) {
       const float pos = jv[r], iw = jaref[r];
+      if (has_eq && r >= nce) {
+        // an equality row: its element's solref / solimp; the impedance of the norm of the element's residual over its rows (MuJoCo)
+        const int* ri = eq_rec(r - nce);
+        const float* rf = reinterpret_cast<const float*>(ri);
+        const int r0 = nce + ri[3], dim = ri[0] == EQ_CONNECT ? 3 : 1;
+        float nn = 0.f;
+        for (int k = 0; k < dim; ++k) nn += jv[r0 + k] * jv[r0 + k];
+        float k, b;
+        kb_params(rf + 15, rf + 17, h, k, b);
+        const float imp = impedance(rf + 17, sqrtf(nn));
+        const float R = fmaxf(iw * (1.f - imp) / imp, MJ_MINVAL);
+        eD[r] = 1.f / R;
+        earef[r] = -b * s - k * imp * pos;
+        return;
+      }
       const bool act = iw > 0.f;  // inactive rows are inert: J = 0, aref = 0, D = 0
       const bool lim = r < nlim;
       if (cp) {  // the row's own solref / solimp: its limit's or its contact slot's
@@ -1642,11 +1746,12 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerBlock) env_kernel(ModelView m
           // (limit rows and contact rows in loops of their own: 16 lanes on 16 dense rows at a time, not on a mixture)
           FOR_G(r, nlim) jaref[r] = jrow_dot(r, qacc) - earef[r];
           FOR_G(rc, 4 * ncon) jaref[nlim + rc] = jrow_dot(nlim + rc, qacc) - earef[nlim + rc];
+          if (has_eq) FOR_G(e, neq) jaref[nce + e] = jrow_dot(nce + e, qacc) - earef[nce + e];
         }
         SYNC();
         float gs = 0.f, cs = 0.f;
         FOR_G(i, nv) gs += (Ma[i] - qfs[i]) * (qacc[i] - qas[i]);
-        FOR_G(r, nefc) { const float x = jaref[r]; if (x < 0.f) cs += eD[r] * x * x; }
+        FOR_G(r, nefc) { const float x = jaref[r]; if (x < 0.f || (has_eq && r >= nce)) cs += eD[r] * x * x; }  // (equality rows: always active)
         gs = 0.5f * group16_sum(gs);
         cs = 0.5f * group16_sum(cs) + gs;
         if (take) { gs_out = gs; cs_out = cs; }
@@ -1657,7 +1762,7 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerBlock) env_kernel(ModelView m
       ctx_eval(warm, true, gauss_w, cost_w);
       // fixed-size kernel: the warm-start context (this lane's entries of Ma and Jaref) is parked in registers while the smooth
       // start is evaluated, and put back if it wins - the run-time-sized kernel evaluates it a second time instead
-      constexpr int kNvR = kDims ? (kSD.nv + kGroupLanes - 1) / kGroupLanes : 1, kEfR = kDims && kSD.nlimit + 4 * kSD.ncon > 0 ? (kSD.nlimit + 4 * kSD.ncon + kGroupLanes - 1) / kGroupLanes : 1;  // (a model without constraint rows never gets here)
+      constexpr int kNvR = kDims ? (kSD.nv + kGroupLanes - 1) / kGroupLanes : 1, kEfR = kDims && kNefc > 0 ? (kNefc + kGroupLanes - 1) / kGroupLanes : 1;  // (a model without constraint rows never gets here)
       float keep_ma[kNvR], keep_ja[kEfR];
       if (kDims) {
         _Pragma("unroll") for (int j = 0; j < kNvR; ++j) { const int i = g + kGroupLanes * j; keep_ma[j] = i < nv ? Ma[i] : 0.f; }
@@ -1677,7 +1782,7 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerBlock) env_kernel(ModelView m
       }
       prev_cost = INFINITY;  // MJX Context.create: cost starts at inf, so the first improvement is inf
       // update_constraint + update_gradient at the starting point
-      FOR_G(r, nefc) { const float x = jaref[r]; force[r] = x < 0.f ? -eD[r] * x : 0.f; }
+      FOR_G(r, nefc) { const float x = jaref[r]; force[r] = x < 0.f || (has_eq && r >= nce) ? -eD[r] * x : 0.f; }
       SYNC();
       FOR_G(i, nv) { const float s = jcol_dot(i, force); qfc[i] = s; grad[i] = Ma[i] - qfs[i] - s; }
       SYNC();
@@ -1698,6 +1803,7 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerBlock) env_kernel(ModelView m
         FOR_G(i, nv) mvv[i] = mrow_dot(i, search);
         FOR_G(r, nlim) jv[r] = jrow_dot(r, search);
         FOR_G(rc, 4 * ncon) jv[nlim + rc] = jrow_dot(nlim + rc, search);
+        if (has_eq) FOR_G(e, neq) jv[nce + e] = jrow_dot(nce + e, search);
         FOR_G(i, nv) { sn += search[i] * search[i]; sMa += search[i] * Ma[i]; sq += search[i] * qfs[i]; }
         SYNC();
         if (it == 0) PT(24);
@@ -1705,7 +1811,17 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerBlock) env_kernel(ModelView m
         FOR_G(i, nv) smv += search[i] * mvv[i];
         sn = group16_sum(sn); sMa = group16_sum(sMa); sq = group16_sum(sq); smv = group16_sum(smv);
         const float gtol = mv.tolerance * mv.ls_tolerance * sqrtf(sn) * scale;
-        const float qg0 = gauss, qg1 = sMa - sq, qg2 = 0.5f * smv;
+        // the equality rows are active at every step length: their quadratic joins the Gauss term once per line search, and the trial
+        // points below sum the inequality rows (0 .. nce - 1) only
+        float qe0 = 0.f, qe1 = 0.f, qe2 = 0.f;
+        if (has_eq) {
+          FOR_G(e, neq) {
+            const float ja = jaref[nce + e], v = jv[nce + e], d = eD[nce + e];
+            qe0 += 0.5f * ja * ja * d; qe1 += v * ja * d; qe2 += 0.5f * v * v * d;
+          }
+          qe0 = group16_sum(qe0); qe1 = group16_sum(qe1); qe2 = group16_sum(qe2);
+        }
+        const float qg0 = has_eq ? gauss + qe0 : gauss, qg1 = has_eq ? (sMa - sq) + qe1 : sMa - sq, qg2 = has_eq ? 0.5f * smv + qe2 : 0.5f * smv;
         // three trial steps at once: sums of the active rows' quadratics
         // A lane's rows (g, g + 16, ...) do not change during the line search.  With compile-time dims their quadratics live in
         // registers for the whole search (kRows of them per lane); the run-time-sized kernel re-reads them from LDS per trial.
@@ -1714,7 +1830,7 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerBlock) env_kernel(ModelView m
         if (kDims) {
           _Pragma("unroll") for (int j = 0; j < kRows; ++j) {
             const int r = g + kGroupLanes * j;
-            const bool in = r < nefc;
+            const bool in = r < nce;
             const float ja = in ? jaref[in ? r : 0] : 0.f, v = in ? jv[in ? r : 0] : 0.f, d = in ? eD[in ? r : 0] : 0.f;
             rja[j] = ja; rv[j] = v;
             rc0[j] = 0.5f * ja * ja * d; rc1[j] = v * ja * d; rc2[j] = 0.5f * v * v * d;  // a row past nefc never tests active: 0 + a 0 < 0 is false
@@ -1730,7 +1846,7 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerBlock) env_kernel(ModelView m
               if (ja + a2 * v < 0.f) { q[6] += c0; q[7] += c1; q[8] += c2; }
             }
           } else {
-            FOR_G(r, nefc) {
+            FOR_G(r, nce) {
               const float ja = jaref[r], v = jv[r], d = eD[r];
               const float c0 = 0.5f * ja * ja * d, c1 = v * ja * d, c2 = 0.5f * v * v * d;
               if (ja + a0 * v < 0.f) { q[0] += c0; q[1] += c1; q[2] += c2; }
@@ -1751,7 +1867,7 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerBlock) env_kernel(ModelView m
               if (rja[j] + a0 * rv[j] < 0.f) { q0 += rc0[j]; q1 += rc1[j]; q2 += rc2[j]; }
             }
           } else {
-            FOR_G(r, nefc) {
+            FOR_G(r, nce) {
               const float ja = jaref[r], v = jv[r], d = eD[r];
               if (ja + a0 * v < 0.f) { q0 += 0.5f * ja * ja * d; q1 += v * ja * d; q2 += 0.5f * v * v * d; }
             }
@@ -1797,11 +1913,11 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerBlock) env_kernel(ModelView m
         if (it == 0) PT(28);
         // ---------------- update_constraint, update_gradient, Polak-Ribiere ----------------
         FOR_G(i, nv) { t1[i] = Mgrad[i]; }  // previous Mgrad (previous grad is re-read below before being overwritten)
-        FOR_G(r, nefc) { const float x = jaref[r]; force[r] = x < 0.f ? -eD[r] * x : 0.f; }
+        FOR_G(r, nefc) { const float x = jaref[r]; force[r] = x < 0.f || (has_eq && r >= nce) ? -eD[r] * x : 0.f; }
         SYNC();
         float gs = 0.f, cs = 0.f, pgm = 0.f;
         FOR_G(i, nv) gs += (Ma[i] - qfs[i]) * (qacc[i] - qas[i]);
-        FOR_G(r, nefc) { const float x = jaref[r]; if (x < 0.f) cs += eD[r] * x * x; }
+        FOR_G(r, nefc) { const float x = jaref[r]; if (x < 0.f || (has_eq && r >= nce)) cs += eD[r] * x * x; }  // (equality rows: always active)
         FOR_G(i, nv) pgm += grad[i] * Mgrad[i];
         gs = 0.5f * group16_sum(gs);
         cs = 0.5f * group16_sum(cs) + gs;
@@ -1833,12 +1949,14 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerBlock) env_kernel(ModelView m
       if (pr.qM) FOR_G(i, nv) for (int k = 0; k < nv; ++k) pr.qM[((size_t)env * nv + i) * nv + k] = Mget(i, k);
       if (pr.qacc_smooth) FOR_G(i, nv) pr.qacc_smooth[(size_t)env * nv + i] = qas[i];
       if (pr.qacc) FOR_G(i, nv) pr.qacc[(size_t)env * nv + i] = qacc[i];
+      // (rows in MJX's order: equality rows first, then limits and contacts; o = the row's place in that order)
+      auto o_of = [&](int r) { return r >= nce ? r - nce : r + neq; };
       if (pr.efc_J) FOR_G(r, nefc) for (int k = 0; k < nv; ++k)
-        pr.efc_J[((size_t)env * nefc + r) * nv + k] = r >= nlim ? (spJ ? (((jmask[(r - nlim) >> 2] >> k) & 1ull) ? reinterpret_cast<const float*>(Jc + ((r - nlim) >> 2) * nv + k)[(r - nlim) & 3] : 0.f)
+        pr.efc_J[((size_t)env * nefc + o_of(r)) * nv + k] = r >= nce ? Je[(r - nce) * ldje + k] : r >= nlim ? (spJ ? (((jmask[(r - nlim) >> 2] >> k) & 1ull) ? reinterpret_cast<const float*>(Jc + ((r - nlim) >> 2) * nv + k)[(r - nlim) & 3] : 0.f)
                                                                         : J[(r - nlim) * ldj + k])
                                                             : (k == TI(jnt_dofadr)[TI(lim_jntid)[r]] ? lim_sign(dlim[k]) : 0.f);
-      if (pr.efc_D) FOR_G(r, nefc) pr.efc_D[(size_t)env * nefc + r] = eD[r];
-      if (pr.efc_aref) FOR_G(r, nefc) pr.efc_aref[(size_t)env * nefc + r] = earef[r];
+      if (pr.efc_D) FOR_G(r, nefc) pr.efc_D[(size_t)env * nefc + o_of(r)] = eD[r];
+      if (pr.efc_aref) FOR_G(r, nefc) pr.efc_aref[(size_t)env * nefc + o_of(r)] = earef[r];
       if (pr.subtree_com1 && g == 0) pr.subtree_com1[env] = new_comx;
       if (pr.solver_niter && g == 0) pr.solver_niter[env] = niter;
     }
@@ -2022,7 +2140,7 @@ static int find_spec(const BlobDims& d) {
     const BlobDims& s = kSpecs[i].d;
     if (s.nq == d.nq && s.nv == d.nv && s.nu == d.nu && s.nbody == d.nbody && s.njnt == d.njnt && s.ncon == d.ncon && s.nlimit == d.nlimit &&
         s.npair == d.npair && s.nlevel == d.nlevel && s.nroot == d.nroot && s.ncvx == d.ncvx && s.ncvxvert == d.ncvxvert && s.hull == d.hull && s.ncyl == d.ncyl &&
-        s.cparam == d.cparam)
+        s.cparam == d.cparam && s.neq == d.neq)
       return i;
   }
   return -1;
@@ -2073,7 +2191,7 @@ static int32_t finalize_layout(mppo_model* m) {
   auto lds_for = [&](bool li_regs) {
     const int forced = env_spill_override();
     return make_phys_lds(v.nq, v.nv, v.nu, v.nbody, v.njnt, v.ncon, v.nefc, v.nroot, v.ncvx, li_regs,
-                         forced >= 0 ? forced : spill_for(v.nq, v.nv, v.nu, v.nbody, v.njnt, v.ncon, v.nefc, v.nroot, v.ncvx, li_regs, m->canon_words));
+                         forced >= 0 ? forced : spill_for(v.nq, v.nv, v.nu, v.nbody, v.njnt, v.ncon, v.nefc, v.nroot, v.ncvx, li_regs, m->canon_words, v.neq), v.neq);
   };
   const bool fixed = m->spec >= 0 || m->jit;
   m->lds = lds_for(fixed && v.nv <= (m->jit ? m->jit_regchol : kRegCholMaxNv));
@@ -2201,7 +2319,8 @@ extern "C" int32_t mppo_model_open(const void* host_blob, size_t nbytes, const v
   if (w[1] != kBlobVersion) return fail(MPPO_EMODEL, "unsupported model blob version %u", w[1]);
   const size_t total = w[2], hull_words = w[35];  // table part + hull section (+ the contact-parameter section: below, once the dims are known)
   if (wi[37] != 0 && wi[37] != 1) return fail(MPPO_EMODEL, "model blob: header word 37 (per-row contact parameters) is %d, not 0 or 1", wi[37]);
-  if ((total + hull_words) * 4 > nbytes || (wi[37] == 0 && (total + hull_words) * 4 != nbytes))
+  if (wi[38] < 0 || wi[38] > kMaxEqRows) return fail(MPPO_EMODEL, "model blob: header word 38 (equality rows) is %d, not in [0, %d]", wi[38], kMaxEqRows);
+  if ((total + hull_words) * 4 > nbytes || (wi[37] == 0 && wi[38] == 0 && (total + hull_words) * 4 != nbytes))
     return fail(MPPO_EMODEL, "model blob size mismatch: header says %zu + %zu words, got %zu bytes", total, hull_words, nbytes);
   if (wi[32] != BLOB_ARRAY_COUNT) return fail(MPPO_EMODEL, "model blob has %d arrays, engine expects %d", wi[32], (int)BLOB_ARRAY_COUNT);
   mppo_model* m = new mppo_model();
@@ -2213,10 +2332,22 @@ extern "C" int32_t mppo_model_open(const void* host_blob, size_t nbytes, const v
   // is computed (tests/test_blob_fuzz.py under UBSan: a dimension of INT_MAX overflowed `4 * ncon` here)
   for (int d : {v.nq, v.nv, v.nu, v.nbody, v.njnt, v.ncon, v.nlimit, v.iterations, v.ls_iterations, v.nlevel, v.nroot, v.npair, v.ncvx, v.ncvxvert, wi[36]})
     if (d < 0 || d > (1 << 16)) { delete m; return fail(MPPO_EMODEL, "model blob: header dimension %d out of range", d); }
-  v.nefc = v.nlimit + 4 * v.ncon;
+  v.neq = wi[38];
+  v.nefc = v.neq + v.nlimit + 4 * v.ncon;
   v.cparam = wi[37];
   const CParamView cpv = cparam_view(v.ncon, v.nlimit, v.ncvx);
-  if (v.cparam && (total + hull_words + (size_t)cpv.words) * 4 != nbytes)
+  // the equality section behind it: its element count is its first word (read only once the words before it are known to exist)
+  const size_t eq_at = total + hull_words + (v.cparam ? (size_t)cpv.words : 0);
+  int eq_nel = 0;
+  if (v.neq > 0) {
+    if ((eq_at + 4) * 4 > nbytes) { delete m; return fail(MPPO_EMODEL, "model blob size mismatch: no room for the equality section"); }
+    eq_nel = wi[eq_at];
+    if (eq_nel < 1 || eq_nel > v.neq) { delete m; return fail(MPPO_EMODEL, "model blob: equality section holds %d elements for %d rows", eq_nel, v.neq); }
+    const EqView ev = eq_view(v.neq, eq_nel);
+    if ((eq_at + (size_t)ev.words) * 4 != nbytes)
+      { delete m; return fail(MPPO_EMODEL, "model blob size mismatch: header says %zu + %d words (equality section), got %zu bytes", eq_at, ev.words, nbytes); }
+  }
+  if (v.neq == 0 && v.cparam && (total + hull_words + (size_t)cpv.words) * 4 != nbytes)
     return fail(MPPO_EMODEL, "model blob size mismatch: header says %zu + %zu + %d words (contact-parameter section), got %zu bytes", total, hull_words, cpv.words, nbytes);
   v.timestep = wf[16]; v.tolerance = wf[17]; v.ls_tolerance = wf[18]; v.impratio = wf[19]; v.plane_z = wf[20]; v.meaninertia = wf[21];
   auto bad = [&](const char* what) { delete m; return fail(MPPO_EMODEL, "model blob: %s", what); };
@@ -2226,7 +2357,7 @@ extern "C" int32_t mppo_model_open(const void* host_blob, size_t nbytes, const v
     return bad("dimension out of the supported range (nbody<=128, nv<=64)");
   if (!(v.timestep > 0.f) || !(v.meaninertia > 0.f) || !(v.impratio > 0.f)) return bad("non-positive timestep / meaninertia / impratio");
   const int32_t* dir = wi + kBlobHeaderWords;
-  BlobDims bd{v.nq, v.nv, v.nu, v.nbody, v.njnt, v.ncon, v.nlimit, v.npair, v.nlevel, v.nroot, v.ncvx, v.ncvxvert, 0, 0, 0};
+  BlobDims bd{v.nq, v.nv, v.nu, v.nbody, v.njnt, v.ncon, v.nlimit, v.npair, v.nlevel, v.nroot, v.ncvx, v.ncvxvert, 0, 0, 0, 0};
   const BlobOffsets canon = blob_offsets(bd);
   const size_t dir_end = kBlobHeaderWords + 2 * (size_t)BLOB_ARRAY_COUNT;
   if (dir_end > total) return bad("directory past the end");
@@ -2366,7 +2497,40 @@ extern "C" int32_t mppo_model_open(const void* host_blob, size_t nbytes, const v
   v.obs_dim = v.nq + 2 * v.nv + (v.include_c ? 16 * (v.nbody - 1) : 0);  // env.py:246-259
   v.obs_pad = (v.obs_dim + 3) & ~3;
   v.rec_dim = v.obs_pad + ((v.nv + 2 + 3) & ~3);
-  bd.hull = v.hull_words > 0 ? 1 : 0; bd.ncyl = v.ncyl; bd.cparam = v.cparam;
+  if (v.neq > 0) {
+    // the equality section: every element's kind, bodies / joints and rows, and finite parameters in MuJoCo's ranges - the kernel follows
+    // these ids into the tables without another check
+    const int32_t* es = wi + eq_at;
+    const float* ef = wf + eq_at;
+    const EqView ev = eq_view(v.neq, eq_nel);
+    auto fin = [](float x) { return x == x && x - x == 0.f; };
+    const int32_t* jtype = HI(BI_jnt_type);
+    int next_row = 0;
+    for (int e = 0; e < eq_nel; ++e) {
+      const int32_t* ri = es + ev.rec + kEqRecordWords * e;
+      const float* rf = ef + ev.rec + kEqRecordWords * e;
+      const int dim = ri[0] == EQ_CONNECT ? 3 : ri[0] == EQ_JOINT ? 1 : 0;
+      if (dim == 0) return bad("equality section: an element that is neither connect nor joint");
+      if (ri[3] != next_row || ri[3] + dim > v.neq) return bad("equality section: an element's rows are not the next ones");
+      for (int k = 0; k < dim; ++k) if (es[ev.row + ri[3] + k] != e) return bad("equality section: a row that is not its element's");
+      next_row += dim;
+      if (ri[0] == EQ_CONNECT) {
+        if (ri[1] < 1 || ri[1] >= v.nbody || ri[2] < 0 || ri[2] >= v.nbody || ri[1] == ri[2]) return bad("equality section: a connect's bodies out of range");
+      } else {
+        if (ri[1] < 0 || ri[1] >= v.njnt || ri[2] < -1 || ri[2] >= v.njnt || ri[1] == ri[2]) return bad("equality section: a joint equality's joints out of range");
+        if (jtype[ri[1]] == JNT_FREE || (ri[2] >= 0 && jtype[ri[2]] == JNT_FREE)) return bad("equality section: a joint equality on a free joint");
+      }
+      for (int k = 4; k < 23; ++k) if (!fin(rf[k])) return bad("equality section: a value is not finite");
+      const float* sr = rf + 15;
+      const float* si = rf + 17;
+      if ((sr[0] <= 0.f) != (sr[1] <= 0.f) || !(si[0] >= MJ_MINIMP && si[0] <= MJ_MAXIMP && si[1] >= MJ_MINIMP && si[1] <= MJ_MAXIMP && si[2] > 0.f &&
+                                                si[3] >= MJ_MINIMP && si[3] <= MJ_MAXIMP && si[4] >= 1.f))
+        return bad("equality section: solref / solimp outside MuJoCo's ranges");
+      if (!(rf[22] > 0.f)) return bad("equality section: invweight must be positive");
+    }
+    if (next_row != v.neq) return bad("equality section: the elements' rows do not add up to header word 38");
+  }
+  bd.hull = v.hull_words > 0 ? 1 : 0; bd.ncyl = v.ncyl; bd.cparam = v.cparam; bd.neq = v.neq;
   m->spec = find_spec(bd);
   m->canon_words = canon.words;
   if (int32_t rc = mppo::finalize_layout(m); rc != MPPO_OK) { delete m; return rc; }
@@ -2418,9 +2582,9 @@ extern "C" int32_t mppo_model_attach_kernel(mppo_model_t* m, const void* image, 
     const char* e = getenv("MPPO_ENV_GENERIC");
     if ((e && e[0] == '1') || env_spill_override() >= 0) return MPPO_OK;  // (the switches that force the run-time-sized kernel)
   }
-  // the kernels' names spell the dimensions they were compiled for: StaticModel<nq, nv, nu, nbody, njnt, ncon, nlimit, npair, nlevel, nroot, ncvx, ncvxvert, hull, ncyl, cparam>, MODE
+  // the kernels' names spell the dimensions they were compiled for: StaticModel<nq, nv, nu, nbody, njnt, ncon, nlimit, npair, nlevel, nroot, ncvx, ncvxvert, hull, ncyl, neq, cparam>, MODE
   const ModelView& v = m->mv;
-  const int dims[15] = {v.nq, v.nv, v.nu, v.nbody, v.njnt, v.ncon, v.nlimit, v.npair, v.nlevel, v.nroot, v.ncvx, v.ncvxvert, v.hull_words > 0 ? 1 : 0, v.ncyl, v.cparam};
+  const int dims[16] = {v.nq, v.nv, v.nu, v.nbody, v.njnt, v.ncon, v.nlimit, v.npair, v.nlevel, v.nroot, v.ncvx, v.ncvxvert, v.hull_words > 0 ? 1 : 0, v.ncyl, v.neq, v.cparam};
   char want[256];
   int o = snprintf(want, sizeof want, "StaticModelI");
   for (int d : dims) o += snprintf(want + o, sizeof want - o, "Li%dE", d);

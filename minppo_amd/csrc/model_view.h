@@ -31,7 +31,7 @@ enum BlobF32 {
 };
 
 constexpr uint32_t kBlobMagic = 0x4D50504F;
-constexpr uint32_t kBlobVersion = 8;
+constexpr uint32_t kBlobVersion = 9;
 constexpr int kBlobHeaderWords = 64;
 constexpr int JNT_FREE = 0, JNT_HINGE = 2, JNT_SLIDE = 3;
 constexpr float MJ_MINVAL = 1e-15f, MJ_MINIMP = 0.0001f, MJ_MAXIMP = 0.9999f;
@@ -53,6 +53,7 @@ struct ModelView {
   int ncyl;          // cylinders against the plane: three contact slots each (con_cvx = -2, -3, -4); run-time-sized kernel only
   int hull_words;    // the hull section behind it (0: the model has no convex geom in a geom-geom pair); read from global memory
   int cparam;        // 1: contact / limit parameters per row - the contact-parameter section behind the hull section (CParamView); 0: model-uniform
+  int neq;           // equality constraint rows (header word 38; <= kMaxEqRows): the equality section behind the contact-parameter section (EqView)
   int o[BLOB_ARRAY_COUNT];
 };
 
@@ -60,7 +61,8 @@ struct ModelView {
 // array padded to 4 words, first array right after the directory).  mppo_model_open refuses a blob laid out differently, so a
 // kernel compiled for fixed dims may take the offsets as constants.
 struct BlobDims { int nq, nv, nu, nbody, njnt, ncon, nlimit, npair, nlevel, nroot, ncvx, ncvxvert;
-                  int hull, ncyl, cparam; };  // (hull: 1 if the model has a hull section; ncyl: its cylinders; cparam: per-row contact parameters - they select code, not table sizes)
+                  int hull, ncyl, neq, cparam; };  // (hull: 1 if the model has a hull section; ncyl: its cylinders; neq: equality rows; cparam: per-row contact
+                                                   // parameters - they select code and size the LDS rows, not the table part)
 struct BlobOffsets { int o[BLOB_ARRAY_COUNT]; int words; };
 __host__ __device__ constexpr inline int blob_array_len(const BlobDims& d, int k) {
   switch (k) {
@@ -148,6 +150,21 @@ __host__ __device__ constexpr inline CParamView cparam_view(int ncon, int nlimit
   return c;
 }
 
+// The equality section (model.py _eq_section, blob version 9; header word 38 = neq, the equality constraint rows): it sits behind the
+// contact-parameter section (or the hull section, or the table part) and is read from global memory.  Four words (nel, 0, 0, 0), the
+// element of each row (neq ints, padded to 4), then one record of kEqRecordWords per element:
+//   0 type (EQ_CONNECT | EQ_JOINT), 1 obj1, 2 obj2 (connect: bodies, obj2 0 = the world; joint: joints, obj2 -1 = none), 3 the element's first row,
+//   4-9 anchor in body1's frame, anchor in body2's frame (f32), 10-14 polycoef, 15-16 solref, 17-21 solimp, 22 invweight, 23-31 zero.
+// A connect takes three rows (the world-frame residual p1 - p2), a joint equality one.  The equality rows come first in the constraint
+// (efc_* of the probe), then the joint limits, then the contacts (MJX's order); they are always active.
+constexpr int kMaxEqRows = 32, kEqRecordWords = 32, EQ_CONNECT = 0, EQ_JOINT = 1;
+struct EqView { int nel, row, rec, words; };
+__host__ __device__ constexpr inline EqView eq_view(int neq, int nel) {
+  EqView e{};
+  e.nel = nel; e.row = 4; e.rec = 4 + ((neq + 3) & ~3); e.words = e.rec + kEqRecordWords * nel;
+  return e;
+}
+
 // Per-environment LDS layout (offsets in floats).  What is alive from one end of a step to the other sits in front; region "A" is
 // time-shared by four lifetimes that follow one another (each separated from the next by a synchronisation point of the kernel):
 //   A1 kinematics: poses (xpos, xquat, xipos), joint anchors / axes (the rotation matrices of bodies and inertial frames are recomputed
@@ -184,12 +201,18 @@ struct PhysLds {
   // (nvq = ceil(nv / 4); lanes of an environment read consecutive 16-byte words.)  jmask: per contact slot, in LDS, the dofs its rows
   // touch (the ancestors of its one or two bodies) if the contact is active this step, else 0 - writers and readers skip the rest.
   int spill, gJc, gJq, gM, gwords, jmask;
+  // equality rows (neq > 0): their Jacobian, dense [neq][ldj] after the contact rows in region A4, or [neq][nv] in the record in global
+  // memory (gJe) when the contact Jacobian is there too; eqpos: per row, the world points p1, p2 of its connect (written while the poses of
+  // region A1 are alive, read by make_constraint; region B's first lifetime)
+  int Je, gJe, eqpos;
 };
 constexpr int kSpillJ = 1, kSpillM = 2;
 
 __host__ __device__ constexpr inline int imax_(int a, int b) { return a > b ? a : b; }
 
-__host__ __device__ constexpr inline PhysLds make_phys_lds(int nq, int nv, int nu, int nbody, int njnt, int ncon, int nefc, int nroot, int ncvx = 0, bool li_regs = false, int spill = 0) {
+// (nefc: every constraint row, the neq equality rows included)
+__host__ __device__ constexpr inline PhysLds make_phys_lds(int nq, int nv, int nu, int nbody, int njnt, int ncon, int nefc, int nroot, int ncvx = 0, bool li_regs = false, int spill = 0,
+                                                           int neq = 0) {
   PhysLds p{};
   int o = 0;
   auto take = [&](int n) { int r = o; o += (n + 3) & ~3; return r; };
@@ -215,6 +238,7 @@ __host__ __device__ constexpr inline PhysLds make_phys_lds(int nq, int nv, int n
   // born after that (qacc stays until the end of the step: it is the next step's warm start)
   const int B = o;
   p.cdof = take(6 * nv); p.conpos = take(3 * (ncon > 0 ? ncon : 1)); p.condist = take(ncon > 0 ? ncon : 1); p.confr = take(6 * (ncon > 0 ? ncon : 1));
+  p.eqpos = take(6 * neq);
   const int B1 = o;
   o = B; p.qacc = take(nv); p.Ma = take(nv); p.grad = take(nv); p.Mgrad = take(nv); p.search = take(nv); p.mv = take(nv); p.qfc = take(nv);
   o = imax_(o, B1);
@@ -225,7 +249,8 @@ __host__ __device__ constexpr inline PhysLds make_phys_lds(int nq, int nv, int n
   o = p.A; p.C = take(li_regs ? imax_(nv * imax_(p.ldm, p.ldc), 2 * ntri) : ntri); end = imax_(end, o);
   o = p.A; p.cdofdot = take(6 * nv); p.cfrc = take(6 * nbody); p.cvel = take(6 * nbody); end = imax_(end, o);
   p.ldj = nv + 1;
-  o = p.A; p.J = (p.spill & kSpillJ) ? o : take((ncon > 0 ? 4 * ncon : 1) * p.ldj); end = imax_(end, o);
+  o = p.A; p.J = (p.spill & kSpillJ) ? o : take((ncon > 0 ? 4 * ncon : 1) * p.ldj);
+  p.Je = (p.spill & kSpillJ) ? o : take(neq * p.ldj); end = imax_(end, o);
   {
     const int nvq = (nv + 3) / 4;
     int go = 0;
@@ -233,6 +258,7 @@ __host__ __device__ constexpr inline PhysLds make_phys_lds(int nq, int nv, int n
     p.gJc = (p.spill & kSpillJ) ? gtake(ncon * nv * 4) : -1;
     p.gJq = (p.spill & kSpillJ) ? gtake(nvq * 4 * ncon * 4) : -1;
     p.gM = (p.spill & kSpillM) ? gtake(nvq * nv * 4) : -1;
+    p.gJe = (p.spill & kSpillJ) && neq > 0 ? gtake(neq * nv) : -1;
     p.gwords = go;
   }
   // an environment's arrays start 16 banks after its neighbour's (total = 16 mod 64 words): the four environments of a wave read the
@@ -255,12 +281,12 @@ __host__ __device__ constexpr inline int waves_per_cu(long long blob_words, long
   }
   return best;
 }
-__host__ __device__ constexpr inline int spill_for(int nq, int nv, int nu, int nbody, int njnt, int ncon, int nefc, int nroot, int ncvx, bool li_regs, int blob_words) {
+__host__ __device__ constexpr inline int spill_for(int nq, int nv, int nu, int nbody, int njnt, int ncon, int nefc, int nroot, int ncvx, bool li_regs, int blob_words, int neq = 0) {
   int best = 0, best_w = -1;
   const int opts[3] = {0, kSpillJ, kSpillJ | kSpillM};
   for (int t = 0; t < 3; ++t) {
     const int s = opts[t];
-    const int w = waves_per_cu(blob_words, make_phys_lds(nq, nv, nu, nbody, njnt, ncon, nefc, nroot, ncvx, li_regs, s).total, 4);
+    const int w = waves_per_cu(blob_words, make_phys_lds(nq, nv, nu, nbody, njnt, ncon, nefc, nroot, ncvx, li_regs, s, neq).total, 4);
     const int wc = w > 4 ? 4 : w;
     if (wc > best_w) { best_w = wc; best = s; }
   }

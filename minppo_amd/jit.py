@@ -61,7 +61,7 @@ def sources_key() -> str:
 
 def dims_of(cm) -> Tuple[int, ...]:
     t = cm.t
-    return tuple((1 if int(t["nhull"]) > 0 else 0) if k == "hull" else int(t[k]) for k in _build._SPEC_KEYS)
+    return _build.spec_dims_of(t)
 
 
 def kernel_symbols(image: bytes) -> List[str]:

@@ -39,6 +39,12 @@ Subset
             mix = solmix1 / (solmix1 + solmix2), solref mixed in standard form / elementwise minimum in direct form, solimp mixed, margin and gap
             the larger (includemargin = margin - gap); a joint limit takes its joint's values.  Refused: priority, condim 4 / 6, a margin on a pair with
             a box / mesh hull of another body, margin / gap / own solref on an explicit <pair>
+  <equality>: <connect body1 body2 anchor/> (body form; body2 defaults to the world; anchor in body1's frame, body2's anchor computed so that
+            the constraint holds at qpos0) and <joint joint1 joint2 polycoef/> (hinge / slide joints; no joint2: the joint is locked at
+            qpos0 + polycoef[0]), each with solref / solimp (MuJoCo's defaults), `class` and <default><equality>; active="false" compiles the
+            element out (one log line: nothing switches it on later).  Refused: weld / tendon / flex equalities, site-based connect, a joint
+            equality on a free joint, unknown names, more than model.MAX_EQ_ROWS rows.  Deviation from MuJoCo: an <equality> section that holds
+            no connect / joint element is an error (MuJoCo accepts it)
 Contacts: geom-vs-ground-plane, and the geom pairs between bodies that MuJoCo would test (contype / conaffinity masks, same-body and
 parent-child pairs filtered, <exclude>d body pairs dropped): sphere / capsule among themselves, and a sphere or capsule against a box
 or a mesh hull of another body (MJX sphere_convex / capsule_convex); a box or mesh that the masks pair with another box or mesh is an
@@ -55,13 +61,13 @@ from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from minppo_amd.model import (GEOM_BOX, GEOM_CAPSULE, GEOM_CYLINDER, GEOM_MESH, GEOM_SPHERE, JNT_FREE, JNT_HINGE, JNT_SLIDE, MAX_CONVEX_VERTS, ActuatorSpec, BodySpec, GeomSpec, JointSpec,
-                              ModelSpec, _normalize, _qmat, _qmul, mix_contact_params)
+from minppo_amd.model import (GEOM_BOX, GEOM_CAPSULE, GEOM_CYLINDER, GEOM_MESH, GEOM_SPHERE, JNT_FREE, JNT_HINGE, JNT_SLIDE, MAX_CONVEX_VERTS, ActuatorSpec, BodySpec, EqualitySpec,
+                              GeomSpec, JointSpec, ModelSpec, _normalize, _qmat, _qmul, mix_contact_params)
 
 logger = logging.getLogger(__name__)
 
 _IGNORED_TOP = {"asset", "visual", "sensor", "keyframe", "statistic", "size", "custom", "extension"}
-_UNSUPPORTED_TOP = {"equality", "tendon", "deformable", "flexcomp", "composite"}
+_UNSUPPORTED_TOP = {"tendon", "deformable", "flexcomp", "composite"}
 _DEFAULT_DENSITY = 1000.0
 _MJ_SOLREF = (0.02, 1.0)
 _MJ_SOLIMP = (0.9, 0.95, 0.001, 0.5, 2.0)
@@ -175,7 +181,7 @@ class _Compiler:
 class _Defaults:
     """`<default>` tree: class name -> {element tag -> attributes}, children inherit from their parents."""
 
-    TAGS = ("joint", "geom", "position", "motor", "general", "velocity", "mesh")
+    TAGS = ("joint", "geom", "position", "motor", "general", "velocity", "mesh", "equality")
 
     def __init__(self, root: ET.Element):
         self.classes: Dict[str, Dict[str, Dict[str, str]]] = {"main": {t: {} for t in self.TAGS}}
@@ -198,7 +204,7 @@ class _Defaults:
                     del attrs["frictionloss"]
                 cur[ch.tag].update(attrs)
             elif ch.tag in ("material", "site", "camera", "light", "pair", "equality", "tendon"):
-                if ch.tag in ("equality", "tendon", "pair"):
+                if ch.tag in ("tendon", "pair"):
                     raise ValueError(f"<default><{ch.tag}> is outside the supported MJCF subset")
             else:
                 raise ValueError(f"<default><{ch.tag}> is outside the supported MJCF subset")
@@ -386,7 +392,7 @@ def parse_mjcf(xml: str, name: str = "mjcf", base_dir: Optional[Path] = None) ->
     for ch in root:
         if ch.tag in _UNSUPPORTED_TOP:
             raise ValueError(f"<{ch.tag}> is outside the supported MJCF subset")
-        if ch.tag not in _IGNORED_TOP | {"compiler", "option", "default", "worldbody", "actuator", "contact", "include"}:
+        if ch.tag not in _IGNORED_TOP | {"compiler", "option", "default", "worldbody", "actuator", "contact", "include", "equality"}:
             raise ValueError(f"<{ch.tag}> is outside the supported MJCF subset")
     comp_el = _merged(root, "compiler")
     comp = _Compiler(comp_el)
@@ -804,7 +810,59 @@ def parse_mjcf(xml: str, name: str = "mjcf", base_dir: Optional[Path] = None) ->
         spec_kw["contact_pairs"] = pairs
         if any(c != 3 for c in pair_condim):
             spec_kw["contact_pair_condim"] = pair_condim
+    eqs = _parse_equality(root, dfl)
+    if eqs:
+        spec_kw["equalities"] = eqs
     return ModelSpec(name=name, bodies=bodies, actuators=acts, free_root_z=free_root_z, **spec_kw)
+
+
+_EQ_ATTRS = {"connect": {"name", "class", "body1", "body2", "anchor", "active", "solref", "solimp"},
+             "joint": {"name", "class", "joint1", "joint2", "polycoef", "active", "solref", "solimp"}}
+
+
+def _parse_equality(root: ET.Element, dfl: "_Defaults") -> List[EqualitySpec]:
+    """<equality>: <connect body1 body2 anchor> (body form) and <joint joint1 joint2 polycoef>, with solref / solimp / active and default
+    classes (<default><equality>, `class`).  An element with active="false" is compiled out (nothing switches it on later).  Deviation from
+    MuJoCo: an <equality> that holds no connect / joint element is an error."""
+    out: List[EqualitySpec] = []
+    secs = root.findall("equality")
+    for sec in secs:
+        for el in sec:
+            what = f"<equality><{el.tag}{' name=' + repr(el.get('name')) if el.get('name') else ''}>"
+            if el.tag in ("weld", "tendon", "flex", "flexvert", "flexstrain"):
+                raise ValueError(f"{what}: {el.tag} equalities are outside the supported MJCF subset (connect and joint are supported)")
+            if el.tag not in _EQ_ATTRS:
+                raise ValueError(f"{what} is outside the supported MJCF subset (connect and joint are supported)")
+            a = dfl.resolve("equality", el, None)
+            for k in a:
+                if k in ("site1", "site2"):
+                    raise ValueError(f"{what}: site-based connect (site1 / site2) is not supported; give body1 / body2 and anchor")
+                if k not in _EQ_ATTRS[el.tag]:
+                    raise ValueError(f"{what}: attribute {k!r} is outside the supported MJCF subset")
+            if a.get("active", "true") == "false":
+                logger.info("%s has active=\"false\": compiled out (equality constraints cannot be switched on at run time here)", what)
+                continue
+            if a.get("active", "true") != "true":
+                raise ValueError(f"{what}: active={a['active']!r} (true or false)")
+            imp = _floats(a["solimp"]) if "solimp" in a else list(_MJ_SOLIMP)
+            kw = dict(solref=tuple(_floats(a["solref"], 2, what)) if "solref" in a else _MJ_SOLREF, solimp=tuple(imp + list(_MJ_SOLIMP[len(imp):])), name=a.get("name", ""))
+            if el.tag == "connect":
+                if "body1" not in a:
+                    raise ValueError(f"{what}: body1 is required (site-based connect is not supported)")
+                if "anchor" not in a:
+                    raise ValueError(f"{what}: anchor is required")
+                out.append(EqualitySpec("connect", a["body1"], a.get("body2", ""), anchor=tuple(_floats(a["anchor"], 3, what)), **kw))
+            else:
+                if "joint1" not in a:
+                    raise ValueError(f"{what}: joint1 is required")
+                pc = _floats(a.get("polycoef", "0 1 0 0 0"))
+                if len(pc) > 5:
+                    raise ValueError(f"{what}: polycoef has {len(pc)} values (at most 5)")
+                pc = pc + [0.0, 1.0, 0.0, 0.0, 0.0][len(pc):]
+                out.append(EqualitySpec("joint", a["joint1"], a.get("joint2", ""), polycoef=tuple(pc), **kw))
+    if secs and not out and not any(len(sec) for sec in secs):
+        raise ValueError("<equality> holds no <connect> / <joint> element")
+    return out
 
 
 def load_mjcf(path: str) -> ModelSpec:
@@ -917,5 +975,13 @@ def to_mjcf(spec: ModelSpec) -> str:
             mixed = mix_contact_params(own[g1], own[g2]) if g1 in own and g2 in own else dict(solref=spec.contact_solref, solimp=spec.contact_solimp)
             ET.SubElement(con, "pair", geom1=g1, geom2=g2, solref=_fmt(mixed["solref"]), solimp=_fmt(mixed["solimp"]),
                           **({} if mu is None else {"friction": _fmt([mu, mu, 0.005, 0.0001, 0.0001])}), **({} if cd == 3 else {"condim": str(cd)}))
+    if spec.equalities:
+        eq = ET.SubElement(root, "equality")
+        for e in spec.equalities:
+            kw = dict(solref=_fmt(e.solref), solimp=_fmt(e.solimp), **({"name": e.name} if e.name else {}))
+            if e.kind == "connect":
+                ET.SubElement(eq, "connect", body1=e.obj1, anchor=_fmt(e.anchor), **({"body2": e.obj2} if e.obj2 else {}), **kw)
+            else:
+                ET.SubElement(eq, "joint", joint1=e.obj1, polycoef=_fmt(e.polycoef), **({"joint2": e.obj2} if e.obj2 else {}), **kw)
     ET.indent(root)
     return ET.tostring(root, encoding="unicode")

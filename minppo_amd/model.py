@@ -37,10 +37,11 @@ GEOM_SPHERE, GEOM_CAPSULE, GEOM_CYLINDER, GEOM_BOX, GEOM_MESH = 2, 3, 5, 6, 7  #
 
 MJ_MINVAL = 1e-15
 MAX_CONVEX_VERTS = 64  # hull vertices of one mesh collider (the kernel scans them five times per step)
+MAX_EQ_ROWS = 32  # equality constraint rows of one model (a connect takes three, a joint equality one): the environment kernel's cap
 MAX_BODIES = 128  # subtree sets are two 64-bit words per body (one up to 64 bodies); dofs: one word, 64
 
 BLOB_MAGIC = 0x4D50504F  # "MPPO"
-BLOB_VERSION = 8  # 8: per-slot / per-limit contact parameters (header word 37, a section behind the hull section); 7: hull section carries the hulls' edge directions (convex_convex: box / mesh against box / mesh); 6: dof_actfrcrange (joint actuatorfrcrange); 2: header word include_c_vals; 3: geom-geom pairs (npair, pair_body, pair_geom) and con_axis; 4: convex (mesh) geoms against the plane; 5: hull section (sphere / capsule against box / mesh)
+BLOB_VERSION = 9  # 9: equality constraints (header word 38 = equality rows, a section behind the contact-parameter section); 8: per-slot / per-limit contact parameters (header word 37, a section behind the hull section); 7: hull section carries the hulls' edge directions (convex_convex: box / mesh against box / mesh); 6: dof_actfrcrange (joint actuatorfrcrange); 2: header word include_c_vals; 3: geom-geom pairs (npair, pair_body, pair_geom) and con_axis; 4: convex (mesh) geoms against the plane; 5: hull section (sphere / capsule against box / mesh)
 
 
 # ---------------------------------------------------------------------------
@@ -121,6 +122,23 @@ class ActuatorSpec:
 
 
 @dataclass
+class EqualitySpec:
+    """An MJCF <equality> element: `connect` (body form) or `joint` (hinge / slide joints).  MuJoCo's semantics:
+      connect: obj1 / obj2 are bodies ("" = the world); `anchor` is in obj1's frame, obj2's anchor is computed so that the constraint
+               holds at qpos0; three rows, residual p1 - p2 in the world frame.
+      joint:   obj1 / obj2 are joints ("" = none: the joint is locked at qpos0 + polycoef[0]); one row,
+               q1 - ref1 - sum_i polycoef[i] (q2 - ref2)^i with ref = qpos0."""
+    kind: str
+    obj1: str
+    obj2: str = ""
+    anchor: Sequence[float] = (0.0, 0.0, 0.0)
+    polycoef: Sequence[float] = (0.0, 1.0, 0.0, 0.0, 0.0)
+    solref: Sequence[float] = (0.02, 1.0)
+    solimp: Sequence[float] = (0.9, 0.95, 0.001, 0.5, 2.0)
+    name: str = ""
+
+
+@dataclass
 class ModelSpec:
     name: str
     bodies: List[BodySpec]
@@ -159,6 +177,7 @@ class ModelSpec:
     plane_condim: int = 3
     plane_margin: float = 0.0
     plane_gap: float = 0.0
+    equalities: List[EqualitySpec] = field(default_factory=list)  # MJCF <equality><connect> / <joint> (active ones only)
 
 
 # ---------------------------------------------------------------------------
@@ -253,8 +272,13 @@ class CompiledModel:
         return int(self.t["ncvx"])
 
     @property
+    def neq(self) -> int:
+        """equality constraint rows (three per connect, one per joint equality): the first rows of the constraint."""
+        return int(self.t.get("neq", 0))
+
+    @property
     def nefc(self) -> int:
-        return self.nlimit + 4 * self.ncon
+        return self.neq + self.nlimit + 4 * self.ncon
 
     def obs_size(self, include_c_vals: bool = True) -> int:
         """`get_obs` width (reference `minppo/env.py:245-261`)."""
@@ -900,7 +924,81 @@ def compile_model(spec: ModelSpec) -> CompiledModel:
 
     cm = CompiledModel(spec.name, t, names, joint_names, spec.meaninertia)
     _set_const(cm)
+    if spec.equalities:
+        _compile_equalities(cm, spec.equalities)
     return cm
+
+
+EQ_CONNECT, EQ_JOINT = 0, 1
+
+
+def _compile_equalities(cm: CompiledModel, eqs: Sequence[EqualitySpec]) -> None:
+    """Equality constraints -> tables (blob version 9; only for a model that has some, so that every other model keeps its tables).
+    connect: body2's anchor from the poses at qpos0 (MuJoCo's compiler); invweight body_invweight0[b1, 0] + body_invweight0[b2, 0].
+    joint: invweight dof_invweight0[dof1] (+ dof_invweight0[dof2])."""
+    t = cm.t
+    f = _forward_position0(cm)
+    etype, eobj, rowadr, anchor, poly, sref, simp, iw, rows = [], [], [], [], [], [], [], [], []
+    for e in eqs:
+        what = f"<equality><{e.kind}{' name=' + repr(e.name) if e.name else ''}>"
+        sr, si = tuple(map(float, e.solref)), _solimp5(e.solimp)
+        if len(sr) != 2 or (sr[0] > 0) != (sr[1] > 0) or not (0.0001 <= si[0] <= 0.9999 and 0.0001 <= si[1] <= 0.9999 and si[2] > 0 and 0.0001 <= si[3] <= 0.9999 and si[4] >= 1):
+            raise ValueError(f"{what}: solref {sr} / solimp {si}: solref in standard (both > 0) or direct (both <= 0) form, solimp dmin / dmax / midpoint "
+                             "in [0.0001, 0.9999], width > 0, power >= 1")
+        a6 = [0.0] * 6
+        pc = [0.0] * 5
+        if e.kind == "connect":
+            if e.obj1 not in cm.body_names[1:]:
+                raise ValueError(f"{what}: unknown body1 {e.obj1!r}")
+            if e.obj2 and e.obj2 not in cm.body_names:
+                raise ValueError(f"{what}: unknown body2 {e.obj2!r}")
+            b1, b2 = cm.body_names.index(e.obj1), cm.body_names.index(e.obj2) if e.obj2 else 0
+            if b1 == b2:
+                raise ValueError(f"{what}: body1 and body2 are the same body {e.obj1!r}")
+            a1 = np.asarray(e.anchor, np.float64).reshape(3)
+            p1 = f["xpos"][b1] + _qrot(f["xquat"][b1], a1)
+            a2 = _qmat(f["xquat"][b2]).T @ (p1 - f["xpos"][b2])  # body2's anchor: the constraint holds at qpos0
+            a6 = list(a1) + list(a2)
+            etype.append(EQ_CONNECT); eobj.append([b1, b2]); n = 3
+            iw.append(float(t["body_invweight0"][b1, 0] + t["body_invweight0"][b2, 0]))
+        elif e.kind == "joint":
+            ids = []
+            for k, jn in (("joint1", e.obj1), ("joint2", e.obj2)):
+                if not jn:
+                    ids.append(-1)
+                    continue
+                if jn not in cm.joint_names:
+                    raise ValueError(f"{what}: unknown {k} {jn!r}")
+                j = cm.joint_names.index(jn)
+                if int(t["jnt_type"][j]) not in (JNT_HINGE, JNT_SLIDE):
+                    raise ValueError(f"{what}: {k} {jn!r} is a free joint (a joint equality couples hinge / slide joints)")
+                ids.append(j)
+            if ids[0] < 0:
+                raise ValueError(f"{what}: joint1 is required")
+            if ids[0] == ids[1]:
+                raise ValueError(f"{what}: joint1 and joint2 are the same joint {e.obj1!r}")
+            pc = list(map(float, e.polycoef)) + [0.0] * 5
+            pc = pc[:5]
+            etype.append(EQ_JOINT); eobj.append(ids); n = 1
+            d1 = int(t["jnt_dofadr"][ids[0]])
+            iw.append(float(t["dof_invweight0"][d1] + (t["dof_invweight0"][int(t["jnt_dofadr"][ids[1]])] if ids[1] >= 0 else 0.0)))
+        else:
+            raise ValueError(f"<equality><{e.kind}>: only connect and joint equalities are supported")
+        rowadr.append(len(rows))
+        rows += [len(etype) - 1] * n
+        anchor.append(a6); poly.append(pc); sref.append(sr); simp.append(si)
+    if len(rows) > MAX_EQ_ROWS:
+        raise ValueError(f"<equality>: {len(rows)} equality constraint rows (a connect takes three, a joint equality one); the environment kernel holds {MAX_EQ_ROWS}")
+    t["neq"] = np.asarray(len(rows), np.int32)
+    t["eq_type"] = np.asarray(etype, np.int32)
+    t["eq_obj"] = np.asarray(eobj, np.int32).reshape(-1, 2)
+    t["eq_rowadr"] = np.asarray(rowadr, np.int32)
+    t["eq_row"] = np.asarray(rows, np.int32)
+    t["eq_anchor"] = np.asarray(anchor, np.float64).reshape(-1, 6)
+    t["eq_polycoef"] = np.asarray(poly, np.float64).reshape(-1, 5)
+    t["eq_solref"] = np.asarray(sref, np.float64).reshape(-1, 2)
+    t["eq_solimp"] = np.asarray(simp, np.float64).reshape(-1, 5)
+    t["eq_invweight"] = np.asarray(iw, np.float64)
 
 
 # ---------------------------------------------------------------------------
@@ -1054,8 +1152,9 @@ _BLOB_F32 = [
 ]
 _HDR_INT = ["nq", "nv", "nu", "nbody", "njnt", "ncon", "nlimit", "iterations", "ls_iterations", "nlevel", "nroot", "include_c_vals", "npair"]
 _HDR_F32 = ["timestep", "tolerance", "ls_tolerance", "impratio", "plane_z", "meaninertia"]
-_HDR_INT2 = ["ncvx", "ncvxvert", "hull_words", "ncyl", "cparam"]  # words 33..: dims that arrived after the first header block was full (hull_words: length of the hull section behind the table part;
-# cparam, word 37: 0 = the contact / limit parameters are model-uniform (the model-wide tables), 1 = the contact-parameter section follows the hull section)
+_HDR_INT2 = ["ncvx", "ncvxvert", "hull_words", "ncyl", "cparam", "neq"]  # words 33..: dims that arrived after the first header block was full (hull_words: length of the hull section behind the table part;
+# cparam, word 37: 0 = the contact / limit parameters are model-uniform (the model-wide tables), 1 = the contact-parameter section follows the hull section;
+# neq, word 38: equality constraint rows - if nonzero, the equality section follows the contact-parameter section)
 BLOB_HEADER_WORDS = 64  # fixed-size header; array directory follows
 
 
@@ -1070,7 +1169,8 @@ def _to_blob(cm: CompiledModel, include_c_vals: bool = True) -> bytes:
     global memory, a few lines per step): eight words (nhull, nvert, nface, nfidx, nedge, 0, 0, 0), then the arrays of
     _HULL_ARRAYS in that order, each padded to 4 words.  Behind that, if header word 37 (`cparam`) is 1, the CONTACT-PARAMETER
     section: the arrays of _CPARAM_ARRAYS in that order, each padded to 4 words, lengths following from ncon / nlimit / ncvx (read
-    from global memory by the kernel's per-row path).  The C side (csrc/model_view.h) mirrors this layout.
+    from global memory by the kernel's per-row path).  Behind that, if header word 38 (`neq`) is nonzero, the EQUALITY section
+    (_eq_section).  The C side (csrc/model_view.h) mirrors this layout.
     """
     t = cm.t
     names = _BLOB_INT + _BLOB_F32
@@ -1109,7 +1209,7 @@ def _to_blob(cm: CompiledModel, include_c_vals: bool = True) -> bytes:
     d += b"\0" * (4 * (base - BLOB_HEADER_WORDS - 2 * ndir))
     blob = bytes(hdr) + bytes(d) + bytes(payload)
     assert len(blob) == 4 * total, (len(blob), total)
-    return blob + hull + _cparam_section(t)
+    return blob + hull + _cparam_section(t) + _eq_section(t)
 
 
 _HULL_ARRAYS = [("hull_vadr", "<i4"), ("hull_fadr", "<i4"), ("hull_eadr", "<i4"), ("hull_face_adr", "<i4"), ("hull_fidx", "<i4"), ("hull_edge", "<i4"),
@@ -1127,6 +1227,29 @@ def _cparam_section(t: Dict[str, np.ndarray]) -> bytes:
     for k, dt in _CPARAM_ARRAYS:
         raw = np.ascontiguousarray(t[k]).reshape(-1).astype(dt).tobytes()
         out += raw + b"\0" * ((-len(raw)) % 16)
+    return bytes(out)
+
+
+EQ_RECORD_WORDS = 32
+
+
+def _eq_section(t: Dict[str, np.ndarray]) -> bytes:
+    """Four words (nel, 0, 0, 0); the element of every row (neq ints, padded to 4 words); then one record of EQ_RECORD_WORDS words per element:
+    0 type (0 connect, 1 joint), 1 obj1, 2 obj2 (connect: bodies, body2 0 = world; joint: joints, joint2 -1 = none), 3 first row,
+    4-9 anchor1, anchor2 (f32), 10-14 polycoef, 15-16 solref, 17-21 solimp, 22 invweight, the rest zero (csrc/model_view.h EqView)."""
+    neq = int(t.get("neq", 0))
+    if neq == 0:
+        return b""
+    nel = len(t["eq_type"])
+    out = bytearray(struct.pack("<4i", nel, 0, 0, 0))
+    raw = np.asarray(t["eq_row"], "<i4").tobytes()
+    out += raw + b"\0" * ((-len(raw)) % 16)
+    for e in range(nel):
+        rec = bytearray(4 * EQ_RECORD_WORDS)
+        struct.pack_into("<4i", rec, 0, int(t["eq_type"][e]), int(t["eq_obj"][e, 0]), int(t["eq_obj"][e, 1]), int(t["eq_rowadr"][e]))
+        fl = list(t["eq_anchor"][e]) + list(t["eq_polycoef"][e]) + list(t["eq_solref"][e]) + list(t["eq_solimp"][e]) + [t["eq_invweight"][e]]
+        struct.pack_into(f"<{len(fl)}f", rec, 16, *map(float, fl))
+        out += rec
     return bytes(out)
 
 

@@ -100,6 +100,34 @@ __device__ unsigned long long g_phys_t[40];
 #define TU(name) (reinterpret_cast<const u64*>(tabI + MVO(BI_##name)))
 #define MVO(k) (SD::kStatic ? kSO.o[k] : mv.o[k])  // word offset of table k inside the blob: a constant in a model-specialised kernel
 
+// Dof sets (body_ancdof_mask per body, dof_velmask per dof, jmask per contact slot): one 64-bit word per element for dofs 0 .. 63, and in
+// a model of more than 64 dofs (`wide`) a second block of words behind the first for dofs 64 .. 127 - word w of element i at set[w * n + i].
+// A 64-bit shift on gfx950 uses the low six bits of its amount (a one-word test of dof 70 reads dof 6), so every dof-set site goes through
+// these.  `wide` is a compile-time false in a model-specialised kernel of up to 64 dofs: the second word folds away.
+__device__ __forceinline__ u64 dof_word(const u64* set, int n, bool wide, int i, int d) { return wide ? set[(d >> 6) * n + i] : set[i]; }
+__device__ __forceinline__ int dof_bit(bool wide, int d) { return wide ? d & 63 : d; }
+__device__ __forceinline__ bool dof_in(const u64* set, int n, bool wide, int i, int d) { return (dof_word(set, n, wide, i, d) >> dof_bit(wide, d)) & 1ull; }
+// { BODY } for every dof d of set i (none unless `on`), in ascending order: word 0, then word 1.  Two loops written out by a macro - not a
+// loop over the words, not a function taking the body as a lambda: both moved the register allocation of the model-specialised kernels of up
+// to 64 dofs; with `wide` a compile-time false this is, token for token, the one-word loop those kernels had.
+#define DOF_FOR_EACH(d, set, n, wide, i, on, ...)                                                      \
+  do {                                                                                                 \
+    u64 dmask_ = (on) ? (set)[i] : 0ull;                                                               \
+    while (dmask_) {                                                                                   \
+      const int d = __ffsll((long long)dmask_) - 1;                                                    \
+      dmask_ &= dmask_ - 1;                                                                            \
+      __VA_ARGS__                                                                                      \
+    }                                                                                                  \
+    if (wide) {                                                                                        \
+      dmask_ = (on) ? (set)[(n) + (i)] : 0ull;                                                         \
+      while (dmask_) {                                                                                 \
+        const int d = 64 + __ffsll((long long)dmask_) - 1;                                             \
+        dmask_ &= dmask_ - 1;                                                                          \
+        __VA_ARGS__                                                                                    \
+      }                                                                                                \
+    }                                                                                                  \
+  } while (0)
+
 // ---- small vector helpers (registers) -------------------------------------------------------
 struct V3 { float x, y, z; };
 struct Q4 { float w, x, y, z; };
@@ -675,6 +703,7 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerBlock) env_kernel(ModelView m
   const int neq = kDims ? kSD.neq : mv.neq, nce = nefc - neq;
   const bool has_eq = kDims ? kSD.neq > 0 : mv.neq > 0;
   const int nlevel = kDims ? kSD.nlevel : mv.nlevel, nroot = kDims ? kSD.nroot : mv.nroot;
+  const bool dwide = kDims ? kSD.nv > 64 : mv.nv > 64;  // dof sets of two words (dof_word above)
   const int ldm = P.ldm, ldj = P.ldj;
   const int nvq = (nv + 3) >> 2;  // dof quads (the global-memory matrices hold four consecutive dofs per 16-byte word)
   const float h = mv.timestep;
@@ -1262,29 +1291,38 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerBlock) env_kernel(ModelView m
         }
       }
       SYNC();
-      for (int k = 0; k < nv; ++k) {
-        const int tk = k * (k + 1) / 2;
-        float vv[4];  // this lane's rows g, g + 16, .. (at most 64 dofs)
-        _Pragma("unroll") for (int q = 0; q < 4; ++q) {
-          const int i = g + kGroupLanes * q;
-          vv[q] = 0.f;
-          if (i >= k && i < nv) {
-            const int ti = i * (i + 1) / 2;
-            float v = Lp[ti + k];
-  DOT_UNROLL
-            for (int j = 0; j < k; ++j) v -= Lp[ti + j] * Lp[tk + j];
-            vv[q] = v;
-            if (i == k) Lp[tk + k] = v;
-          }
-        }
-        SYNC();
-        const float r = rsqrtf(fmaxf(Lp[tk + k], MJ_MINVAL));
-        _Pragma("unroll") for (int q = 0; q < 4; ++q) {
-          const int i = g + kGroupLanes * q;
-          if (i > k && i < nv) Lp[i * (i + 1) / 2 + k] = vv[q] * r;
-        }
-        SYNC();
+      // this lane's rows g, g + 16, ..: KQ of them - four up to 64 dofs, eight beyond.  The column loop is written out once per count (a
+      // macro) and the run-time-sized kernel picks one by a wave-uniform test: its loop for up to 64 dofs is the one-word kernel's own.
+#define MPPO_LEFT_LOOKING_COLUMNS(KQ)                                                     \
+      for (int k = 0; k < nv; ++k) {                                                      \
+        const int tk = k * (k + 1) / 2;                                                   \
+        float vv[KQ];                                                                     \
+        _Pragma("unroll") for (int q = 0; q < KQ; ++q) {                                  \
+          const int i = g + kGroupLanes * q;                                              \
+          vv[q] = 0.f;                                                                    \
+          if (i >= k && i < nv) {                                                         \
+            const int ti = i * (i + 1) / 2;                                               \
+            float v = Lp[ti + k];                                                         \
+  DOT_UNROLL                                                                              \
+            for (int j = 0; j < k; ++j) v -= Lp[ti + j] * Lp[tk + j];                     \
+            vv[q] = v;                                                                    \
+            if (i == k) Lp[tk + k] = v;                                                   \
+          }                                                                               \
+        }                                                                                 \
+        SYNC();                                                                           \
+        const float r = rsqrtf(fmaxf(Lp[tk + k], MJ_MINVAL));                             \
+        _Pragma("unroll") for (int q = 0; q < KQ; ++q) {                                  \
+          const int i = g + kGroupLanes * q;                                              \
+          if (i > k && i < nv) Lp[i * (i + 1) / 2 + k] = vv[q] * r;                       \
+        }                                                                                 \
+        SYNC();                                                                           \
       }
+      if ((kDims && kSD.nv <= 4 * kGroupLanes) || !dwide) {
+        MPPO_LEFT_LOOKING_COLUMNS(4)
+      } else {
+        MPPO_LEFT_LOOKING_COLUMNS(8)
+      }
+#undef MPPO_LEFT_LOOKING_COLUMNS
       if (pass == 0) PT(6);
       // triangular inverse, one column per lane (no cross-lane dependency inside a column)
       FOR_G(j, nv) {
@@ -1307,13 +1345,10 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerBlock) env_kernel(ModelView m
     // ================= fwd_velocity: com_vel, passive, rne (closed forms over ancestor masks) =======
     FOR_G(b, nb) {
       float v[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-      u64 mask = b ? TU(body_ancdof_mask)[b] : 0ull;
-      while (mask) {
-        const int d = __ffsll((long long)mask) - 1;
-        mask &= mask - 1;
+      DOF_FOR_EACH(d, TU(body_ancdof_mask), nb, dwide, b, b != 0, {
         const float qd = qvel[d];
         for (int k = 0; k < 6; ++k) v[k] += cdof[6 * d + k] * qd;
-      }
+      });
       for (int k = 0; k < 6; ++k) cvel[6 * b + k] = v[k];
     }
     FOR_G(d, nv) {
@@ -1323,13 +1358,10 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerBlock) env_kernel(ModelView m
         for (int k = 0; k < 6; ++k) out[k] = 0.f;
       } else {
         float v[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-        u64 mask = TU(dof_velmask)[d];
-        while (mask) {
-          const int e = __ffsll((long long)mask) - 1;
-          mask &= mask - 1;
+        DOF_FOR_EACH(e, TU(dof_velmask), nv, dwide, d, true, {
           const float qd = qvel[e];
           for (int k = 0; k < 6; ++k) v[k] += cdof[6 * e + k] * qd;
-        }
+        });
         cross_motion(v, cdof + 6 * d, out);
       }
     }
@@ -1340,13 +1372,10 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerBlock) env_kernel(ModelView m
         for (int k = 0; k < 6; ++k) f[k] = 0.f;
       } else {
         float acc[6] = {0.f, 0.f, 0.f, -TF(gravity)[0], -TF(gravity)[1], -TF(gravity)[2]};
-        u64 mask = TU(body_ancdof_mask)[b];
-        while (mask) {
-          const int d = __ffsll((long long)mask) - 1;
-          mask &= mask - 1;
+        DOF_FOR_EACH(d, TU(body_ancdof_mask), nb, dwide, b, true, {
           const float qd = qvel[d];
           for (int k = 0; k < 6; ++k) acc[k] += cdofdot[6 * d + k] * qd;
-        }
+        });
         float ia[6], iv[6], cf[6];
         inert_mul(cinert + 10 * b, acc, ia);
         inert_mul(cinert + 10 * b, cvel + 6 * b, iv);
@@ -1452,6 +1481,11 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerBlock) env_kernel(ModelView m
         u64 m = TU(body_ancdof_mask)[TI(con_bodyid)[c]];
         if (c >= nplane) m |= TU(body_ancdof_mask)[TI(pair_body)[2 * (c - nplane)]];
         jmask[c] = condist[c] < (cp ? cpf[cpv.con_margin + c] : 0.f) ? m : 0ull;
+        if (dwide) {  // the second word of every set (dof_word): dofs 64 .. 127
+          u64 m1 = TU(body_ancdof_mask)[nb + TI(con_bodyid)[c]];
+          if (c >= nplane) m1 |= TU(body_ancdof_mask)[nb + TI(pair_body)[2 * (c - nplane)]];
+          jmask[ncon + c] = condist[c] < (cp ? cpf[cpv.con_margin + c] : 0.f) ? m1 : 0ull;
+        }
       }
     }
     SYNC();
@@ -1473,7 +1507,7 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerBlock) env_kernel(ModelView m
       for (int side = 0; side < 2; ++side) {
         if (side == 1 && c < nplane) break;
         const int b = side == 0 ? TI(con_bodyid)[c] : TI(pair_body)[2 * (c - nplane)];
-        if ((TU(body_ancdof_mask)[b] >> d) & 1ull) {
+        if (dof_in(TU(body_ancdof_mask), nb, dwide, b, d)) {
           int ri = 0;
           for (int r = 0; r < nroot; ++r) if (TI(root_body)[r] == TI(body_rootid)[b]) ri = r;
           const V3 off = sub3(ld3(conpos + 3 * c), ld3(rootcom + 3 * ri));
@@ -1495,10 +1529,10 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerBlock) env_kernel(ModelView m
       const int nv4 = 4 * nvq, R = 4 * ncon;
       for (int item = g; item < ncon * nv4; item += kGroupLanes) {  // (contact, dof) per item, the last quad's padding included
         const int c = item / nv4, d = item - c * nv4;
-        const u64 m = jmask[c];
-        if (!((m >> (d & ~3)) & 15ull)) continue;  // nobody reads this quad
+        const u64 m = dof_word(jmask, ncon, dwide, c, d);  // (a quad of dofs never straddles two words)
+        if (!((m >> dof_bit(dwide, d & ~3)) & 15ull)) continue;  // nobody reads this quad
         float r4[4] = {0.f, 0.f, 0.f, 0.f};
-        const bool any = d < nv && ((m >> d) & 1ull) && contact_rows(c, d, r4);
+        const bool any = d < nv && ((m >> dof_bit(dwide, d)) & 1ull) && contact_rows(c, d, r4);
         if (any) Jc[c * nv + d] = make_float4(r4[0], r4[1], r4[2], r4[3]);
         float* q = reinterpret_cast<float*>(Jq + ((d >> 2) * R + 4 * c)) + (d & 3);
         q[0] = r4[0]; q[4] = r4[1]; q[8] = r4[2]; q[12] = r4[3];
@@ -1514,7 +1548,7 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerBlock) env_kernel(ModelView m
         for (int side = 0; side < 2; ++side) {
           if (side == 1 && c < nplane) break;
           const int b = side == 0 ? TI(con_bodyid)[c] : TI(pair_body)[2 * (c - nplane)];
-          if ((TU(body_ancdof_mask)[b] >> d) & 1ull) {
+          if (dof_in(TU(body_ancdof_mask), nb, dwide, b, d)) {
             int ri = 0;
             for (int r = 0; r < nroot; ++r) if (TI(root_body)[r] == TI(body_rootid)[b]) ri = r;
             const V3 off = sub3(ld3(conpos + 3 * c), ld3(rootcom + 3 * ri));
@@ -1573,7 +1607,7 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerBlock) env_kernel(ModelView m
           const int k = r - ri[3];
           for (int side = 0; side < 2; ++side) {
             const int b = ri[1 + side];
-            if (b > 0 && ((TU(body_ancdof_mask)[b] >> d) & 1ull)) {
+            if (b > 0 && dof_in(TU(body_ancdof_mask), nb, dwide, b, d)) {
               int rr = 0;
               for (int q = 0; q < nroot; ++q) if (TI(root_body)[q] == TI(body_rootid)[b]) rr = q;
               const V3 off = sub3(ld3(eqpos + 6 * r + 3 * side), ld3(rootcom + 3 * rr));
@@ -1631,8 +1665,9 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerBlock) env_kernel(ModelView m
         // the row's dof quads that hold anything, in ascending order: the dense sum's terms minus exact zeros
         const int rc = r - nlim, R = 4 * ncon;
         const u64 m = jmask[rc >> 2];
+        const int nq0 = dwide ? 16 : nvq;  // (beyond 64 dofs: quads 16 .. from the sets' second word, in a loop of their own)
   #pragma unroll 4
-        for (int k4 = 0; k4 < nvq; ++k4) {
+        for (int k4 = 0; k4 < nq0; ++k4) {
           if ((m >> (4 * k4)) & 15ull) {
             const float4 w = Jq[k4 * R + rc];
             const int k = 4 * k4;
@@ -1640,6 +1675,19 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerBlock) env_kernel(ModelView m
             s += w.y * (k + 1 < nv ? x[k + 1] : 0.f);
             s += w.z * (k + 2 < nv ? x[k + 2] : 0.f);
             s += w.w * (k + 3 < nv ? x[k + 3] : 0.f);
+          }
+        }
+        if (dwide) {
+          const u64 m1 = jmask[ncon + (rc >> 2)];
+          for (int k4 = 16; k4 < nvq; ++k4) {
+            if ((m1 >> (4 * k4 - 64)) & 15ull) {
+              const float4 w = Jq[k4 * R + rc];
+              const int k = 4 * k4;
+              s += w.x * x[k];
+              s += w.y * (k + 1 < nv ? x[k + 1] : 0.f);
+              s += w.z * (k + 2 < nv ? x[k + 2] : 0.f);
+              s += w.w * (k + 3 < nv ? x[k + 3] : 0.f);
+            }
           }
         }
         return s;
@@ -1652,9 +1700,11 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerBlock) env_kernel(ModelView m
       float s = 0.f;
       if (nlim > 0) { const int dl = dlim[i]; s = lim_sign(dl) * f[lim_row(dl)]; }
       if (spJ) {
+        const u64* jm = dwide && i >= 64 ? jmask + ncon : jmask;  // (the word of every slot's set that holds dof i)
+        const int ib = dof_bit(dwide, i);
   #pragma unroll 4
         for (int c = 0; c < ncon; ++c) {
-          if ((jmask[c] >> i) & 1ull) {
+          if ((jm[c] >> ib) & 1ull) {
             const float4 w = Jc[c * nv + i];
             const float* fc = f + nlim + 4 * c;
             s += w.x * fc[0]; s += w.y * fc[1]; s += w.z * fc[2]; s += w.w * fc[3];
@@ -1952,7 +2002,7 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerBlock) env_kernel(ModelView m
       // (rows in MJX's order: equality rows first, then limits and contacts; o = the row's place in that order)
       auto o_of = [&](int r) { return r >= nce ? r - nce : r + neq; };
       if (pr.efc_J) FOR_G(r, nefc) for (int k = 0; k < nv; ++k)
-        pr.efc_J[((size_t)env * nefc + o_of(r)) * nv + k] = r >= nce ? Je[(r - nce) * ldje + k] : r >= nlim ? (spJ ? (((jmask[(r - nlim) >> 2] >> k) & 1ull) ? reinterpret_cast<const float*>(Jc + ((r - nlim) >> 2) * nv + k)[(r - nlim) & 3] : 0.f)
+        pr.efc_J[((size_t)env * nefc + o_of(r)) * nv + k] = r >= nce ? Je[(r - nce) * ldje + k] : r >= nlim ? (spJ ? (dof_in(jmask, ncon, dwide, (r - nlim) >> 2, k) ?reinterpret_cast<const float*>(Jc + ((r - nlim) >> 2) * nv + k)[(r - nlim) & 3] : 0.f)
                                                                         : J[(r - nlim) * ldj + k])
                                                             : (k == TI(jnt_dofadr)[TI(lim_jntid)[r]] ? lim_sign(dlim[k]) : 0.f);
       if (pr.efc_D) FOR_G(r, nefc) pr.efc_D[(size_t)env * nefc + o_of(r)] = eD[r];
@@ -2351,10 +2401,10 @@ extern "C" int32_t mppo_model_open(const void* host_blob, size_t nbytes, const v
     return fail(MPPO_EMODEL, "model blob size mismatch: header says %zu + %zu + %d words (contact-parameter section), got %zu bytes", total, hull_words, cpv.words, nbytes);
   v.timestep = wf[16]; v.tolerance = wf[17]; v.ls_tolerance = wf[18]; v.impratio = wf[19]; v.plane_z = wf[20]; v.meaninertia = wf[21];
   auto bad = [&](const char* what) { delete m; return fail(MPPO_EMODEL, "model blob: %s", what); };
-  if (v.nq < 1 || v.nv < 1 || v.nbody < 2 || v.nbody > 128 || v.nv > 64 || v.nq > 128 || v.nu < 0 || v.nu > v.nv || v.njnt < 1 ||
+  if (v.nq < 1 || v.nv < 1 || v.nbody < 2 || v.nbody > 128 || v.nv > 128 || v.nq > 256 || v.nu < 0 || v.nu > v.nv || v.njnt < 1 ||
       v.ncon < 0 || v.npair < 0 || v.npair > v.ncon || v.nlimit < 0 || v.nroot < 1 || v.nlevel < 1 || v.iterations < 0 || v.ls_iterations < 0 ||
       v.ncvx < 0 || 4 * v.ncvx > v.ncon - v.npair || v.ncvxvert < 4 * v.ncvx || v.ncvxvert > 64 * 64)
-    return bad("dimension out of the supported range (nbody<=128, nv<=64)");
+    return bad("dimension out of the supported range (nbody<=128, nv<=128, nq<=256)");
   if (!(v.timestep > 0.f) || !(v.meaninertia > 0.f) || !(v.impratio > 0.f)) return bad("non-positive timestep / meaninertia / impratio");
   const int32_t* dir = wi + kBlobHeaderWords;
   BlobDims bd{v.nq, v.nv, v.nu, v.nbody, v.njnt, v.ncon, v.nlimit, v.npair, v.nlevel, v.nroot, v.ncvx, v.ncvxvert, 0, 0, 0, 0};

@@ -81,8 +81,11 @@ __host__ __device__ constexpr inline int blob_array_len(const BlobDims& d, int k
     case BI_level_body: return d.nbody - 1;
     case BI_root_body: return d.nroot;
     case BI_body_subtree_mask: return (d.nbody > 64 ? 4 : 2) * d.nbody;  // a 64-bit word per body: bodies 0..63 of its subtree; beyond 64 bodies a second block of words: bodies 64..127
-    case BI_body_ancdof_mask: case BF_body_invweight0: return 2 * d.nbody;
-    case BI_dof_velmask: case BF_dof_actfrcrange: return 2 * d.nv;
+    // dof sets: a 64-bit word per body / dof for dofs 0..63; beyond 64 dofs a second block of words: dofs 64..127
+    case BI_body_ancdof_mask: return (d.nv > 64 ? 4 : 2) * d.nbody;
+    case BI_dof_velmask: return (d.nv > 64 ? 4 : 2) * d.nv;
+    case BF_body_invweight0: return 2 * d.nbody;
+    case BF_dof_actfrcrange: return 2 * d.nv;
     case BF_gravity: return 3;
     case BF_body_pos: case BF_body_ipos: case BF_body_inertia: return 3 * d.nbody;
     case BF_body_quat: case BF_body_iquat: return 4 * d.nbody;
@@ -199,7 +202,8 @@ struct PhysLds {
   //   gJq  [nvq][4 ncon][4]    four consecutive dofs of a row side by side: lane = row reads one float4 per dof quad      (J x)
   //   gM   [nvq][nv][4]        four consecutive columns of a row side by side: lane = row reads one float4 per quad       (M x)
   // (nvq = ceil(nv / 4); lanes of an environment read consecutive 16-byte words.)  jmask: per contact slot, in LDS, the dofs its rows
-  // touch (the ancestors of its one or two bodies) if the contact is active this step, else 0 - writers and readers skip the rest.
+  // touch (the ancestors of its one or two bodies) if the contact is active this step, else 0 - writers and readers skip the rest
+  // (a dof set: one 64-bit word per slot, a second block of words behind the first beyond 64 dofs).
   int spill, gJc, gJq, gM, gwords, jmask;
   // equality rows (neq > 0): their Jacobian, dense [neq][ldj] after the contact rows in region A4, or [neq][nv] in the record in global
   // memory (gJe) when the contact Jacobian is there too; eqpos: per row, the world points p1, p2 of its connect (written while the poses of
@@ -233,7 +237,7 @@ __host__ __device__ constexpr inline PhysLds make_phys_lds(int nq, int nv, int n
   const int rows1 = o;
   o = rows0; p.cinert = take(10 * nbody); o = imax_(o, rows1);
   p.cvxsel = take(12 * ncvx); p.cvxok = take(4 * ncvx);
-  p.jmask = (p.spill & kSpillJ) ? take(2 * ncon) : 0;
+  p.jmask = (p.spill & kSpillJ) ? take((nv > 64 ? 4 : 2) * ncon) : 0;  // (a 64-bit word per slot; beyond 64 dofs a second block: dofs 64..127)
   // region B, two lifetimes: the dynamics' cdof and the contact geometry, dead once the Jacobian is built | the solver's nv-vectors,
   // born after that (qacc stays until the end of the step: it is the next step's warm start)
   const int B = o;
@@ -289,6 +293,15 @@ __host__ __device__ constexpr inline int spill_for(int nq, int nv, int nu, int n
     const int w = waves_per_cu(blob_words, make_phys_lds(nq, nv, nu, nbody, njnt, ncon, nefc, nroot, ncvx, li_regs, s, neq).total, 4);
     const int wc = w > 4 ? 4 : w;
     if (wc > best_w) { best_w = wc; best = s; }
+  }
+  // Not even one four-environment wave fits (the run-time-sized kernel then carries two or one environments per wave: mppo_model_open).  The
+  // matrices stay in LDS while ONE environment with them fits; beyond that (a robot of about 100 dofs and more) the smallest set that leaves
+  // LDS so that two environments per wave fit, else one.  A 128-dof robot with 123 contact slots and 614 constraint rows: 66 KB of M and
+  // 254 KB of contact Jacobian per environment in LDS; both outside, two triangular factors of 33 KB each remain (tests/test_many_dofs.py).
+  if (best_w == 0 && waves_per_cu(blob_words, make_phys_lds(nq, nv, nu, nbody, njnt, ncon, nefc, nroot, ncvx, li_regs, 0, neq).total, 1) == 0) {
+    for (int epw = 2; epw >= 1; epw /= 2)
+      for (int t = 1; t < 3; ++t)
+        if (waves_per_cu(blob_words, make_phys_lds(nq, nv, nu, nbody, njnt, ncon, nefc, nroot, ncvx, li_regs, opts[t], neq).total, epw) > 0) return opts[t];
   }
   return best;
 }

@@ -19,6 +19,9 @@ Built-in robots are *stand-ins* and are labelled as such everywhere:
   synth_stompy_full : + 2 arms x 5 hinges             (nq=27 nv=26 nu=20, O=415)
 `kscale_id: 5eb3cb7f23232298` resolves to synth_stompy_pro.
 
+Limits of the physics kernel: 128 bodies (the world included) and 128 dofs - its topology tables are
+sets of 64-bit words, one per entry up to 64 bodies / dofs and a second block of words beyond.
+
 Conventions follow MuJoCo: quaternions are (w,x,y,z); body 0 is the world;
 spatial vectors are [rotational(3), translational(3)].
 """
@@ -38,7 +41,8 @@ GEOM_SPHERE, GEOM_CAPSULE, GEOM_CYLINDER, GEOM_BOX, GEOM_MESH = 2, 3, 5, 6, 7  #
 MJ_MINVAL = 1e-15
 MAX_CONVEX_VERTS = 64  # hull vertices of one mesh collider (the kernel scans them five times per step)
 MAX_EQ_ROWS = 32  # equality constraint rows of one model (a connect takes three, a joint equality one): the environment kernel's cap
-MAX_BODIES = 128  # subtree sets are two 64-bit words per body (one up to 64 bodies); dofs: one word, 64
+MAX_BODIES = 128  # subtree sets are two 64-bit words per body (one up to 64 bodies)
+MAX_DOFS = 128  # dof sets (ancestor dofs per body, cdof_dot sets per dof) likewise: two 64-bit words per entry (one up to 64 dofs)
 
 BLOB_MAGIC = 0x4D50504F  # "MPPO"
 BLOB_VERSION = 9  # 9: equality constraints (header word 38 = equality rows, a section behind the contact-parameter section); 8: per-slot / per-limit contact parameters (header word 37, a section behind the hull section); 7: hull section carries the hulls' edge directions (convex_convex: box / mesh against box / mesh); 6: dof_actfrcrange (joint actuatorfrcrange); 2: header word include_c_vals; 3: geom-geom pairs (npair, pair_body, pair_geom) and con_axis; 4: convex (mesh) geoms against the plane; 5: hull section (sphere / capsule against box / mesh)
@@ -507,8 +511,8 @@ def compile_model(spec: ModelSpec) -> CompiledModel:
     for bi in range(1, nbody):
         depth[bi] = depth[body_parent[bi]] + 1
 
-    if nbody > MAX_BODIES or nv > 64:
-        raise ValueError(f"the physics kernel supports at most {MAX_BODIES} bodies (the world included) and 64 dofs (bitmask topology tables); "
+    if nbody > MAX_BODIES or nv > MAX_DOFS:
+        raise ValueError(f"the physics kernel supports at most {MAX_BODIES} bodies (the world included) and {MAX_DOFS} dofs (bitmask topology tables); "
                          f"this model has {nbody} bodies and {nv} dofs")
     # bodies grouped by depth (level-synchronous kinematics)
     nlevel = int(depth.max()) if nbody > 1 else 0
@@ -525,25 +529,25 @@ def compile_model(spec: ModelSpec) -> CompiledModel:
     for b in range(nbody - 1, 0, -1):
         subtree[b] |= 1 << b
         subtree[body_parent[b]] |= subtree[b]
-    ancdof = np.zeros(nbody, np.uint64)
+    ancdof = [0] * nbody  # (Python integers: up to 128 bits)
     for b in range(1, nbody):
         ancdof[b] = ancdof[body_parent[b]]
         for d in range(body_dofadr[b], body_dofadr[b] + body_dofnum[b]) if body_dofnum[b] > 0 else []:
-            ancdof[b] |= np.uint64(1) << np.uint64(d)
-    velmask = np.zeros(nv, np.uint64)
+            ancdof[b] |= 1 << int(d)
+    velmask = [0] * nv
     for j in range(njnt):
         b, da = jnt_bodyid[j], jnt_dofadr[j]
         before = ancdof[body_parent[b]]
         for jj in range(body_jntadr[b], j):  # earlier joints of the same body
             nd = 6 if jnt_type[jj] == JNT_FREE else 1
             for d in range(jnt_dofadr[jj], jnt_dofadr[jj] + nd):
-                before |= np.uint64(1) << np.uint64(d)
+                before |= 1 << int(d)
         if jnt_type[j] == JNT_FREE:
             for k in range(3):
                 velmask[da + k] = before  # value unused: translational cdof_dot is 0
             trans = before
             for k in range(3):
-                trans |= np.uint64(1) << np.uint64(da + k)
+                trans |= 1 << int(da + k)
             for k in range(3, 6):
                 velmask[da + k] = trans  # all three rotational cdof_dot use the velocity after translation only
         else:
@@ -842,8 +846,9 @@ def compile_model(spec: ModelSpec) -> CompiledModel:
     # bodies 0 .. 63 of every body's subtree, then (models with more than 64 bodies only) bodies 64 .. 127 of every body's subtree
     lo64 = (1 << 64) - 1
     put("body_subtree_mask", np.concatenate([_m64([m & lo64 for m in subtree])] + ([_m64([m >> 64 for m in subtree])] if nbody > 64 else [])), np.int32)
-    put("body_ancdof_mask", _m64(ancdof), np.int32)
-    put("dof_velmask", _m64(velmask), np.int32)
+    # dof sets likewise: dofs 0 .. 63, then (models with more than 64 dofs only) dofs 64 .. 127
+    put("body_ancdof_mask", np.concatenate([_m64([m & lo64 for m in ancdof])] + ([_m64([m >> 64 for m in ancdof])] if nv > 64 else [])), np.int32)
+    put("dof_velmask", np.concatenate([_m64([m & lo64 for m in velmask])] + ([_m64([m >> 64 for m in velmask])] if nv > 64 else [])), np.int32)
     put("dof_qposadr", dof_qposadr, np.int32)
     put("body_pos", body_pos)
     put("body_quat", body_quat)

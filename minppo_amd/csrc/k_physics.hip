@@ -203,6 +203,14 @@ __device__ __forceinline__ Q4 axis_angle(V3 axis, float angle) {
   sincosf(0.5f * angle, &s, &c);
   return {c, axis.x * s, axis.y * s, axis.z * s};
 }
+// rotation vector (axis x angle, angle in (-pi, pi]) of a unit quaternion: MuJoCo mju_quat2Vel with dt = 1, MJX math.quat_to_axis_angle
+__device__ __forceinline__ V3 quat_rotvec(Q4 q) {
+  const V3 v = {q.x, q.y, q.z};
+  const float s = sqrtf(dot3(v, v));
+  float ang = 2.f * atan2f(s, q.w);
+  if (ang > 3.14159265358979323846f) ang -= 6.28318530717958647692f;
+  return mul3(v, s > 0.f ? ang / s : 0.f);
+}
 // ---- a sphere / capsule of one body against a convex hull (box, mesh) of another: MJX collision_convex._sphere_convex / _capsule_convex.
 // The 16 lanes of an environment work on ONE pair together: lanes stride over the hull's faces (support) and edges (closest approach),
 // the winners are found with DPP row reductions (the first index among equal values, as argmax / argmin give it), the winning face's
@@ -648,13 +656,23 @@ __device__ __forceinline__ float impedance(const float* solimp, float pos) {
 // Instantiations are listed in spec_dims.inc (generated by minppo_amd/build.py); other models run the RuntimeModel kernel.
 struct RuntimeModel {
   static constexpr bool kStatic = false;
+  static constexpr bool kBall = false;
+  static constexpr BlobDims dims() { return BlobDims{}; }
+};
+// ... and the run-time-sized kernel of a robot with ball joints: an instantiation of its own, so that the joint-type branches cost every other
+// robot nothing - RuntimeModel's kernel is, instruction for instruction, what it was before ball joints existed (profiles/ball_joints_codegen.txt; a first
+// version with one kernel and wave-uniform tests was 0.5 % / 1.0 % slower on the 16-dof stand-in / the export biped: profiles/ball_joints_env_time.txt)
+struct RuntimeBallModel {
+  static constexpr bool kStatic = false;
+  static constexpr bool kBall = true;
   static constexpr BlobDims dims() { return BlobDims{}; }
 };
 template <int NQ, int NV, int NU, int NBODY, int NJNT, int NCON, int NLIMIT, int NPAIR, int NLEVEL, int NROOT, int NCVX = 0, int NCVXVERT = 0, int HULL = 0, int NCYL = 0, int NEQ = 0,
-          int CPARAM = 0>
+          int NBALL = 0, int CPARAM = 0>
 struct StaticModel {
   static constexpr bool kStatic = true;
-  static constexpr BlobDims dims() { return BlobDims{NQ, NV, NU, NBODY, NJNT, NCON, NLIMIT, NPAIR, NLEVEL, NROOT, NCVX, NCVXVERT, HULL, NCYL, NEQ, CPARAM}; }
+  static constexpr bool kBall = NBALL > 0;
+  static constexpr BlobDims dims() { return BlobDims{NQ, NV, NU, NBODY, NJNT, NCON, NLIMIT, NPAIR, NLEVEL, NROOT, NCVX, NCVXVERT, HULL, NCYL, NEQ, NBALL, CPARAM}; }
 };
 // MODE (EnvArgs::mode) is a template parameter too: the step kernel carries neither the probe's 17 output pointers nor its stores.
 template <class SD, int MODE>
@@ -665,8 +683,8 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerBlock) env_kernel(ModelView m
   // fixed-size kernel, up to 32 dofs: a lane's rows / columns of the Cholesky factors live in registers (see factor_m below)
   constexpr bool kRegChol = kDims && kSD.nv <= kRegCholMaxNv;
   constexpr int kNefc = kSD.neq + kSD.nlimit + 4 * kSD.ncon;
-  constexpr int kSpill = kDims ? spill_for(kSD.nq, kSD.nv, kSD.nu, kSD.nbody, kSD.njnt, kSD.ncon, kNefc, kSD.nroot, kSD.ncvx, kRegChol, kSO.words, kSD.neq) : 0;
-  constexpr PhysLds kSP = make_phys_lds(kSD.nq, kSD.nv, kSD.nu, kSD.nbody, kSD.njnt, kSD.ncon, kNefc, kSD.nroot, kSD.ncvx, kRegChol, kSpill, kSD.neq);
+  constexpr int kSpill = kDims ? spill_for(kSD.nq, kSD.nv, kSD.nu, kSD.nbody, kSD.njnt, kSD.ncon, kNefc, kSD.nroot, kSD.ncvx, kRegChol, kSO.words, kSD.neq, kSD.nball) : 0;
+  constexpr PhysLds kSP = make_phys_lds(kSD.nq, kSD.nv, kSD.nu, kSD.nbody, kSD.njnt, kSD.ncon, kNefc, kSD.nroot, kSD.ncvx, kRegChol, kSpill, kSD.neq, kSD.nball);
   const PhysLds P = SD::kStatic ? kSP : Prt;
   constexpr int NV = kDims ? kSD.nv : 0;
   constexpr int kDotU = dot_unroll(NV);
@@ -702,6 +720,8 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerBlock) env_kernel(ModelView m
   // as MJX orders them); a model without any (neq = 0) runs exactly the code of version 8 - in a specialised kernel none of it is compiled in
   const int neq = kDims ? kSD.neq : mv.neq, nce = nefc - neq;
   const bool has_eq = kDims ? kSD.neq > 0 : mv.neq > 0;
+  // ball joints: a model without any runs exactly the code it ran before they existed - none of theirs is compiled into its kernel
+  constexpr bool has_ball = SD::kBall;  // (compile-time in the run-time-sized kernels too: RuntimeModel / RuntimeBallModel)
   const int nlevel = kDims ? kSD.nlevel : mv.nlevel, nroot = kDims ? kSD.nroot : mv.nroot;
   const bool dwide = kDims ? kSD.nv > 64 : mv.nv > 64;  // dof sets of two words (dof_word above)
   const int ldm = P.ldm, ldj = P.ldj;
@@ -712,6 +732,8 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerBlock) env_kernel(ModelView m
   float* xpos = S + P.xpos; float* xquat = S + P.xquat; float* xipos = S + P.xipos; float* rootcom = S + P.rootcom;  // (poses: region A1)
   float* cinert = S + P.cinert; float* cdof = S + P.cdof; float* cvel = S + P.cvel;
   int* dlim = reinterpret_cast<int*>(S + P.dlim);
+  // models with ball joints: every dof's entry in its active limit row (+-1: hinge / slide; a component of -axis: a ball joint's three dofs), behind dlim
+  float* lcoef = S + P.dlim + ((nv + 3) & ~3);
   float* M = (float*)__builtin_assume_aligned(S + P.M, 16); float* LL = (float*)__builtin_assume_aligned(S + P.LL, 16);
   float* qfs = (float*)__builtin_assume_aligned(S + P.qfs, 16); float* qas = (float*)__builtin_assume_aligned(S + P.qas, 16); float* qacc = (float*)__builtin_assume_aligned(S + P.qacc, 16); float* Ma = (float*)__builtin_assume_aligned(S + P.Ma, 16);
   float* grad = (float*)__builtin_assume_aligned(S + P.grad, 16); float* Mgrad = (float*)__builtin_assume_aligned(S + P.Mgrad, 16); float* search = (float*)__builtin_assume_aligned(S + P.search, 16); float* mvv = (float*)__builtin_assume_aligned(S + P.mv, 16); float* qfc = (float*)__builtin_assume_aligned(S + P.qfc, 16);
@@ -826,6 +848,11 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerBlock) env_kernel(ModelView m
             const V3 axis = qrot(ql, ld3(TF(jnt_axis) + 3 * j));
             st3(xanchor + 3 * j, anchor);
             st3(xaxis + 3 * j, axis);
+            if (has_ball && jt == JNT_BALL) {  // the hinge's form with the rotation taken from qpos
+              ql = qmul(ql, qnormalize(ld4(qpos + qa)));
+              pl = sub3(anchor, qrot(ql, ld3(TF(jnt_pos) + 3 * j)));
+              continue;
+            }
             const float disp = qpos[qa] - TF(qpos0)[qa];
             if (jt == JNT_HINGE) {
               ql = qmul(ql, axis_angle(ld3(TF(jnt_axis) + 3 * j), disp));
@@ -1110,6 +1137,14 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerBlock) env_kernel(ModelView m
           float* cr = cdof + 6 * (da + 3 + k);
           st3(cr, ax);
           st3(cr + 3, cross3(ax, off));
+        }
+      } else if (has_ball && jt == JNT_BALL) {  // the free joint's rotational half, about the joint anchor
+        float R[9];  // xmat
+        qmat(ld4(xquat + 4 * b), R);
+        _Pragma("unroll") for (int k = 0; k < 3; ++k) {
+          const V3 ax = {R[k], R[3 + k], R[6 + k]};
+          st3(cdof + 6 * (da + k), ax);
+          st3(cdof + 6 * (da + k) + 3, cross3(ax, off));
         }
       } else if (jt == JNT_HINGE) {
         const V3 ax = ld3(xaxis + 3 * j);
@@ -1404,11 +1439,29 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerBlock) env_kernel(ModelView m
         const float stiff = TF(jnt_stiffness)[TI(dof_jntid)[d]];
         if (stiff != 0.f) passive -= stiff * (qpos[qa] - TF(qpos_spring)[qa]);
       }
+      // a ball joint's dof: the joint's first dof (where its actuators are attached) and which of the three this one is
+      const int jd = has_ball ? TI(dof_jntid)[d] : 0;
+      const bool balld = has_ball && TI(jnt_type)[jd] == JNT_BALL;
+      const int dact = balld ? TI(jnt_dofadr)[jd] : d, kb = d - dact;
+      if (balld) {
+        // the spring of a ball joint acts on the rotation vector of its quaternion (qpos_spring is the identity): mju_subQuat, MJX passive
+        const float stiff = TF(jnt_stiffness)[jd];
+        if (stiff != 0.f) {
+          const V3 rv = quat_rotvec(qnormalize(ld4(qpos + TI(jnt_qposadr)[jd])));
+          passive -= stiff * (kb == 0 ? rv.x : kb == 1 ? rv.y : rv.z);
+        }
+      }
       float act = 0.f;
       for (int u = 0; u < nu; ++u) {
-        if (TI(act_dofid)[u] == d) {
+        if (TI(act_dofid)[u] == dact) {
           float c = ctrl[u];
           if (TI(act_ctrllimited)[u]) c = fminf(fmaxf(c, TF(act_ctrlrange)[2 * u]), TF(act_ctrlrange)[2 * u + 1]);
+          if (balld) {  // a motor on a ball joint: the scalar force times the gear's three components (kept in the actuator's bias row: no length, no bias there)
+            float fo = TF(act_gain)[u] * c;
+            if (TI(act_forcelimited)[u]) fo = fminf(fmaxf(fo, TF(act_forcerange)[2 * u]), TF(act_forcerange)[2 * u + 1]);
+            act += fo * TF(act_bias)[3 * u + kb];
+            continue;
+          }
           const float gear = TF(act_gear)[u];
           const float len = gear * qpos[TI(act_qposadr)[u]], vel = gear * qvel[d];
           float fo = TF(act_gain)[u] * c + TF(act_bias)[3 * u] + TF(act_bias)[3 * u + 1] * len + TF(act_bias)[3 * u + 2] * vel;
@@ -1471,6 +1524,7 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerBlock) env_kernel(ModelView m
     // dense row gave bit for bit (the other terms of that row's sum were exact zeros).
     if (!spJ) FOR_G(r, 4 * ncon) for (int k = 0; k < nv; ++k) J[r * ldj + k] = 0.f;
     FOR_G(i, nv) dlim[i] = 0;
+    if (has_ball) FOR_G(i, nv) lcoef[i] = 0.f;
     // Jacobian in global memory (large robots): per contact slot the set of dofs its rows touch - the ancestors of its one or two bodies -
     // if the contact is active, else none; the rows are written and read through these sets only (every other entry is an exact zero)
     u64* jmask = reinterpret_cast<u64*>(S + P.jmask);
@@ -1492,10 +1546,25 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerBlock) env_kernel(ModelView m
     FOR_G(r, nlim) {  // joint limits: one row each
       const int jid = TI(lim_jntid)[r];
       const int qa = TI(jnt_qposadr)[jid], da = TI(jnt_dofadr)[jid];
+      if (has_ball && TI(jnt_type)[jid] == JNT_BALL) {
+        // MJX _instantiate_limit_ball: the rotation angle (>= 0, about whatever axis) against range[1]; the row is -axis on the joint's three dofs
+        float ang;
+        const V3 ax = normalize_norm(quat_rotvec(qnormalize(ld4(qpos + qa))), ang);
+        const float bpos = TF(jnt_range)[2 * jid + 1] - ang - (cp ? cpf[cpv.lim_margin + r] : 0.f);
+        const bool bact = bpos < 0.f;
+        if (bact) {
+          dlim[da] = r + 1; dlim[da + 1] = r + 1; dlim[da + 2] = r + 1;
+          lcoef[da] = -ax.x; lcoef[da + 1] = -ax.y; lcoef[da + 2] = -ax.z;
+        }
+        jv[r] = bact ? bpos : 0.f;
+        jaref[r] = bact ? TF(dof_invweight0)[da] : 0.f;
+        continue;
+      }
       const float dlo = qpos[qa] - TF(jnt_range)[2 * jid], dhi = TF(jnt_range)[2 * jid + 1] - qpos[qa];
       const float pos = cp ? fminf(dlo, dhi) - cpf[cpv.lim_margin + r] : fminf(dlo, dhi);  // (per-row: active within the joint's margin)
       const bool act = pos < 0.f;
       if (act) dlim[da] = dlo < dhi ? r + 1 : -(r + 1);
+      if (has_ball && act) lcoef[da] = dlo < dhi ? 1.f : -1.f;
       jv[r] = act ? pos : 0.f;               // pos, parked in jv until the row parameters are built
       jaref[r] = act ? TF(dof_invweight0)[da] : 0.f;  // invweight, parked in jaref
     }
@@ -1659,6 +1728,12 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerBlock) env_kernel(ModelView m
         for (int k = 0; k < nv; ++k) s += jr[k] * x[k];
         return s;
       }
+      if (has_ball && r < nlim) {  // the row's entries from lcoef: one of a hinge / slide, three of a ball joint
+        const int jid = TI(lim_jntid)[r], da = TI(jnt_dofadr)[jid];
+        float s = lcoef[da] * x[da];
+        if (TI(jnt_type)[jid] == JNT_BALL) { s += lcoef[da + 1] * x[da + 1]; s += lcoef[da + 2] * x[da + 2]; }
+        return s;
+      }
       if (r < nlim) { const int da = TI(jnt_dofadr)[TI(lim_jntid)[r]]; return lim_sign(dlim[da]) * x[da]; }
       float s = 0.f;
       if (spJ) {
@@ -1698,7 +1773,7 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerBlock) env_kernel(ModelView m
     };
     auto jcol_dot_ineq = [&](int i, const float* f) {
       float s = 0.f;
-      if (nlim > 0) { const int dl = dlim[i]; s = lim_sign(dl) * f[lim_row(dl)]; }
+      if (nlim > 0) { const int dl = dlim[i]; s = (has_ball ? lcoef[i] : lim_sign(dl)) * f[lim_row(dl)]; }
       if (spJ) {
         const u64* jm = dwide && i >= 64 ? jmask + ncon : jmask;  // (the word of every slot's set that holds dof i)
         const int ib = dof_bit(dwide, i);
@@ -2004,6 +2079,7 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerBlock) env_kernel(ModelView m
       if (pr.efc_J) FOR_G(r, nefc) for (int k = 0; k < nv; ++k)
         pr.efc_J[((size_t)env * nefc + o_of(r)) * nv + k] = r >= nce ? Je[(r - nce) * ldje + k] : r >= nlim ? (spJ ? (dof_in(jmask, ncon, dwide, (r - nlim) >> 2, k) ?reinterpret_cast<const float*>(Jc + ((r - nlim) >> 2) * nv + k)[(r - nlim) & 3] : 0.f)
                                                                         : J[(r - nlim) * ldj + k])
+                                                            : has_ball ? (dlim[k] != 0 && lim_row(dlim[k]) == r ? lcoef[k] : 0.f)
                                                             : (k == TI(jnt_dofadr)[TI(lim_jntid)[r]] ? lim_sign(dlim[k]) : 0.f);
       if (pr.efc_D) FOR_G(r, nefc) pr.efc_D[(size_t)env * nefc + o_of(r)] = eD[r];
       if (pr.efc_aref) FOR_G(r, nefc) pr.efc_aref[(size_t)env * nefc + o_of(r)] = earef[r];
@@ -2032,6 +2108,11 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerBlock) env_kernel(ModelView m
         const float n = sqrtf(dot3(w, w));
         const V3 ax = n > 0.f ? mul3(w, 1.f / n) : w;
         st4(qpos + qa + 3, qnormalize(qmul(ld4(qpos + qa + 3), axis_angle(ax, n * h))));
+      } else if (has_ball && TI(jnt_type)[j] == JNT_BALL) {  // the free joint's quaternion update
+        const V3 w = ld3(qvel + da);
+        const float n = sqrtf(dot3(w, w));
+        const V3 ax = n > 0.f ? mul3(w, 1.f / n) : w;
+        st4(qpos + qa, qnormalize(qmul(ld4(qpos + qa), axis_angle(ax, n * h))));
       } else {
         qpos[qa] += h * qvel[da];
       }
@@ -2190,7 +2271,7 @@ static int find_spec(const BlobDims& d) {
     const BlobDims& s = kSpecs[i].d;
     if (s.nq == d.nq && s.nv == d.nv && s.nu == d.nu && s.nbody == d.nbody && s.njnt == d.njnt && s.ncon == d.ncon && s.nlimit == d.nlimit &&
         s.npair == d.npair && s.nlevel == d.nlevel && s.nroot == d.nroot && s.ncvx == d.ncvx && s.ncvxvert == d.ncvxvert && s.hull == d.hull && s.ncyl == d.ncyl &&
-        s.cparam == d.cparam && s.neq == d.neq)
+        s.cparam == d.cparam && s.neq == d.neq && s.nball == d.nball)
       return i;
   }
   return -1;
@@ -2241,7 +2322,7 @@ static int32_t finalize_layout(mppo_model* m) {
   auto lds_for = [&](bool li_regs) {
     const int forced = env_spill_override();
     return make_phys_lds(v.nq, v.nv, v.nu, v.nbody, v.njnt, v.ncon, v.nefc, v.nroot, v.ncvx, li_regs,
-                         forced >= 0 ? forced : spill_for(v.nq, v.nv, v.nu, v.nbody, v.njnt, v.ncon, v.nefc, v.nroot, v.ncvx, li_regs, m->canon_words, v.neq), v.neq);
+                         forced >= 0 ? forced : spill_for(v.nq, v.nv, v.nu, v.nbody, v.njnt, v.ncon, v.nefc, v.nroot, v.ncvx, li_regs, m->canon_words, v.neq, v.nball), v.neq, v.nball);
   };
   const bool fixed = m->spec >= 0 || m->jit;
   m->lds = lds_for(fixed && v.nv <= (m->jit ? m->jit_regchol : kRegCholMaxNv));
@@ -2407,7 +2488,7 @@ extern "C" int32_t mppo_model_open(const void* host_blob, size_t nbytes, const v
     return bad("dimension out of the supported range (nbody<=128, nv<=128, nq<=256)");
   if (!(v.timestep > 0.f) || !(v.meaninertia > 0.f) || !(v.impratio > 0.f)) return bad("non-positive timestep / meaninertia / impratio");
   const int32_t* dir = wi + kBlobHeaderWords;
-  BlobDims bd{v.nq, v.nv, v.nu, v.nbody, v.njnt, v.ncon, v.nlimit, v.npair, v.nlevel, v.nroot, v.ncvx, v.ncvxvert, 0, 0, 0, 0};
+  BlobDims bd{v.nq, v.nv, v.nu, v.nbody, v.njnt, v.ncon, v.nlimit, v.npair, v.nlevel, v.nroot, v.ncvx, v.ncvxvert, 0, 0, 0, 0, 0};
   const BlobOffsets canon = blob_offsets(bd);
   const size_t dir_end = kBlobHeaderWords + 2 * (size_t)BLOB_ARRAY_COUNT;
   if (dir_end > total) return bad("directory past the end");
@@ -2507,10 +2588,25 @@ extern "C" int32_t mppo_model_open(const void* host_blob, size_t nbytes, const v
   {
     const int32_t *jt = HI(BI_jnt_type), *qa = HI(BI_jnt_qposadr), *da = HI(BI_jnt_dofadr), *jn = HI(BI_body_jntnum), *ja = HI(BI_body_jntadr),
                   *par = HI(BI_body_parent), *dp = HI(BI_dof_parentid), *la = HI(BI_level_adr);
+    const int32_t *dj = HI(BI_dof_jntid), *jb = HI(BI_jnt_bodyid), *jl = HI(BI_jnt_limited), *lj = HI(BI_lim_jntid);
+    const float* jr = wf + dir[2 * BF_jnt_range];
+    v.nball = 0;
     for (int j = 0; j < v.njnt; ++j) {
-      if (jt[j] != JNT_FREE && jt[j] != JNT_HINGE && jt[j] != JNT_SLIDE) return bad("unsupported joint type");
+      if (jt[j] != JNT_FREE && jt[j] != JNT_BALL && jt[j] != JNT_HINGE && jt[j] != JNT_SLIDE) return bad("unsupported joint type");
       if (jt[j] == JNT_FREE && (qa[j] + 7 > v.nq || da[j] + 6 > v.nv)) return bad("free joint address out of range");
+      if (jt[j] == JNT_BALL) {
+        // a quaternion and three dofs of its own, alone in its body (its axes are the body's), a limit on the rotation angle: range = (0, max)
+        if (qa[j] + 4 > v.nq || da[j] + 3 > v.nv) return bad("ball joint address out of range");
+        for (int k = 0; k < 3; ++k) if (dj[da[j] + k] != j) return bad("ball joint: its three dofs must name it in dof_jntid");
+        if (jn[jb[j]] != 1 || ja[jb[j]] != j) return bad("a ball joint must be the only joint of its body");
+        bool limited = jl[j] != 0;
+        for (int r = 0; r < v.nlimit; ++r) limited = limited || lj[r] == j;
+        if (limited && !(jr[2 * j] == 0.f && jr[2 * j + 1] > 0.f)) return bad("a limited ball joint needs range = (0, max) with max > 0");
+        ++v.nball;
+      }
     }
+    // (... and nobody else's: the kernel takes a ball dof's place among the three from its distance to the joint's first dof)
+    for (int d = 0; d < v.nv; ++d) if (jt[dj[d]] == JNT_BALL && (d < da[dj[d]] || d >= da[dj[d]] + 3)) return bad("ball joint: a dof outside its three names it in dof_jntid");
     for (int b = 1; b < v.nbody; ++b) {
       if (par[b] >= b) return bad("bodies are not topologically ordered");
       if (jn[b] > 0 && (ja[b] < 0 || ja[b] + jn[b] > v.njnt)) return bad("body joint range out of bounds");
@@ -2569,6 +2665,7 @@ extern "C" int32_t mppo_model_open(const void* host_blob, size_t nbytes, const v
       } else {
         if (ri[1] < 0 || ri[1] >= v.njnt || ri[2] < -1 || ri[2] >= v.njnt || ri[1] == ri[2]) return bad("equality section: a joint equality's joints out of range");
         if (jtype[ri[1]] == JNT_FREE || (ri[2] >= 0 && jtype[ri[2]] == JNT_FREE)) return bad("equality section: a joint equality on a free joint");
+        if (jtype[ri[1]] == JNT_BALL || (ri[2] >= 0 && jtype[ri[2]] == JNT_BALL)) return bad("equality section: a joint equality on a ball joint");
       }
       for (int k = 4; k < 23; ++k) if (!fin(rf[k])) return bad("equality section: a value is not finite");
       const float* sr = rf + 15;
@@ -2580,7 +2677,7 @@ extern "C" int32_t mppo_model_open(const void* host_blob, size_t nbytes, const v
     }
     if (next_row != v.neq) return bad("equality section: the elements' rows do not add up to header word 38");
   }
-  bd.hull = v.hull_words > 0 ? 1 : 0; bd.ncyl = v.ncyl; bd.cparam = v.cparam; bd.neq = v.neq;
+  bd.hull = v.hull_words > 0 ? 1 : 0; bd.ncyl = v.ncyl; bd.cparam = v.cparam; bd.neq = v.neq; bd.nball = v.nball;
   m->spec = find_spec(bd);
   m->canon_words = canon.words;
   if (int32_t rc = mppo::finalize_layout(m); rc != MPPO_OK) { delete m; return rc; }
@@ -2632,9 +2729,9 @@ extern "C" int32_t mppo_model_attach_kernel(mppo_model_t* m, const void* image, 
     const char* e = getenv("MPPO_ENV_GENERIC");
     if ((e && e[0] == '1') || env_spill_override() >= 0) return MPPO_OK;  // (the switches that force the run-time-sized kernel)
   }
-  // the kernels' names spell the dimensions they were compiled for: StaticModel<nq, nv, nu, nbody, njnt, ncon, nlimit, npair, nlevel, nroot, ncvx, ncvxvert, hull, ncyl, neq, cparam>, MODE
+  // the kernels' names spell the dimensions they were compiled for: StaticModel<nq, nv, nu, nbody, njnt, ncon, nlimit, npair, nlevel, nroot, ncvx, ncvxvert, hull, ncyl, neq, nball, cparam>, MODE
   const ModelView& v = m->mv;
-  const int dims[16] = {v.nq, v.nv, v.nu, v.nbody, v.njnt, v.ncon, v.nlimit, v.npair, v.nlevel, v.nroot, v.ncvx, v.ncvxvert, v.hull_words > 0 ? 1 : 0, v.ncyl, v.neq, v.cparam};
+  const int dims[17] = {v.nq, v.nv, v.nu, v.nbody, v.njnt, v.ncon, v.nlimit, v.npair, v.nlevel, v.nroot, v.ncvx, v.ncvxvert, v.hull_words > 0 ? 1 : 0, v.ncyl, v.neq, v.nball, v.cparam};
   char want[256];
   int o = snprintf(want, sizeof want, "StaticModelI");
   for (int d : dims) o += snprintf(want + o, sizeof want - o, "Li%dE", d);
@@ -2720,7 +2817,7 @@ static int32_t launch_env(const mppo_model_t* m, EnvArgs a, hipStream_t stream, 
 #ifdef MPPO_JIT_ONLY  // (the device-side compile of minppo_amd/jit.py: one robot's instantiation and nothing else)
   return kSpecs[0].launch(m->mv, a, m->lds, m->lds_bytes, blocks, m->waves, stream);
 #else
-  return (m->spec >= 0 ? kSpecs[m->spec].launch : &launch_env_t<RuntimeModel>)(m->mv, a, m->lds, m->lds_bytes, blocks, m->waves, stream);
+  return (m->spec >= 0 ? kSpecs[m->spec].launch : m->mv.nball > 0 ? &launch_env_t<RuntimeBallModel> : &launch_env_t<RuntimeModel>)(m->mv, a, m->lds, m->lds_bytes, blocks, m->waves, stream);
 #endif
 }
 // the engine's entry: mppo_env_step with the out-of-LDS matrices in a region of the engine's arena (hipGraph capture: nothing is allocated)

@@ -33,7 +33,7 @@ enum BlobF32 {
 constexpr uint32_t kBlobMagic = 0x4D50504F;
 constexpr uint32_t kBlobVersion = 9;
 constexpr int kBlobHeaderWords = 64;
-constexpr int JNT_FREE = 0, JNT_HINGE = 2, JNT_SLIDE = 3;
+constexpr int JNT_FREE = 0, JNT_BALL = 1, JNT_HINGE = 2, JNT_SLIDE = 3;  // MuJoCo's mjtJoint
 constexpr float MJ_MINVAL = 1e-15f, MJ_MINIMP = 0.0001f, MJ_MAXIMP = 0.9999f;
 
 typedef unsigned long long u64;
@@ -47,6 +47,7 @@ struct ModelView {
   int obs_dim, obs_pad, rec_dim;
   int include_c;  // observation = qpos, qvel, cinert[1:], cvel[1:], qfrc_actuator (1) or qpos, qvel, qfrc_actuator (0): env.py:246-259
   float timestep, tolerance, ls_tolerance, impratio, plane_z, meaninertia;
+  int nball;         // ball joints (counted from jnt_type by mppo_model_open; it sits in what was alignment padding in front of the pointer: the struct keeps its size)
   const int* blob;   // device copy of the whole blob (16-byte aligned)
   int blob_words;    // multiple of 4: the TABLE part (what the kernel copies into LDS)
   int epw;           // environments per wave of the run-time-sized kernel: 4, or 2 / 1 for a robot whose working set would not fit LDS four at a time
@@ -61,8 +62,8 @@ struct ModelView {
 // array padded to 4 words, first array right after the directory).  mppo_model_open refuses a blob laid out differently, so a
 // kernel compiled for fixed dims may take the offsets as constants.
 struct BlobDims { int nq, nv, nu, nbody, njnt, ncon, nlimit, npair, nlevel, nroot, ncvx, ncvxvert;
-                  int hull, ncyl, neq, cparam; };  // (hull: 1 if the model has a hull section; ncyl: its cylinders; neq: equality rows; cparam: per-row contact
-                                                   // parameters - they select code and size the LDS rows, not the table part)
+                  int hull, ncyl, neq, nball, cparam; };  // (hull: 1 if the model has a hull section; ncyl: its cylinders; neq: equality rows; cparam: per-row contact
+                                                          // parameters; nball: ball joints - they select code and size the LDS rows, not the table part)
 struct BlobOffsets { int o[BLOB_ARRAY_COUNT]; int words; };
 __host__ __device__ constexpr inline int blob_array_len(const BlobDims& d, int k) {
   switch (k) {
@@ -190,7 +191,9 @@ struct PhysLds {
   int M, LL, ldm;  // LL (kernels that keep the factor in LDS): the inverse Cholesky factor as a packed lower triangle (row i at i (i + 1) / 2) - of M during the
                    // step, of M + h*D once the second factorisation at the end of the step has run (round 6; round 5 kept both in one square)
   int qfs, qas, qacc, Ma, grad, Mgrad, search, mv, qfc, t0, t1;
-  int dlim;        // per dof, an int: +-(row + 1) of its active joint-limit row, the sign being the row's single Jacobian entry (0: none)
+  int dlim;        // per dof, an int: +-(row + 1) of its active joint-limit row, the sign being the row's single Jacobian entry (0: none).
+                   // A model with ball joints (nball > 0) keeps a float per dof right behind it, at dlim + (nv rounded up to 4): the dof's entry in its
+                   // limit row - +-1 for a hinge / slide, a component of -axis for a ball joint, whose limit row has three entries (k_physics.hip lcoef)
   int D, aref, jaref, jv, force;  // force shares jv's storage (jv is dead once the step along the search direction is taken)
   int conpos, condist, confr;  // per contact slot: point, distance, frame rows (normal, first tangent)
   int cvxsel, cvxok;           // per convex geom: the four hull vertices chosen this step (body frame) and whether each slot is a first occurrence
@@ -216,7 +219,7 @@ __host__ __device__ constexpr inline int imax_(int a, int b) { return a > b ? a 
 
 // (nefc: every constraint row, the neq equality rows included)
 __host__ __device__ constexpr inline PhysLds make_phys_lds(int nq, int nv, int nu, int nbody, int njnt, int ncon, int nefc, int nroot, int ncvx = 0, bool li_regs = false, int spill = 0,
-                                                           int neq = 0) {
+                                                           int neq = 0, int nball = 0) {
   PhysLds p{};
   int o = 0;
   auto take = [&](int n) { int r = o; o += (n + 3) & ~3; return r; };
@@ -231,6 +234,7 @@ __host__ __device__ constexpr inline PhysLds make_phys_lds(int nq, int nv, int n
   p.qfs = take(nv); p.qas = take(nv); p.t0 = take(nv); p.t1 = take(nv);
   p.ctrl = p.t1;
   p.dlim = take(nv);
+  if (nball > 0) (void)take(nv);  // the limit rows' coefficients per dof (models with ball joints only: every other model keeps its layout)
   const int ne = nefc > 0 ? nefc : 1;
   const int rows0 = o;
   p.D = take(ne); p.aref = take(ne); p.jaref = take(ne); p.jv = take(ne); p.force = p.jv;
@@ -285,12 +289,13 @@ __host__ __device__ constexpr inline int waves_per_cu(long long blob_words, long
   }
   return best;
 }
-__host__ __device__ constexpr inline int spill_for(int nq, int nv, int nu, int nbody, int njnt, int ncon, int nefc, int nroot, int ncvx, bool li_regs, int blob_words, int neq = 0) {
+__host__ __device__ constexpr inline int spill_for(int nq, int nv, int nu, int nbody, int njnt, int ncon, int nefc, int nroot, int ncvx, bool li_regs, int blob_words, int neq = 0,
+                                                       int nball = 0) {
   int best = 0, best_w = -1;
   const int opts[3] = {0, kSpillJ, kSpillJ | kSpillM};
   for (int t = 0; t < 3; ++t) {
     const int s = opts[t];
-    const int w = waves_per_cu(blob_words, make_phys_lds(nq, nv, nu, nbody, njnt, ncon, nefc, nroot, ncvx, li_regs, s, neq).total, 4);
+    const int w = waves_per_cu(blob_words, make_phys_lds(nq, nv, nu, nbody, njnt, ncon, nefc, nroot, ncvx, li_regs, s, neq, nball).total, 4);
     const int wc = w > 4 ? 4 : w;
     if (wc > best_w) { best_w = wc; best = s; }
   }
@@ -298,10 +303,10 @@ __host__ __device__ constexpr inline int spill_for(int nq, int nv, int nu, int n
   // matrices stay in LDS while ONE environment with them fits; beyond that (a robot of about 100 dofs and more) the smallest set that leaves
   // LDS so that two environments per wave fit, else one.  A 128-dof robot with 123 contact slots and 614 constraint rows: 66 KB of M and
   // 254 KB of contact Jacobian per environment in LDS; both outside, two triangular factors of 33 KB each remain (tests/test_many_dofs.py).
-  if (best_w == 0 && waves_per_cu(blob_words, make_phys_lds(nq, nv, nu, nbody, njnt, ncon, nefc, nroot, ncvx, li_regs, 0, neq).total, 1) == 0) {
+  if (best_w == 0 && waves_per_cu(blob_words, make_phys_lds(nq, nv, nu, nbody, njnt, ncon, nefc, nroot, ncvx, li_regs, 0, neq, nball).total, 1) == 0) {
     for (int epw = 2; epw >= 1; epw /= 2)
       for (int t = 1; t < 3; ++t)
-        if (waves_per_cu(blob_words, make_phys_lds(nq, nv, nu, nbody, njnt, ncon, nefc, nroot, ncvx, li_regs, opts[t], neq).total, epw) > 0) return opts[t];
+        if (waves_per_cu(blob_words, make_phys_lds(nq, nv, nu, nbody, njnt, ncon, nefc, nroot, ncvx, li_regs, opts[t], neq, nball).total, epw) > 0) return opts[t];
   }
   return best;
 }

@@ -18,7 +18,12 @@ Subset
             `childclass` on <body>, `class` on elements
   <worldbody>: one <geom type="plane"> (the ground), <body name pos quat|euler|axisangle|xyaxes|zaxis childclass>
       <inertial pos quat|euler mass diaginertia|fullinertia>
-      <freejoint/> | <joint type="free|hinge|slide" name pos axis range limited ref springref damping armature stiffness actuatorfrcrange>
+      <freejoint/> | <joint type="free|ball|hinge|slide" name pos axis range limited ref springref damping armature stiffness actuatorfrcrange>
+            (free / ball / hinge / slide: all four of MuJoCo's joint types.  A ball joint - a quaternion in qpos, three angular dofs in the body's
+             frame - ignores `axis` as MuJoCo does, takes range="0 max" (a limit on the rotation angle whatever the axis; anything else is an
+             error), a spring on the rotation vector of its quaternion (stiffness), damping, armature, margin / solreflimit / solimplimit and
+             actuatorfrcrange (each of its three dofs).  Refused on a ball joint: a nonzero ref / springref, a second joint in its body, a
+             joint equality, and any actuator other than a motor)
       <geom type="sphere|capsule|cylinder|box|mesh" size pos quat|euler fromto friction mass density contype conaffinity mesh>
             (a box - the convex mesh of its eight corners - and a mesh collide with the ground as a CONVEX HULL, as in
              MuJoCo / MJX - up to four contacts per step, MJX's plane_convex; a cylinder meets the ground with three contacts per step,
@@ -30,7 +35,9 @@ Subset
             maxhullvert caps the hull as MuJoCo does, so a mesh of thousands of vertices loads with maxhullvert="64" instead of being
             decimated by hand); everything else under <asset> is visual and ignored
   <actuator>: <position joint kp kv gear ctrlrange forcerange>, <motor joint gear ctrlrange forcerange>, <velocity joint kv ...>,
-            <general joint gainprm biastype="none|affine" biasprm ...> (dyntype none, gaintype fixed)
+            <general joint gainprm biastype="none|affine" biasprm ...> (dyntype none, gaintype fixed).  On a ball joint: <motor joint
+            gear="gx gy gz"> and <general> with biastype="none" - the scalar force times the gear's three components is the torque on the
+            joint's three dofs (MuJoCo's joint transmission); <position>, <velocity> and an affine bias are refused there
   <contact><exclude body1 body2/>: no contacts between the geoms of these two bodies; <pair geom1 geom2 friction solref solimp/>: an explicit
             geom pair (or a geom with the ground plane) with a sliding friction of its own, whatever masks / kinship / excludes say
   contact parameters: solref solimp solmix condim="1|3" margin gap on geoms and the ground plane (also through <default><geom>), solreflimit
@@ -43,7 +50,7 @@ Subset
             the constraint holds at qpos0) and <joint joint1 joint2 polycoef/> (hinge / slide joints; no joint2: the joint is locked at
             qpos0 + polycoef[0]), each with solref / solimp (MuJoCo's defaults), `class` and <default><equality>; active="false" compiles the
             element out (one log line: nothing switches it on later).  Refused: weld / tendon / flex equalities, site-based connect, a joint
-            equality on a free joint, unknown names, more than model.MAX_EQ_ROWS rows.  Deviation from MuJoCo: an <equality> section that holds
+            equality on a free or a ball joint, unknown names, more than model.MAX_EQ_ROWS rows.  Deviation from MuJoCo: an <equality> section that holds
             no connect / joint element is an error (MuJoCo accepts it)
 Contacts: geom-vs-ground-plane, and the geom pairs between bodies that MuJoCo would test (contype / conaffinity masks, same-body and
 parent-child pairs filtered, <exclude>d body pairs dropped): sphere / capsule among themselves, and a sphere or capsule against a box
@@ -61,7 +68,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from minppo_amd.model import (GEOM_BOX, GEOM_CAPSULE, GEOM_CYLINDER, GEOM_MESH, GEOM_SPHERE, JNT_FREE, JNT_HINGE, JNT_SLIDE, MAX_CONVEX_VERTS, ActuatorSpec, BodySpec, EqualitySpec,
+from minppo_amd.model import (GEOM_BOX, GEOM_CAPSULE, GEOM_CYLINDER, GEOM_MESH, GEOM_SPHERE, JNT_BALL, JNT_FREE, JNT_HINGE, JNT_SLIDE, MAX_CONVEX_VERTS, ActuatorSpec, BodySpec, EqualitySpec,
                               GeomSpec, JointSpec, ModelSpec, _normalize, _qmat, _qmul, mix_contact_params)
 
 logger = logging.getLogger(__name__)
@@ -585,16 +592,19 @@ def parse_mjcf(xml: str, name: str = "mjcf", base_dir: Optional[Path] = None) ->
                     logger.warning("%s: frictionloss=%s is dropped (the engine, like MJX behind the reference, models no dry joint friction; "
                                    "the reference strips the attribute from <default><joint>, env.py:41-45)", what, ch.attrib["frictionloss"])
                 a.pop("frictionloss", None)
-                jt = {"free": JNT_FREE, "hinge": JNT_HINGE, "slide": JNT_SLIDE}.get(a.get("type", "hinge"))
+                jt = {"free": JNT_FREE, "ball": JNT_BALL, "hinge": JNT_HINGE, "slide": JNT_SLIDE}.get(a.get("type", "hinge"))
                 if jt is None:
-                    raise ValueError(f"{what}: joint type {a.get('type')!r} is outside the supported MJCF subset (free, hinge, slide)")
+                    raise ValueError(f"{what}: joint type {a.get('type')!r} is outside the supported MJCF subset (free, ball, hinge, slide)")
                 jn = a.get("name", f"{bname}_joint{len(joints)}")
                 rng = None
                 if "range" in a:
                     lim = a.get("limited", "auto")
                     if lim == "true" or (lim == "auto" and comp.autolimits):
                         r = _floats(a["range"], 2, what)
-                        rng = (comp.ang(r[0]), comp.ang(r[1])) if jt == JNT_HINGE else (r[0], r[1])
+                        rng = (comp.ang(r[0]), comp.ang(r[1])) if jt in (JNT_HINGE, JNT_BALL) else (r[0], r[1])
+                        if jt == JNT_BALL and not (rng[0] == 0.0 and rng[1] > 0.0):
+                            # MuJoCo's XML reference: a ball joint's range limits the rotation angle whatever the axis - only the second value is used, the first is 0
+                            raise ValueError(f"joint {jn}: joint type 'ball' takes range=\"0 max\" (a limit on the rotation angle), got ({rng[0]:.6g}, {rng[1]:.6g})")
                 elif a.get("limited") == "true":
                     raise ValueError(f"{what}: limited='true' without range")
                 for k in ("solreflimit", "solimplimit"):
@@ -606,6 +616,8 @@ def parse_mjcf(xml: str, name: str = "mjcf", base_dir: Optional[Path] = None) ->
                                  "springref", "margin", "group", "user", "actuatorfrcrange", "actuatorfrclimited"):
                         raise ValueError(f"{what}: attribute {k!r} is outside the supported MJCF subset")
                 ref, sref = float(a.get("ref", "0")), float(a.get("springref", "0"))  # MuJoCo: qpos0 = ref, qpos_spring = springref (both default 0)
+                if jt == JNT_BALL and (ref != 0.0 or sref != 0.0):
+                    raise ValueError(f"joint {jn}: ref / springref have no meaning on a joint of type 'ball' (got ref={ref!r}, springref={sref!r})")
                 # actuatorfrcrange: the joint's total actuator force is clamped (what URDF-derived exports make of an <effort> limit)
                 frc = None
                 if "actuatorfrcrange" in a:
@@ -616,11 +628,13 @@ def parse_mjcf(xml: str, name: str = "mjcf", base_dir: Optional[Path] = None) ->
                         frc = tuple(_floats(a["actuatorfrcrange"], 2, what))
                 elif a.get("actuatorfrclimited") == "true":
                     raise ValueError(f"{what}: actuatorfrclimited='true' without actuatorfrcrange")
-                joints.append(JointSpec(jn, jt, pos=tuple(_floats(a.get("pos", "0 0 0"), 3, what)), axis=tuple(_floats(a.get("axis", "0 0 1"), 3, what)), range=rng,
+                joints.append(JointSpec(jn, jt, pos=tuple(_floats(a.get("pos", "0 0 0"), 3, what)), axis=(0.0, 0.0, 1.0) if jt == JNT_BALL else tuple(_floats(a.get("axis", "0 0 1"), 3, what)), range=rng,  # (a ball joint ignores `axis`, as MuJoCo does)
                                         damping=float(a.get("damping", "0")), armature=float(a.get("armature", "0")), stiffness=float(a.get("stiffness", "0")),
                                         ref=comp.ang(ref) if jt == JNT_HINGE else ref, springref=comp.ang(sref) if jt == JNT_HINGE else sref, actuatorfrcrange=frc,
                                         solreflimit=tuple(_floats(a["solreflimit"], 2, what)) if "solreflimit" in a else None,
                                         solimplimit=None if limp is None else tuple(limp + list(_MJ_SOLIMP[len(limp):])), margin=float(a.get("margin", "0"))))
+                if jt == JNT_BALL:
+                    joints[-1].springref = None  # (qpos_spring of a ball joint is the identity quaternion)
             elif ch.tag == "geom":
                 kind, gs, part = geom_spec(dfl.resolve("geom", ch, cc), what)
                 if kind == "plane":
@@ -643,6 +657,10 @@ def parse_mjcf(xml: str, name: str = "mjcf", base_dir: Optional[Path] = None) ->
             inertial = (m, tuple(ipos), tuple(iquat), tuple(diag))
         elif inertial is None:
             raise ValueError(f"body {bname}: no <inertial> (inertiafromgeom='false')")
+        for j in joints:
+            if j.type == JNT_BALL and len(joints) > 1:
+                raise ValueError(f"body {bname}: ball joint {j.name!r} must be the only joint of its body (it shares it with "
+                                 f"{', '.join(repr(o.name) for o in joints if o is not j)}): MuJoCo forms a ball joint's axes from the body's final orientation")
         if any(j.type == JNT_FREE for j in joints):
             free_z.append(pos[2])
             if len(free_z) == 1:  # ModelSpec keeps the height of the first free root separately (qpos0[2] = free_root_z)
@@ -692,6 +710,7 @@ def parse_mjcf(xml: str, name: str = "mjcf", base_dir: Optional[Path] = None) ->
             b.mass, b.inertia = b.mass * scale, tuple(x * scale for x in b.inertia)
 
     joint_names = {j.name for b in bodies for j in b.joints}
+    ball_joints = {j.name for b in bodies for j in b.joints if j.type == JNT_BALL}
     acts: List[ActuatorSpec] = []
     act_el = _merged(root, "actuator")
     for ch in (act_el if act_el is not None else []):
@@ -704,6 +723,14 @@ def parse_mjcf(xml: str, name: str = "mjcf", base_dir: Optional[Path] = None) ->
         if a["joint"] not in joint_names:
             raise ValueError(f"{what}: unknown joint {a['joint']!r}")
         gear = _floats(a.get("gear", "1"))[0]
+        on_ball = a["joint"] in ball_joints
+        if on_ball:
+            # MuJoCo's joint transmission on a ball joint: gear's first three components, the torque axis in the joint's frame
+            what = f"<actuator><{ch.tag} name={a.get('name', '')!r} joint={a['joint']!r}>"
+            gear = tuple((_floats(a.get("gear", "1")) + [0.0, 0.0])[:3])
+            if ch.tag in ("position", "velocity") or (ch.tag == "general" and a.get("biastype", "none") != "none"):
+                raise ValueError(f"{what}: on a ball joint only <motor> and <general biastype='none'> are supported (the length of a position / velocity "
+                                 "servo there is an axis-angle projection)")
 
         def rng(key: str, flag: str):
             if key not in a:
@@ -932,6 +959,8 @@ def to_mjcf(spec: ModelSpec) -> str:
             a = dict(name=j.name, type="hinge" if j.type == JNT_HINGE else "slide", pos=_fmt(j.pos), axis=_fmt(j.axis), damping=repr(float(j.damping)),
                      armature=repr(float(j.armature)), stiffness=repr(float(j.stiffness)), ref=repr(float(j.ref)),
                      springref=repr(float(j.ref if j.springref is None else j.springref)))
+            if j.type == JNT_BALL:  # (no axis, ref or springref)
+                a = dict(name=j.name, type="ball", pos=_fmt(j.pos), damping=repr(float(j.damping)), armature=repr(float(j.armature)), stiffness=repr(float(j.stiffness)))
             if j.actuatorfrcrange is not None:
                 a.update(actuatorfrcrange=_fmt(j.actuatorfrcrange), actuatorfrclimited="true")
             if j.range is not None:
@@ -952,12 +981,14 @@ def to_mjcf(spec: ModelSpec) -> str:
                           contype=str(g.contype), conaffinity=str(g.conaffinity), **({"name": g.name} if g.name else {}), **_contact_attrs(g.solref, g.solimp, g.solmix, g.condim, g.margin, g.gap))
     act = ET.SubElement(root, "actuator")
     for a in spec.actuators:
-        kw = dict(joint=a.joint, gear=repr(float(a.gear)))
+        kw = dict(joint=a.joint, gear=repr(float(a.gear)) if np.ndim(a.gear) == 0 else _fmt(a.gear))
         if a.ctrlrange is not None:
             kw["ctrlrange"] = _fmt(a.ctrlrange)
         if a.forcerange is not None:
             kw["forcerange"] = _fmt(a.forcerange)
-        if a.gain is not None:
+        if a.gain is not None and np.ndim(a.gear) != 0:  # (on a ball joint: no bias)
+            ET.SubElement(act, "general", gainprm=repr(float(a.gain)), **kw)
+        elif a.gain is not None:
             ET.SubElement(act, "general", gainprm=repr(float(a.gain)), biastype="affine", biasprm=_fmt(a.bias), **kw)
         elif a.kp != 0:
             ET.SubElement(act, "position", kp=repr(float(a.kp)), kv=repr(float(a.kv)), **kw)

@@ -35,7 +35,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-JNT_FREE, JNT_HINGE, JNT_SLIDE = 0, 2, 3  # (ball=1 unsupported)
+JNT_FREE, JNT_BALL, JNT_HINGE, JNT_SLIDE = 0, 1, 2, 3  # MuJoCo's mjtJoint numbering
 GEOM_SPHERE, GEOM_CAPSULE, GEOM_CYLINDER, GEOM_BOX, GEOM_MESH = 2, 3, 5, 6, 7  # MuJoCo's mjtGeom numbering
 
 MJ_MINVAL = 1e-15
@@ -59,7 +59,7 @@ class JointSpec:
     type: int = JNT_HINGE
     pos: Sequence[float] = (0.0, 0.0, 0.0)
     axis: Sequence[float] = (0.0, 0.0, 1.0)
-    range: Optional[Tuple[float, float]] = None
+    range: Optional[Tuple[float, float]] = None  # (a ball joint: (0, max) - a limit on the rotation angle whatever the axis)
     damping: float = 0.0
     armature: float = 0.0
     stiffness: float = 0.0
@@ -114,7 +114,7 @@ class BodySpec:
 @dataclass
 class ActuatorSpec:
     joint: str
-    gear: float = 1.0
+    gear: float = 1.0  # (an actuator on a ball joint: three components - the scalar force times them is the torque on the joint's three dofs)
     kp: float = 0.0  # position servo: force = kp*(ctrl - length) - kv*velocity ; kp=0 -> motor (gain 1)
     kv: float = 0.0
     # MJCF <general gaintype="fixed" biastype="affine"> / <velocity>: force = gain * ctrl + bias[0] + bias[1] * length + bias[2] * velocity; when
@@ -476,6 +476,28 @@ def compile_model(spec: ModelSpec) -> CompiledModel:
                     raise ValueError(f"joint {j.name}: actuatorfrcrange {tuple(j.actuatorfrcrange)} is empty")
                 dof_actfrcrange.append([-F32_MAX, F32_MAX] if j.actuatorfrcrange is None else [float(j.actuatorfrcrange[0]), float(j.actuatorfrcrange[1])])
                 nv += 1
+            elif j.type == JNT_BALL:
+                # a quaternion in qpos, three angular dofs in the body's frame (MuJoCo forms a ball joint's axes from the body's final
+                # orientation: it stands alone in its body here)
+                if len(b.joints) != 1:
+                    raise ValueError(f"body {b.name}: ball joint {j.name!r} must be the only joint of its body (it shares it with "
+                                     f"{', '.join(repr(o.name) for o in b.joints if o is not j)})")
+                if j.ref != 0.0 or (j.springref is not None and j.springref != 0.0):
+                    raise ValueError(f"joint {j.name}: ref / springref have no meaning on a ball joint (got ref {j.ref!r}, springref {j.springref!r})")
+                if j.range is not None and not (float(j.range[0]) == 0.0 and float(j.range[1]) > 0.0):
+                    raise ValueError(f"joint {j.name}: joint type 'ball' takes range=\"0 max\" (a limit on the rotation angle), got {tuple(j.range)}")
+                if j.actuatorfrcrange is not None and not (j.actuatorfrcrange[0] < j.actuatorfrcrange[1]):
+                    raise ValueError(f"joint {j.name}: actuatorfrcrange {tuple(j.actuatorfrcrange)} is empty")
+                qpos0 += [1.0, 0.0, 0.0, 0.0]
+                qpos_spring += [1.0, 0.0, 0.0, 0.0]
+                nq += 4
+                for _ in range(3):
+                    dof_bodyid.append(bi)
+                    dof_jntid.append(jid)
+                    dof_armature.append(j.armature)
+                    dof_damping.append(j.damping)
+                    dof_actfrcrange.append([-F32_MAX, F32_MAX] if j.actuatorfrcrange is None else [float(j.actuatorfrcrange[0]), float(j.actuatorfrcrange[1])])
+                nv += 3
             else:
                 raise ValueError(f"unsupported joint type {j.type}")
         body_dofnum[bi] = nv - (body_dofadr[bi] if body_dofadr[bi] >= 0 else nv)
@@ -539,7 +561,7 @@ def compile_model(spec: ModelSpec) -> CompiledModel:
         b, da = jnt_bodyid[j], jnt_dofadr[j]
         before = ancdof[body_parent[b]]
         for jj in range(body_jntadr[b], j):  # earlier joints of the same body
-            nd = 6 if jnt_type[jj] == JNT_FREE else 1
+            nd = 6 if jnt_type[jj] == JNT_FREE else 3 if jnt_type[jj] == JNT_BALL else 1
             for d in range(jnt_dofadr[jj], jnt_dofadr[jj] + nd):
                 before |= 1 << int(d)
         if jnt_type[j] == JNT_FREE:
@@ -550,18 +572,21 @@ def compile_model(spec: ModelSpec) -> CompiledModel:
                 trans |= 1 << int(da + k)
             for k in range(3, 6):
                 velmask[da + k] = trans  # all three rotational cdof_dot use the velocity after translation only
+        elif jnt_type[j] == JNT_BALL:
+            for k in range(3):
+                velmask[da + k] = before  # mj_comVel forms the three cdof_dot of a ball joint before any of its dofs is added
         else:
             velmask[da] = before
-    dof_qposadr = np.full(nv, -1, np.int32)
+    dof_qposadr = np.full(nv, -1, np.int32)  # (scalar coordinates only: -1 for the dofs of free and ball joints)
     for j in range(njnt):
-        if jnt_type[j] != JNT_FREE:
+        if jnt_type[j] in (JNT_HINGE, JNT_SLIDE):
             dof_qposadr[jnt_dofadr[j]] = jnt_qposadr[j]
 
     def _m64(a):
         a = np.asarray(a, np.uint64)
         return np.stack([(a & np.uint64(0xFFFFFFFF)).astype(np.uint32), (a >> np.uint64(32)).astype(np.uint32)], -1).astype(np.uint32).view(np.int32).reshape(-1)
 
-    # actuators (joint transmission on hinge/slide only)
+    # actuators (joint transmission on hinge / slide joints; a motor on a ball joint: gear of three components)
     nu = len(spec.actuators)
     act_dofid = np.zeros(nu, np.int32)
     act_qposadr = np.zeros(nu, np.int32)
@@ -578,6 +603,25 @@ def compile_model(spec: ModelSpec) -> CompiledModel:
             raise ValueError("actuator on a free joint is not supported")
         act_dofid[ai] = jnt_dofadr[jid]
         act_qposadr[ai] = jnt_qposadr[jid]
+        if jnt_type[jid] == JNT_BALL:
+            # MuJoCo's joint transmission on a ball joint: the scalar force gain * ctrl times the gear's three components is the torque on the
+            # joint's three dofs.  Such an actuator has no length, hence no bias: its act_bias row carries the gear vector (act_gear stays 0),
+            # so that the actuator tables keep their shapes - and a model without one its bytes
+            gear3 = np.asarray(a.gear, np.float64).reshape(-1)
+            if gear3.size != 3:
+                raise ValueError(f"actuator on ball joint {a.joint}: gear needs three components (the torque axis in the joint's frame), got {a.gear!r}")
+            if a.kp != 0 or a.kv != 0 or any(float(x) != 0.0 for x in a.bias):
+                raise ValueError(f"actuator on ball joint {a.joint}: only a motor (fixed gain, no bias) acts on a ball joint - a position / velocity "
+                                 "servo's length would be an axis-angle projection, which is not supported")
+            act_gain[ai] = 1.0 if a.gain is None else a.gain
+            act_bias[ai] = gear3
+            if a.ctrlrange is not None:
+                act_ctrlrange[ai] = a.ctrlrange
+                act_ctrllimited[ai] = 1
+            if a.forcerange is not None:
+                act_forcerange[ai] = a.forcerange
+                act_forcelimited[ai] = 1
+            continue
         act_gear[ai] = a.gear
         if a.gain is not None:
             act_gain[ai] = a.gain
@@ -927,6 +971,9 @@ def compile_model(spec: ModelSpec) -> CompiledModel:
     put("lim_margin", lim_margin)
     put("cvx_margin", cvx_margin)
 
+    if JNT_BALL in jnt_type:  # (only for a model that has some, like neq: every other model keeps its set of tables)
+        put("nball", sum(1 for x in jnt_type if x == JNT_BALL), np.int32)
+
     cm = CompiledModel(spec.name, t, names, joint_names, spec.meaninertia)
     _set_const(cm)
     if spec.equalities:
@@ -976,7 +1023,7 @@ def _compile_equalities(cm: CompiledModel, eqs: Sequence[EqualitySpec]) -> None:
                     raise ValueError(f"{what}: unknown {k} {jn!r}")
                 j = cm.joint_names.index(jn)
                 if int(t["jnt_type"][j]) not in (JNT_HINGE, JNT_SLIDE):
-                    raise ValueError(f"{what}: {k} {jn!r} is a free joint (a joint equality couples hinge / slide joints)")
+                    raise ValueError(f"{what}: {k} {jn!r} is a {'ball' if int(t['jnt_type'][j]) == JNT_BALL else 'free'} joint (a joint equality couples hinge / slide joints)")
                 ids.append(j)
             if ids[0] < 0:
                 raise ValueError(f"{what}: joint1 is required")
@@ -1034,7 +1081,7 @@ def _forward_position0(cm: CompiledModel):
             else:
                 xanchor[j] = pos + _qrot(quat, t["jnt_pos"][j])
                 xaxis[j] = _qrot(quat, t["jnt_axis"][j])
-                # qpos == qpos0 -> zero joint displacement
+                # qpos == qpos0 -> zero joint displacement (a ball joint: the identity quaternion)
         xpos[b], xquat[b] = pos, quat
     xipos = np.array([xpos[b] + _qrot(xquat[b], t["body_ipos"][b]) for b in range(nb)])
     ximat = np.array([_qmat(_qmul(xquat[b], t["body_iquat"][b])) for b in range(nb)])
@@ -1064,6 +1111,11 @@ def _forward_position0(cm: CompiledModel):
                 ax = R[:, k]
                 cdof[da + 3 + k, :3] = ax
                 cdof[da + 3 + k, 3:] = np.cross(ax, off)
+        elif t["jnt_type"][j] == JNT_BALL:  # the free joint's rotational rows, about the joint anchor
+            R = _qmat(xquat[b])
+            for k in range(3):
+                cdof[da + k, :3] = R[:, k]
+                cdof[da + k, 3:] = np.cross(R[:, k], off)
         elif t["jnt_type"][j] == JNT_HINGE:
             cdof[da, :3] = xaxis[j]
             cdof[da, 3:] = np.cross(xaxis[j], off)
@@ -1109,6 +1161,9 @@ def _set_const(cm: CompiledModel) -> None:
             da = t["jnt_dofadr"][j]
             dof_inv[da:da + 3] = dof_inv[da:da + 3].mean()
             dof_inv[da + 3:da + 6] = dof_inv[da + 3:da + 6].mean()
+        elif t["jnt_type"][j] == JNT_BALL:
+            da = t["jnt_dofadr"][j]
+            dof_inv[da:da + 3] = dof_inv[da:da + 3].mean()
     t["dof_invweight0"] = dof_inv
     body_inv = np.zeros((nb, 2))
     for b in range(1, nb):

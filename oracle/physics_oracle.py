@@ -7,8 +7,10 @@ PARITY UNPINNED.  The reference calls `brax.envs.base.PipelineEnv.pipeline_step`
 (`requirements.txt:8-13`; likely brax 0.10-0.11 / mujoco 3.2.x on 2024-10-16),
 absent from /root/reference and not installable here.  This file restates the
 *published* MuJoCo/MJX algorithm for the model class the engine supports
-(free / hinge / slide joints, sphere & capsule geoms against one ground plane,
-joint limits, pyramidal friction cones, affine-bias actuators on joints):
+(free / ball / hinge / slide joints, sphere, capsule, cylinder & convex geoms against
+one ground plane and each other, connect / joint equalities, joint limits, pyramidal
+friction cones with per-row solref / solimp / margin / condim, affine-bias actuators
+on joints):
 
   fwd_position : kinematics, com_pos (subtree_com, cinert, cdof), crb (dense M),
                  collision (plane-sphere, plane-capsule), make_constraint
@@ -19,8 +21,13 @@ joint limits, pyramidal friction cones, affine-bias actuators on joints):
   euler        : implicit joint damping, semi-implicit integration
 
 It is validated by physical invariants and analytic cases
-(tests/test_oracle_physics.py) and pins the HIP kernel through the committed
-fixtures in tests/golden/.  Agreement with MJX itself was never measured.
+(tests/test_oracle_physics.py; closed forms and models stepped along another code
+path in tests/test_contact_params.py, test_equality.py, test_ball_joints.py) and pins
+the HIP kernel through the committed fixtures in tests/golden/.  Agreement with MJX
+itself was never measured: the rules are MuJoCo's / MJX's as their documentation and
+published source state them, and each method below names the rule it restates.
+A feature a model does not use (compiled tables `cparam` = 0, `neq` = 0, no joint of
+type JNT_BALL) changes no value: tests/golden/oracle_features.npz holds it so.
 
 All arrays are batched over environments: shape [N, ...].  dtype-generic
 (float64 for the reference answer, float32 to mimic working precision).
@@ -29,11 +36,12 @@ All arrays are batched over environments: shape [N, ...].  dtype-generic
 from __future__ import annotations
 
 import math
-from typing import Dict, NamedTuple
+from typing import Dict
 
 import numpy as np
 
-JNT_FREE, JNT_HINGE, JNT_SLIDE = 0, 2, 3
+JNT_FREE, JNT_BALL, JNT_HINGE, JNT_SLIDE = 0, 1, 2, 3
+EQ_CONNECT, EQ_JOINT = 0, 1
 MJ_MINVAL = 1e-15
 MJ_MINIMP = 0.0001
 MJ_MAXIMP = 0.9999
@@ -92,6 +100,15 @@ def quat_integrate(q, w, dt):
     ax = w / np.where(n > 0, n, 1.0)[..., None]
     dq = axis_angle_quat(ax, n * dt)
     return safe_normalize(qmul(q, dq))
+
+
+def quat_rotvec(q):
+    """Rotation vector of (unit) quaternions [..., 4]: axis x angle with the angle wrapped into (-pi, pi] (mju_quat2Vel, dt = 1)."""
+    v = q[..., 1:]
+    s = np.linalg.norm(v, axis=-1)
+    ang = 2.0 * np.arctan2(s, q[..., 0])
+    ang = np.where(ang > np.pi, ang - 2.0 * np.pi, ang)
+    return v * (ang / np.where(s > 0, s, 1.0) * (s > 0))[..., None]
 
 
 def inert_mul(i, v):
@@ -465,7 +482,9 @@ class Physics:
         self.nbody, self.njnt = int(t["nbody"]), int(t["njnt"])
         self.ncon, self.nlimit = int(t["ncon"]), int(t["nlimit"])
         self.npair = int(t.get("npair", 0))
-        self.nefc = self.nlimit + 4 * self.ncon
+        self.neq = int(t.get("neq", 0))
+        self.cparam = int(t.get("cparam", 0)) != 0  # rows carry their own solref / solimp / margin / condim (tables con_*, lim_*, cvx_margin)
+        self.nefc = self.neq + self.nlimit + 4 * self.ncon
         self.n_frames = n_frames
         self.timestep = float(t["timestep"])
         self.dt = self.timestep * n_frames
@@ -474,14 +493,11 @@ class Physics:
         for b in range(1, self.nbody):
             p = t["body_parent"][b]
             self.body_lastdof[b] = (t["body_dofadr"][b] + t["body_dofnum"][b] - 1) if t["body_dofnum"][b] > 0 else self.body_lastdof[p]
-        # qpos index of each hinge/slide dof, -1 for free-joint dofs (for passive springs / limits)
-        self.dof_qposadr = np.full(self.nv, -1, np.int64)
-        for j in range(self.njnt):
-            if t["jnt_type"][j] != JNT_FREE:
-                self.dof_qposadr[t["jnt_dofadr"][j]] = t["jnt_qposadr"][j]
 
     # -- fwd_position ---------------------------------------------------------
     def kinematics(self, d: PhysState) -> None:
+        """mj_kinematics.  A ball joint's local rotation is the normalised joint quaternion about the joint anchor: the hinge's form with the
+        rotation taken from qpos (four coordinates) instead of axis / angle."""
         t, nb = self.t, self.nbody
         N = d.qpos.shape[0]
         dt = self.dtype
@@ -505,13 +521,15 @@ class Physics:
                     anchor = pos + qrot(quat, t["jnt_pos"][j])
                     axis = qrot(quat, t["jnt_axis"][j])
                     xanchor[:, j], xaxis[:, j] = anchor, axis
-                    disp = d.qpos[:, qa] - t["qpos0"][qa]
-                    if jt == JNT_HINGE:
-                        qloc = axis_angle_quat(np.broadcast_to(t["jnt_axis"][j], (N, 3)), disp)
+                    if jt == JNT_BALL:
+                        quat = qmul(quat, safe_normalize(d.qpos[:, qa:qa + 4]))
+                        pos = anchor - qrot(quat, t["jnt_pos"][j])
+                    elif jt == JNT_HINGE:
+                        qloc = axis_angle_quat(np.broadcast_to(t["jnt_axis"][j], (N, 3)), d.qpos[:, qa] - t["qpos0"][qa])
                         quat = qmul(quat, qloc)
                         pos = anchor - qrot(quat, t["jnt_pos"][j])  # re-anchor
                     else:  # slide
-                        pos = pos + axis * disp[:, None]
+                        pos = pos + axis * (d.qpos[:, qa] - t["qpos0"][qa])[:, None]
             xpos[:, b], xquat[:, b] = pos, safe_normalize(quat)
         d["xpos"], d["xquat"], d["xanchor"], d["xaxis"] = xpos, xquat, xanchor, xaxis
         d["xmat"] = qmat(xquat)
@@ -519,6 +537,8 @@ class Physics:
         d["ximat"] = qmat(qmul(xquat, np.broadcast_to(t["body_iquat"][None], xquat.shape)))
 
     def com_pos(self, d: PhysState) -> None:
+        """mj_comPos.  cdof of a ball joint: the three columns of the body's rotation matrix about the anchor (the free joint's rotational rows
+        with the anchor offset)."""
         t, nb, nv = self.t, self.nbody, self.nv
         N = d.qpos.shape[0]
         dt = self.dtype
@@ -554,6 +574,11 @@ class Physics:
                     ax = d.xmat[:, b, :, k]
                     cdof[:, da + 3 + k, :3] = ax
                     cdof[:, da + 3 + k, 3:] = np.cross(ax, offj)
+            elif jt == JNT_BALL:
+                for k in range(3):
+                    ax = d.xmat[:, b, :, k]
+                    cdof[:, da + k, :3] = ax
+                    cdof[:, da + k, 3:] = np.cross(ax, offj)
             elif jt == JNT_HINGE:
                 cdof[:, da, :3] = d.xaxis[:, j]
                 cdof[:, da, 3:] = np.cross(d.xaxis[:, j], offj)
@@ -600,7 +625,8 @@ class Physics:
     def collision(self, d: PhysState) -> None:
         """Every candidate keeps a slot (MJX static shapes).  The first ncon - npair slots are ground contacts (MJX
         collision_primitive.plane_sphere / plane_capsule, plane_cylinder, collision_convex.plane_convex for boxes and meshes), the last npair are geom-geom
-        pairs (sphere_sphere / sphere_capsule / capsule_capsule: one contact each)."""
+        pairs (sphere_sphere / sphere_capsule / capsule_capsule: one contact each).  With per-row parameters plane_convex keeps the hull
+        vertices within the geom's includemargin of the plane: candidates are those deeper than max(-includemargin, deepest - 1 mm)."""
         t = self.t
         N = d.qpos.shape[0]
         nc, npair = self.ncon, self.npair
@@ -619,7 +645,8 @@ class Physics:
             R = qmat(d.xquat[:, b])                                                        # [N, 3, 3]: world = R . local
             nl = R[:, 2, :]                                                                # the plane's normal (+z) in the body frame
             support = (t["plane_z"] - d.xpos[:, b, 2])[:, None] - nl @ vert.T               # [N, V]: depth below the plane
-            idx = manifold_points(vert, support > np.maximum(0.0, support.max(1) - 1e-3)[:, None], nl)  # [N, 4]
+            mg = float(t["cvx_margin"][k]) if self.cparam else 0.0
+            idx = manifold_points(vert, support > np.maximum(-mg, support.max(1) - 1e-3)[:, None], nl)  # [N, 4]
             for j in range(4):
                 sel_pos[:, 4 * k + j] = vert[idx[:, j]]
                 sel_ok[:, 4 * k + j] = ~np.any(idx[:, :j] == idx[:, j:j + 1], axis=1)      # unique = first occurrence of the vertex
@@ -727,31 +754,101 @@ class Physics:
         imp = np.where(imp_x > 1.0, dmax, imp).astype(dt)
         return dt.type(k), dt.type(b), imp
 
+    def _row_params(self, kind: str, r: int):
+        """solref, solimp, margin, condim of limit row `r` (kind "lim") or contact slot `r` (kind "con"): the row's own where the model carries
+        per-row parameters (`cparam`: MuJoCo's mixing rules, applied by the compiler), else the model-wide values, margin 0 and condim 3."""
+        t = self.t
+        if not self.cparam:
+            wide = "limit" if kind == "lim" else "contact"
+            return t[wide + "_solref"], t[wide + "_solimp"], 0.0, 3
+        return t[kind + "_solref"][r], t[kind + "_solimp"][r], t[kind + "_margin"][r], (int(t["con_condim"][r]) if kind == "con" else 3)
+
+    def equality_rows(self, d: PhysState):
+        """MJX _instantiate_equality_connect / _joint.  connect: three rows, p1 - p2 in the world frame, jacp(p1, body1) - jacp(p2, body2).
+        joint: one row, q1 - ref1 - poly(q2 - ref2), +1 at dof1 and -dpoly/dq2 at dof2.
+        -> J [N, neq, nv], pos [N, neq], the norm of each row's element residual [N, neq], element of each row."""
+        t, N = self.t, d.qpos.shape[0]
+        J = np.zeros((N, self.neq, self.nv), self.dtype)
+        pos = np.zeros((N, self.neq), self.dtype)
+        for e, kind in enumerate(t["eq_type"]):
+            r0 = int(t["eq_rowadr"][e])
+            o1, o2 = (int(x) for x in t["eq_obj"][e])
+            if kind == EQ_CONNECT:
+                a = np.asarray(t["eq_anchor"][e], self.dtype)
+                p1 = d.xpos[:, o1] + qrot(d.xquat[:, o1], a[:3])
+                p2 = d.xpos[:, o2] + qrot(d.xquat[:, o2], a[3:])
+                pos[:, r0:r0 + 3] = p1 - p2
+                J[:, r0:r0 + 3] = self.jacp(d, p1, o1) - self.jacp(d, p2, o2)
+            else:
+                pc = np.asarray(t["eq_polycoef"][e], self.dtype)
+                qa1, da1 = int(t["jnt_qposadr"][o1]), int(t["jnt_dofadr"][o1])
+                p = d.qpos[:, qa1] - t["qpos0"][qa1] - pc[0]
+                J[:, r0, da1] = 1.0
+                if o2 >= 0:
+                    qa2, da2 = int(t["jnt_qposadr"][o2]), int(t["jnt_dofadr"][o2])
+                    x = d.qpos[:, qa2] - t["qpos0"][qa2]
+                    p = p - (pc[1] * x + pc[2] * x ** 2 + pc[3] * x ** 3 + pc[4] * x ** 4)
+                    J[:, r0, da2] = -(pc[1] + 2 * pc[2] * x + 3 * pc[3] * x ** 2 + 4 * pc[4] * x ** 3)
+                pos[:, r0] = p
+        row = np.asarray(t["eq_row"])
+        nrm = np.zeros_like(pos)
+        for e in range(len(t["eq_type"])):
+            m = row == e
+            nrm[:, m] = np.sqrt(np.sum(pos[:, m] ** 2, -1, keepdims=True))
+        return J, pos, nrm, row
+
     def make_constraint(self, d: PhysState) -> None:
-        """Rows: joint limits (1 each) then contacts (4 pyramid edges each). Inactive rows are zeroed."""
-        t, nv = self.t, self.nv
+        """Rows in MJX's order: equality rows, joint limits (1 each), contacts (4 pyramid edges each).  Inactive rows are zeroed.
+          equality : always active; the impedance of an element's rows is that of the norm of its residual (MuJoCo's rule for an equality of
+                     dimension > 1)
+          limit    : active below the joint's margin, pos = dist - margin.  Ball (MJX _instantiate_limit_ball): angle >= 0 of the joint quaternion
+                     about whatever axis, dist = range[1] - angle, the row is -axis on the joint's three dofs, invweight dof_invweight0[dofadr]
+          contact  : active below the slot's includemargin, pos = dist - includemargin; a frictionless (condim 1) contact has the single normal
+                     row, its three other rows stay inert and keep the slot's layout"""
+        t, nv, ne = self.t, self.nv, self.neq
         N = d.qpos.shape[0]
         dt = self.dtype
         J = np.zeros((N, self.nefc, nv), dt)
         pos = np.zeros((N, self.nefc), dt)
         invw = np.zeros((N, self.nefc), dt)
         act = np.zeros((N, self.nefc), bool)
-        row = 0
-        for jid in t["lim_jntid"]:
+        kk = np.zeros((N, self.nefc), dt)
+        bb = np.zeros((N, self.nefc), dt)
+        imp = np.ones((N, self.nefc), dt)
+        if ne:
+            J[:, :ne], pos[:, :ne], nrm, elem = self.equality_rows(d)
+            invw[:, :ne] = np.asarray(t["eq_invweight"], dt)[elem]
+            act[:, :ne] = True
+            for r in range(ne):
+                kk[:, r], bb[:, r], imp[:, r] = self._kbi(t["eq_solref"][elem[r]], t["eq_solimp"][elem[r]], nrm[:, r])
+        row = ne
+        for r, jid in enumerate(t["lim_jntid"]):
             qa, da = t["jnt_qposadr"][jid], t["jnt_dofadr"][jid]
-            dmin = d.qpos[:, qa] - t["jnt_range"][jid, 0]
-            dmax = t["jnt_range"][jid, 1] - d.qpos[:, qa]
-            p = np.minimum(dmin, dmax)
-            a = p < 0
-            J[:, row, da] = np.where(a, np.where(dmin < dmax, 1.0, -1.0), 0.0)
+            solref, solimp, margin, _ = self._row_params("lim", r)
+            if t["jnt_type"][jid] == JNT_BALL:
+                v = quat_rotvec(safe_normalize(d.qpos[:, qa:qa + 4]))
+                angle = np.linalg.norm(v, axis=-1)
+                axis = v / (angle + dt.type(1e-6) * (angle == 0))[:, None]  # MJX normalize_with_norm
+                p = t["jnt_range"][jid, 1] - angle - margin
+                a = p < 0
+                J[:, row, da:da + 3] = np.where(a[:, None], -axis, 0.0)
+            else:
+                dmin = d.qpos[:, qa] - t["jnt_range"][jid, 0]
+                dmax = t["jnt_range"][jid, 1] - d.qpos[:, qa]
+                p = np.minimum(dmin, dmax) - margin
+                a = p < 0
+                J[:, row, da] = np.where(a, np.where(dmin < dmax, 1.0, -1.0), 0.0)
             pos[:, row] = np.where(a, p, 0.0)
             invw[:, row] = np.where(a, t["dof_invweight0"][da], 0.0)
             act[:, row] = a
+            k_, b_, i_ = self._kbi(solref, solimp, pos[:, row:row + 1])
+            kk[:, row], bb[:, row], imp[:, row] = k_, b_, i_[:, 0]
             row += 1
-        k_l, b_l, imp_l = self._kbi(t["limit_solref"], t["limit_solimp"], pos[:, :self.nlimit])
         for c in range(self.ncon):
             b = t["con_bodyid"][c]
-            a = d.con_dist[:, c] < 0
+            solref, solimp, mg, condim = self._row_params("con", c)
+            frictionless = condim == 1
+            a = d.con_dist[:, c] < mg
             jp = self.jacp(d, d.con_pos[:, c], b)  # [N,3,nv]   (ground contacts: body1 = world -> zero)
             tw = t["body_invweight0"][b, 0]
             if c >= self.ncon - self.npair:  # geom-geom: relative motion of body2 against body1, both translational weights
@@ -760,29 +857,31 @@ class Physics:
                 tw = tw + t["body_invweight0"][b1, 0]
             jc = np.einsum("nij,njv->niv", d.con_frame[:, c], jp)  # rows: normal, t1, t2
             fri = t["con_friction"][c]
-            iw = (tw + fri[0] * fri[0] * tw) * 2 * fri[0] * fri[0] / t["impratio"]
+            iw = tw if frictionless else (tw + fri[0] * fri[0] * tw) * 2 * fri[0] * fri[0] / t["impratio"]
             r = row
             for k in (1, 2):
                 for s in (1.0, -1.0):
-                    J[:, r] = np.where(a[:, None], jc[:, 0] + jc[:, k] * (s * fri[0]), 0.0)  # condim 3: both tangents use the sliding coefficient
-                    pos[:, r] = np.where(a, d.con_dist[:, c], 0.0)
-                    invw[:, r] = np.where(a, iw, 0.0)
-                    act[:, r] = a
+                    on = a & (not frictionless or r == row)
+                    Jr = jc[:, 0] if frictionless else jc[:, 0] + jc[:, k] * (s * fri[0])  # condim 3: both tangents use the sliding coefficient
+                    J[:, r] = np.where(on[:, None], Jr, 0.0)
+                    pos[:, r] = np.where(on, d.con_dist[:, c] - mg, 0.0)
+                    invw[:, r] = np.where(on, iw, 0.0)
+                    act[:, r] = on
                     r += 1
+            k_, b_, i_ = self._kbi(solref, solimp, pos[:, row:row + 4])
+            kk[:, row:row + 4], bb[:, row:row + 4], imp[:, row:row + 4] = k_, b_, i_
             row += 4
-        k_c, b_c, imp_c = self._kbi(t["contact_solref"], t["contact_solimp"], pos[:, self.nlimit:])
-        imp = np.concatenate([imp_l, imp_c], 1)
-        kk = np.concatenate([np.full((N, self.nlimit), k_l, dt), np.full((N, 4 * self.ncon), k_c, dt)], 1)
-        bb = np.concatenate([np.full((N, self.nlimit), b_l, dt), np.full((N, 4 * self.ncon), b_c, dt)], 1)
         R = np.maximum(invw * (1 - imp) / imp, MJ_MINVAL)
         jv = np.einsum("nrv,nv->nr", J, d.qvel)
         d["efc_J"] = J
         d["efc_D"] = np.where(act, 1.0 / R, 0.0).astype(dt)  # inactive rows are inert (J=0, aref=0)
-        d["efc_aref"] = (-bb * jv - kk * imp * pos).astype(dt)
+        d["efc_aref"] = np.where(act, -bb * jv - kk * imp * pos, 0.0).astype(dt)
         d["efc_active_row"] = act
+        d["eq_pos"] = pos[:, :ne]
 
     # -- fwd_velocity -----------------------------------------------------------
     def com_vel(self, d: PhysState) -> None:
+        """mj_comVel.  All three cdof_dot of a ball joint use the velocity accumulated BEFORE the joint, then the three dofs are added."""
         t, nb, nv = self.t, self.nbody, self.nv
         N = d.qpos.shape[0]
         cvel = np.zeros((N, nb, 6), self.dtype)
@@ -798,6 +897,11 @@ class Physics:
                         cdof_dot[:, da + k] = cross_motion(v, d.cdof[:, da + k])
                     for k in range(3, 6):
                         v = v + d.cdof[:, da + k] * d.qvel[:, da + k, None]
+                elif t["jnt_type"][j] == JNT_BALL:
+                    for k in range(3):
+                        cdof_dot[:, da + k] = cross_motion(v, d.cdof[:, da + k])
+                    for k in range(3):
+                        v = v + d.cdof[:, da + k] * d.qvel[:, da + k, None]
                 else:
                     cdof_dot[:, da] = cross_motion(v, d.cdof[:, da])
                     v = v + d.cdof[:, da] * d.qvel[:, da, None]
@@ -805,14 +909,19 @@ class Physics:
         d["cvel"], d["cdof_dot"] = cvel, cdof_dot
 
     def passive(self, d: PhysState) -> None:
+        """Joint damping and springs (MJX passive).  A ball joint's stiffness acts on the rotation vector (axis x angle, angle in (-pi, pi]) of
+        the joint quaternion (mju_subQuat against the identity qpos_spring)."""
         t = self.t
         f = -t["dof_damping"][None] * d.qvel
-        for dof in range(self.nv):
-            qa = self.dof_qposadr[dof]
-            if qa >= 0:
-                stiff = t["jnt_stiffness"][t["dof_jntid"][dof]]
-                if stiff != 0:
-                    f[:, dof] -= stiff * (d.qpos[:, qa] - t["qpos_spring"][qa])
+        for j in range(self.njnt):
+            stiff, jt = t["jnt_stiffness"][j], t["jnt_type"][j]
+            if stiff == 0 or jt == JNT_FREE:
+                continue
+            qa, da = t["jnt_qposadr"][j], t["jnt_dofadr"][j]
+            if jt == JNT_BALL:
+                f[:, da:da + 3] -= stiff * quat_rotvec(safe_normalize(d.qpos[:, qa:qa + 4]))
+            else:
+                f[:, da] -= stiff * (d.qpos[:, qa] - t["qpos_spring"][qa])
         d["qfrc_passive"] = f
 
     def rne(self, d: PhysState) -> None:
@@ -833,6 +942,8 @@ class Physics:
 
     # -- actuation / acceleration -------------------------------------------------
     def fwd_actuation(self, d: PhysState) -> None:
+        """Affine-bias actuators on joints.  On a ball joint: a motor's scalar force (no length, no bias) times its gear's three components
+        (compiled into the actuator's bias row) on the three dofs.  Then actuatorfrcrange per dof."""
         t = self.t
         N = d.qpos.shape[0]
         qfrc = np.zeros((N, self.nv), self.dtype)
@@ -843,9 +954,15 @@ class Physics:
             length = t["act_gear"][None] * d.qpos[:, t["act_qposadr"]]
             velocity = t["act_gear"][None] * d.qvel[:, t["act_dofid"]]
             force = t["act_gain"][None] * ctrl + t["act_bias"][None, :, 0] + t["act_bias"][None, :, 1] * length + t["act_bias"][None, :, 2] * velocity
+            on_ball = t["jnt_type"][t["dof_jntid"][t["act_dofid"]]] == JNT_BALL
+            force = np.where(on_ball[None], t["act_gain"][None] * ctrl, force)
             flim = t["act_forcelimited"].astype(bool)
             force = np.where(flim[None], np.clip(force, t["act_forcerange"][:, 0], t["act_forcerange"][:, 1]), force)
-            np.add.at(qfrc, (slice(None), t["act_dofid"]), force * t["act_gear"][None])
+            for u, da in enumerate(t["act_dofid"]):
+                if on_ball[u]:
+                    qfrc[:, da:da + 3] += force[:, u, None] * t["act_bias"][u][None]
+                else:
+                    qfrc[:, da] += force[:, u] * t["act_gear"][u]
             d["actuator_force"] = force
         # MJX fwd_actuation: qfrc_actuator clipped to the joint's actuatorfrcrange where it has one (the table holds -FLT_MAX / FLT_MAX elsewhere)
         rng_ = np.asarray(t["dof_actfrcrange"], self.dtype)
@@ -859,6 +976,7 @@ class Physics:
     # -- constraint solver (MJX solver.py structure) -------------------------------
     def _ctx_update_constraint(self, d, c):
         active = c["Jaref"] < 0
+        active[:, :self.neq] = True  # equality rows are active on both signs of J qacc - aref (MJX: active.at[:ne].set(True)): force, cost, gradient
         c["active"] = active
         c["efc_force"] = d.efc_D * -c["Jaref"] * active
         c["qfrc_constraint"] = np.einsum("nrv,nr->nv", d.efc_J, c["efc_force"])
@@ -887,6 +1005,7 @@ class Physics:
     def _ls_point(self, alpha, jaref, jv, quad, quad_gauss):
         x = jaref + alpha[:, None] * jv
         active = x < 0
+        active[:, :self.neq] = True  # (and in the line search)
         q = np.sum(quad * active[:, None, :], -1) + quad_gauss  # [N,3]
         cost = alpha * alpha * q[:, 2] + alpha * q[:, 1] + q[:, 0]
         d0 = 2 * alpha * q[:, 2] + q[:, 1]
@@ -1001,6 +1120,8 @@ class Physics:
             if t["jnt_type"][j] == JNT_FREE:
                 qpos[:, qa:qa + 3] = d.qpos[:, qa:qa + 3] + h * qvel[:, da:da + 3]
                 qpos[:, qa + 3:qa + 7] = quat_integrate(d.qpos[:, qa + 3:qa + 7], qvel[:, da + 3:da + 6], h)
+            elif t["jnt_type"][j] == JNT_BALL:  # the free joint's quaternion integration with the joint's three velocities (as stored: in working precision)
+                qpos[:, qa:qa + 4] = quat_integrate(d.qpos[:, qa:qa + 4], qvel[:, da:da + 3].astype(self.dtype), h)
             else:
                 qpos[:, qa] = d.qpos[:, qa] + h * qvel[:, da]
         d["qpos"], d["qvel"] = qpos.astype(self.dtype), qvel.astype(self.dtype)

@@ -78,6 +78,17 @@ def physics_steps():
     np.savez_compressed(OUT / "physics_steps.npz", **{k: np.stack(v) for k, v in recs.items()}, height_min_z=np.array(rcfg.height_min_z))
 
 
+def oracle_features():
+    """Every built-in robot and fixture file through a forward pass and two steps of the oracle (tests/physics_harness.py::feature_record).  First
+    recorded when per-row contact parameters, equalities and ball joints were subclasses stacked on the oracle; the oracle that reads those
+    tables itself regenerates the same arrays on the recording machine."""
+    from physics_harness import feature_models, feature_record
+
+    rec = {f"{name}/{k}": v for name, make in feature_models() for k, v in feature_record(make()).items()}
+    assert all(np.isfinite(v).all() for v in rec.values())
+    np.savez_compressed(OUT / "oracle_features.npz", **rec)
+
+
 def philox():
     from backends import get_backend
 
@@ -89,6 +100,6 @@ def philox():
 
 
 if __name__ == "__main__":
-    ppo_small(); physics_steps(); philox()
+    ppo_small(); physics_steps(); oracle_features(); philox()
     for f in sorted(OUT.glob("*.npz")):
         print(f.name, f.stat().st_size, "bytes")

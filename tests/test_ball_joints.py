@@ -1,5 +1,5 @@
 """Ball joints (MuJoCo's fourth joint type) through the MJCF parser / writer, the model compiler, the blob validator and the environment kernel:
-known answers that pin the float64 reference (tests/ball_ref.py) against closed forms and against models today's oracle steps along another
+known answers that pin the float64 oracle (oracle/physics_oracle.py) against closed forms and against models today's oracle steps along another
 code path, the kernel against that reference on the emulator and the MI355X, bit-equality across kernel instantiations and Jacobian
 placements, mutated blobs, and reproducible training on the ball-joint humanoid."""
 
@@ -10,25 +10,17 @@ from pathlib import Path
 import numpy as np
 import pytest
 
-from ball_ref import BallPhysics, quat_rotvec
-from equality_ref import EqualityPhysics
 from minppo_amd import _native as nat
 from minppo_amd import mjcf
-from minppo_amd.model import BUILTIN_MODELS, JNT_BALL, JNT_FREE, JNT_HINGE, ActuatorSpec, JointSpec, compile_model, load_model
-from oracle.physics_oracle import Physics, PhysState, qmul
+from minppo_amd.model import BUILTIN_MODELS, JNT_BALL, JNT_HINGE, ActuatorSpec, JointSpec, compile_model, load_model
+from oracle.physics_oracle import Physics, PhysState, quat_rotvec
+from physics_harness import (SMOOTH_TOL, assert_bit_equal, assert_oracle_reproduces_the_recording, check_against_oracle, oracle_pair, probe, probe_and_steps, rot_quat,
+                             start_states, startup_kernel_equals_runtime_sized, step_once, trains_reproducibly, walking_states)
 
 f32, f64 = np.float32, np.float64
 GOLDEN = Path(__file__).parent / "golden"
 HUMANOID = str(GOLDEN / "ball_joints" / "ball_humanoid.xml")
 CHAIN = str(GOLDEN / "ball_joints" / "ball_chain.xml")
-
-
-def _rot_quat(v):
-    """Unit quaternions of rotation vectors [..., 3]."""
-    v = np.asarray(v, f64)
-    a = np.linalg.norm(v, axis=-1, keepdims=True)
-    u = v / np.where(a > 0, a, 1.0)
-    return np.concatenate([np.cos(a / 2), u * np.sin(a / 2)], -1)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------------
@@ -146,25 +138,13 @@ def _models_without_ball_joints():
     return out
 
 
-def test_reference_is_the_equality_reference_without_ball_joints():
-    """BallPhysics IS EqualityPhysics, bit for bit, on every built-in robot and every earlier fixture (a forward pass and two steps)."""
-    for name, make in _models_without_ball_joints():
-        cm = make()
-        assert "nball" not in cm.t, name
-        rng = np.random.default_rng(11)
-        N = 3
-        q = np.tile(np.asarray(cm.t["qpos0"], f64), (N, 1))
-        v = 0.1 * rng.standard_normal((N, cm.nv))
-        ctrl = 0.5 * rng.standard_normal((N, cm.nu))
-        res = []
-        for cls in (EqualityPhysics, BallPhysics):
-            ph = cls(cm.t)
-            d = ph.pipeline_init(q, v)
-            for _ in range(2):
-                d = ph.pipeline_step(d, ctrl)
-            res.append(d)
-        for k in ("qpos", "qvel", "qacc", "efc_J", "efc_D", "efc_aref", "qfrc_actuator", "qfrc_passive", "cvel", "cinert"):
-            assert np.array_equal(res[0][k], res[1][k]), (name, k)
+def test_oracle_reproduces_the_recording_without_ball_joints():
+    """Ball joints change nothing for a model without one: the oracle on every built-in robot and every earlier fixture against the recording
+    made before it knew the joint type."""
+    models = _models_without_ball_joints()
+    for name, make in models:
+        assert "nball" not in make().t, name
+    assert_oracle_reproduces_the_recording([n for n, _ in models])
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------------
@@ -191,10 +171,10 @@ def _state(ph, qpos, qvel, ctrl=None):
 def test_eulers_equations():
     """One body on a ball joint at its centre of mass, no gravity: I dw/dt = -(w x I w), componentwise, whatever the orientation."""
     cm = _top('<joint name="j" type="ball"/>')
-    ph = BallPhysics(cm.t)
+    ph = Physics(cm.t)
     rng = np.random.default_rng(0)
     N = 16
-    q = _rot_quat(rng.standard_normal((N, 3)))
+    q = rot_quat(rng.standard_normal((N, 3)))
     w = 3.0 * rng.standard_normal((N, 3))
     d = _state(ph, q, w)
     I = np.asarray(I123)
@@ -207,10 +187,10 @@ def test_ball_at_the_centre_of_mass_is_a_free_body_at_rest():
     stands: orientation and angular velocity follow each other over 500 steps (the same discrete map through different code).
     Measured: 0 (the two paths round alike)."""
     ball, free = _top('<joint name="j" type="ball"/>'), _top("<freejoint/>")
-    pb, pf = BallPhysics(ball.t), Physics(free.t)
+    pb, pf = Physics(ball.t), Physics(free.t)
     rng = np.random.default_rng(1)
     N = 4
-    q = _rot_quat(rng.standard_normal((N, 3)))
+    q = rot_quat(rng.standard_normal((N, 3)))
     w = 4.0 * rng.standard_normal((N, 3))
     db = pb.pipeline_init(q, w)
     df = pf.pipeline_init(np.concatenate([np.zeros((N, 2)), np.ones((N, 1)), q], 1), np.concatenate([np.zeros((N, 3)), w], 1))
@@ -228,9 +208,9 @@ def test_planar_ball_is_a_hinge():
     (today's oracle): the rotation angle of the ball's quaternion is the hinge angle over 500 steps of 1 ms.  Measured: 1.2e-14, nothing out of the plane."""
     ball = _top('<joint name="j" type="ball" pos="0 0 0.25"/>', g="-9.81")
     hinge = _top('<joint name="j" type="hinge" axis="0 1 0" pos="0 0 0.25"/>', g="-9.81")
-    pb, ph = BallPhysics(ball.t), Physics(hinge.t)
+    pb, ph = Physics(ball.t), Physics(hinge.t)
     th0, w0 = np.array([0.4, -1.1]), np.array([1.5, 0.3])
-    db = pb.pipeline_init(_rot_quat(np.stack([0 * th0, th0, 0 * th0], 1)), np.stack([0 * w0, w0, 0 * w0], 1))
+    db = pb.pipeline_init(rot_quat(np.stack([0 * th0, th0, 0 * th0], 1)), np.stack([0 * w0, w0, 0 * w0], 1))
     dh = ph.pipeline_init(th0[:, None], w0[:, None])
     worst = off = 0.0
     for _ in range(500):
@@ -257,8 +237,8 @@ def test_ball_is_three_coincident_hinges_at_qpos0():
     ball = compile_model(mjcf.parse_mjcf(TREE_XML.format(joints='<joint name="s" type="ball" pos="0.02 -0.01 0.03"/>')))
     three = compile_model(mjcf.parse_mjcf(TREE_XML.format(joints="".join(f'<joint name="s{k}" type="hinge" pos="0.02 -0.01 0.03" axis="{a}"/>' for k, a in enumerate(("1 0 0", "0 1 0", "0 0 1"))))))
     assert ball.nv == three.nv == 4 and ball.ncon == three.ncon == 3
-    db = _state(BallPhysics(ball.t), np.asarray(ball.t["qpos0"])[None], np.zeros((1, 4)))
-    dh = _state(EqualityPhysics(three.t), np.asarray(three.t["qpos0"])[None], np.zeros((1, 4)))
+    db = _state(Physics(ball.t), np.asarray(ball.t["qpos0"])[None], np.zeros((1, 4)))
+    dh = _state(Physics(three.t), np.asarray(three.t["qpos0"])[None], np.zeros((1, 4)))
     assert (db.efc_D > 0).sum() >= 4 and np.array_equal(db.efc_D > 0, dh.efc_D > 0)  # (the sphere touches the ground)
     for k in ("qM", "qfrc_bias", "qacc_smooth", "xpos", "efc_J", "efc_D", "efc_aref", "qacc"):
         dev = np.abs(db[k] - dh[k]).max() / (np.abs(dh[k]).max() + 1e-300)
@@ -277,14 +257,14 @@ def test_limit_row(rmax, margin):
     theta near pi and the quaternion's other sign (the wrap)."""
     cm = compile_model(mjcf.parse_mjcf(LIMIT_XML.format(rmax=rmax, jattr=f'margin="{margin}" solreflimit="0.03 0.9"' if margin else "", tail="")))
     assert cm.nlimit == 1 and int(cm.t["cparam"]) == (1 if margin else 0)
-    ph = BallPhysics(cm.t)
+    ph = Physics(cm.t)
     rng = np.random.default_rng(2)
     u = rng.standard_normal((6, 3))
     u /= np.linalg.norm(u, axis=1, keepdims=True)
     theta = np.array([rmax + 0.3, rmax + 0.01, rmax - margin - 0.01, 0.1, 3.1, rmax - 0.5 * margin if margin else rmax + 1e-3])
     for sign in (1.0, -1.0):
         w = rng.standard_normal((6, 3))
-        d = _state(ph, sign * _rot_quat(u * theta[:, None]), w)
+        d = _state(ph, sign * rot_quat(u * theta[:, None]), w)
         pos = rmax - theta - margin
         act = pos < 0
         assert list(act) == [True, True, False, False, True, True]
@@ -302,7 +282,7 @@ def test_spring_and_motor():
     per dof by actuatorfrcrange."""
     tail = '<actuator><general name="m" joint="j" gear="2 -3 0.5" gainprm="4" ctrlrange="-1 1" ctrllimited="true" forcerange="-3 3" forcelimited="true"/></actuator>'
     cm = compile_model(mjcf.parse_mjcf(LIMIT_XML.format(rmax=3.0, jattr='stiffness="2.5" damping="0.1" actuatorfrcrange="-7 7" actuatorfrclimited="true"', tail=tail)))
-    ph = BallPhysics(cm.t)
+    ph = Physics(cm.t)
     rng = np.random.default_rng(3)
     N = 8
     u = rng.standard_normal((N, 3))
@@ -310,7 +290,7 @@ def test_spring_and_motor():
     theta = rng.uniform(0.05, 2.9, N)
     w = rng.standard_normal((N, 3))
     ctrl = np.array([0.2, -0.5, 0.7, 0.9, -1.0, 1.7, -2.0, 0.0])[:, None]
-    d = _state(ph, _rot_quat(u * theta[:, None]) * np.where(np.arange(N) % 2, -1.0, 1.0)[:, None], w, ctrl)
+    d = _state(ph, rot_quat(u * theta[:, None]) * np.where(np.arange(N) % 2, -1.0, 1.0)[:, None], w, ctrl)
     np.testing.assert_allclose(d.qfrc_passive, -2.5 * theta[:, None] * u - 0.1 * w, atol=1e-12)
     force = np.clip(4.0 * np.clip(ctrl, -1, 1), -3, 3)
     want = np.clip(force * np.array([2.0, -3.0, 0.5]), -7, 7)
@@ -323,8 +303,8 @@ def test_pendulum_dropped_beyond_its_limit_comes_to_rest_inside():
       <body name="a" pos="0 0 1"><joint name="j" type="ball" range="0 0.8" stiffness="0.5" damping="0.08"/><inertial pos="0 0 -0.2" mass="1" diaginertia="0.01 0.012 0.004"/></body>
       </worldbody></mujoco>"""
     cm = compile_model(mjcf.parse_mjcf(xml))
-    ph = BallPhysics(cm.t)
-    d = ph.pipeline_init(_rot_quat(np.array([[1.2, 0.3, 0.2], [-0.7, 1.0, -0.4]])), np.zeros((2, 3)))
+    ph = Physics(cm.t)
+    d = ph.pipeline_init(rot_quat(np.array([[1.2, 0.3, 0.2], [-0.7, 1.0, -0.4]])), np.zeros((2, 3)))
     assert (d.efc_D > 0).all()  # released beyond the limit
     worst = 0.0
     for _ in range(4000):
@@ -344,85 +324,12 @@ def _ball_adr(cm):
     return [(int(cm.t["jnt_qposadr"][j]), int(cm.t["jnt_dofadr"][j])) for j in range(cm.njnt) if int(cm.t["jnt_type"][j]) == JNT_BALL]
 
 
-def _start(cm, N, rng, spread=0.05):
-    """qpos0 with every scalar joint moved by noise and every ball quaternion turned by a small random rotation."""
-    q = np.tile(np.asarray(cm.t["qpos0"], f64), (N, 1))
-    for j in range(cm.njnt):
-        qa, jt = int(cm.t["jnt_qposadr"][j]), int(cm.t["jnt_type"][j])
-        if jt == JNT_BALL:
-            q[:, qa:qa + 4] = qmul(q[:, qa:qa + 4], _rot_quat(spread * rng.standard_normal((N, 3))))
-        elif jt != JNT_FREE:
-            q[:, qa] += spread * rng.standard_normal(N)
-    return q
-
-
-def _walking_states(cm, N, seed, steps=6):
-    """States the float64 reference reaches from near qpos0 under random controls."""
-    ph = BallPhysics(cm.t)
-    rng = np.random.default_rng(seed)
-    d = ph.pipeline_init(_start(cm, N, rng), 0.2 * rng.standard_normal((N, cm.nv)))
-    for _ in range(steps):
-        d = ph.pipeline_step(d, 0.5 * rng.standard_normal((N, cm.nu)))
-    return d.qpos, d.qvel, 0.5 * rng.standard_normal((N, cm.nu)), d.qacc_warmstart
-
-
-def _refs(cm, q32):
-    N = q32[0].shape[0]
-
-    def ref_(dtype):
-        d = PhysState(qpos=q32[0].astype(dtype), qvel=q32[1].astype(dtype), ctrl=q32[2].astype(dtype)[:, :cm.nu], qacc_warmstart=q32[3].astype(dtype), time=np.zeros(N, dtype))
-        BallPhysics(cm.t, dtype).forward(d)
-        return d
-
-    ref, ref32 = ref_(f64), ref_(f32)
-    scale = lambda k: np.abs(ref[k]).max() + 1e-6
-    # the "well-conditioned" environments: those where the float32 and the float64 run of the REFERENCE agree (tests/test_equality.py's definition)
-    good = (np.abs(ref32.efc_J - ref.efc_J).reshape(N, -1).max(1) <= 2e-4 * scale("efc_J")) & (np.abs(ref32.efc_aref - ref.efc_aref).max(1) <= 5e-4 * scale("efc_aref")) & \
-           ((ref32.efc_D > 0) == (ref.efc_D > 0)).all(1)
-    return ref, ref32, good, scale
-
-
-def _check_against_reference(be, cm, qpos, qvel, ctrl, warm, what, tol_rows, strict_cost=True):
-    """tests/test_equality.py::_check_against_reference with BallPhysics as the reference: the same quantities, tolerances and filter."""
-    from test_kernels_physics import _cost, _probe
-
-    N = qpos.shape[0]
-    q32 = [x.astype(f32) for x in (qpos, qvel, ctrl if cm.nu else np.zeros((N, 1)), warm)]
-    ref, ref32, good, scale = _refs(cm, q32)
-    assert good.sum() >= N // 2, (what, good)  # (the reference alone: asserted before the kernel is looked at)
-    h, dims, _keep = be.model(cm)
-    assert dims.lds_bytes <= 160 * 1024
-    got = _probe(be, h, cm, *q32)
-    be.lib.model_close(h)
-    for k, tol in dict(qM=2e-5, qfrc_bias=2e-4, qacc_smooth=5e-4, xpos=1e-5).items():
-        assert np.abs(got[k].reshape(ref[k].shape) - ref[k]).max() <= tol * scale(k), (what, k, np.abs(got[k].reshape(ref[k].shape) - ref[k]).max() / scale(k))
-    assert ((got["efc_D"].reshape(N, -1) > 0) == (ref.efc_D > 0))[good].all(), what
-    for k, tol in tol_rows.items():
-        r, g = ref[k], got[k].reshape(ref[k].shape)
-        assert np.abs(g[good] - r[good]).max() <= tol * scale(k), (what, k, np.abs(g[good] - r[good]).max() / scale(k))
-
-    def cost(qacc):
-        c = _cost(ref, qacc)
-        jar = np.einsum("nrv,nv->nr", ref.efc_J[:, :cm.neq], qacc.astype(f64)) - ref.efc_aref[:, :cm.neq]
-        return c + 0.5 * np.sum(ref.efc_D[:, :cm.neq] * jar * jar * (jar >= 0), -1)
-
-    c_ref, c32, c_got, c_smooth = cost(ref.qacc), cost(ref32.qacc), cost(got["qacc"]), cost(ref.qacc_smooth)
-    conv = good & (np.abs(c32 - c_ref) <= 5e-2 * np.abs(c_ref) + 1e-3)
-    rel = np.abs(c_got - c_ref)[conv] / (np.abs(c_ref)[conv] + 1e-3)
-    if strict_cost:
-        assert rel.max() <= 5e-2, (what, rel)
-    else:
-        assert np.median(rel) <= 5e-2 and rel.max() <= 0.3, (what, rel)
-    assert np.all(c_got <= c_smooth * (1 + 1e-5) + 1e-6), what
-    assert np.all(got["niter"] <= 6)
-    return ref, got, good
-
-
 def test_kernel_follows_the_reference_on_the_fixtures(be):
     for path in (HUMANOID, CHAIN):
         cm = load_model(path)
         for s in range(2):
-            ref, got, _ = _check_against_reference(be, cm, *_walking_states(cm, 12, s), f"{Path(path).name}/{s}", dict(efc_J=1e-5, efc_D=5e-4, efc_aref=5e-4))
+            ref, got, _ = check_against_oracle(be, cm, walking_states(cm, 12, s), f"{Path(path).name}/{s}", SMOOTH_TOL, dict(efc_J=1e-5, efc_D=5e-4, efc_aref=5e-4), min_good=6,
+                                               strict_cost=True)
             # the spring on the quaternion and the three-component gear, relative to each quantity's largest magnitude.  qfrc_actuator is a product of three
             # float32 numbers and a sum of at most three such terms (a few 1.2e-7 roundings): 1e-6.  qfrc_passive goes through sqrtf / atan2f / a division on
             # float32 inputs before the stiffness multiplies it - the bound of the other quantity built from single-precision transcendentals here, qM: 2e-5
@@ -459,18 +366,16 @@ def test_kernel_follows_the_reference_on_random_robots(be):
     for seed in BALL_SEEDS:
         cm = compile_model(random_ball_model(seed))
         assert int(cm.t["nball"]) >= 1
-        _check_against_reference(be, cm, *_walking_states(cm, 8, seed), f"random/{seed}", dict(efc_D=1e-3, efc_aref=1e-3, efc_J=5e-4), strict_cost=False)
+        check_against_oracle(be, cm, walking_states(cm, 8, seed), f"random/{seed}", SMOOTH_TOL, dict(efc_D=1e-3, efc_aref=1e-3, efc_J=5e-4), min_good=4, strict_cost=False)
 
 
 def test_ball_limit_row_of_the_kernel(be):
     """States placed past the limit (not left to the walk): the kernel's active set is the reference's, its rows within the efc_J tolerance."""
-    from test_kernels_physics import _probe
-
     for path in (CHAIN, HUMANOID):
         cm = load_model(path)
         rng = np.random.default_rng(5)
         N = 12
-        q = _start(cm, N, rng)
+        q = start_states(cm, N, rng)
         lim = [int(j) for j in cm.t["lim_jntid"] if int(cm.t["jnt_type"][j]) == JNT_BALL]
         assert lim
         for j in lim:
@@ -478,12 +383,12 @@ def test_ball_limit_row_of_the_kernel(be):
             u = rng.standard_normal((N, 3))
             u /= np.linalg.norm(u, axis=1, keepdims=True)
             theta = rmax + rng.uniform(-0.3, 0.6, N)  # on both sides of the limit
-            q[:, qa:qa + 4] = _rot_quat(u * theta[:, None]) * np.where(rng.random(N) < 0.5, -1.0, 1.0)[:, None]
+            q[:, qa:qa + 4] = rot_quat(u * theta[:, None]) * np.where(rng.random(N) < 0.5, -1.0, 1.0)[:, None]
         q32 = [x.astype(f32) for x in (q, 0.3 * rng.standard_normal((N, cm.nv)), np.zeros((N, max(cm.nu, 1))), np.zeros((N, cm.nv)))]
-        ref, _, good, scale = _refs(cm, q32)
+        ref, _, good, scale = oracle_pair(cm, q32)
         assert good.sum() >= N // 2
         h, _dims, _keep = be.model(cm)
-        got = _probe(be, h, cm, *q32)
+        got = probe(be, h, cm, *q32)
         be.lib.model_close(h)
         rows = [cm.neq + r for r, j in enumerate(cm.t["lim_jntid"]) if int(j) in lim]
         gD, gJ, gA = got["efc_D"].reshape(N, -1), got["efc_J"].reshape(ref.efc_J.shape), got["efc_aref"].reshape(N, -1)
@@ -533,45 +438,16 @@ def test_env_steps_keep_ball_quaternions_normalised_and_resets_restore_identity(
 # ---------------------------------------------------------------------------------------------------------------------------------------
 
 
-def _probe_and_steps(be, cm, seed=7, N=9, steps=6):
-    from test_kernels_physics import _probe
-
-    qpos, qvel, ctrl, warm = _walking_states(cm, N, seed)
-    q32 = [x.astype(f32) for x in (qpos, qvel, ctrl, warm)]
-    h, dims, _keep = be.model(cm)
-    flag = C.c_int32(-1)
-    be.lib.model_is_specialized(h, C.byref(flag))
-    got = _probe(be, h, cm, *q32)
-    OP, R = dims.obs_pad, dims.rec_dim
-    state, reset_rec, obs = be.zeros((N, R)), be.zeros((R,)), be.zeros((N, OP))
-    rew, done = be.zeros((N,)), be.zeros((N,), np.uint8)
-    be.lib.env_reset(h, N, be.ptr(state), be.ptr(reset_rec), be.ptr(obs), OP, be.ptr(rew), be.ptr(done), None, be.stream)
-    rc = nat.RewardCfg(0.45, 2.0, 2.0, 0.2, 0.5, 0.1, 4.0, 1.0, 1.25)
-    r2 = np.random.default_rng(3)
-    for _ in range(steps):
-        act = be.arr((0.8 * r2.standard_normal((N, cm.nu))).astype(f32))
-        be.lib.env_step(h, N, 2, C.byref(rc), be.ptr(state), be.ptr(reset_rec), be.ptr(act), cm.nu, be.ptr(obs), OP, be.ptr(rew), be.ptr(done), None, be.stream)
-        be.sync()
-    got.update(state=be.host(state).copy(), obs=be.host(obs).copy(), rew=be.host(rew).copy(), done=be.host(done).copy())
-    be.lib.model_close(h)
-    return flag.value, got
-
-
-def _assert_bit_equal(a, b):
-    for k in a:
-        assert np.array_equal(np.asarray(a[k]).view(np.uint8), np.asarray(b[k]).view(np.uint8)), k
-
-
 def test_specialised_ball_humanoid_kernel_equals_the_runtime_sized_kernel(be, monkeypatch):
     cm = load_model(HUMANOID)
     monkeypatch.delenv("MPPO_ENV_GENERIC", raising=False)
     monkeypatch.delenv("MPPO_ENV_SPILL", raising=False)
-    flag, spec = _probe_and_steps(be, cm)
+    flag, spec = probe_and_steps(be, cm)
     assert flag == 1
     monkeypatch.setenv("MPPO_ENV_GENERIC", "1")
-    flag, gen = _probe_and_steps(be, cm)
+    flag, gen = probe_and_steps(be, cm)
     assert flag == 0
-    _assert_bit_equal(spec, gen)
+    assert_bit_equal(spec, gen)
 
 
 @pytest.mark.parametrize("path", [HUMANOID, CHAIN])
@@ -581,9 +457,9 @@ def test_jacobian_placements_are_bit_equal(be, monkeypatch, path):
     res = []
     for spill in ("0", "1", "3"):
         monkeypatch.setenv("MPPO_ENV_SPILL", spill)
-        res.append(_probe_and_steps(be, cm)[1])
+        res.append(probe_and_steps(be, cm)[1])
     for r in res[1:]:
-        _assert_bit_equal(res[0], r)
+        assert_bit_equal(res[0], r)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------------
@@ -634,7 +510,6 @@ def test_fuzzed_ball_blobs_are_refused_or_harmless(path):
     library refuses the blob or steps it on the emulator without a fault."""
     from backends import get_backend
     from minppo_amd.model import _BLOB_INT
-    from test_blob_fuzz import _step_once
 
     be = get_backend("emu")
     words = np.frombuffer(load_model(path).to_blob(True), np.uint8).copy().view(np.int32)
@@ -660,7 +535,7 @@ def test_fuzzed_ball_blobs_are_refused_or_harmless(path):
             continue
         accepted += 1
         try:
-            _step_once(be, h)
+            step_once(be, h)
         except nat.NativeError:
             pass
         be.lib.model_close(h)
@@ -682,68 +557,12 @@ def test_spec_dims_carry_the_number_of_ball_joints():
 
 @pytest.mark.gpu
 def test_kernel_compiled_at_start_up_equals_the_runtime_sized_kernel(tmp_path, monkeypatch):
-    import torch
-
     from minppo_amd import build as _build
-    from minppo_amd import jit
-    from test_jit import _run
 
-    monkeypatch.setenv(jit.CACHE_ENV, str(tmp_path))
-    lib = nat.load()
-    cm = load_model(HUMANOID)
-    dims_ = jit.dims_of(cm)
-    assert dims_[_build._SPEC_KEYS.index("nball")] == 4
-    image = jit.compile_kernel(dims_, 48).read_bytes()
-    blob = np.frombuffer(cm.to_blob(), np.uint8)
-    dblob = torch.from_numpy(blob.copy()).cuda()
-    outs = []
-    for attach in (False, True):
-        monkeypatch.setenv("MPPO_ENV_GENERIC", "1")
-        h = C.c_void_p()
-        lib.model_open(blob.ctypes.data, blob.size, dblob.data_ptr(), C.byref(h))
-        monkeypatch.delenv("MPPO_ENV_GENERIC")
-        if attach:
-            assert jit.attach(lib, h, image, 48)
-            kind = C.c_int32(-1)
-            lib.model_is_specialized(h, C.byref(kind))
-            assert kind.value == 2
-        dims = nat.ModelDims()
-        lib.model_get_dims(h, C.byref(dims))
-        outs.append((h, _run(lib, h, dims, 300, 12, torch)))
-    for t, (a, b) in enumerate(zip(outs[0][1], outs[1][1])):
-        for x, y, what in zip(a, b, ("state", "observation", "reward", "done")):
-            assert np.array_equal(x.view(np.uint8), y.view(np.uint8)), f"{what} differs at step {t}"
-    for h, _ in outs:
-        lib.model_close(h)
+    startup_kernel_equals_runtime_sized(load_model(HUMANOID), tmp_path, monkeypatch, lambda dims: dims[_build._SPEC_KEYS.index("nball")] == 4)
 
 
 @pytest.mark.gpu
 def test_engine_trains_on_the_ball_humanoid_reproducibly():
     """make_train on the ball-joint humanoid (environment.model=...): two runs with one seed give bit-identical parameters, no NaN, finite episode metrics."""
-    from minppo_amd.config import load_config_from_cli
-    from minppo_amd.train import make_train
-
-    res = []
-    for _ in range(2):
-        cfg = load_config_from_cli(["stompy_pro", f"environment.model={HUMANOID}", "training.num_envs=512", "training.num_minibatches=4", "training.update_epochs=2",
-                                    "training.total_timesteps=20480"])
-        res.append(make_train(cfg)(1337, log_every=1))
-    flat = [np.concatenate([_host(x).reshape(-1).astype(f32) for x in _leaves(o.runner_state.train_state.params)]) for o in res]
-    assert flat[0].size > 0 and np.isfinite(flat[0]).all()
-    assert np.array_equal(flat[0].view(np.uint8), flat[1].view(np.uint8))
-    for o in res:
-        assert len(o.metrics["mean_reward"]) == 4
-        for k in ("mean_reward", "done_fraction", "mean_episode_return", "mean_episode_length", "total_loss"):
-            assert np.isfinite(np.asarray(o.metrics[k], f64)).all(), k
-
-
-def _host(x):
-    return x.detach().cpu().numpy() if hasattr(x, "detach") else np.asarray(x)
-
-
-def _leaves(tree):
-    if isinstance(tree, dict):
-        return [x for k in sorted(tree) for x in _leaves(tree[k])]
-    if isinstance(tree, (list, tuple)):
-        return [x for v in tree for x in _leaves(v)]
-    return [tree]
+    trains_reproducibly(HUMANOID)

@@ -13,6 +13,7 @@ import pytest
 from backends import get_backend
 from minppo_amd import _native as nat
 from minppo_amd.model import _BLOB_F32, _BLOB_INT, compile_model, load_model
+from physics_harness import step_once
 
 f32 = np.float32
 
@@ -22,18 +23,6 @@ def _models():
 
     return [("cvx_scene", compile_model(scene())), ("synth_can", load_model("synth_can")), ("synth_wedge", load_model("synth_wedge")),
             ("synth_stompy_pro_sc", load_model("synth_stompy_pro_sc"))]
-
-
-def _step_once(be, h, N=4):
-    dims = nat.ModelDims()
-    be.lib.model_get_dims(h, C.byref(dims))
-    OP, R = dims.obs_pad, dims.rec_dim
-    state, reset_rec, obs = be.zeros((N, R)), be.zeros((R,)), be.zeros((N, OP))
-    rew, done = be.zeros((N,)), be.zeros((N,), np.uint8)
-    be.lib.env_reset(h, N, be.ptr(state), be.ptr(reset_rec), be.ptr(obs), OP, be.ptr(rew), be.ptr(done), None, be.stream)
-    rc = nat.RewardCfg(-0.2, 2.0, 2.0, 0.2, 0.5, 0.1, 4.0, 1.0, 1.25)
-    a = be.zeros((N, max(dims.nu, 1)))
-    be.lib.env_step(h, N, 1, C.byref(rc), be.ptr(state), be.ptr(reset_rec), be.ptr(a), max(dims.nu, 1), be.ptr(obs), OP, be.ptr(rew), be.ptr(done), None, be.stream)
 
 
 @pytest.mark.parametrize("which", [0, 1, 2, 3])
@@ -75,7 +64,7 @@ def test_mutated_blobs_are_refused_or_harmless(which):
             continue
         accepted += 1
         try:
-            _step_once(be, h)          # must not fault (under ASan: must not read or write out of range)
+            step_once(be, h)          # must not fault (under ASan: must not read or write out of range)
         except nat.NativeError:
             pass                       # a launch-time argument check may still refuse it
         be.lib.model_close(h)
@@ -95,6 +84,6 @@ def test_mutated_blobs_are_refused_or_harmless(which):
                     refused += 1
                     continue
                 accepted += 1
-                _step_once(be, h)
+                step_once(be, h)
                 be.lib.model_close(h)
     assert refused >= 40, (name, accepted, refused)   # (most mutations of an index are out of range; the rest are other valid models)

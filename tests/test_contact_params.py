@@ -1,6 +1,6 @@
 """Per-geom and per-joint contact parameters (blob version 8): MuJoCo's mixing rules in the compiler, condim 1, margin / gap, per-joint
 solreflimit / solimplimit / margin - compiler known answers, the existing tables unchanged, known-answer physics and the environment kernel
-against the float64 reference of tests/contact_params_ref.py on the emulator and the MI355X."""
+against the float64 oracle (oracle/physics_oracle.py) on the emulator and the MI355X."""
 
 import ctypes as C
 import hashlib
@@ -10,11 +10,12 @@ from pathlib import Path
 import numpy as np
 import pytest
 
-from contact_params_ref import ContactParamPhysics
 from minppo_amd import _native as nat
 from minppo_amd import mjcf
-from minppo_amd.model import BUILTIN_MODELS, GEOM_BOX, GEOM_MESH, JNT_FREE, compile_model, load_model, mix_contact_params
+from minppo_amd.model import GEOM_BOX, GEOM_MESH, JNT_FREE, compile_model, load_model, mix_contact_params
 from oracle.physics_oracle import Physics, PhysState
+from physics_harness import (assert_bit_equal, assert_oracle_reproduces_the_recording, check_against_oracle, existing_models, probe, random_states, startup_kernel_equals_runtime_sized,
+                             trains_reproducibly)
 
 f32, f64 = np.float32, np.float64
 GOLDEN = Path(__file__).parent / "golden"
@@ -136,19 +137,11 @@ def _table_hashes(cm):
     return out
 
 
-def _existing_models():
-    out = [(n, lambda f=f: compile_model(f())) for n, f in sorted(BUILTIN_MODELS.items())]
-    for p in sorted(list(GOLDEN.glob("*.xml")) + [GOLDEN / "export_biped" / "robot.xml"]):
-        if p.name != "contact_params_humanoid.xml":
-            out.append((str(p.relative_to(GOLDEN)), lambda p=p: compile_model(mjcf.load_mjcf(str(p)))))
-    return out
-
-
 def test_existing_tables_are_byte_identical():
     """Every table the compiler produced before blob version 8, for every built-in robot and fixture: sha256 recorded from the tree before
     the change (tests/golden/table_sha256.json; the new tables are left out).  These models are all uniform (cparam 0)."""
     want = json.loads((GOLDEN / "table_sha256.json").read_text())
-    models = _existing_models()
+    models = existing_models()
     assert sorted(n for n, _ in models) == sorted(want)
     for name, make in models:
         cm = make()
@@ -156,23 +149,10 @@ def test_existing_tables_are_byte_identical():
         assert int(cm.t["cparam"]) == 0, name
 
 
-def test_reference_equals_the_oracle_on_uniform_models():
-    """ContactParamPhysics is oracle.physics_oracle.Physics, bit for bit, wherever every row takes the model-wide values."""
-    for name, make in _existing_models():
-        cm = make()
-        N = 3
-        rng = np.random.default_rng(4)
-        q = np.tile(np.asarray(cm.t["qpos0"], f64), (N, 1))
-        q[:, :min(cm.nq, 3)] += 0.01 * rng.standard_normal((N, min(cm.nq, 3)))
-        res = []
-        for cls in (Physics, ContactParamPhysics):
-            ph = cls(cm.t)
-            d = ph.pipeline_init(q.copy(), 0.3 * rng.standard_normal((N, cm.nv)) * 0 + 0.1)
-            for _ in range(3):
-                d = ph.pipeline_step(d, 0.3 * np.ones((N, cm.nu)))
-            res.append(d)
-        for k in ("qpos", "qvel", "qacc", "efc_D", "efc_aref", "efc_J"):
-            np.testing.assert_array_equal(np.asarray(res[0][k]), np.asarray(res[1][k]), err_msg=f"{name}: {k}")
+def test_oracle_reproduces_the_recording_on_uniform_models():
+    """Per-row contact parameters change nothing where every row takes the model-wide values (cparam 0): the oracle on every such model
+    against the recording made before it read the per-row tables."""
+    assert_oracle_reproduces_the_recording([n for n, _ in existing_models()])
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------------
@@ -181,15 +161,13 @@ def test_reference_equals_the_oracle_on_uniform_models():
 
 
 def _forward(be, cm, qpos, qvel):
-    from test_kernels_physics import _probe
-
     h, dims, _keep = be.model(cm)
     N = qpos.shape[0]
     q32 = [x.astype(f32) for x in (qpos, qvel, np.zeros((N, max(cm.nu, 1))), np.zeros((N, cm.nv)))]
-    got = _probe(be, h, cm, *q32)
+    got = probe(be, h, cm, *q32)
     be.lib.model_close(h)
     ref = PhysState(qpos=q32[0].astype(f64), qvel=q32[1].astype(f64), ctrl=np.zeros((N, cm.nu)), qacc_warmstart=np.zeros((N, cm.nv)), time=np.zeros(N))
-    ContactParamPhysics(cm.t).forward(ref)
+    Physics(cm.t).forward(ref)
     return got, ref
 
 
@@ -287,7 +265,7 @@ def _fixture_states(cm, N, rng):
         q[:, qa] = np.where(rng.random(N) < 0.4, near, rng.uniform(lo, hi, N))
     x = np.array([1.0, 0.0, 0.0, 0.0]) + 0.3 * rng.normal(size=(N, 4))
     q[:, 3:7] = x / np.linalg.norm(x, axis=1, keepdims=True)
-    ph = ContactParamPhysics(t)
+    ph = Physics(t)
     d = ph.make_data(N)
     d["qpos"] = q.copy()
     ph.kinematics(d); ph.com_pos(d); ph.collision(d)
@@ -315,48 +293,10 @@ def _classes(cm, ref):
                 limit_margin=int(lim_band.sum()))
 
 
-def _check_against_reference(be, cm, qpos, qvel, ctrl, what, tol_rows, strict_cost=True):
-    from test_kernels_physics import _probe
-
-    N = qpos.shape[0]
-    h, dims, _keep = be.model(cm)
-    assert dims.lds_bytes <= 160 * 1024
-    q32 = [x.astype(f32) for x in (qpos, qvel, ctrl if cm.nu else np.zeros((N, 1)), np.zeros((N, cm.nv)))]
-
-    def ref_(dtype):
-        d = PhysState(qpos=q32[0].astype(dtype), qvel=q32[1].astype(dtype), ctrl=q32[2].astype(dtype)[:, :cm.nu], qacc_warmstart=np.zeros((N, cm.nv), dtype), time=np.zeros(N, dtype))
-        ContactParamPhysics(cm.t, dtype).forward(d)
-        return d
-
-    ref, ref32 = ref_(f64), ref_(f32)
-    got = _probe(be, h, cm, *q32)
-    be.lib.model_close(h)
-    scale = lambda k: np.abs(ref[k]).max() + 1e-6
-    for k, tol in dict(qM=2e-5, qfrc_bias=2e-4, qfrc_passive=1e-5, qacc_smooth=5e-4, xpos=1e-5).items():
-        r = ref[k]
-        assert np.abs(got[k].reshape(r.shape) - r).max() <= tol * scale(k), (what, k)
-    # constraint rows: the poses where float32 arithmetic itself is well-conditioned (as tests/test_model_fuzz.py)
-    from test_kernels_physics import _cost
-
-    c_ref, c32, c_smooth = _cost(ref, ref.qacc), _cost(ref, ref32.qacc), _cost(ref, ref.qacc_smooth)
-    good = (np.abs(ref32.efc_J - ref.efc_J).reshape(N, -1).max(1) <= 2e-4 * scale("efc_J")) & (np.abs(ref32.efc_aref - ref.efc_aref).max(1) <= 5e-4 * scale("efc_aref")) & \
-           ((ref32.efc_D > 0) == (ref.efc_D > 0)).all(1)
-    assert good.sum() >= N // 2, (what, good)
-    assert ((got["efc_D"].reshape(N, -1) > 0) == (ref.efc_D > 0))[good].all(), what
-    for k, tol in tol_rows.items():
-        r, g = ref[k], got[k].reshape(ref[k].shape)
-        assert np.abs(g[good] - r[good]).max() <= tol * scale(k), (what, k, np.abs(g[good] - r[good]).max() / scale(k))
-    # the solver: the cost it reaches (test_forward_matches_oracle's 5e-2), where six float32 CG iterations of the reference itself reach
-    # float64's within that envelope (random robots: a few poses do not - tests/test_model_fuzz.py leaves the solver out for them)
-    c_got = _cost(ref, got["qacc"])
-    conv = good & (np.abs(c32 - c_ref) <= 5e-2 * np.abs(c_ref) + 1e-3)
-    rel = np.abs(c_got - c_ref)[conv] / (np.abs(c_ref)[conv] + 1e-3)
-    if strict_cost:
-        assert rel.max() <= 5e-2, (what, rel)
-    else:  # (random robots: stiff, unconverged after six iterations - the float32 kernel and the float32 reference part by up to 10 % on single poses)
-        assert np.median(rel) <= 5e-2 and rel.max() <= 0.3, (what, rel)
-    assert np.all(c_got <= c_smooth * (1 + 1e-5) + 1e-6), what
-    assert np.all(got["niter"] <= 6)
+def _check(be, cm, qpos, qvel, ctrl, what, tol_rows, strict_cost=True):
+    """physics_harness.check_against_oracle from a zero warm start, qfrc_passive among the smooth quantities -> the classes of rows that were active."""
+    ref, _, _ = check_against_oracle(be, cm, (qpos, qvel, ctrl, np.zeros((qpos.shape[0], cm.nv))), what, dict(qM=2e-5, qfrc_bias=2e-4, qfrc_passive=1e-5, qacc_smooth=5e-4, xpos=1e-5),
+                                     tol_rows, qpos.shape[0] // 2, strict_cost)
     return _classes(cm, ref)
 
 
@@ -366,20 +306,17 @@ PARAM_SEEDS = list(range(8))
 def test_kernel_follows_the_reference(be):
     """The fixture and eight random robots with random per-geom / per-joint parameters: the kernel's constraint rows against the float64
     reference, with every class of new row active somewhere."""
-    from test_model_fuzz import _states
-
     seen = dict(margin_band=0, condim1_self=0, mixed_floor=0, limit_margin=0)
     cm = load_model(FIXTURE)
     for s in range(2):
         # (test_forward_matches_oracle's tolerances)
-        for k, v in _check_against_reference(be, cm, *_fixture_states(cm, 16, np.random.default_rng(s)), f"fixture/{s}", dict(efc_J=1e-5, efc_D=5e-4, efc_aref=5e-4)).items():
+        for k, v in _check(be, cm, *_fixture_states(cm, 16, np.random.default_rng(s)), f"fixture/{s}", dict(efc_J=1e-5, efc_D=5e-4, efc_aref=5e-4)).items():
             seen[k] += v
     for seed in PARAM_SEEDS:
         cm = compile_model(random_param_model(seed))
         assert int(cm.t["cparam"]) == 1
         # (tests/test_model_fuzz.py's, for the same generator: pair normals between nearly coincident points)
-        for k, v in _check_against_reference(be, cm, *_states(cm, 8, np.random.default_rng(seed)), f"random/{seed}", dict(efc_D=1e-3, efc_aref=1e-3, efc_J=5e-4),
-                                             strict_cost=False).items():
+        for k, v in _check(be, cm, *random_states(cm, 8, np.random.default_rng(seed)), f"random/{seed}", dict(efc_D=1e-3, efc_aref=1e-3, efc_J=5e-4), strict_cost=False).items():
             seen[k] += v
     assert all(v > 0 for v in seen.values()), seen
 
@@ -391,8 +328,6 @@ def test_kernel_follows_the_reference(be):
 
 def test_specialised_fixture_kernel_equals_the_runtime_sized_kernel(be, monkeypatch):
     """The fixture has an instantiation of its own in the library (csrc/spec_dims.inc, cparam = 1): bit-equal to the run-time-sized kernel."""
-    from test_kernels_physics import _probe
-
     cm = load_model(FIXTURE)
     N = 9
     qpos, qvel, _ = _fixture_states(cm, N, np.random.default_rng(7))
@@ -408,7 +343,7 @@ def test_specialised_fixture_kernel_equals_the_runtime_sized_kernel(be, monkeypa
         flag = C.c_int32(-1)
         be.lib.model_is_specialized(h, C.byref(flag))
         assert flag.value == (0 if generic else 1)
-        got = _probe(be, h, cm, *q32)
+        got = probe(be, h, cm, *q32)
         OP, R = dims.obs_pad, dims.rec_dim
         state, reset_rec, obs = be.zeros((N, R)), be.zeros((R,)), be.zeros((N, OP))
         rew, done = be.zeros((N,)), be.zeros((N,), np.uint8)
@@ -422,9 +357,7 @@ def test_specialised_fixture_kernel_equals_the_runtime_sized_kernel(be, monkeypa
         got.update(state=be.host(state).copy(), obs=be.host(obs).copy(), rew=be.host(rew).copy(), done=be.host(done).copy())
         res.append(got)
         be.lib.model_close(h)
-    for k in res[0]:
-        a_, b_ = np.asarray(res[0][k]), np.asarray(res[1][k])
-        assert np.array_equal(a_.view(np.uint8), b_.view(np.uint8)), k
+    assert_bit_equal(res[0], res[1])
 
 
 @pytest.mark.gpu
@@ -432,60 +365,10 @@ def test_kernel_compiled_at_start_up_equals_the_runtime_sized_kernel(tmp_path, m
     """The fixture's kernel compiled at start-up (minppo_amd/jit.py) against the run-time-sized one: the path of
     tests/test_jit.py::test_attached_kernel_equals_the_runtime_sized_kernel (the library's own instantiation is bypassed for the comparison by
     asking for the run-time-sized kernel on one handle and attaching the compiled one to the other)."""
-    import torch
-
-    from minppo_amd import jit
-    from test_jit import _run
-
-    monkeypatch.setenv(jit.CACHE_ENV, str(tmp_path))
-    lib = nat.load()
-    cm = load_model(FIXTURE)
-    dims_ = jit.dims_of(cm)
-    assert dims_[-1] == 1
-    path = jit.compile_kernel(dims_, 48)
-    image = path.read_bytes()
-    blob = np.frombuffer(cm.to_blob(), np.uint8)
-    dblob = torch.from_numpy(blob.copy()).cuda()
-    outs = []
-    for attach in (False, True):
-        monkeypatch.setenv("MPPO_ENV_GENERIC", "1")  # (both handles start on the run-time-sized kernel)
-        h = C.c_void_p()
-        lib.model_open(blob.ctypes.data, blob.size, dblob.data_ptr(), C.byref(h))
-        monkeypatch.delenv("MPPO_ENV_GENERIC")
-        if attach:
-            # the library holds the fixture's kernel itself: attach the compiled code object directly
-            assert jit.attach(lib, h, image, 48)
-            kind = C.c_int32(-1)
-            lib.model_is_specialized(h, C.byref(kind))
-            assert kind.value == 2
-        dims = nat.ModelDims()
-        lib.model_get_dims(h, C.byref(dims))
-        outs.append((h, _run(lib, h, dims, 300, 12, torch)))
-    for t, (a, b) in enumerate(zip(outs[0][1], outs[1][1])):
-        for x, y, what in zip(a, b, ("state", "observation", "reward", "done")):
-            assert np.array_equal(x.view(np.uint8), y.view(np.uint8)), f"{what} differs at step {t}"
-    for h, _ in outs:
-        lib.model_close(h)
+    startup_kernel_equals_runtime_sized(load_model(FIXTURE), tmp_path, monkeypatch, lambda dims: dims[-1] == 1)
 
 
 @pytest.mark.gpu
 def test_engine_trains_on_the_fixture_reproducibly():
     """Five PPO updates at 1024 environments on the contact-parameter humanoid: finite parameters, and two runs with one seed agree bit for bit."""
-    import torch
-
-    from minppo_amd.config import load_config_from_cli
-    from minppo_amd.train import Trainer
-
-    res = []
-    for _ in range(2):
-        cfg = load_config_from_cli(["stompy_pro", f"environment.model={FIXTURE}", "training.num_envs=1024", "training.num_minibatches=4", "training.update_epochs=2",
-                                    "training.total_timesteps=1000000"])
-        tr = Trainer(cfg)
-        tr.reset()
-        for _ in range(5):
-            tr.update()
-        torch.cuda.synchronize()
-        res.append(tr.params_flat())
-        tr.close()
-    assert res[0].size > 0 and np.isfinite(res[0]).all()
-    assert np.array_equal(res[0].view(np.uint8), res[1].view(np.uint8))
+    trains_reproducibly(FIXTURE, trainer=True)

@@ -10,7 +10,8 @@ import pytest
 from minppo_amd import mjcf
 from minppo_amd.model import (GEOM_BOX, GEOM_CAPSULE, GEOM_MESH, GEOM_SPHERE, JNT_FREE, BodySpec, GeomSpec, JointSpec, ModelSpec, compile_model,
                               hull_topology)
-from oracle.physics_oracle import Hull, Physics, PhysState, capsule_convex, convex_convex, sphere_convex
+from oracle.physics_oracle import Hull, Physics, capsule_convex, convex_convex, sphere_convex
+from physics_harness import cost, oracle_pair, probe
 
 f32, f64 = np.float32, np.float64
 
@@ -267,8 +268,6 @@ def test_hull_pair_contacts_match_the_oracle(be):
     """Round 6, MJX convex_convex (box / mesh against box / mesh, four slots a pair): the kernel's rows of all twelve slots against the oracle
     on 96 poses, as for the round pairs above - active sets equal, reference accelerations and Jacobian rows at 5e-4 on the poses where the
     float32 and float64 oracles agree (a tie between two axes or faces, or a clipped point on a side plane, is ill-conditioned)."""
-    from test_kernels_physics import _probe
-
     cm = compile_model(hull_scene())
     assert cm.npair == 12 and cm.t["pair_body"].tolist() == [[1, 2]] * 4 + [[1, 3]] * 4 + [[2, 3]] * 4
     h, dims, _keep = be.model(cm)
@@ -276,8 +275,8 @@ def test_hull_pair_contacts_match_the_oracle(be):
     rng = np.random.default_rng(2)
     qpos, qvel = hull_scene_states(cm, N, rng), 0.2 * rng.standard_normal((N, cm.nv))
     q32 = [x.astype(f32) for x in (qpos, qvel, np.zeros((N, 1)), np.zeros((N, cm.nv)))]
-    ref, ref32 = _reference(cm, q32), _reference(cm, q32, f32)
-    got = _probe(be, h, cm, *q32)
+    ref, ref32, _, _ = oracle_pair(cm, q32)  # (the filter below is this file's own: tighter on efc_aref, its scale with 1e-9)
+    got = probe(be, h, cm, *q32)
     scale = lambda k: np.abs(ref[k]).max() + 1e-9
     good = (np.abs(ref32.efc_J - ref.efc_J).reshape(N, -1).max(1) <= 2e-4 * scale("efc_J")) & \
            (np.abs(ref32.efc_aref - ref.efc_aref).max(1) <= 2e-4 * scale("efc_aref")) & ((ref32.efc_D > 0) == (ref.efc_D > 0)).all(1)
@@ -310,30 +309,19 @@ def test_hull_pair_contacts_match_the_oracle(be):
 # ---------------------------------------------------------------------------
 
 
-def _reference(cm, q32, dtype=f64):
-    N = q32[0].shape[0]
-    ref = PhysState(qpos=q32[0].astype(f64), qvel=q32[1].astype(f64), ctrl=np.zeros((N, 0)), qacc_warmstart=np.zeros((N, cm.nv)), time=np.zeros(N))
-    if dtype is not f64:
-        ref = PhysState({k: v.astype(dtype) for k, v in ref.items()})
-    Physics(cm.t, dtype).forward(ref)
-    return ref
-
-
 def test_convex_pair_contacts_match_the_oracle(be):
     """Constraint rows of all seven slots from 96 poses: which are active (efc_D), the reference acceleration (a function of the
     distance) and the Jacobian rows (normal and contact point).  A pose in which the float32 oracle itself departs from the float64 one
     (a tie between two faces or edges, a contact point on top of the sphere's centre) is ill-conditioned and left out of the Jacobian /
     solver comparison; at least 85 % of the poses must remain, and every hull slot must fire among them."""
-    from test_kernels_physics import _cost, _probe
-
     cm = compile_model(scene())
     h, dims, _keep = be.model(cm)
     N = 96
     rng = np.random.default_rng(1)
     qpos, qvel = scene_states(cm, N, rng), 0.2 * rng.standard_normal((N, cm.nv))
     q32 = [x.astype(f32) for x in (qpos, qvel, np.zeros((N, 1)), np.zeros((N, cm.nv)))]
-    ref, ref32 = _reference(cm, q32), _reference(cm, q32, f32)
-    got = _probe(be, h, cm, *q32)
+    ref, ref32, _, _ = oracle_pair(cm, q32)  # (the filter below is this file's own: tighter on efc_aref, its scale with 1e-9)
+    got = probe(be, h, cm, *q32)
     scale = lambda k: np.abs(ref[k]).max() + 1e-9
     good = (np.abs(ref32.efc_J - ref.efc_J).reshape(N, -1).max(1) <= 2e-4 * scale("efc_J")) & \
            (np.abs(ref32.efc_aref - ref.efc_aref).max(1) <= 2e-4 * scale("efc_aref"))
@@ -343,11 +331,11 @@ def test_convex_pair_contacts_match_the_oracle(be):
     for k, tol in dict(efc_D=5e-4, efc_aref=5e-4, efc_J=5e-4, qM=1e-5, xpos=1e-5).items():
         r, g = ref[k], got[k].reshape(ref[k].shape)
         assert np.abs(g[good] - r[good]).max() <= tol * scale(k), (k, np.abs(g[good] - r[good]).max() / scale(k))
-    c_got, c_ref = _cost(ref, got["qacc"]), _cost(ref, ref.qacc)
+    c_got, c_ref = cost(ref, got["qacc"]), cost(ref, ref.qacc)
     # (six CG iterations from a cold start on overlaps of up to 0.18 m do not converge; float32 and float64 stop at different points of
     # the same descent - the solver's envelope, DESIGN.md section 5 - while the rows they descend on agree to 5e-4)
     crel = np.abs(c_got - c_ref)[good] / (c_ref[good] + 1e-3)
-    assert np.median(crel) <= 1e-3 and crel.max() <= 0.25 and np.all(c_got[good] <= _cost(ref, ref.qacc_smooth)[good] * (1 + 1e-5) + 1e-6), (np.median(crel), crel.max())
+    assert np.median(crel) <= 1e-3 and crel.max() <= 0.25 and np.all(c_got[good] <= cost(ref, ref.qacc_smooth)[good] * (1 + 1e-5) + 1e-6), (np.median(crel), crel.max())
     shallow = good & (ref.con_dist.min(1) > -0.05)  # (the solver's result itself: where no overlap is deeper than 5 cm)
     rel = (np.abs(got["qacc"] - ref.qacc).max(1) / (np.abs(ref.qacc).max(1) + 1e-9))[shallow]
     assert shallow.mean() >= 0.4 and active[shallow].any(1).sum() >= 15 and np.median(rel) <= 5e-3 and rel.max() <= 0.3, (shallow.mean(), np.median(rel), rel.max())

@@ -73,7 +73,7 @@ def _poses(cm, N, rng):
 
 
 def test_cylinder_contacts_match_the_oracle(be):
-    from test_kernels_physics import _cost, _probe
+    from physics_harness import cost, probe
 
     cm = load_model("synth_can")
     h, dims, _keep = be.model(cm)
@@ -86,12 +86,12 @@ def test_cylinder_contacts_match_the_oracle(be):
     Physics(cm.t).forward(ref)
     active = (ref.con_dist < 0)
     assert active[:, :3].any(1).sum() >= 20 and active[:, 3:].any(1).sum() >= 4 and active[0, :3].all() and active[2, :2].all()   # all three regimes, both geoms
-    got = _probe(be, h, cm, *q32)
+    got = probe(be, h, cm, *q32)
     for k, tol in dict(efc_D=5e-4, efc_aref=5e-4, efc_J=2e-5, qM=1e-5, xpos=1e-5).items():
         r, g = ref[k], got[k].reshape(ref[k].shape)
         assert np.abs(g - r).max() <= tol * (np.abs(r).max() + 1e-9), (k, np.abs(g - r).max() / (np.abs(r).max() + 1e-9))
     assert ((got["efc_D"].reshape(N, -1) > 0) == (ref.efc_D > 0)).all()
-    c_got, c_ref = _cost(ref, got["qacc"]), _cost(ref, ref.qacc)
+    c_got, c_ref = cost(ref, got["qacc"]), cost(ref, ref.qacc)
     crel = np.abs(c_got - c_ref) / (c_ref + 1e-3)
     assert np.median(crel) <= 1e-3 and crel.max() <= 0.25, (np.median(crel), crel.max())
     be.lib.model_close(h)

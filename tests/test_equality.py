@@ -1,5 +1,5 @@
 """MJCF equality constraints (blob version 9): <connect> (body form) and <joint> through the parser, the compiler, the blob validator and the
-environment kernel - known answers of the float64 reference (tests/equality_ref.py), the kernel against it on the emulator and the MI355X,
+environment kernel - known answers of the float64 oracle (oracle/physics_oracle.py), the kernel against it on the emulator and the MI355X,
 bit-equality across kernel instantiations and Jacobian placements, and reproducible training on the four-bar biped."""
 
 import ctypes as C
@@ -9,12 +9,12 @@ from pathlib import Path
 import numpy as np
 import pytest
 
-from contact_params_ref import ContactParamPhysics
-from equality_ref import EqualityPhysics
 from minppo_amd import _native as nat
 from minppo_amd import mjcf
 from minppo_amd.model import JNT_FREE, MAX_EQ_ROWS, EqualitySpec, compile_model, load_model
-from oracle.physics_oracle import PhysState
+from oracle.physics_oracle import Physics
+from physics_harness import (SMOOTH_TOL, assert_bit_equal, assert_oracle_reproduces_the_recording, check_against_oracle, existing_models, probe_and_steps,
+                             startup_kernel_equals_runtime_sized, trains_reproducibly, walking_states)
 
 f32, f64 = np.float32, np.float64
 GOLDEN = Path(__file__).parent / "golden"
@@ -114,29 +114,15 @@ def test_empty_equality_section_is_still_an_error():
         _hang("<equality/>")
 
 
-def test_models_without_equalities_are_unchanged():
-    """No new tables and the row count of before for every model without equality constraints; the reference is its parent bit for bit."""
-    from test_contact_params import _existing_models
-
-    for name, make in _existing_models() + [("contact_params_humanoid", lambda: load_model(str(GOLDEN / "contact_params_humanoid.xml")))]:
+def test_models_without_equalities_reproduce_the_recording():
+    """No new tables and the row count of before for every model without equality constraints; the oracle steps them as it did before it
+    knew equality rows (the recording)."""
+    models = existing_models() + [("contact_params_humanoid.xml", lambda: load_model(str(GOLDEN / "contact_params_humanoid.xml")))]
+    for name, make in models:
         cm = make()
         assert not any(k == "neq" or k.startswith("eq_") for k in cm.t), name
         assert cm.neq == 0 and cm.nefc == cm.nlimit + 4 * cm.ncon, name
-    for name in ("synth_stompy_pro", "synth_pile", str(GOLDEN / "contact_params_humanoid.xml")):
-        cm = load_model(name)
-        N = 3
-        rng = np.random.default_rng(5)
-        q = np.tile(np.asarray(cm.t["qpos0"], f64), (N, 1))
-        q[:, :3] += 0.02 * rng.standard_normal((N, 3))
-        res = []
-        for cls in (ContactParamPhysics, EqualityPhysics):
-            ph = cls(cm.t)
-            d = ph.pipeline_init(q.copy(), np.full((N, cm.nv), 0.1))
-            for _ in range(3):
-                d = ph.pipeline_step(d, 0.3 * np.ones((N, cm.nu)))
-            res.append(d)
-        for k in ("qpos", "qvel", "qacc", "efc_D", "efc_aref", "efc_J"):
-            np.testing.assert_array_equal(np.asarray(res[0][k]), np.asarray(res[1][k]), err_msg=f"{name}: {k}")
+    assert_oracle_reproduces_the_recording([n for n, _ in models])
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------------
@@ -152,7 +138,7 @@ def _run(ph, d, steps, ctrl=None):
 
 def test_body_hung_from_the_world_settles_and_swings():
     cm = compile_model(mjcf.parse_mjcf(PENDULUM_XML))
-    ph = EqualityPhysics(cm.t)
+    ph = Physics(cm.t)
     assert cm.neq == 3
     # at rest under its anchor: the constraint force carries the weight (2 kg), the anchor stays put
     q = np.tile(np.asarray(cm.t["qpos0"], f64), (1, 1))
@@ -173,7 +159,7 @@ def test_body_hung_from_the_world_settles_and_swings():
 
 def test_mimic_pair_tracks_a_torque_on_joint2_only():
     cm = load_model(COUPLED)
-    ph = EqualityPhysics(cm.t)
+    ph = Physics(cm.t)
     qa = {n: int(cm.t["jnt_qposadr"][cm.joint_names.index(n)]) for n in ("drive", "mimic", "poly_in", "poly_out", "lock")}
     d = ph.pipeline_init(np.tile(np.asarray(cm.t["qpos0"], f64), (1, 1)), np.zeros((1, cm.nv)))
     travel, worst = 0.0, 0.0
@@ -187,7 +173,7 @@ def test_mimic_pair_tracks_a_torque_on_joint2_only():
 
 def test_polynomial_coupling_follows_its_polynomial():
     cm = load_model(COUPLED)
-    ph = EqualityPhysics(cm.t)
+    ph = Physics(cm.t)
     qi, qo = (int(cm.t["jnt_qposadr"][cm.joint_names.index(n)]) for n in ("poly_in", "poly_out"))
     d = ph.pipeline_init(np.tile(np.asarray(cm.t["qpos0"], f64), (1, 1)), np.zeros((1, cm.nv)))
     seen, worst = [], 0.0
@@ -202,7 +188,7 @@ def test_polynomial_coupling_follows_its_polynomial():
 
 def test_four_bar_loop_stays_closed_while_the_crank_is_driven():
     cm = load_model(FOURBAR)
-    ph = EqualityPhysics(cm.t)
+    ph = Physics(cm.t)
     d = ph.pipeline_init(np.tile(np.asarray(cm.t["qpos0"], f64), (2, 1)), np.zeros((2, cm.nv)))
     crank = [int(cm.t["jnt_qposadr"][cm.joint_names.index(n)]) for n in ("crank_l", "crank_r")]
     ankle = [int(cm.t["jnt_qposadr"][cm.joint_names.index(n)]) for n in ("ankle_l", "ankle_r")]
@@ -251,67 +237,6 @@ def random_equality_model(seed: int):
     return spec
 
 
-def _walking_states(cm, N, seed, steps=6):
-    """States the float64 reference reaches from qpos0 under random controls (equalities near satisfied, contacts and limits as they come)."""
-    ph = EqualityPhysics(cm.t)
-    rng = np.random.default_rng(seed)
-    q = np.tile(np.asarray(cm.t["qpos0"], f64), (N, 1))
-    for j in range(cm.njnt):
-        if int(cm.t["jnt_type"][j]) != JNT_FREE:
-            q[:, int(cm.t["jnt_qposadr"][j])] += 0.05 * rng.standard_normal(N)
-    d = ph.pipeline_init(q, 0.2 * rng.standard_normal((N, cm.nv)))
-    for _ in range(steps):
-        d = ph.pipeline_step(d, 0.5 * rng.standard_normal((N, cm.nu)))
-    return d.qpos, d.qvel, 0.5 * rng.standard_normal((N, cm.nu)), d.qacc_warmstart
-
-
-def _check_against_reference(be, cm, qpos, qvel, ctrl, warm, what, tol_rows, strict_cost=True):
-    from test_kernels_physics import _cost, _probe
-
-    N = qpos.shape[0]
-    h, dims, _keep = be.model(cm)
-    assert dims.lds_bytes <= 160 * 1024
-    q32 = [x.astype(f32) for x in (qpos, qvel, ctrl if cm.nu else np.zeros((N, 1)), warm)]
-
-    def ref_(dtype):
-        d = PhysState(qpos=q32[0].astype(dtype), qvel=q32[1].astype(dtype), ctrl=q32[2].astype(dtype)[:, :cm.nu], qacc_warmstart=q32[3].astype(dtype), time=np.zeros(N, dtype))
-        EqualityPhysics(cm.t, dtype).forward(d)
-        return d
-
-    ref, ref32 = ref_(f64), ref_(f32)
-    got = _probe(be, h, cm, *q32)
-    be.lib.model_close(h)
-    scale = lambda k: np.abs(ref[k]).max() + 1e-6
-    for k, tol in dict(qM=2e-5, qfrc_bias=2e-4, qacc_smooth=5e-4, xpos=1e-5).items():
-        assert np.abs(got[k].reshape(ref[k].shape) - ref[k]).max() <= tol * scale(k), (what, k)
-    good = (np.abs(ref32.efc_J - ref.efc_J).reshape(N, -1).max(1) <= 2e-4 * scale("efc_J")) & (np.abs(ref32.efc_aref - ref.efc_aref).max(1) <= 5e-4 * scale("efc_aref")) & \
-           ((ref32.efc_D > 0) == (ref.efc_D > 0)).all(1)
-    assert good.sum() >= N // 2, (what, good)
-    assert ((got["efc_D"].reshape(N, -1) > 0) == (ref.efc_D > 0))[good].all(), what
-    assert (ref.efc_D[:, :cm.neq] > 0).all() and (got["efc_D"].reshape(N, -1)[:, :cm.neq] > 0).all(), what  # equality rows: always active
-    for k, tol in tol_rows.items():
-        r, g = ref[k], got[k].reshape(ref[k].shape)
-        assert np.abs(g[good] - r[good]).max() <= tol * scale(k), (what, k, np.abs(g[good] - r[good]).max() / scale(k))
-        # the equality rows on their own scale (they come first: efc rows 0 .. neq - 1)
-        re, ge = r[:, :cm.neq], g[:, :cm.neq]
-        assert np.abs(ge[good] - re[good]).max() <= tol * (np.abs(re).max() + 1e-6), (what, k, "equality rows")
-
-    def cost(qacc):  # the Gauss cost with the equality rows active on both signs
-        c = _cost(ref, qacc)
-        jar = np.einsum("nrv,nv->nr", ref.efc_J[:, :cm.neq], qacc.astype(f64)) - ref.efc_aref[:, :cm.neq]
-        return c + 0.5 * np.sum(ref.efc_D[:, :cm.neq] * jar * jar * (jar >= 0), -1)
-
-    c_ref, c32, c_got, c_smooth = cost(ref.qacc), cost(ref32.qacc), cost(got["qacc"]), cost(ref.qacc_smooth)
-    conv = good & (np.abs(c32 - c_ref) <= 5e-2 * np.abs(c_ref) + 1e-3)
-    rel = np.abs(c_got - c_ref)[conv] / (np.abs(c_ref)[conv] + 1e-3)
-    if strict_cost:
-        assert rel.max() <= 5e-2, (what, rel)
-    else:
-        assert np.median(rel) <= 5e-2 and rel.max() <= 0.3, (what, rel)
-    assert np.all(c_got <= c_smooth * (1 + 1e-5) + 1e-6), what
-    assert np.all(got["niter"] <= 6)
-
-
 EQ_SEEDS = list(range(8))
 
 
@@ -319,14 +244,14 @@ def test_kernel_follows_the_reference_on_the_fixtures(be):
     for path in (FOURBAR, COUPLED):
         cm = load_model(path)
         for s in range(2):
-            _check_against_reference(be, cm, *_walking_states(cm, 12, s), f"{Path(path).name}/{s}", dict(efc_J=1e-5, efc_D=5e-4, efc_aref=5e-4))
+            check_against_oracle(be, cm, walking_states(cm, 12, s), f"{Path(path).name}/{s}", SMOOTH_TOL, dict(efc_J=1e-5, efc_D=5e-4, efc_aref=5e-4), min_good=6, strict_cost=True)
 
 
 def test_kernel_follows_the_reference_on_random_robots(be):
     for seed in EQ_SEEDS:
         cm = compile_model(random_equality_model(seed))
         assert cm.neq > 0
-        _check_against_reference(be, cm, *_walking_states(cm, 8, seed), f"random/{seed}", dict(efc_D=1e-3, efc_aref=1e-3, efc_J=5e-4), strict_cost=False)
+        check_against_oracle(be, cm, walking_states(cm, 8, seed), f"random/{seed}", SMOOTH_TOL, dict(efc_D=1e-3, efc_aref=1e-3, efc_J=5e-4), min_good=4, strict_cost=False)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------------
@@ -334,45 +259,16 @@ def test_kernel_follows_the_reference_on_random_robots(be):
 # ---------------------------------------------------------------------------------------------------------------------------------------
 
 
-def _probe_and_steps(be, cm, seed=7, N=9, steps=6):
-    from test_kernels_physics import _probe
-
-    qpos, qvel, ctrl, warm = _walking_states(cm, N, seed)
-    q32 = [x.astype(f32) for x in (qpos, qvel, ctrl, warm)]
-    h, dims, _keep = be.model(cm)
-    flag = C.c_int32(-1)
-    be.lib.model_is_specialized(h, C.byref(flag))
-    got = _probe(be, h, cm, *q32)
-    OP, R = dims.obs_pad, dims.rec_dim
-    state, reset_rec, obs = be.zeros((N, R)), be.zeros((R,)), be.zeros((N, OP))
-    rew, done = be.zeros((N,)), be.zeros((N,), np.uint8)
-    be.lib.env_reset(h, N, be.ptr(state), be.ptr(reset_rec), be.ptr(obs), OP, be.ptr(rew), be.ptr(done), None, be.stream)
-    rc = nat.RewardCfg(0.45, 2.0, 2.0, 0.2, 0.5, 0.1, 4.0, 1.0, 1.25)  # (a height band the biped leaves now and then: resets inside the stretch)
-    r2 = np.random.default_rng(3)
-    for _ in range(steps):
-        act = be.arr((0.8 * r2.standard_normal((N, cm.nu))).astype(f32))
-        be.lib.env_step(h, N, 2, C.byref(rc), be.ptr(state), be.ptr(reset_rec), be.ptr(act), cm.nu, be.ptr(obs), OP, be.ptr(rew), be.ptr(done), None, be.stream)
-        be.sync()
-    got.update(state=be.host(state).copy(), obs=be.host(obs).copy(), rew=be.host(rew).copy(), done=be.host(done).copy())
-    be.lib.model_close(h)
-    return flag.value, got
-
-
-def _assert_bit_equal(a, b):
-    for k in a:
-        assert np.array_equal(np.asarray(a[k]).view(np.uint8), np.asarray(b[k]).view(np.uint8)), k
-
-
 def test_specialised_fourbar_kernel_equals_the_runtime_sized_kernel(be, monkeypatch):
     cm = load_model(FOURBAR)
     monkeypatch.delenv("MPPO_ENV_GENERIC", raising=False)
     monkeypatch.delenv("MPPO_ENV_SPILL", raising=False)
-    flag, spec = _probe_and_steps(be, cm)
+    flag, spec = probe_and_steps(be, cm)
     assert flag == 1
     monkeypatch.setenv("MPPO_ENV_GENERIC", "1")
-    flag, gen = _probe_and_steps(be, cm)
+    flag, gen = probe_and_steps(be, cm)
     assert flag == 0
-    _assert_bit_equal(spec, gen)
+    assert_bit_equal(spec, gen)
 
 
 @pytest.mark.parametrize("path", [FOURBAR, COUPLED])
@@ -383,9 +279,9 @@ def test_jacobian_placements_are_bit_equal(be, monkeypatch, path):
     res = []
     for spill in ("0", "1", "3"):
         monkeypatch.setenv("MPPO_ENV_SPILL", spill)
-        res.append(_probe_and_steps(be, cm)[1])
+        res.append(probe_and_steps(be, cm)[1])
     for r in res[1:]:
-        _assert_bit_equal(res[0], r)
+        assert_bit_equal(res[0], r)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------------
@@ -447,68 +343,13 @@ def test_mutated_equality_blobs_are_refused():
 
 @pytest.mark.gpu
 def test_kernel_compiled_at_start_up_equals_the_runtime_sized_kernel(tmp_path, monkeypatch):
-    import torch
-
     from minppo_amd import build as _build
-    from minppo_amd import jit
-    from test_jit import _run
 
-    monkeypatch.setenv(jit.CACHE_ENV, str(tmp_path))
-    lib = nat.load()
     cm = load_model(FOURBAR)
-    dims_ = jit.dims_of(cm)
-    assert dims_[_build._SPEC_KEYS.index("neq")] == cm.neq == 6
-    image = jit.compile_kernel(dims_, 48).read_bytes()
-    blob = np.frombuffer(cm.to_blob(), np.uint8)
-    dblob = torch.from_numpy(blob.copy()).cuda()
-    outs = []
-    for attach in (False, True):
-        monkeypatch.setenv("MPPO_ENV_GENERIC", "1")
-        h = C.c_void_p()
-        lib.model_open(blob.ctypes.data, blob.size, dblob.data_ptr(), C.byref(h))
-        monkeypatch.delenv("MPPO_ENV_GENERIC")
-        if attach:
-            assert jit.attach(lib, h, image, 48)
-            kind = C.c_int32(-1)
-            lib.model_is_specialized(h, C.byref(kind))
-            assert kind.value == 2
-        dims = nat.ModelDims()
-        lib.model_get_dims(h, C.byref(dims))
-        outs.append((h, _run(lib, h, dims, 300, 12, torch)))
-    for t, (a, b) in enumerate(zip(outs[0][1], outs[1][1])):
-        for x, y, what in zip(a, b, ("state", "observation", "reward", "done")):
-            assert np.array_equal(x.view(np.uint8), y.view(np.uint8)), f"{what} differs at step {t}"
-    for h, _ in outs:
-        lib.model_close(h)
+    startup_kernel_equals_runtime_sized(cm, tmp_path, monkeypatch, lambda dims: dims[_build._SPEC_KEYS.index("neq")] == cm.neq == 6)
 
 
 @pytest.mark.gpu
 def test_engine_trains_on_the_fourbar_biped_reproducibly():
     """make_train on the four-bar biped (environment.model=...): two runs with one seed give bit-identical parameters, no NaN, finite episode metrics."""
-    from minppo_amd.config import load_config_from_cli
-    from minppo_amd.train import make_train
-
-    res = []
-    for _ in range(2):
-        cfg = load_config_from_cli(["stompy_pro", f"environment.model={FOURBAR}", "training.num_envs=512", "training.num_minibatches=4", "training.update_epochs=2",
-                                    "training.total_timesteps=20480"])
-        res.append(make_train(cfg)(1337, log_every=1))
-    flat = [np.concatenate([_host(x).reshape(-1).astype(f32) for x in _leaves(o.runner_state.train_state.params)]) for o in res]
-    assert flat[0].size > 0 and np.isfinite(flat[0]).all()
-    assert np.array_equal(flat[0].view(np.uint8), flat[1].view(np.uint8))
-    for o in res:
-        assert len(o.metrics["mean_reward"]) == 4
-        for k in ("mean_reward", "done_fraction", "mean_episode_return", "mean_episode_length", "total_loss"):
-            assert np.isfinite(np.asarray(o.metrics[k], f64)).all(), k
-
-
-def _host(x):
-    return x.detach().cpu().numpy() if hasattr(x, "detach") else np.asarray(x)
-
-
-def _leaves(tree):
-    if isinstance(tree, dict):
-        return [x for k in sorted(tree) for x in _leaves(tree[k])]
-    if isinstance(tree, (list, tuple)):
-        return [x for v in tree for x in _leaves(v)]
-    return [tree]
+    trains_reproducibly(FOURBAR)

@@ -12,6 +12,7 @@ from minppo_amd import jit
 from minppo_amd.model import compile_model, load_model
 
 from backends import get_backend
+from physics_harness import many_dof_robot, run_steps
 from test_model_fuzz import random_model
 
 ROBOT = "synth_can"  # (a small robot the library has no instantiation for: compiles in seconds)
@@ -40,9 +41,7 @@ def test_code_object_holds_the_three_kernels_of_the_robot(can_object):
     assert jit.compile_kernel(jit.dims_of(cm), 48).read_bytes() == image
     # a robot whose kernel keeps a lambda as a function of its own (40 dofs, three rows per lane: the solve is not inlined): the function's symbol
     # carries the kernel's name inside its own - it is not one of the three
-    from test_kernels_physics import _many_dof_robot
-
-    big = jit.compile_kernel(jit.dims_of(_many_dof_robot()), 48).read_bytes()
+    big = jit.compile_kernel(jit.dims_of(many_dof_robot()), 48).read_bytes()
     assert all(n.startswith("_ZN4mppo10env_kernelI") for n in jit.kernel_symbols(big))
     with pytest.raises(ValueError):
         jit.kernel_symbols(b"\x7fELF" + bytes(200))
@@ -92,27 +91,6 @@ def test_library_refuses_what_is_not_this_robots_kernel(can_object):
     be.lib.model_close(h2)
 
 
-def _run(lib, h, dims, N, steps, torch, seed=0):
-    state = torch.zeros(N, dims.rec_dim, device="cuda")
-    reset = torch.zeros(dims.rec_dim, device="cuda")
-    obs = torch.zeros(N, dims.obs_pad, device="cuda")
-    rew = torch.zeros(N, device="cuda")
-    done = torch.zeros(N, dtype=torch.uint8, device="cuda")
-    s = torch.cuda.current_stream().cuda_stream
-    lib.env_reset(h, N, state.data_ptr(), reset.data_ptr(), obs.data_ptr(), dims.obs_pad, 0, 0, None, s)
-    g = torch.Generator(device="cuda")
-    g.manual_seed(seed)
-    rc = nat.RewardCfg(-0.2, 2.0, 2.0, 0.2, 0.5, 0.1, 4.0, 1.0, 1.25)
-    out = []
-    nu = max(dims.nu, 1)
-    for _ in range(steps):
-        act = torch.randn(N, nu, device="cuda", generator=g)
-        lib.env_step(h, N, 1, C.byref(rc), state.data_ptr(), reset.data_ptr(), act.data_ptr(), nu, obs.data_ptr(), dims.obs_pad, rew.data_ptr(), done.data_ptr(), None, s)
-        torch.cuda.synchronize()
-        out.append((state.cpu().numpy().copy(), obs.cpu().numpy().copy(), rew.cpu().numpy().copy(), done.cpu().numpy().copy()))
-    return out
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("robot", [ROBOT, "synth_stompy_frames", "random4"])
 def test_attached_kernel_equals_the_runtime_sized_kernel(robot, tmp_path, monkeypatch):
@@ -135,7 +113,7 @@ def test_attached_kernel_equals_the_runtime_sized_kernel(robot, tmp_path, monkey
     for h in hs:
         dims = nat.ModelDims()
         lib.model_get_dims(h, C.byref(dims))
-        outs.append(_run(lib, h, dims, 300, 12, torch))
+        outs.append(run_steps(lib, h, dims, 300, 12, torch))
     for t, (a, b) in enumerate(zip(*outs)):
         for x, y, what in zip(a, b, ("state", "observation", "reward", "done")):
             assert np.array_equal(x.view(np.uint8), y.view(np.uint8)), f"{robot}: {what} differs at step {t}"

@@ -33,6 +33,7 @@ from minppo_amd import _native as nat
 from minppo_amd.model import load_model
 from oracle.env_oracle import EnvOracle, RewardCfg
 from oracle.physics_oracle import Physics, PhysState
+from physics_harness import cost, euler_acc, many_dof_robot, pack, probe
 
 f32 = np.float32
 
@@ -44,37 +45,6 @@ def _NOT_IN_THE_LIBRARY(be):
     if os.environ.get("MPPO_ENV_GENERIC") == "1" or os.environ.get("MPPO_ENV_SPILL"):
         return 0  # (the switches that force the run-time-sized kernel)
     return 2 if (os.environ.get("MPPO_TEST_JIT") == "1" and be.name == "hip") else 0
-
-
-def _probe(be, h, cm, qpos, qvel, ctrl, warm):
-    N = qpos.shape[0]
-    nv, nb, nefc = cm.nv, cm.nbody, max(cm.nefc, 1)
-    shapes = dict(qM=(N, nv, nv), qfrc_bias=(N, nv), qfrc_passive=(N, nv), qfrc_actuator=(N, nv), qacc_smooth=(N, nv), efc_J=(N, nefc, nv),
-                  efc_D=(N, nefc), efc_aref=(N, nefc), qacc=(N, nv), cinert=(N, nb, 10), cvel=(N, nb, 6), subtree_com1=(N,), xpos=(N, nb, 3),
-                  qacc_euler=(N, nv))
-    out = {k: be.zeros(s) for k, s in shapes.items()}
-    niter = be.zeros((N,), np.int32)
-    d_in = [be.arr(x.astype(f32)) for x in (qpos, qvel, ctrl if cm.nu else np.zeros((N, 1)), warm)]
-    pr = nat.ForwardProbe(**{k: be.ptr(v) for k, v in out.items()}, solver_niter=be.ptr(niter))
-    be.lib.physics_forward(h, N, be.ptr(d_in[0]), be.ptr(d_in[1]), be.ptr(d_in[2]) if cm.nu else 0, be.ptr(d_in[3]), C.byref(pr), be.stream)
-    res = {k: be.host(v) for k, v in out.items()}
-    res["niter"] = be.host(niter)
-    return res
-
-
-def _cost(ref, qacc):
-    qacc = qacc.astype(np.float64)
-    jar = np.einsum("nrv,nv->nr", ref.efc_J, qacc) - ref.efc_aref
-    Ma = np.einsum("nij,nj->ni", ref.qM, qacc)
-    return 0.5 * np.sum(ref.efc_D * jar * jar * (jar < 0), -1) + 0.5 * np.sum((Ma - ref.qfrc_smooth) * (qacc - ref.qacc_smooth), -1)
-
-
-def _euler_acc(cm, ref):
-    """the acceleration the integrator applies (MJX euler with implicit joint damping):
-    (M + h diag(damping))^-1 (qfrc_smooth + qfrc_constraint) - for an undamped model too (MJX has no test for that; physics_oracle.euler)"""
-    damp = np.asarray(cm.t["dof_damping"], np.float64)
-    dh = ref.qM + float(cm.t["timestep"]) * np.eye(cm.nv)[None] * damp[None, :, None]
-    return np.linalg.solve(dh, (ref.qfrc_smooth + ref.qfrc_constraint)[..., None])[..., 0]
 
 
 def _walk(cm, N, steps, seed, scale=0.3):
@@ -110,7 +80,7 @@ def test_forward_matches_oracle(be, model, N):
     ref = PhysState(qpos=q32[0].astype(np.float64), qvel=q32[1].astype(np.float64), ctrl=q32[2].astype(np.float64),
                     qacc_warmstart=q32[3].astype(np.float64), time=np.zeros(N))
     ph.forward(ref)
-    got = _probe(be, h, cm, *q32)
+    got = probe(be, h, cm, *q32)
     tol = dict(qM=1e-5, qfrc_bias=1e-4, qfrc_passive=1e-5, qfrc_actuator=1e-5, qacc_smooth=2e-4, efc_J=1e-5, efc_D=5e-4, efc_aref=5e-4, cinert=1e-5,
                cvel=1e-4, xpos=1e-5)
     for k, t in tol.items():
@@ -121,7 +91,7 @@ def test_forward_matches_oracle(be, model, N):
         assert np.abs(got[k].reshape(r.shape) - r).max() <= t * scale, (k, np.abs(got[k].reshape(r.shape) - r).max(), scale)
     assert np.allclose(got["subtree_com1"], ref.subtree_com[:, 1, 0], atol=1e-5)
     if cm.nefc:
-        c_got, c_ref, c_smooth = _cost(ref, got["qacc"]), _cost(ref, ref.qacc), _cost(ref, ref.qacc_smooth)
+        c_got, c_ref, c_smooth = cost(ref, got["qacc"]), cost(ref, ref.qacc), cost(ref, ref.qacc_smooth)
         np.testing.assert_allclose(c_got, c_ref, rtol=5e-2, atol=1e-3)
         assert np.all(c_got <= c_smooth * (1 + 1e-5) + 1e-6)
         assert np.all(got["niter"] <= 6)
@@ -130,7 +100,7 @@ def test_forward_matches_oracle(be, model, N):
         assert np.median(rel) <= 5e-3 and rel.max() <= 0.3, (np.median(rel), rel.max())
         # and what the integrator does with it: qvel' = qvel + h (M + h D)^-1 (qfrc_smooth + qfrc_constraint)
         # (qfrc_constraint = J^T efc_force enters here: the oracle's value is the float64 one)
-        ref_e = _euler_acc(cm, ref)
+        ref_e = euler_acc(cm, ref)
         rel_e = np.abs(got["qacc_euler"] - ref_e).max(1) / (np.abs(ref_e).max(1) + 1e-9)
         # (the export-style biped: 87 constraint rows on light end bodies whose implicit damping h D is larger than their inertia - the same
         # float32 envelope of the unconverged solver reads wider in this quantity: 4 of 12 states at 0.3 - 0.65 on the GPU, median 6e-3)
@@ -170,7 +140,7 @@ def test_forward_matches_the_f64_oracle_at_full_size(model, N):
     assert np.isfinite(rec).all() and np.unique(q32[0][:, 7]).size > N // 2 and q32[0][:, 7].std() > 1e-3  # N different poses, not N copies of one
     ref = PhysState(qpos=q32[0].astype(np.float64), qvel=q32[1].astype(np.float64), ctrl=q32[2].astype(np.float64), qacc_warmstart=q32[3].astype(np.float64), time=np.zeros(N))
     Physics(cm.t).forward(ref)
-    got = _probe(be, h, cm, *q32)
+    got = probe(be, h, cm, *q32)
     tol = dict(qM=1e-5, qfrc_bias=1e-4, qfrc_passive=1e-5, qfrc_actuator=1e-5, qacc_smooth=2e-4, cinert=1e-5, cvel=1e-4, xpos=1e-5)
     for k, t in tol.items():
         r = ref[k]
@@ -192,12 +162,12 @@ def test_forward_matches_the_f64_oracle_at_full_size(model, N):
         assert diff[same].max() <= t * scale, (k, diff[same].max(), scale)
     ok = same.all(1)  # environments whose active sets agree: the solver saw the same problem
     assert ok.mean() >= 0.99
-    c_got, c_ref, c_smooth = _cost(ref, got["qacc"]), _cost(ref, ref.qacc), _cost(ref, ref.qacc_smooth)
+    c_got, c_ref, c_smooth = cost(ref, got["qacc"]), cost(ref, ref.qacc), cost(ref, ref.qacc_smooth)
     np.testing.assert_allclose(c_got[ok], c_ref[ok], rtol=5e-2, atol=1e-3)
     assert np.all(c_got[ok] <= c_smooth[ok] * (1 + 1e-5) + 1e-6) and np.all(got["niter"] <= 6)
     rel = (np.abs(got["qacc"] - ref.qacc).max(1) / (np.abs(ref.qacc).max(1) + 1e-9))[ok]
     assert np.median(rel) <= 5e-3 and np.quantile(rel, 0.999) <= 0.3, (np.median(rel), np.quantile(rel, 0.999), rel.max())
-    ref_e = _euler_acc(cm, ref)
+    ref_e = euler_acc(cm, ref)
     rel_e = (np.abs(got["qacc_euler"] - ref_e).max(1) / (np.abs(ref_e).max(1) + 1e-9))[ok]
     assert np.median(rel_e) <= 5e-3 and np.quantile(rel_e, 0.9) <= 0.3, (np.median(rel_e), np.quantile(rel_e, 0.9))
     be.lib.model_close(h)
@@ -252,10 +222,10 @@ def test_solver_is_tight_where_the_active_set_is_stable(be, model, state, med, q
     ph.forward(ref)
     nact = (ref.efc_D > 0).sum(1)
     assert nact.min() >= (2 if state == "limits" else 4), nact  # the case really has active rows
-    got = _probe(be, h, cm, *q32)
+    got = probe(be, h, cm, *q32)
     rel = np.abs(got["qacc"] - ref.qacc).max(1) / (np.abs(ref.qacc).max(1) + 1e-9)
     assert np.median(rel) <= med and np.quantile(rel, 0.75) <= q75 and rel.max() <= 0.3, (np.median(rel), np.quantile(rel, 0.75), rel.max())
-    ref_e = _euler_acc(cm, ref)
+    ref_e = euler_acc(cm, ref)
     # at rest the net acceleration is the small difference of gravity and contact forces: its scale is that of qacc_smooth
     rel_e = np.abs(got["qacc_euler"] - ref_e).max(1) / np.maximum(np.abs(ref_e).max(1), np.abs(ref.qacc_smooth).max(1))
     # (no bound on the maximum here: qfrc_constraint = J^T D (aref - J qacc) multiplies a solver outlier by the constraint
@@ -263,7 +233,7 @@ def test_solver_is_tight_where_the_active_set_is_stable(be, model, state, med, q
     assert np.median(rel_e) <= med and np.quantile(rel_e, 0.75) <= (2e-2 if state == "limits" else 2 * q75), (np.median(rel_e), np.quantile(rel_e, 0.75), rel_e.max())
     # the cost reached: the bulk equal to the oracle's, no environment more than 2x above it (measured: 1.36x in one of 32;
     # the outlier environments also land BELOW the oracle's cost, by up to 20 %)
-    c_got, c_ref = _cost(ref, got["qacc"]), _cost(ref, ref.qacc)
+    c_got, c_ref = cost(ref, got["qacc"]), cost(ref, ref.qacc)
     assert np.all(c_got <= 2.0 * c_ref + 1e-3), (c_got / (c_ref + 1e-9)).max()
     assert np.median(np.abs(c_got - c_ref) / (c_ref + 1e-3)) <= 1e-4
     be.lib.model_close(h)
@@ -292,13 +262,13 @@ def test_box_collider_corner_contacts(be, steps, min_rows, med):
     ref = PhysState(qpos=q32[0].astype(np.float64), qvel=q32[1].astype(np.float64), ctrl=np.zeros((N, 0)), qacc_warmstart=q32[3].astype(np.float64), time=np.zeros(N))
     ph.forward(ref)
     assert ((ref.efc_D > 0).sum(1) >= min_rows).all(), (ref.efc_D > 0).sum(1)
-    got = _probe(be, h, cm, *q32)
+    got = probe(be, h, cm, *q32)
     for k, t in dict(qM=1e-5, efc_J=1e-5, efc_D=5e-4, efc_aref=5e-4, xpos=1e-5).items():
         r = ref[k]
         assert np.abs(got[k].reshape(r.shape) - r).max() <= t * (np.abs(r).max() + 1e-6), k
     rel = np.abs(got["qacc"] - ref.qacc).max(1) / (np.abs(ref.qacc).max(1) + np.abs(ref.qacc_smooth).max(1))
     assert np.median(rel) <= med and rel.max() <= 0.3, (np.median(rel), rel.max())
-    c_got, c_ref = _cost(ref, got["qacc"]), _cost(ref, ref.qacc)
+    c_got, c_ref = cost(ref, got["qacc"]), cost(ref, ref.qacc)
     np.testing.assert_allclose(c_got, c_ref, rtol=5e-2, atol=1e-3)
     be.lib.model_close(h)
 
@@ -326,13 +296,13 @@ def test_mesh_collider_plane_convex_contacts(be, steps, min_rows, med):
     ref = PhysState(qpos=q32[0].astype(np.float64), qvel=q32[1].astype(np.float64), ctrl=q32[2].astype(np.float64), qacc_warmstart=q32[3].astype(np.float64), time=np.zeros(N))
     ph.forward(ref)
     assert ((ref.efc_D[:, cm.nlimit:] > 0).sum(1) >= min_rows).all(), (ref.efc_D > 0).sum(1)
-    got = _probe(be, h, cm, *q32)
+    got = probe(be, h, cm, *q32)
     for k, t in dict(qM=1e-5, efc_J=2e-5, efc_D=5e-4, efc_aref=5e-4, xpos=1e-5).items():
         r = ref[k]
         assert np.abs(got[k].reshape(r.shape) - r).max() <= t * (np.abs(r).max() + 1e-6), k
     rel = np.abs(got["qacc"] - ref.qacc).max(1) / (np.abs(ref.qacc).max(1) + np.abs(ref.qacc_smooth).max(1))
     assert np.median(rel) <= med and rel.max() <= 0.3, (np.median(rel), rel.max())
-    c_got, c_ref = _cost(ref, got["qacc"]), _cost(ref, ref.qacc)
+    c_got, c_ref = cost(ref, got["qacc"]), cost(ref, ref.qacc)
     np.testing.assert_allclose(c_got, c_ref, rtol=5e-2, atol=1e-3)
     be.lib.model_close(h)
 
@@ -404,7 +374,7 @@ def test_geom_pair_contacts(be, model, N):
     first_pair_row = cm.nlimit + 4 * (cm.ncon - cm.npair)
     pair_active = (ref.efc_D[:, first_pair_row:] > 0).reshape(N, cm.npair, 4)[:, :, 0]
     assert pair_active.any(0).sum() >= (3 if model == "synth_tumblers" else 2), pair_active.sum(0)  # which candidates fire somewhere in the batch
-    got = _probe(be, h, cm, *q32)
+    got = probe(be, h, cm, *q32)
     # The contact normal is (p2 - p1) / |p2 - p1| between the closest points of the two segments: it is ill-conditioned when
     # those points nearly coincide (deep overlap), and for parallel capsules the points themselves are (MJX divides rounding
     # noise by 1e-6 there).  The distance is well-conditioned always.  So: efc_D (a function of the distance) everywhere;
@@ -420,7 +390,7 @@ def test_geom_pair_contacts(be, model, N):
         r, gk = ref[k], got[k].reshape(ref[k].shape)
         sel = slice(None) if k in ("efc_D", "qM", "xpos") else good
         assert np.abs(gk[sel] - r[sel]).max() <= t * (np.abs(r).max() + 1e-6), (k, np.abs(gk[sel] - r[sel]).max())
-    c_got, c_ref, c_smooth = _cost(ref, got["qacc"]), _cost(ref, ref.qacc), _cost(ref, ref.qacc_smooth)
+    c_got, c_ref, c_smooth = cost(ref, got["qacc"]), cost(ref, ref.qacc), cost(ref, ref.qacc_smooth)
     np.testing.assert_allclose(c_got[good], c_ref[good], rtol=5e-2, atol=1e-3)
     assert np.all(c_got[good] <= c_smooth[good] * (1 + 1e-5) + 1e-6)
     rel = (np.abs(got["qacc"] - ref.qacc).max(1) / (np.abs(ref.qacc).max(1) + 1e-9))[good]
@@ -466,34 +436,10 @@ def test_colliding_spheres_conserve_momentum(be):
     be.lib.model_close(h)
 
 
-def _many_dof_robot():
-    """The 26-dof stand-in with a 4-joint neck and two 5-joint tails: 40 dofs, 37 bodies - past what the model-specialised kernels and the
-    register Cholesky cover (32 dofs), so the run-time-sized kernel's LDS factorisation (two triangular work copies) is what runs."""
-    from minppo_amd import model as M
-
-    spec = M.synth_stompy_full()
-    extra, acts = [], []
-
-    def chain(prefix, parent, n, pos0, axis_cycle, step):
-        par = parent
-        for k in range(n):
-            name = f"{prefix}{k}"
-            extra.append(M.BodySpec(name, par, pos=pos0 if k == 0 else step, mass=0.3, inertia=(0.0008, 0.0008, 0.0004), ipos=(0.0, 0.0, 0.5 * step[2]),
-                                    joints=[M.JointSpec(name, M.JNT_HINGE, axis=axis_cycle[k % len(axis_cycle)], range=(-0.7, 0.7), damping=0.5, armature=0.02)],
-                                    geoms=[M.GeomSpec(M.GEOM_SPHERE, (0.03,), pos=(0.0, 0.0, step[2]))] if k == n - 1 else []))
-            acts.append(M.ActuatorSpec(name, kp=8.0, kv=0.0, ctrlrange=(-1.0, 1.0), forcerange=(-10.0, 10.0)))
-            par = name
-
-    chain("neck", "torso", 4, (0.0, 0.0, 0.40), [(0, 1, 0), (1, 0, 0), (0, 0, 1)], (0.0, 0.0, 0.06))
-    chain("tail_l", "torso", 5, (-0.10, 0.05, 0.0), [(0, 1, 0), (1, 0, 0)], (0.0, 0.0, -0.09))
-    chain("tail_r", "torso", 5, (-0.10, -0.05, 0.0), [(0, 1, 0), (1, 0, 0)], (0.0, 0.0, -0.09))
-    return M.compile_model(M.ModelSpec(name="many_dof", bodies=spec.bodies + extra, actuators=spec.actuators + acts, free_root_z=spec.free_root_z))
-
-
 def test_forty_dof_robot_runs_the_runtime_sized_kernel(be):
     """More dofs than the register Cholesky / model-specialised kernels cover: dims, the LDS budget of one four-environment wave,
     the forward pass against the oracle and a few steps against the environment oracle's done flags."""
-    cm = _many_dof_robot()
+    cm = many_dof_robot()
     assert cm.nv == 40 and cm.nu == 34
     h, dims, _keep = be.model(cm)
     flag = C.c_int32(-1)
@@ -506,14 +452,14 @@ def test_forty_dof_robot_runs_the_runtime_sized_kernel(be):
     ref = PhysState(qpos=q32[0].astype(np.float64), qvel=q32[1].astype(np.float64), ctrl=q32[2].astype(np.float64),
                     qacc_warmstart=q32[3].astype(np.float64), time=np.zeros(N))
     ph.forward(ref)
-    got = _probe(be, h, cm, *q32)
+    got = probe(be, h, cm, *q32)
     for k, t in dict(qM=1e-5, qfrc_bias=2e-4, qacc_smooth=5e-4, efc_J=1e-5, efc_D=5e-4, efc_aref=5e-4, cinert=1e-5, cvel=1e-4, xpos=1e-5).items():
         r = ref[k]
         scale = np.abs(r).max() + 1e-6
         assert np.abs(got[k].reshape(r.shape) - r).max() <= t * scale, (k, np.abs(got[k].reshape(r.shape) - r).max(), scale)
-    np.testing.assert_allclose(_cost(ref, got["qacc"]), _cost(ref, ref.qacc), rtol=5e-2, atol=1e-3)
+    np.testing.assert_allclose(cost(ref, got["qacc"]), cost(ref, ref.qacc), rtol=5e-2, atol=1e-3)
     # the Euler solve goes through the second factor (M + h D)
-    acc = _euler_acc(cm, ref)
+    acc = euler_acc(cm, ref)
     assert np.median(np.abs(got["qacc_euler"] - acc)) <= 5e-3 * (np.abs(acc).max() + 1e-6)
     be.lib.model_close(h)
 
@@ -577,7 +523,7 @@ def test_specialised_kernel_equals_the_runtime_sized_kernel(be, monkeypatch):
             flag = C.c_int32(-1)
             be.lib.model_is_specialized(h, C.byref(flag))
             assert flag.value == (0 if generic else 1)
-            got = _probe(be, h, cm, *q32)
+            got = probe(be, h, cm, *q32)
             OP, R = dims.obs_pad, dims.rec_dim
             state, reset_rec, obs = be.zeros((N, R)), be.zeros((R,)), be.zeros((N, OP))
             rew, done = be.zeros((N,)), be.zeros((N,), np.uint8)
@@ -630,7 +576,7 @@ def test_matrices_in_global_memory_change_nothing(be, monkeypatch):
         nb = C.c_size_t(0)
         be.lib.model_scratch_bytes(h, N, C.byref(nb))
         scratch.append(nb.value); lds.append(dims.lds_bytes)
-        got = _probe(be, h, cm, *q32)
+        got = probe(be, h, cm, *q32)
         OP, R = dims.obs_pad, dims.rec_dim
         state, reset_rec, obs = be.zeros((N, R)), be.zeros((R,)), be.zeros((N, OP))
         rew, done = be.zeros((N,)), be.zeros((N,), np.uint8)
@@ -676,17 +622,6 @@ def test_free_fall_is_exact_semi_implicit_euler(be):
     be.lib.model_close(h)
 
 
-def _pack(env, s, dims, nv):
-    N = s.qpos.shape[0]
-    O, OP = dims.obs_dim, dims.obs_pad
-    rec = np.zeros((N, dims.rec_dim), f32)
-    rec[:, :O] = env.get_obs(s)
-    rec[:, OP:OP + nv] = s.qacc_warmstart
-    rec[:, OP + nv] = s.subtree_com[:, 1, 0]
-    rec[:, OP + nv + 1] = s.time
-    return rec
-
-
 @pytest.mark.parametrize("model,n_frames,c_vals", [("synth_stompy_pro", 1, True), ("synth_stompy_pro", 2, True), ("synth_stompy_full", 1, True),
                                                     ("synth_stompy_pro", 1, False),  # environment.include_c_vals = false (env.py:254-259)
                                                     ("synth_stompy_pro_sc", 1, True)])  # with geom-geom candidates (8 f1)
@@ -709,7 +644,7 @@ def test_env_step_matches_env_oracle(be, model, n_frames, c_vals):
     es = env.reset(N)
     np.testing.assert_allclose(be.host(obs)[:, :O], es["obs"], atol=1e-5)
     assert (be.host(obs)[:, O:] == 0).all()
-    np.testing.assert_allclose(be.host(state), _pack(env, es["pipeline_state"], dims, nv), atol=2e-3)
+    np.testing.assert_allclose(be.host(state), pack(env, es["pipeline_state"], dims, nv), atol=2e-3)
     np.testing.assert_allclose(be.host(reset_rec), be.host(state)[0])
     for k in met:
         assert (be.host(met[k]) == 0).all(), k
@@ -723,7 +658,7 @@ def test_env_step_matches_env_oracle(be, model, n_frames, c_vals):
             es["pipeline_state"]["qvel"][3, 2] = -30.0  # slammed down: terminates by height
         if t == 15:
             es["pipeline_state"]["qvel"][5, 0] = np.nan  # NaN guard (env.py:173-176)
-        be.put(state, _pack(env, es["pipeline_state"], dims, nv))
+        be.put(state, pack(env, es["pipeline_state"], dims, nv))
         for k in met:
             be.put(met[k], es["metrics"][k].astype(met_np[k]))
         da = be.arr(a)
@@ -782,7 +717,7 @@ def test_export_style_biped_compiles_steps_and_follows_the_oracle(be, model):
     rng = np.random.default_rng(4)
     for t in range(12):
         a = (0.5 * rng.standard_normal((N, nu))).astype(f32)
-        be.put(state, _pack(env, es["pipeline_state"], dims, nv))
+        be.put(state, pack(env, es["pipeline_state"], dims, nv))
         be.lib.env_step(h, N, 1, C.byref(rc), be.ptr(state), be.ptr(reset_rec), be.ptr(be.arr(a)), nu, be.ptr(obs), OP, be.ptr(rew), be.ptr(done), None, be.stream)
         es = env.step(es, a.astype(np.float64))
         assert (be.host(done).astype(bool) == es["done"]).all(), t

@@ -4,8 +4,8 @@ bits of its amount, so a dof-set site that still reads one word turns dof 70 int
 
 The fixture, tests/golden/many_dofs/hands_humanoid.xml (tests/golden/many_dofs/make_hands_humanoid.py): a humanoid with two five-finger hands, 77 dofs, the
 arms and hands declared before the legs - every leg dof, leg limit, leg actuator and foot contact row sits at dof index 65 .. 76.  Its
-fingers are coupled by joint equalities (mimic joints), so the float64 reference of the kernel is tests/equality_ref.py (the physics
-oracle plus MJX's equality rows); variants without the equalities are compared with oracle/physics_oracle.py itself."""
+fingers are coupled by joint equalities (mimic joints): the float64 oracle (oracle/physics_oracle.py) puts MJX's equality rows first in
+the constraint; variants without the equalities are compared at test_forward_matches_oracle's tolerances."""
 
 import ctypes as C
 import os
@@ -14,13 +14,14 @@ from pathlib import Path
 import numpy as np
 import pytest
 
-from equality_ref import EqualityPhysics
 from minppo_amd import _native as nat
 from minppo_amd import model as M
 from minppo_amd.mjcf import load_mjcf
 from minppo_amd.model import JNT_FREE, JNT_HINGE, JNT_SLIDE, MAX_DOFS, compile_model, load_model
 from oracle.env_oracle import EnvOracle, RewardCfg
 from oracle.physics_oracle import Physics, PhysState
+from physics_harness import (SMOOTH_TOL, assert_bit_equal, check_against_oracle, cost, euler_acc, pack, probe, probe_and_steps, random_states,
+                             startup_kernel_equals_runtime_sized, walking_states)
 
 f32, f64 = np.float32, np.float64
 HANDS = str(Path(__file__).parent / "golden" / "many_dofs" / "hands_humanoid.xml")  # (a directory of its own: tests/golden/*.xml are the
@@ -149,7 +150,7 @@ def test_128_dof_robots_get_a_layout_within_lds(be):
         be.lib.model_close(h)
     cm = compile_model(_largest_robot())
     assert cm.nv == 128 and cm.nefc == 614
-    _forward_vs_oracle(be, cm, Physics, N=2, seed=3, solver=False)
+    _forward_vs_oracle(be, cm, N=2, seed=3, solver=False)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------------
@@ -163,8 +164,6 @@ def test_a_dof_beyond_64_moves_its_subtree_only(be, monkeypatch, spill):
     fingertips are in contact.  cvel is non-zero exactly on the right foot; column k of a contact's Jacobian rows is zero whenever dof
     k does not move the contact's body - so column d is exactly zero on a left fingertip (which dof d - 64 does move: a one-word test of d
     reads it) and on the left foot (which neither moves).  Also with the Jacobian in LDS (MPPO_ENV_SPILL=0, the run-time-sized kernel)."""
-    from test_kernels_physics import _probe
-
     if spill is None:
         monkeypatch.delenv("MPPO_ENV_SPILL", raising=False)
     else:
@@ -181,7 +180,7 @@ def test_a_dof_beyond_64_moves_its_subtree_only(be, monkeypatch, spill):
     qpos[1, int(t["jnt_qposadr"][cm.joint_names.index("r_knee")])] = 0.7  # (a second pose: the joint axes move)
     qvel = np.zeros((N, cm.nv))
     qvel[:, d] = 1.5
-    got = _probe(be, h, cm, qpos.astype(f32), qvel.astype(f32), np.zeros((N, cm.nu), f32), np.zeros((N, cm.nv), f32))
+    got = probe(be, h, cm, qpos.astype(f32), qvel.astype(f32), np.zeros((N, cm.nu), f32), np.zeros((N, cm.nv), f32))
     be.lib.model_close(h)
     anc, _ = _sets(t, cm.nbody, cm.nv)
     moved = np.array([(anc[b] >> d) & 1 for b in range(cm.nbody)], bool)
@@ -220,32 +219,16 @@ def test_a_dof_beyond_64_moves_its_subtree_only(be, monkeypatch, spill):
 # ---------------------------------------------------------------------------------------------------------------------------------------
 
 
-def _walk_states(cm, ph_cls, N, seed, steps=6):
-    """qpos0 with every joint moved a little, random velocities, then `steps` steps of the float64 model under random controls."""
-    ph = ph_cls(cm.t)
-    rng = np.random.default_rng(seed)
-    q = np.tile(np.asarray(cm.t["qpos0"], f64), (N, 1))
-    for j in range(cm.njnt):
-        if int(cm.t["jnt_type"][j]) != JNT_FREE:
-            q[:, int(cm.t["jnt_qposadr"][j])] += 0.05 * rng.standard_normal(N)
-    d = ph.pipeline_init(q, 0.2 * rng.standard_normal((N, cm.nv)))
-    for _ in range(steps):
-        d = ph.pipeline_step(d, 0.5 * rng.standard_normal((N, cm.nu)))
-    return d.qpos, d.qvel, 0.5 * rng.standard_normal((N, cm.nu)), d.qacc_warmstart
-
-
-def _forward_vs_oracle(be, cm, ph_cls, N, seed, solver=True, states=None):
+def _forward_vs_oracle(be, cm, N, seed, solver=True, states=None):
     """The comparisons of tests/test_kernels_physics.py::test_forward_matches_oracle at its tolerances: tight before the solver, the solver through
     its cost and the Euler envelope."""
-    from test_kernels_physics import _cost, _euler_acc, _probe
-
     h, dims, _keep = be.model(cm)
     assert dims.obs_dim == cm.obs_size() and dims.nefc == cm.nefc and dims.lds_bytes <= 160 * 1024
-    qpos, qvel, ctrl, warm = states if states is not None else _walk_states(cm, ph_cls, N, seed)
+    qpos, qvel, ctrl, warm = states if states is not None else walking_states(cm, N, seed)
     q32 = [x.astype(f32) for x in (qpos, qvel, ctrl if cm.nu else np.zeros((N, 1)), warm)]
     ref = PhysState(qpos=q32[0].astype(f64), qvel=q32[1].astype(f64), ctrl=q32[2].astype(f64)[:, :cm.nu], qacc_warmstart=q32[3].astype(f64), time=np.zeros(N))
-    ph_cls(cm.t).forward(ref)
-    got = _probe(be, h, cm, *q32)
+    Physics(cm.t).forward(ref)
+    got = probe(be, h, cm, *q32)
     be.lib.model_close(h)
     tol = dict(qM=1e-5, qfrc_bias=1e-4, qfrc_passive=1e-5, qfrc_actuator=1e-5, qacc_smooth=2e-4, efc_J=1e-5, efc_D=5e-4, efc_aref=5e-4, cinert=1e-5,
                cvel=1e-4, xpos=1e-5)
@@ -258,12 +241,12 @@ def _forward_vs_oracle(be, cm, ph_cls, N, seed, solver=True, states=None):
     assert np.allclose(got["subtree_com1"], ref.subtree_com[:, 1, 0], atol=1e-5)
     if not solver:
         return
-    c_got, c_ref, c_smooth = _cost(ref, got["qacc"]), _cost(ref, ref.qacc), _cost(ref, ref.qacc_smooth)
+    c_got, c_ref, c_smooth = cost(ref, got["qacc"]), cost(ref, ref.qacc), cost(ref, ref.qacc_smooth)
     np.testing.assert_allclose(c_got, c_ref, rtol=5e-2, atol=1e-3)
     assert np.all(c_got <= c_smooth * (1 + 1e-5) + 1e-6) and np.all(got["niter"] <= 6)
     rel = np.abs(got["qacc"] - ref.qacc).max(1) / (np.abs(ref.qacc).max(1) + 1e-9)
     assert np.median(rel) <= 5e-3 and rel.max() <= 0.3, (cm.name, np.median(rel), rel.max())
-    ref_e = _euler_acc(cm, ref)
+    ref_e = euler_acc(cm, ref)
     rel_e = np.abs(got["qacc_euler"] - ref_e).max(1) / (np.abs(ref_e).max(1) + 1e-9)
     # (the fixture's fingers are light end bodies whose implicit damping h D exceeds their inertia, as on the export-style biped: measured on the
     # emulator, per-state 3e-3 .. 8.4e-2 (median 2.2e-2) as declared, 2e-4 .. 2.5e-2 legs first - and the float32 ORACLE on the same states
@@ -280,21 +263,19 @@ def test_forward_without_equalities_matches_the_oracle(be, legs_first):
     assert cm.nv == 77 and cm.neq == 0
     if legs_first:
         assert max(_dof(cm, f"{s}_{j}") for s in "lr" for j in ("hip_z", "ankle_x")) < 64 and _dof(cm, "r_thumb_dip") == cm.nv - 1
-    _forward_vs_oracle(be, cm, Physics, N=6, seed=5)
+    _forward_vs_oracle(be, cm, N=6, seed=5)
 
 
 @pytest.mark.parametrize("legs_first", [False, True])
 def test_fixture_follows_the_equality_reference(be, legs_first):
-    """The fixture itself (mimic rows first in the constraint): tests/equality_ref.py at the tolerances test_equality.py holds its fixtures to."""
-    from test_equality import _check_against_reference
-
+    """The fixture itself (mimic rows first in the constraint) at the tolerances test_equality.py holds its fixtures to."""
     cm = compile_model(_spec(legs_first=legs_first))
     assert cm.neq == 10
     for s in range(2):
         # (the solver's cost on the median, at most 0.3 away in single states - the bound of test_equality.py's random robots: measured on the
         # emulator, one of the six legs-first states of seed 11 ends 0.26 from the float64 cost, the others within 2e-3)
-        _check_against_reference(be, cm, *_walk_states(cm, EqualityPhysics, 6, 10 + s), f"hands/{legs_first}/{s}", dict(efc_J=1e-5, efc_D=5e-4, efc_aref=5e-4),
-                                 strict_cost=False)
+        check_against_oracle(be, cm, walking_states(cm, 6, 10 + s), f"hands/{legs_first}/{s}", SMOOTH_TOL, dict(efc_J=1e-5, efc_D=5e-4, efc_aref=5e-4), min_good=3,
+                             strict_cost=False)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------------
@@ -346,41 +327,16 @@ MANY_DOF_SEEDS = list(range(int(os.environ.get("MPPO_FUZZ_MANY_DOF_ROBOTS", "4")
 
 @pytest.mark.parametrize("seed", MANY_DOF_SEEDS)
 def test_kernel_follows_the_oracle_on_a_random_many_dof_robot(be, seed):
-    from test_kernels_physics import _probe
-    from test_model_fuzz import _states
-
     cm = compile_model(random_many_dof_model(seed))
     assert 64 < cm.nv <= MAX_DOFS and cm.npair > 0 and cm.ncon > cm.npair
     lim_dofs = {int(cm.t["jnt_dofadr"][j]) for j in cm.t["lim_jntid"]}
     act_dofs = {int(x) for x in cm.t["act_dofid"]}
     assert {6, cm.nv - 1} <= lim_dofs and {6, cm.nv - 1} <= act_dofs
-    h, dims, _keep = be.model(cm)
-    assert dims.lds_bytes <= 160 * 1024
     N = 6
-    rng = np.random.default_rng(seed)
-    qpos, qvel, ctrl = _states(cm, N, rng)
-    q32 = [x.astype(f32) for x in (qpos, qvel, ctrl, np.zeros((N, cm.nv)))]
-
-    def oracle(dtype):
-        d = PhysState(qpos=q32[0].astype(dtype), qvel=q32[1].astype(dtype), ctrl=q32[2].astype(dtype), qacc_warmstart=np.zeros((N, cm.nv), dtype), time=np.zeros(N, dtype))
-        Physics(cm.t, dtype).forward(d)
-        return d
-
-    ref, ref32 = oracle(f64), oracle(f32)
-    got = _probe(be, h, cm, *q32)
-    be.lib.model_close(h)
-    scale = lambda k: np.abs(ref[k]).max() + 1e-6
-    for k, tol in dict(qM=2e-5, qfrc_bias=2e-4, qfrc_passive=1e-5, qfrc_actuator=1e-5, qacc_smooth=5e-4, cinert=2e-5, cvel=1e-4, xpos=1e-5).items():
-        r = ref[k]
-        assert np.abs(got[k].reshape(r.shape) - r).max() <= tol * scale(k), (seed, k, np.abs(got[k].reshape(r.shape) - r).max() / scale(k))
-    good = (np.abs(ref32.efc_J - ref.efc_J).reshape(N, -1).max(1) <= 2e-4 * scale("efc_J")) & (np.abs(ref32.efc_aref - ref.efc_aref).max(1) <= 5e-4 * scale("efc_aref")) & \
-           ((ref32.efc_D > 0) == (ref.efc_D > 0)).all(1)
-    assert good.sum() >= N // 2, (seed, good)
-    assert ((got["efc_D"].reshape(N, -1) > 0) == (ref.efc_D > 0))[good].all(), seed
+    states = (*random_states(cm, N, np.random.default_rng(seed)), np.zeros((N, cm.nv)))
+    ref, _, good = check_against_oracle(be, cm, states, seed, dict(qM=2e-5, qfrc_bias=2e-4, qfrc_passive=1e-5, qfrc_actuator=1e-5, qacc_smooth=5e-4, cinert=2e-5, cvel=1e-4, xpos=1e-5),
+                                        dict(efc_D=1e-3, efc_aref=1e-3, efc_J=5e-4), min_good=N // 2, strict_cost=None)
     assert (ref.efc_D[good] > 0).sum() > 0, seed  # (some rows are active)
-    for k, tol in dict(efc_D=1e-3, efc_aref=1e-3, efc_J=5e-4).items():
-        r, g = ref[k], got[k].reshape(ref[k].shape)
-        assert np.abs(g[good] - r[good]).max() <= tol * scale(k), (seed, k, np.abs(g[good] - r[good]).max() / scale(k))
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------------
@@ -400,18 +356,16 @@ def _fits(be, cm):
 def test_placements_and_waves_are_bit_equal(be, monkeypatch):
     """The fixture's forward probe and a stretch of env steps: every MPPO_ENV_SPILL placement that fits LDS and one or two waves per workgroup
     (MPPO_ENV_WAVES) give the same bits as the default."""
-    from test_equality import _assert_bit_equal, _probe_and_steps
-
     cm = load_model(HANDS)
     for k in ("MPPO_ENV_SPILL", "MPPO_ENV_WAVES", "MPPO_ENV_GENERIC"):
         monkeypatch.delenv(k, raising=False)
-    _, base = _probe_and_steps(be, cm, N=5, steps=4)
+    _, base = probe_and_steps(be, cm, N=5, steps=4)
     tried = []
     for var, vals in (("MPPO_ENV_SPILL", ("0", "1", "3")), ("MPPO_ENV_WAVES", ("1", "2"))):
         for v in vals:
             monkeypatch.setenv(var, v)
             if _fits(be, cm):
-                _assert_bit_equal(base, _probe_and_steps(be, cm, N=5, steps=4)[1])
+                assert_bit_equal(base, probe_and_steps(be, cm, N=5, steps=4)[1])
                 tried.append(f"{var}={v}")
             monkeypatch.delenv(var)
     assert "MPPO_ENV_SPILL=3" in tried and "MPPO_ENV_WAVES=1" in tried, tried
@@ -422,38 +376,8 @@ def test_kernel_compiled_at_start_up_equals_the_runtime_sized_kernel(tmp_path, m
     """minppo_amd/jit.py compiles the environment kernel for the 77-dof fixture (the dof sets' second word a compile-time constant, eight factor
     rows per lane); its layout holds four environments per wave in 151 KB of LDS, so the library attaches it - and env steps with it equal the
     run-time-sized kernel's bit for bit."""
-    import torch
-
-    from minppo_amd import jit
-    from test_jit import _run
-
-    monkeypatch.setenv(jit.CACHE_ENV, str(tmp_path))
     monkeypatch.delenv("MPPO_ENV_SPILL", raising=False)
-    lib = nat.load()
-    cm = load_model(HANDS)
-    image = jit.compile_kernel(jit.dims_of(cm), 48).read_bytes()
-    blob = np.frombuffer(cm.to_blob(), np.uint8)
-    dblob = torch.from_numpy(blob.copy()).cuda()
-    outs = []
-    for attach in (False, True):
-        monkeypatch.setenv("MPPO_ENV_GENERIC", "1")
-        h = C.c_void_p()
-        lib.model_open(blob.ctypes.data, blob.size, dblob.data_ptr(), C.byref(h))
-        monkeypatch.delenv("MPPO_ENV_GENERIC")
-        if attach:
-            assert jit.attach(lib, h, image, 48)
-            kind = C.c_int32(-1)
-            lib.model_is_specialized(h, C.byref(kind))
-            assert kind.value == 2
-        dims = nat.ModelDims()
-        lib.model_get_dims(h, C.byref(dims))
-        assert dims.lds_bytes <= 160 * 1024
-        outs.append((h, _run(lib, h, dims, 256, 8, torch)))
-    for t, (a, b) in enumerate(zip(outs[0][1], outs[1][1])):
-        for x, y, what in zip(a, b, ("state", "observation", "reward", "done")):
-            assert np.array_equal(x.view(np.uint8), y.view(np.uint8)), f"{what} differs at step {t}"
-    for h, _ in outs:
-        lib.model_close(h)
+    startup_kernel_equals_runtime_sized(load_model(HANDS), tmp_path, monkeypatch, N=256, steps=8)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------------
@@ -462,16 +386,12 @@ def test_kernel_compiled_at_start_up_equals_the_runtime_sized_kernel(tmp_path, m
 
 
 def test_env_steps_follow_the_env_oracle(be):
-    """A few env_steps of the fixture, the kernel re-seeded from the oracle state before each (oracle/env_oracle.py with the equality
-    reference's physics): reward and done flags."""
-    from test_kernels_physics import _pack
-
+    """A few env_steps of the fixture, the kernel re-seeded from the oracle state before each (oracle/env_oracle.py): reward and done flags."""
     cm = load_model(HANDS)
     h, dims, _keep = be.model(cm)
     N, OP, R = 5, dims.obs_pad, dims.rec_dim
     rcfg = RewardCfg(height_min_z=0.8)
     env = EnvOracle(cm.t, rcfg)
-    env.ph = EqualityPhysics(cm.t, f64, 1)
     state, reset_rec, obs = be.zeros((N, R)), be.zeros((R,)), be.zeros((N, OP))
     rew, done = be.zeros((N,)), be.zeros((N,), np.uint8)
     be.lib.env_reset(h, N, be.ptr(state), be.ptr(reset_rec), be.ptr(obs), OP, be.ptr(rew), be.ptr(done), None, be.stream)
@@ -484,7 +404,7 @@ def test_env_steps_follow_the_env_oracle(be):
         a = (0.5 * rng.standard_normal((N, cm.nu))).astype(f32)
         if t == 2:
             es["pipeline_state"]["qvel"][1, 2] = -40.0  # slammed down: ends by height
-        be.put(state, _pack(env, es["pipeline_state"], dims, cm.nv))
+        be.put(state, pack(env, es["pipeline_state"], dims, cm.nv))
         da = be.arr(a)
         be.lib.env_step(h, N, 1, C.byref(rc), be.ptr(state), be.ptr(reset_rec), be.ptr(da), cm.nu, be.ptr(obs), OP, be.ptr(rew), be.ptr(done), None, be.stream)
         es = env.step(es, a.astype(f64))

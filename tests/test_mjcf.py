@@ -541,7 +541,7 @@ def test_explicit_contact_pairs_outside_the_subset_are_loud_errors(contact, msg)
 def test_kernel_follows_the_oracle_on_explicit_pairs(be):
     """The scene of test_explicit_contact_pairs through the environment kernel (emulator / MI355X) against the float64 oracle: two spheres pressed together
     by an explicit pair while every mask is zero, one of them on the ground through its pair with the plane."""
-    from test_kernels_physics import _probe
+    from physics_harness import probe
     from test_model_fuzz import Physics, PhysState, f32, f64
 
     cm = compile_model(mjcf.parse_mjcf(PAIR_XML.format(contact='<pair geom1="ga" geom2="gb" friction="0.8 0.8"/><pair geom1="floor" geom2="gb"/><pair geom1="ga2" geom2="ga"/>')))
@@ -557,7 +557,7 @@ def test_kernel_follows_the_oracle_on_explicit_pairs(be):
     q32 = [x.astype(f32) for x in (qpos, qvel, np.zeros((N, 1)), np.zeros((N, cm.nv)))]
     d = PhysState(qpos=q32[0].astype(f64), qvel=q32[1].astype(f64), ctrl=np.zeros((N, 0)), qacc_warmstart=np.zeros((N, cm.nv)), time=np.zeros(N))
     Physics(cm.t, f64).forward(d)
-    got = _probe(be, h, cm, *q32)
+    got = probe(be, h, cm, *q32)
     act = d.efc_D > 0
     assert act[:, :4].all() and act[:, 4:8].all() and not act[:, 8:12].any()  # ground slot of gb, the ga-gb pair; the capsule stays clear of its parent's sphere
     assert ((got["efc_D"].reshape(N, -1) > 0) == act).all()

@@ -9,7 +9,8 @@ from minppo_amd import _native as nat
 nat.HIP_LIB_PATH = Path(sys.argv[1]).resolve()
 from backends import HipBackend
 from minppo_amd.model import load_model
-from test_kernels_physics import _probe, _walk
+from physics_harness import probe
+from test_kernels_physics import _walk
 be = HipBackend()
 cm = load_model(sys.argv[2])
 N = int(sys.argv[3]) if len(sys.argv) > 3 else 9
@@ -24,7 +25,7 @@ for generic in (False, True):
         if waves: os.environ["MPPO_ENV_WAVES"] = waves
         h, dims, _keep = be.model(cm)
         flag = C.c_int32(-1); be.lib.model_is_specialized(h, C.byref(flag))
-        got = _probe(be, h, cm, *q32)
+        got = probe(be, h, cm, *q32)
         OP, R = dims.obs_pad, dims.rec_dim
         state, reset_rec, obs = be.zeros((N, R)), be.zeros((R,)), be.zeros((N, OP))
         rew, done = be.zeros((N,)), be.zeros((N,), np.uint8)

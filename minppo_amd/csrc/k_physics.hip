@@ -2194,7 +2194,13 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerBlock) env_kernel(ModelView m
       FOR_G(i, nv) { recw[nq + i] = qvel[i]; recw[OP + i] = warm[i]; }
       for (int i = O + g; i < OP; i += kGroupLanes) recw[i] = 0.f;
       for (int i = OP + nv + 2 + g; i < rec_dim; i += kGroupLanes) recw[i] = 0.f;
-      if (g == 0) { recw[OP + nv] = new_comx; recw[OP + nv + 1] = time_in + dt_env; }
+      if (g == 0) {
+        // the time advances frame by frame, one float32 addition each, as the reference's n_frames mjx.step calls advance it: n_frames = k leaves
+        // the record that k calls with n_frames = 1 leave, in this word too (time_in + h * k rounds once and differs in the last bit at large times)
+        float time_out = time_in;
+        for (int f = 0; f < a.n_frames; ++f) time_out += h;
+        recw[OP + nv] = new_comx; recw[OP + nv + 1] = time_out;
+      }
     }
   }
   if (valid && g == 0) {

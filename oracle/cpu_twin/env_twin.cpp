@@ -903,6 +903,11 @@ void* twin_model_open(const void* host_blob, size_t nbytes) {
   m->obs_dim = m->nq + 2 * m->nv + (m->include_c ? 16 * (m->nb - 1) : 0);
   m->obs_pad = (m->obs_dim + 3) & ~3;
   m->rec_dim = m->obs_pad + ((m->nv + 2 + 3) & ~3);
+  // the twin has free, hinge and slide joints only: a ball joint is refused like the sections it does not read (it used to be stepped as a slide)
+  for (int j = 0; j < m->njnt; ++j) {
+    const int jt = m->I(BI_jnt_type)[j];
+    if (jt != JNT_FREE && jt != JNT_HINGE && jt != JNT_SLIDE) { delete m; return nullptr; }
+  }
   return m;
 }
 void twin_model_close(void* h) { delete static_cast<Model*>(h); }
@@ -1023,7 +1028,9 @@ void twin_env_step(const void* h, int32_t N, int32_t n_frames, const RewardCfg* 
         }
         std::copy(w.qact.begin(), w.qact.end(), rec + o);
         std::copy(warm.begin(), warm.end(), rec + OP);
-        rec[OP + nv] = comx; rec[OP + nv + 1] = time_in + dt_env;
+        float time_out = time_in;
+        for (int f = 0; f < n_frames; ++f) time_out += hstep;  // frame by frame, one float32 addition each (the kernel's epilogue; the reference's n_frames mjx.step calls)
+        rec[OP + nv] = comx; rec[OP + nv + 1] = time_out;
       }
       reward[e] = rew; done[e] = dn ? 1 : 0;
       if (met && met->episode_returns) {

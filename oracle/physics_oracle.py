@@ -102,6 +102,26 @@ def quat_integrate(q, w, dt):
     return safe_normalize(qmul(q, dq))
 
 
+def integrate_positions(t, qpos, qvel_new, h, dtype):
+    """The position half of MJX forward.euler in `dtype` arithmetic: qpos advanced by `h` with the NEW velocity (semi-implicit) - hinge and
+    slide joints q + h v, a free joint's position the same, free and ball quaternions by quat_integrate with the joint's angular velocity
+    (in the body's frame).  `t`: the model's tables.  Physics.euler calls this; so do the tests that pin the kernel's integrator."""
+    dtype = np.dtype(dtype)
+    h = dtype.type(h)
+    q0, v = np.asarray(qpos, dtype), np.asarray(qvel_new, dtype)
+    qpos = q0.copy()
+    for j in range(int(t["njnt"])):
+        qa, da = int(t["jnt_qposadr"][j]), int(t["jnt_dofadr"][j])
+        if t["jnt_type"][j] == JNT_FREE:
+            qpos[:, qa:qa + 3] = q0[:, qa:qa + 3] + h * v[:, da:da + 3]
+            qpos[:, qa + 3:qa + 7] = quat_integrate(q0[:, qa + 3:qa + 7], v[:, da + 3:da + 6], h)
+        elif t["jnt_type"][j] == JNT_BALL:  # the free joint's quaternion integration with the joint's three velocities
+            qpos[:, qa:qa + 4] = quat_integrate(q0[:, qa:qa + 4], v[:, da:da + 3], h)
+        else:
+            qpos[:, qa] = q0[:, qa] + h * v[:, da]
+    return qpos.astype(dtype)
+
+
 def quat_rotvec(q):
     """Rotation vector of (unit) quaternions [..., 4]: axis x angle with the angle wrapped into (-pi, pi] (mju_quat2Vel, dt = 1)."""
     v = q[..., 1:]
@@ -1114,17 +1134,7 @@ class Physics:
         dh = d.qM + h * np.eye(self.nv, dtype=self.dtype)[None] * t["dof_damping"][None, :, None]
         qacc = np.linalg.solve(dh, (d.qfrc_smooth + d.qfrc_constraint)[..., None])[..., 0]
         qvel = d.qvel + qacc * h
-        qpos = d.qpos.copy()
-        for j in range(self.njnt):
-            qa, da = t["jnt_qposadr"][j], t["jnt_dofadr"][j]
-            if t["jnt_type"][j] == JNT_FREE:
-                qpos[:, qa:qa + 3] = d.qpos[:, qa:qa + 3] + h * qvel[:, da:da + 3]
-                qpos[:, qa + 3:qa + 7] = quat_integrate(d.qpos[:, qa + 3:qa + 7], qvel[:, da + 3:da + 6], h)
-            elif t["jnt_type"][j] == JNT_BALL:  # the free joint's quaternion integration with the joint's three velocities (as stored: in working precision)
-                qpos[:, qa:qa + 4] = quat_integrate(d.qpos[:, qa:qa + 4], qvel[:, da:da + 3].astype(self.dtype), h)
-            else:
-                qpos[:, qa] = d.qpos[:, qa] + h * qvel[:, da]
-        d["qpos"], d["qvel"] = qpos.astype(self.dtype), qvel.astype(self.dtype)
+        d["qpos"], d["qvel"] = integrate_positions(t, d.qpos, qvel, h, self.dtype), qvel.astype(self.dtype)
         d["time"] = d.time + h
 
     # -- public: mjx.forward / mjx.step / brax pipeline_init / pipeline_step ---------

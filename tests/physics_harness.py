@@ -12,6 +12,7 @@ from minppo_amd import _native as nat
 from minppo_amd import mjcf
 from minppo_amd.model import BUILTIN_MODELS, JNT_BALL, JNT_FREE, compile_model, load_model
 from oracle.physics_oracle import Physics, PhysState, qmul
+from oracle.physics_oracle import integrate_positions as _integrate_positions
 
 f32, f64 = np.float32, np.float64
 GOLDEN = Path(__file__).parent / "golden"
@@ -81,8 +82,9 @@ def step_once(be, h, N=4):
     be.lib.env_step(h, N, 1, C.byref(rc), be.ptr(state), be.ptr(reset_rec), be.ptr(a), max(dims.nu, 1), be.ptr(obs), OP, be.ptr(rew), be.ptr(done), None, be.stream)
 
 
-def run_steps(lib, h, dims, N, steps, torch, seed=0):
-    """`steps` env steps of the HIP library on cuda tensors under random actions -> [(state, observation, reward, done)] per step."""
+def run_steps(lib, h, dims, N, steps, torch, seed=0, start=None, actions=None):
+    """`steps` env steps of the HIP library on cuda tensors under random actions -> [(state, observation, reward, done)] per step.
+    `start`, `actions`: lists that receive the records after the reset and every step's actions (host arrays)."""
     state = torch.zeros(N, dims.rec_dim, device="cuda")
     reset = torch.zeros(dims.rec_dim, device="cuda")
     obs = torch.zeros(N, dims.obs_pad, device="cuda")
@@ -90,6 +92,9 @@ def run_steps(lib, h, dims, N, steps, torch, seed=0):
     done = torch.zeros(N, dtype=torch.uint8, device="cuda")
     s = torch.cuda.current_stream().cuda_stream
     lib.env_reset(h, N, state.data_ptr(), reset.data_ptr(), obs.data_ptr(), dims.obs_pad, 0, 0, None, s)
+    if start is not None:
+        torch.cuda.synchronize()
+        start.append(state.cpu().numpy().copy())
     g = torch.Generator(device="cuda")
     g.manual_seed(seed)
     rc = nat.RewardCfg(-0.2, 2.0, 2.0, 0.2, 0.5, 0.1, 4.0, 1.0, 1.25)
@@ -99,6 +104,8 @@ def run_steps(lib, h, dims, N, steps, torch, seed=0):
         act = torch.randn(N, nu, device="cuda", generator=g)
         lib.env_step(h, N, 1, C.byref(rc), state.data_ptr(), reset.data_ptr(), act.data_ptr(), nu, obs.data_ptr(), dims.obs_pad, rew.data_ptr(), done.data_ptr(), None, s)
         torch.cuda.synchronize()
+        if actions is not None:
+            actions.append(act.cpu().numpy().copy())
         out.append((state.cpu().numpy().copy(), obs.cpu().numpy().copy(), rew.cpu().numpy().copy(), done.cpu().numpy().copy()))
     return out
 
@@ -286,6 +293,193 @@ def check_against_oracle(be, cm, states, what, tol_smooth, tol_rows, min_good, s
     assert np.all(c_got <= c_smooth * (1 + 1e-5) + 1e-6), (what, (c_got / c_smooth).max())
     assert np.all(got["niter"] <= 6), (what, got["niter"].max())
     return ref, got, good
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# after the solver: the integrator, the frames loop and the epilogue from the record's own values (tests/test_step_exact.py)
+# ---------------------------------------------------------------------------------------------------------------------------------------
+
+ULP32 = 2.0 ** -24  # one float32 rounding of a unit-scale value
+METRIC_TYPES = dict(episode_returns=f32, episode_lengths=np.int32, returned_episode_returns=f32, returned_episode_lengths=np.int32, timestep=np.int32,
+                    returned_episode=np.uint8)
+
+
+def integrate_positions(cm, qpos, qvel_new, h, dtype):
+    """The position half of Physics.euler (which calls the same function) on given arrays, in `dtype` arithmetic."""
+    return _integrate_positions(cm.t, qpos, qvel_new, h, dtype)
+
+
+def record_of(dims, cm, qpos, qvel, warm, com_x, time):
+    """The kernel's state record from given values (the inverse of `pack`, without an EnvOracle): [qpos, qvel, c-vals and qfrc_actuator zero
+    (a step reads them only to copy them out as the observation) | padding | warm start, com_x, time | padding]."""
+    N = qpos.shape[0]
+    OP, nq, nv = dims.obs_pad, cm.nq, cm.nv
+    rec = np.zeros((N, dims.rec_dim), f32)
+    rec[:, :nq] = qpos
+    rec[:, nq:nq + nv] = qvel
+    rec[:, OP:OP + nv] = warm
+    rec[:, OP + nv] = com_x
+    rec[:, OP + nv + 1] = time
+    return rec
+
+
+class KernelStepper:
+    """mppo_env_step of a backend (emulator or HIP library) on host state records."""
+
+    def __init__(self, be, cm):
+        self.be, self.cm, self.name = be, cm, be.name
+        self.h, self.dims, self._keep = be.model(cm)
+        self.reset_rec = self._reset(1)[1]
+
+    def _reset(self, N):
+        be, d = self.be, self.dims
+        state, reset_rec, obs = be.zeros((N, d.rec_dim)), be.zeros((d.rec_dim,)), be.zeros((N, d.obs_pad))
+        be.lib.env_reset(self.h, N, be.ptr(state), be.ptr(reset_rec), be.ptr(obs), d.obs_pad, 0, 0, None, be.stream)
+        return be.host(state).copy(), be.host(reset_rec).copy()
+
+    def step(self, rec, action, n_frames, rc, metrics=None):
+        """-> record', observation, reward, done (host arrays; `metrics`, a dict of host arrays, is advanced in place)"""
+        be, d, N = self.be, self.dims, rec.shape[0]
+        nu = max(d.nu, 1)
+        state, reset_rec, obs = be.arr(rec.astype(f32)), be.arr(self.reset_rec), be.full((N, d.obs_pad), np.nan)
+        rew, done = be.zeros((N,)), be.zeros((N,), np.uint8)
+        act = be.arr(np.zeros((N, nu), f32) if d.nu == 0 else action.astype(f32))
+        met = {k: be.arr(np.asarray(metrics[k], METRIC_TYPES[k])) for k in METRIC_TYPES} if metrics is not None else None
+        M = nat.EnvMetrics(**{k: be.ptr(v) for k, v in met.items()}) if met else None
+        be.lib.env_step(self.h, N, n_frames, C.byref(nat.RewardCfg(*rc)), be.ptr(state), be.ptr(reset_rec), be.ptr(act), nu, be.ptr(obs), d.obs_pad, be.ptr(rew),
+                        be.ptr(done), C.byref(M) if met else None, be.stream)
+        be.sync()
+        if met:
+            for k in met:
+                metrics[k] = be.host(met[k]).copy()
+        return be.host(state).copy(), be.host(obs).copy(), be.host(rew).copy(), be.host(done).copy()
+
+    def close(self):
+        self.be.lib.model_close(self.h)
+
+
+class TwinStepper:
+    """oracle.cpu_twin.Twin.step on the same records."""
+
+    name = "twin"
+
+    def __init__(self, cm):
+        from oracle.cpu_twin import Twin
+
+        self.cm, self.tw = cm, Twin(cm)
+        tw = self.tw
+        self.dims = nat.ModelDims(nq=tw.nq, nv=tw.nv, nu=tw.nu, nbody=tw.nbody, nefc=tw.nefc, obs_dim=tw.obs_dim, obs_pad=tw.obs_pad, rec_dim=tw.rec_dim,
+                                  timestep=float(cm.t["timestep"]))
+        tw.reset(1)
+        self.reset_rec = tw.reset_rec.copy()
+
+    def step(self, rec, action, n_frames, rc, metrics=None):
+        from oracle.cpu_twin import Metrics, RewardCfg as TwinReward
+
+        tw, N = self.tw, rec.shape[0]
+        if tw.N != N:
+            tw.reset(N)
+        tw.state[...] = rec
+        tw.obs[...] = np.nan
+        tw.rc = TwinReward(*rc)
+        a = np.ascontiguousarray(np.zeros((N, 1), f32) if tw.nu == 0 else action, f32)
+        met = {k: np.ascontiguousarray(metrics[k], METRIC_TYPES[k]) for k in METRIC_TYPES} if metrics is not None else None
+        M = Metrics(**{k: v.ctypes.data for k, v in met.items()}) if met else None
+        tw.dll.twin_env_step(tw.h, N, n_frames, C.byref(tw.rc), tw.state.ctypes.data, tw.reset_rec.ctypes.data, a.ctypes.data, a.shape[1], tw.obs.ctypes.data, tw.obs_pad,
+                             tw.reward.ctypes.data, tw.done.ctypes.data, C.byref(M) if met else None)
+        if met:
+            metrics.update(met)
+        return tw.state.copy(), tw.obs.copy(), tw.reward.copy(), tw.done.copy()
+
+    def close(self):
+        self.tw.close()
+
+
+def quaternion_joints(cm):
+    """[(qpos address of the quaternion, dof address of its angular velocity)] of every free and ball joint."""
+    out = []
+    for j in range(cm.njnt):
+        jt, qa, da = int(cm.t["jnt_type"][j]), int(cm.t["jnt_qposadr"][j]), int(cm.t["jnt_dofadr"][j])
+        if jt == JNT_FREE:
+            out.append((qa + 3, da + 3))
+        elif jt == JNT_BALL:
+            out.append((qa, da))
+    return out
+
+
+def fast_states(cm, N, seed):
+    """States on which a subtly wrong integrator shows: walking_states with velocities put on top - every free and ball joint turning with
+    |w| h in [0.1, 0.5], every other dof (a free joint's translation included) with |v| h in [0.01, 0.1], either sign.  Environment 0
+    has w = 0 exactly on every quaternion joint (the integrator's `n > 0` branch); environment 1 stores its quaternions with norm
+    1 +- 1e-3 (kinematics normalises on read, the integrator normalises what it writes) -> float32 qpos, qvel, ctrl, warm start."""
+    assert N >= 3
+    qpos, qvel, ctrl, warm = walking_states(cm, N, seed)
+    rng = np.random.default_rng(1000 + seed)
+    h = float(cm.t["timestep"])
+    qvel = rng.uniform(0.01, 0.1, (N, cm.nv)) / h * rng.choice([-1.0, 1.0], (N, cm.nv))
+    qpos = qpos.copy()
+    for k, (qa, da) in enumerate(quaternion_joints(cm)):
+        u = rng.standard_normal((N, 3))
+        qvel[:, da:da + 3] = u / np.linalg.norm(u, axis=1, keepdims=True) * rng.uniform(0.1, 0.5, (N, 1)) / h
+        qvel[0, da:da + 3] = 0.0
+        qpos[1, qa:qa + 4] *= 1.0 + (1e-3 if k % 2 == 0 else -1e-3)
+    return qpos.astype(f32), qvel.astype(f32), ctrl.astype(f32), warm.astype(f32)
+
+
+def position_bound(cm, qpos, qvel_new):
+    """The float64 integration of float32 `qpos` with the float32 `qvel_new` and, per entry, how far a float32 kernel may be from it:
+    max(4 x |float32 reference - float64 reference| on the same inputs, 2^-22 max(1, |q|)) - 4 x for a device's sinf / cosf / sqrtf of
+    1 - 2 ulp where NumPy's are correctly rounded, the floor four float32 roundings of a unit-scale value.  Both from the reference.
+    -> ref64, bound"""
+    h = f32(cm.t["timestep"])
+    r64 = integrate_positions(cm, qpos.astype(f64), qvel_new.astype(f64), float(h), f64)
+    r32 = integrate_positions(cm, qpos.astype(f32), qvel_new.astype(f32), h, f32)
+    return r64, np.maximum(4.0 * np.abs(r32.astype(f64) - r64), 2.0 ** -22 * np.maximum(1.0, np.abs(r64)))
+
+
+def wrong_integrators(cm, qpos, qvel_old, qvel_new):
+    """Three subtly wrong position updates in float64: the quaternion multiplied on the wrong side (w read in the world frame), a first-order
+    quaternion update q + h/2 q (0, w) instead of the axis-angle one, positions advanced with the OLD velocity.  The first two are None for
+    a robot without a quaternion joint."""
+    h = float(f32(cm.t["timestep"]))
+    q, v = qpos.astype(f64), qvel_new.astype(f64)
+    good = integrate_positions(cm, q, v, h, f64)
+    out = dict(world_frame=None, first_order=None, old_velocity=integrate_positions(cm, q, qvel_old.astype(f64), h, f64))
+    qj = quaternion_joints(cm)
+    if qj:
+        wf, fo = good.copy(), good.copy()
+        for qa, da in qj:
+            w = v[:, da:da + 3]
+            n = np.linalg.norm(w, axis=-1, keepdims=True)
+            ax = w / np.where(n > 0, n, 1.0)
+            dq = np.concatenate([np.cos(0.5 * n * h), ax * np.sin(0.5 * n * h)], -1)
+            x = qmul(dq, q[:, qa:qa + 4])
+            wf[:, qa:qa + 4] = x / np.linalg.norm(x, axis=-1, keepdims=True)
+            x = q[:, qa:qa + 4] + 0.5 * h * qmul(q[:, qa:qa + 4], np.concatenate([np.zeros_like(n), w], -1))
+            fo[:, qa:qa + 4] = x / np.linalg.norm(x, axis=-1, keepdims=True)
+        out.update(world_frame=wf, first_order=fo)
+    return out
+
+
+def reward_from_records(cm, rec0, rec1, action, rc, n_frames, dims):
+    """The reward of env.py:199-235 in float64 from the records themselves - |qpos0 - qpos| over all of qpos, z and com_x of the pre-step
+    record, the action, com_x of the post-step record - and the budget of float32 roundings a kernel may be away from it:
+    64 x 2^-24 x the sum of the weighted terms' magnitudes.  `rc`: the nine values of RewardCfg as float32 holds them.  -> reward, bound, clipped"""
+    rc = [float(f32(x)) for x in rc]
+    hmin, hmax, ec, sf, mdn, w_ctrl, w_pos, w_healthy, w_vel = rc
+    nq, nv, OP = cm.nq, cm.nv, dims.obs_pad
+    q = rec0[:, :nq].astype(f64)
+    p0 = np.linalg.norm(np.asarray(cm.t["qpos0"], f32).astype(f64)[None] - q, axis=-1)
+    e, cl = np.exp(-ec * p0), np.clip(p0, 0.0, mdn)
+    z = q[:, 2]
+    healthy = np.where((z < hmin) | (z > hmax), 0.0, 1.0)
+    a = np.zeros((q.shape[0], 0)) if cm.nu == 0 else action.astype(f32).astype(f64)
+    asq = np.sum(a * a, -1)
+    dt_env = float(f32(f32(cm.t["timestep"]) * f32(n_frames)))
+    vel = (rec1[:, OP + nv].astype(f64) - rec0[:, OP + nv].astype(f64)) / dt_env
+    reward = -w_ctrl * asq + w_pos * (e - sf * cl) + w_vel * vel + w_healthy * healthy
+    size = np.abs(w_ctrl) * asq + np.abs(w_pos) * (e + np.abs(sf) * cl) + np.abs(w_vel * vel) + np.abs(w_healthy) * healthy
+    return reward, 64.0 * ULP32 * size, p0 > mdn
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------------

@@ -129,6 +129,25 @@ int32_t mppo_env_reset(const mppo_model_t* m, int32_t N, float* state, float* re
 int32_t mppo_env_step(const mppo_model_t* m, int32_t N, int32_t n_frames, const mppo_reward_cfg_t* rc, float* state,
                       const float* reset_rec, const float* action, int32_t act_ld, float* obs, int32_t obs_ld,
                       float* reward, uint8_t* done, const mppo_env_metrics_t* metrics, void* stream);
+/* mppo_env_reinit : `_get_reset_state` with reset_noise_scale = `scale` > 0 (env.py:115-121) for the environments `mask` names ([N] bytes in
+ *                   device memory, non-zero: reset; NULL: every environment): qpos = qpos0 + U(-scale, scale) on all nq words (quaternion words
+ *                   too, left unnormalised as MJX leaves them), qvel = U(-scale, scale), ctrl = 0, warm start 0, then pipeline_init's one forward
+ *                   pass.  Writes the state rows and (obs may be NULL) the observation rows of those environments and nothing else: after a
+ *                   mppo_env_step with mask = its `done` it turns the step's constant-record restarts into the reference's randomised ones.  A
+ *                   workgroup without a masked-in environment leaves before it loads the model.  scale = 0: the plain reset's rows.
+ *                   The noise is drawn inside the kernel, per environment and element, from one of two streams:
+ *   rng_impl 1      the reference's threefry tree: key_n = split(K, N)[n]; r1, r2 = split(key_n); uniform(r1, (nq,)), uniform(r2, (nv,))
+ *                   (train.py:135,164; env.py:116-119; conventions of minppo_amd/jaxrng.py), K = key2[0..1] in DEVICE memory: the reset key
+ *                   (train.py:142) or a step key (train.py:163).  seed / rank / counter are not read.
+ *   rng_impl 2      the same with the environments' keys given: key2 = [N][2] words, key_n = key2[n] (the `step_rngs` of train.py:164)
+ *   rng_impl 0      the engine's Philox4x32-10: element i (0 .. nq - 1: qpos, then qvel) of environment n at event c is word i & 3 of
+ *                   philox(counter = {n, c, lo(S + (i >> 2)), hi(S)}, key = seed) with S = ("RESET" << 24) + (rank << 16) and the event
+ *                   c = (counter ? *counter : 0) + counter_offset, `counter` a word in DEVICE memory that the caller advances there (so that a
+ *                   replayed hipGraph draws fresh values).  key2 is not read.
+ *                   Bits become a float as jax.random.uniform makes one: (bits >> 9 | 0x3f800000) - 1, times 2 scale, minus scale, clamped below. */
+int32_t mppo_env_reinit(const mppo_model_t* m, int32_t N, float* state, float* obs, int32_t obs_ld, const uint8_t* mask, float scale,
+                        int32_t rng_impl, uint64_t seed, int32_t rank, const uint32_t* key2, const int32_t* counter, int32_t counter_offset,
+                        void* stream);
 /* Debug / parity probe: one mjx.forward on caller-given (qpos,qvel,ctrl,qacc_warmstart) [N,*]
  * with every intermediate the parity tests compare exported.  Any output pointer may be NULL.
  * M [N,nv,nv]; efc_* [N,nefc]; J [N,nefc,nv]; cinert [N,nbody,10]; cvel [N,nbody,6]. */
@@ -294,6 +313,9 @@ int32_t mppo_permutation(uint64_t seed, uint64_t stream_id, int32_t B, int32_t* 
 int32_t mppo_threefry_normal(const uint32_t* key2, size_t n, float* out, void* stream);
 int32_t mppo_threefry_bits(const uint32_t* key2, size_t n, uint32_t* out, void* stream);
 int32_t mppo_threefry_update_keys(uint32_t* rng2, int32_t T, int32_t E, int32_t rounds, uint32_t* act_keys, uint32_t* sort_keys, void* stream);
+/* mppo_threefry_update_keys that also writes the T step keys (`rng, step_rng = split(rng)`, train.py:163), step_keys [T][2] */
+int32_t mppo_threefry_update_keys_step(uint32_t* rng2, int32_t T, int32_t E, int32_t rounds, uint32_t* act_keys, uint32_t* sort_keys,
+                                       uint32_t* step_keys, void* stream);
 int32_t mppo_threefry_permutation(const uint32_t* sort_keys, int32_t rounds, int32_t B, int32_t* idx, void* ws, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
@@ -327,7 +349,7 @@ typedef struct mppo_engine_cfg {
  * every buffer out inside it.  mppo_engine_arena_bytes gives the size; named regions can be
  * located with mppo_engine_region (offset in bytes, size in bytes) to view them as tensors:
  * "params" "adam_m" "adam_v" "grad" "count" "state" "reset_rec" "obs" "action" "value" "reward"
- * "log_prob" "done" "last_val" "adv" "target" "noise" "perm" "adv_stats" "losses" "rollout_stats"
+ * "log_prob" "done" "last_val" "adv" "target" "noise" "perm" "adv_stats" "losses" "rollout_stats" "jax_rng" "reset_rng"
  * (8 floats: sum reward, episodes ended, sum of their returns, sum of their lengths, the two means, 0, 0) ... */
 int32_t mppo_engine_arena_bytes(const mppo_model_t* m, const mppo_engine_cfg_t* cfg, size_t* out);
 int32_t mppo_engine_create(const mppo_model_t* m, const mppo_engine_cfg_t* cfg, void* arena, size_t arena_bytes,
@@ -375,6 +397,15 @@ int32_t mppo_engine_peer_latency(mppo_engine_t* e, int32_t other_rank, int32_t i
 int32_t mppo_engine_peer_disable(mppo_engine_t* e);
 /* env reset (train.py:142-144) */
 int32_t mppo_engine_reset(mppo_engine_t* e, void* stream);
+/* Reset noise (`HumanoidEnv.reset_noise_scale`, env.py:87,115-121; 0, the default: every environment restarts from the constant reset record
+ * and nothing changes).  scale > 0: mppo_engine_reset follows its plain reset - which still makes the noise-free "reset_rec" - with
+ * mppo_env_reinit over all environments, and every rollout step is followed by one masked mppo_env_reinit over that step's done[t] (state rows and
+ * the rows of observation slot t + 1), inside the captured graph too.  Streams per cfg.rng_impl: threefry keys live in arena region "reset_rng"
+ * ([T][2] step keys of the current update, written by the update's key kernel - with external_random = 1 by the caller - then [2] the reset
+ * key, written by the caller before mppo_engine_reset); the Philox events are 0 for the reset and u * T + 1 + t for step t of update u, u the
+ * device's update index "count"[1].  Call before mppo_engine_reset: after it (with another scale than the one the reset ran with: the environments hold that
+ * scale's initial states), after mppo_engine_prepare or after the first mppo_engine_update it returns MPPO_ESTATE. */
+int32_t mppo_engine_set_reset_noise(mppo_engine_t* e, float scale);
 /* one full update: T rollout steps, bootstrap value, GAE, E epochs x M minibatches */
 int32_t mppo_engine_update(mppo_engine_t* e, void* stream);
 /* what mppo_engine_update does before it enqueues anything: the one-time capture of the update into a hipGraph (no device work).

@@ -98,6 +98,7 @@ SIGNATURES = {
     "mppo_env_reset": (c_i32, [c_vp, c_i32, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, P(EnvMetrics), c_vp]),
     "mppo_env_step": (c_i32, [c_vp, c_i32, c_i32, P(RewardCfg), c_vp, c_vp, c_vp, c_i32, c_vp, c_i32, c_vp, c_vp,
                               P(EnvMetrics), c_vp]),
+    "mppo_env_reinit": (c_i32, [c_vp, c_i32, c_vp, c_vp, c_i32, c_vp, c_f, c_i32, c_u64, c_i32, c_vp, c_vp, c_i32, c_vp]),
     "mppo_physics_forward": (c_i32, [c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, P(ForwardProbe), c_vp]),
     "mppo_param_count": (c_sz, [P(Net)]),
     "mppo_policy_ws_bytes": (c_sz, [P(Net), c_i32]),
@@ -127,6 +128,7 @@ SIGNATURES = {
     "mppo_threefry_normal": (c_i32, [c_vp, c_sz, c_vp, c_vp]),
     "mppo_threefry_bits": (c_i32, [c_vp, c_sz, c_vp, c_vp]),
     "mppo_threefry_update_keys": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
+    "mppo_threefry_update_keys_step": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
     "mppo_threefry_permutation": (c_i32, [c_vp, c_i32, c_i32, c_vp, c_vp, c_sz, c_vp]),
     "mppo_engine_arena_bytes": (c_i32, [c_vp, P(EngineCfg), P(c_sz)]),
     "mppo_engine_create": (c_i32, [c_vp, P(EngineCfg), c_vp, c_sz, P(c_vp)]),
@@ -142,6 +144,7 @@ SIGNATURES = {
     "mppo_engine_peer_latency": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_vp, P(C.c_double)]),
     "mppo_engine_peer_disable": (c_i32, [c_vp]),
     "mppo_engine_reset": (c_i32, [c_vp, c_vp]),
+    "mppo_engine_set_reset_noise": (c_i32, [c_vp, c_f]),
     "mppo_engine_update": (c_i32, [c_vp, c_vp]),
     "mppo_engine_prepare": (c_i32, [c_vp, c_vp]),
     "mppo_engine_graph_active": (c_i32, [c_vp, P(c_i32)]),

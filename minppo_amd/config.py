@@ -58,6 +58,11 @@ class EnvironmentConfig:
     # cached) - the counterpart of the reference's jax.jit of its step function (env.py:123,147; train.py:306).  Bit-identical results (checked on the device
     # before use), 1.2x - 1.6x faster than the run-time-sized kernel; no effect for the robots the library was built for.
     jit_kernel: bool = field(default=False)
+    # Extension: `HumanoidEnv.reset_noise_scale` (env.py:87, a class attribute the reference ships at 0) as a config key.  Above 0 every environment
+    # starts, and restarts after `done`, from qpos0 + U(-s, s) / qvel = U(-s, s) (env.py:115-121; 1e-2 is customary for Brax humanoids), drawn inside
+    # the environment kernel from the stream `training.rng_impl` names (threefry: the reference's own keys, train.py:135,142,163-165).  0: every
+    # environment restarts from the one constant state, as before.  Negative: ValueError.
+    reset_noise_scale: float = field(default=0.0)
 
 
 @dataclass
@@ -249,6 +254,8 @@ def make_config(yaml_dict: dict | None = None, overrides: Sequence[str] = ()) ->
         _merge_into(cfg, yaml_dict)
     if overrides:
         _merge_into(cfg, _dotlist_to_dict(overrides))
+    if not cfg.environment.reset_noise_scale >= 0.0:
+        raise ValueError(f"environment.reset_noise_scale = {cfg.environment.reset_noise_scale!r}: the half-width of the reset noise cannot be negative")
     return cfg
 
 

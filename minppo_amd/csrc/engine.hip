@@ -33,6 +33,8 @@ int32_t env_step_ws(const mppo_model_t* m, int32_t N, int32_t n_frames, const mp
                     int32_t act_ld, float* obs, int32_t obs_ld, float* reward, uint8_t* done, const mppo_env_metrics_t* metrics, float* ws, size_t ws_bytes, hipStream_t stream);
 int32_t env_reset_ws(const mppo_model_t* m, int32_t N, float* state, float* reset_rec, float* obs, int32_t obs_ld, const mppo_env_metrics_t* metrics, float* ws, size_t ws_bytes,
                      hipStream_t stream);
+int32_t env_reinit_ws(const mppo_model_t* m, int32_t N, float* state, float* obs, int32_t obs_ld, const uint8_t* mask, float scale, int32_t rng_impl, uint64_t seed,
+                      int32_t rank, const uint32_t* key2, const int32_t* counter, int32_t counter_mul, int32_t counter_add, float* ws, size_t ws_bytes, hipStream_t stream);
 
 // end of an update: the Adam step index and the update index move on; `zero` (optional): words another kernel of the update wants back
 // at zero before its next use (the bucket counters of the two-launch permutation, k_perm.hip).  The LAST of those words is that form's
@@ -132,6 +134,10 @@ struct mppo_engine {
   mppo::GraphExec* graph;
   bool graph_failed, was_reset, graph_agreed;
   float* flag_ws;        // one float of the arena: the ranks' agreement on the graph capture (RCCL path)
+  // reset noise (mppo_engine_set_reset_noise; 0: every environment restarts from the one constant reset record, nothing below is used)
+  float reset_noise;
+  unsigned* reset_rng;   // [T][2] this update's step keys (train.py:163) | [2] the reset key (train.py:142): the threefry stream's keys (rng_impl = 1)
+  bool prepared;         // an update has been prepared (captured or not): the launch sequence is fixed
 };
 
 namespace mppo {
@@ -191,6 +197,8 @@ static size_t layout(mppo_engine* e, bool assign) {
   // a large robot's mass matrices and contact Jacobians, one record per environment (k_physics.hip; nothing for the robots whose working set fits LDS)
   e->env_ws_bytes = model_scratch_bytes(e->model, (int)N);
   e->env_ws = e->env_ws_bytes ? (float*)take("env_scratch", e->env_ws_bytes) : nullptr;
+  // the keys of the reset noise's threefry stream: behind everything else, so that every other region is where it was ("jax_rng" keeps its size and meaning)
+  e->reset_rng = (unsigned*)take("reset_rng", (2 * T + 2) * 4);
   return align_up(off, 256);
 }
 
@@ -227,6 +235,10 @@ static void fill_dims(mppo_engine* e) {
 
 constexpr unsigned long long kStreamNoise = 0x4E4F495345ull << 24;  // "NOISE"
 constexpr unsigned long long kStreamPerm = 0x5045524Dull << 24;     // "PERM"
+// ("RESET" << 24, kStreamReset: the reset noise's stream, drawn inside the environment kernel - k_physics.hip)
+
+// The reset noise's event counter (Philox stream): event 0 is mppo_engine_reset, step t of update u is event u * T + 1 + t, with u read on the device from
+// count[1] - the update index that advance_counters_kernel moves on at the end of every update, so a replayed graph draws fresh values at every step.
 
 
 static bool shadow_enabled() {  // MPPO_NO_SHADOW=1: A/B switch for measurements
@@ -249,7 +261,7 @@ static int32_t do_rollout(mppo_engine* e, hipStream_t s) {
     if (c.rng_impl == 1) {
       // the reference's key plumbing (train.py:158,163,252): this update's action keys and sort keys from the carried key,
       // then one jax.random.normal(action_rng, (N, A)) per env step (what `pi.sample(seed=action_rng)` draws)
-      MPPO_TRY(threefry_chain(e->jax_rng, e->T, e->E, e->jax_rounds, e->jax_rng + 2, e->jax_rng + 2 + 2 * e->T, s));
+      MPPO_TRY(threefry_chain(e->jax_rng, e->T, e->E, e->jax_rounds, e->jax_rng + 2, e->jax_rng + 2 + 2 * e->T, e->reset_noise > 0.f ? e->reset_rng : nullptr, s));
       for (int t = 0; t < e->T; ++t) MPPO_TRY(threefry_normal(e->jax_rng + 2 + 2 * t, N * A, e->noise + (size_t)t * N * A, s));
     } else {
       MPPO_TRY(normal_fill_ctr(c.seed, kStreamNoise + ((unsigned long long)c.rank << 16), e->count + 1, (size_t)e->T * N * A, e->noise, s));
@@ -272,6 +284,11 @@ static int32_t do_rollout(mppo_engine* e, hipStream_t s) {
                             defer_critic ? nullptr : e->value + (size_t)t * N, nullptr, s));                          // train.py:157-160
     MPPO_TRY(env_step_ws(e->model, e->N, c.n_frames, &c.reward, e->state, e->reset_rec, e->action + t * N * A, e->A, e->obs + (size_t)(t + 1) * N * OP,
                          e->OP, e->reward + t * N, e->done + t * N, &e->met, e->env_ws, e->env_ws_bytes, static_cast<hipStream_t>(s)));                                  // :165
+    // reset noise: the environments whose episode ended at this step restart from a randomised state instead of the constant record the step kernel
+    // gave them (env.py:166,179-180) - one masked launch of the reset kernel over done[t]; a workgroup without an ended episode leaves at once
+    if (e->reset_noise > 0.f)
+      MPPO_TRY(env_reinit_ws(e->model, e->N, e->state, e->obs + (size_t)(t + 1) * N * OP, e->OP, e->done + t * N, e->reset_noise, c.rng_impl, c.seed, c.rank,
+                             e->reset_rng + 2 * t, e->count + 1, e->T, 1 + t, e->env_ws, e->env_ws_bytes, s));
   }
   if (defer_critic)  // value[t] of all T steps and the bootstrap value in ONE critic launch over the [T + 1][N] observation rows (nothing before GAE reads them)
     MPPO_TRY(policy_forward(c.net, e->params, (e->T + 1) * e->N, e->obs, e->OP, fb, nullptr, nullptr, nullptr, e->value, nullptr, s));
@@ -397,6 +414,7 @@ extern "C" int32_t mppo_engine_create(const mppo_model_t* m, const mppo_engine_c
   const size_t need = layout(e, true);
   if (arena_bytes < need) { delete e; return fail(MPPO_ENOMEM, "mppo_engine_create: arena %zu < %zu bytes", arena_bytes, need); }
   e->comm = nullptr; e->peer = nullptr; e->graph = nullptr; e->graph_failed = false; e->was_reset = false; e->graph_agreed = false;
+  e->reset_noise = 0.f; e->prepared = false;
   *out = e;
   return MPPO_OK;
 }
@@ -445,7 +463,25 @@ extern "C" int32_t mppo_engine_reset(mppo_engine_t* e, void* stream) {
   MPPO_CHECK_HIP(hipMemsetAsync(e->obs, 0, (size_t)(e->T + 1) * e->N * e->OP * 4, s));
   MPPO_TRY(permutation_batch_prepare(e->B, e->E, e->perm_ws, e->perm_ws_bytes, s));
   MPPO_TRY(env_reset_ws(e->model, e->N, e->state, e->reset_rec, e->obs, e->OP, &e->met, e->env_ws, e->env_ws_bytes, static_cast<hipStream_t>(s)));  // train.py:142-144
+  // reset noise: the plain reset above made the noise-free reset record and the zeroed metrics; every environment then starts from a state of its own
+  // (event 0 of the Philox stream; the reset key behind the step keys of region "reset_rng" for threefry: the caller writes it before this call)
+  if (e->reset_noise > 0.f)
+    MPPO_TRY(env_reinit_ws(e->model, e->N, e->state, e->obs, e->OP, nullptr, e->reset_noise, e->cfg.rng_impl, e->cfg.seed, e->cfg.rank, e->reset_rng + 2 * e->T, nullptr, 0, 0,
+                           e->env_ws, e->env_ws_bytes, s));
   e->was_reset = true;
+  return MPPO_OK;
+}
+
+extern "C" int32_t mppo_engine_set_reset_noise(mppo_engine_t* e, float scale) {
+  MPPO_REQUIRE(e, "mppo_engine_set_reset_noise: null engine");
+  MPPO_REQUIRE(scale >= 0.f, "mppo_engine_set_reset_noise: scale %g is negative (or not a number)", (double)scale);
+  if (e->graph || e->prepared)
+    return fail(MPPO_ESTATE, "mppo_engine_set_reset_noise: the update has been prepared already (its launch sequence is fixed, a captured graph holds it): "
+                             "set the scale before mppo_engine_prepare and the first mppo_engine_update");
+  if (e->was_reset && scale != e->reset_noise)
+    return fail(MPPO_ESTATE, "mppo_engine_set_reset_noise: mppo_engine_reset has run already (the environments hold the initial states of scale %g): set the scale before it",
+                (double)e->reset_noise);
+  e->reset_noise = scale;
   return MPPO_OK;
 }
 
@@ -491,6 +527,7 @@ static int32_t agree_on_graph(mppo_engine_t* e, hipStream_t s) {
 }
 
 static int32_t prepare_update(mppo_engine_t* e, hipStream_t s, bool* replay) {
+  e->prepared = true;
   // RCCL path: the all-reduces are captured into the graph together with the kernels only on request (MPPO_GRAPH_COMM=1; it has never
   // run on more than one GPU), by default several ranks with an RCCL communicator launch eagerly.  The peer-to-peer path is captured
   // like any sequence of kernels.

@@ -18,6 +18,8 @@
 // 2.9 KB at O = 225).  The kernel is bound by the instructions one wave issues, not by bandwidth.
 #include "model_view.h"
 #include "mppo_common.h"
+#include "philox.h"
+#include "threefry.h"
 #include <wave_ops.h>
 
 #include <algorithm>
@@ -53,7 +55,32 @@ struct EnvArgs {
   const float *p_qpos, *p_qvel, *p_ctrl, *p_warm;
   mppo_forward_probe_t probe;
   float* scratch;  // per-environment records in global memory for the matrices a large robot keeps out of LDS (PhysLds::gwords floats each; null if none)
+  // mode 0 only - the reset from randomised states (env.py:115-121 with reset_noise_scale > 0): qpos = qpos0 + U(-s, s), qvel = U(-s, s), drawn in the
+  // kernel per environment and element.  Behind everything the step kernel reads, so that its argument offsets stay what they were.
+  const unsigned char* mask;    // [N], null: every environment; an environment whose byte is 0 is left alone (the engine passes a step's done[t])
+  float noise_scale;            // s; 0: the plain reset
+  int noise_impl;               // 0: the engine's Philox stream kStreamReset, 1: the reference's threefry tree (split(K, N)[n] -> split -> uniform), 2: the same from given key_n
+  const unsigned* noise_key;    // threefry: K, two words in device memory (the reset key, train.py:142, or a step key, :163); impl 2: the N keys split(K, N), [N][2]
+  unsigned long long noise_seed, noise_stream;  // philox: the key and the stream id (kStreamReset + (rank << 16))
+  const int* noise_ctr;         // philox: the event counter's word in device memory (null: 0) ...
+  int noise_ctr_mul, noise_ctr_add;  // ... event = word * mul + add: the engine's update index * T + 1 + t, so that a replayed graph draws fresh values
 };
+
+// The reset noise of element i (0 .. nq - 1: qpos, nq .. nq + nv - 1: qvel) of environment `env`; `r1`, `r2`: the environment's two threefry keys
+constexpr unsigned long long kStreamReset = 0x5245534554ull << 24;  // "RESET" (engine.hip: beside kStreamNoise / kStreamPerm)
+__device__ __forceinline__ float reset_noise(const EnvArgs& a, int env, unsigned event, U2 r1, U2 r2, int i, int nq, int nv) {
+  unsigned bits;
+  if (a.noise_impl != 0) {
+    bits = i < nq ? threefry_iota_word(r1, (unsigned)i, (unsigned)nq) : threefry_iota_word(r2, (unsigned)(i - nq), (unsigned)nv);
+  } else {
+    // block i >> 2 of the environment's event: counter (env, event, stream + block), key = seed; word i & 3
+    const unsigned long long st = a.noise_stream + (unsigned long long)(i >> 2);
+    const U4 r = philox4x32((unsigned)env, event, (unsigned)st, (unsigned)(st >> 32), (unsigned)a.noise_seed, (unsigned)(a.noise_seed >> 32));
+    const int w = i & 3;
+    bits = w == 0 ? r.x : w == 1 ? r.y : w == 2 ? r.z : r.w;
+  }
+  return uniform_from_bits(bits, -a.noise_scale, a.noise_scale);
+}
 
 // wave-level synchronisation point: an environment's LDS arrays are touched by ONE wavefront only, whose LDS instructions
 // execute in program order - all that is needed is that the compiler keeps that order (the emulator yields here instead)
@@ -696,8 +723,21 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerBlock) env_kernel(ModelView m
   const int epw = kDims ? kEnvsPerWave : mv.epw;
   const int el = (tid >> 6) * epw + row;          // environment inside the workgroup
   int env = blockIdx.x * ((int)(blockDim.x >> 6) * epw) + el;  // the launch chooses the waves per workgroup (launch_env)
-  const bool valid = env < a.N;
-  if (!valid) env = a.N - 1;  // surplus groups shadow the last environment and never store
+  // (the rule of kFlagAsBallot below for a per-lane flag that crosses divergent code, applied to the reset's mask: the instantiations that spill vector registers
+  // carry it as the wave's ballot)
+  constexpr bool kMaskAsBallot = MODE == 0 && kRegChol && kDims && kSD.nv > 2 * kGroupLanes;
+  bool in_mask = true;
+  if (MODE == 0 && a.mask) {
+    // masked reset: a workgroup none of whose environments is masked in leaves before it stages the model tables.  Every wave reads the flags of the
+    // whole workgroup (at most kMaxWavesPerBlock x 4 bytes, lane l of every 16-lane row the l-th), so the decision is the same in all of them.
+    const int per_block = (int)(blockDim.x >> 6) * epw, first = blockIdx.x * per_block;
+    const bool mine = g < per_block && first + g < a.N && a.mask[first + g] != 0;
+    if (!wave_any(mine)) return;
+    in_mask = env < a.N && a.mask[env] != 0;
+  }
+  const group16_flags_t in_flags = kMaskAsBallot ? group16_flags(in_mask) : group16_flags_t{};
+  const bool valid = env < a.N && (kMaskAsBallot ? group16_flag_set(in_flags) : in_mask);
+  if (!(env < a.N)) env = a.N - 1;  // surplus groups shadow the last environment and never store (nor does an environment the mask leaves out)
   // model tables: one coalesced copy of the blob into LDS per workgroup, then every table read is a ds_read
   int* tabI = reinterpret_cast<int*>(smem_raw);
   const float* tabF = reinterpret_cast<const float*>(smem_raw);
@@ -775,8 +815,19 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerBlock) env_kernel(ModelView m
     FOR_G(i, nq) qpos[i] = rec[i];
     FOR_G(i, nv) { qvel[i] = rec[nq + i]; warm[i] = rec[OP + i]; }
   } else if (MODE == 0) {
-    FOR_G(i, nq) qpos[i] = TF(qpos0)[i];
-    FOR_G(i, nv) { qvel[i] = 0.f; warm[i] = 0.f; }
+    if (a.noise_scale > 0.f) {  // (uniform: a launch is noisy or it is not)
+      const unsigned event = (a.noise_ctr ? (unsigned)a.noise_ctr[0] : 0u) * (unsigned)a.noise_ctr_mul + (unsigned)a.noise_ctr_add;  // (modulo 2^32: no signed overflow)
+      U2 r1{0u, 0u}, r2{0u, 0u};
+      if (a.noise_impl != 0) {  // key_n = split(K, N)[n] (or, impl 2, the caller's key_n); r1, r2 = split(key_n)   (train.py:135,164 -> env.py:116)
+        const U2 kn = a.noise_impl == 2 ? U2{a.noise_key[2 * env], a.noise_key[2 * env + 1]} : split_key_n(U2{a.noise_key[0], a.noise_key[1]}, (unsigned)a.N, (unsigned)env);
+        r1 = split_key(kn, 0); r2 = split_key(kn, 1);
+      }
+      FOR_G(i, nq) qpos[i] = TF(qpos0)[i] + reset_noise(a, env, event, r1, r2, i, nq, nv);  // (quaternion words too, left unnormalised, as MJX leaves them)
+      FOR_G(i, nv) { qvel[i] = reset_noise(a, env, event, r1, r2, nq + i, nq, nv); warm[i] = 0.f; }
+    } else {
+      FOR_G(i, nq) qpos[i] = TF(qpos0)[i];
+      FOR_G(i, nv) { qvel[i] = 0.f; warm[i] = 0.f; }
+    }
   } else {
     FOR_G(i, nq) qpos[i] = a.p_qpos[(size_t)env * nq + i];
     FOR_G(i, nv) { qvel[i] = a.p_qvel[(size_t)env * nv + i]; warm[i] = a.p_warm[(size_t)env * nv + i]; }
@@ -2127,13 +2178,13 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerBlock) env_kernel(ModelView m
   // The new record's derived fields (cinert, cvel, qfrc_actuator, subtree_com) are those of the LAST forward
   // pass, i.e. they belong to the pre-integration pose: exactly what the MJX data carries.
   if (MODE == 0) {
-    // reset: record = [qpos0, 0, cinert[1:], cvel[1:], qfrc_actuator | pad | qacc_warmstart = qacc | com_x | time = 0]
+    // reset: record = [qpos0 (+ noise), 0 (noise), cinert[1:], cvel[1:], qfrc_actuator | pad | qacc_warmstart = qacc | com_x | time = 0]
     // (cinert / cvel were written when RNE had read them, qfrc_actuator when it was computed)
     FOR_G(i, mv.rec_dim) {
       if (i >= o_ci && i < O) continue;  // (cinert, cvel, qfrc_actuator: in place)
       float v = 0.f;
       if (i < nq) v = qpos[i];
-      else if (i < o_ci) v = 0.f;
+      else if (i < o_ci) v = qvel[i - nq];  // (zeros in the plain reset)
       else if (i < OP) v = 0.f;
       else if (i < OP + nv) v = qacc[i - OP];
       else if (i == OP + nv) v = new_comx;
@@ -2842,6 +2893,19 @@ int32_t env_reset_ws(const mppo_model_t* m, int32_t N, float* state, float* rese
   if (metrics) a.met = *metrics;
   return launch_env(m, a, stream, ws, ws_bytes);
 }
+// the reset from randomised states over the environments `mask` names (null: all of them): the reset kernel with its noise fields set and nothing
+// but the state rows and the observation rows to write - reward, done and the metrics are the step's, the reset record stays the noise-free one
+int32_t env_reinit_ws(const mppo_model_t* m, int32_t N, float* state, float* obs, int32_t obs_ld, const uint8_t* mask, float scale, int32_t rng_impl, uint64_t seed,
+                      int32_t rank, const uint32_t* key2, const int32_t* counter, int32_t counter_mul, int32_t counter_add, float* ws, size_t ws_bytes, hipStream_t stream) {
+  // (the Philox stream numbers an environment's blocks of four elements in the 16 bits of the stream id below the rank)
+  MPPO_REQUIRE(m->mv.nq + m->mv.nv <= 4 * 65536, "reset noise: %d noise elements per environment", m->mv.nq + m->mv.nv);
+  EnvArgs a{};
+  a.N = N; a.mode = 0; a.n_frames = 1; a.state = state; a.obs = obs; a.obs_ld = obs_ld;
+  a.mask = mask; a.noise_scale = scale; a.noise_impl = rng_impl; a.noise_key = key2; a.noise_seed = seed;
+  a.noise_stream = kStreamReset + ((unsigned long long)rank << 16);
+  a.noise_ctr = counter; a.noise_ctr_mul = counter_mul; a.noise_ctr_add = counter_add;
+  return launch_env(m, a, stream, ws, ws_bytes);
+}
 }  // namespace mppo
 
 extern "C" int32_t mppo_model_is_specialized(const mppo_model_t* m, int32_t* out) {
@@ -2861,6 +2925,20 @@ extern "C" int32_t mppo_env_reset(const mppo_model_t* m, int32_t N, float* state
   a.N = N; a.mode = 0; a.n_frames = 1; a.state = state; a.reset_out = reset_rec; a.obs = obs; a.obs_ld = obs_ld; a.reward = reward; a.done = done;
   if (metrics) a.met = *metrics;
   return launch_env(m, a, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int32_t mppo_env_reinit(const mppo_model_t* m, int32_t N, float* state, float* obs, int32_t obs_ld, const uint8_t* mask, float scale, int32_t rng_impl,
+                                   uint64_t seed, int32_t rank, const uint32_t* key2, const int32_t* counter, int32_t counter_offset, void* stream) {
+  using namespace mppo;
+  MPPO_REQUIRE(m && state, "mppo_env_reinit: null model / state");
+  MPPO_REQUIRE(N >= 1, "mppo_env_reinit: N = %d", N);
+  MPPO_REQUIRE(m->mv.nq >= 3, "mppo_env_reinit: the environment reads qpos[2] as the height (env.py:239); nq = %d", m->mv.nq);
+  MPPO_REQUIRE(!obs || obs_ld >= m->mv.obs_pad, "mppo_env_reinit: obs_ld %d < padded observation width %d", obs_ld, m->mv.obs_pad);
+  MPPO_REQUIRE(scale >= 0.f, "mppo_env_reinit: scale %g is negative (or not a number)", (double)scale);
+  MPPO_REQUIRE(rng_impl >= 0 && rng_impl <= 2, "mppo_env_reinit: rng_impl %d (0 philox, 1 threefry, 2 threefry from per-environment keys)", rng_impl);
+  MPPO_REQUIRE(rng_impl == 0 || scale == 0.f || key2, "mppo_env_reinit: the threefry stream needs a key (two words in device memory)");
+  MPPO_REQUIRE(rank >= 0 && rank < 256, "mppo_env_reinit: rank %d (0 .. 255)", rank);
+  return env_reinit_ws(m, N, state, obs, obs_ld, mask, scale, rng_impl, seed, rank, key2, counter, 1, counter_offset, nullptr, 0, static_cast<hipStream_t>(stream));
 }
 
 extern "C" int32_t mppo_env_step(const mppo_model_t* m, int32_t N, int32_t n_frames, const mppo_reward_cfg_t* rc, float* state,

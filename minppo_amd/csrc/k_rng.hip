@@ -8,41 +8,15 @@
 //   threefry_bits_kernel   : jax.random.bits(key, (n,)) + the identity permutation (first sort round)
 //   threefry_chain_kernel  : the split tree of one `_update_step`, one thread: T x {action key, step key}, E x {epoch key ->
 //                            one sub-key per sort round}; the carried key lives in the arena, so a captured graph draws fresh
-//                            keys every replay
+//                            keys every replay.  The step keys (train.py:163: what `step_rngs` are split from) are written out when
+//                            the caller asks for them: the environment kernel's reset noise draws from them (k_physics.hip)
 #include <wave_ops.h>
 
 #include "mppo_common.h"
 #include "ppo_layout.h"
+#include "threefry.h"
 
 namespace mppo {
-
-struct U2 { unsigned x, y; };
-
-__host__ __device__ inline unsigned rotl32(unsigned v, int r) { return (v << r) | (v >> (32 - r)); }
-
-__host__ __device__ inline U2 threefry2x32(unsigned k0, unsigned k1, unsigned x0, unsigned x1) {
-  const unsigned k2 = k0 ^ k1 ^ 0x1BD11BDAu;
-  // (written out: indexed key / rotation tables end up in scratch memory on the device)
-#define TF_MIX(R) { x0 += x1; x1 = rotl32(x1, R) ^ x0; }
-#define TF_ROUNDS_A TF_MIX(13) TF_MIX(15) TF_MIX(26) TF_MIX(6)
-#define TF_ROUNDS_B TF_MIX(17) TF_MIX(29) TF_MIX(16) TF_MIX(24)
-  x0 += k0; x1 += k1;
-  TF_ROUNDS_A x0 += k1; x1 += k2 + 1u;
-  TF_ROUNDS_B x0 += k2; x1 += k0 + 2u;
-  TF_ROUNDS_A x0 += k0; x1 += k1 + 3u;
-  TF_ROUNDS_B x0 += k1; x1 += k2 + 4u;
-  TF_ROUNDS_A x0 += k2; x1 += k0 + 5u;
-#undef TF_ROUNDS_A
-#undef TF_ROUNDS_B
-#undef TF_MIX
-  return {x0, x1};
-}
-
-// jax.random.split(key)[which]: threefry_2x32(key, [0, 1, 2, 3]) -> halves (0, 1 | 2, 3) -> out = [y0(0,2), y0(1,3), y1(0,2), y1(1,3)]
-__host__ __device__ inline U2 split_key(U2 key, int which) {
-  const U2 a = threefry2x32(key.x, key.y, 0u, 2u), b = threefry2x32(key.x, key.y, 1u, 3u);
-  return which == 0 ? U2{a.x, b.x} : U2{a.y, b.y};
-}
 
 __device__ __forceinline__ float normal_from_bits(unsigned bits) {
   const float lo = -0.99999994f;  // nextafter(-1, 0)
@@ -83,14 +57,16 @@ __global__ void __launch_bounds__(256) threefry_bits_kernel(const unsigned* __re
   if (j < n) { out[j] = y.y; if (iota) iota[j] = (int)j; }
 }
 
-__global__ void threefry_chain_kernel(unsigned* __restrict__ rng2, int T, int E, int rounds, unsigned* __restrict__ act_keys, unsigned* __restrict__ sort_keys) {
+__global__ void threefry_chain_kernel(unsigned* __restrict__ rng2, int T, int E, int rounds, unsigned* __restrict__ act_keys, unsigned* __restrict__ sort_keys,
+                                      unsigned* __restrict__ step_keys) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
   U2 rng{rng2[0], rng2[1]};
   for (int t = 0; t < T; ++t) {
     const U2 act = split_key(rng, 1);  // rng, action_rng = split(rng)   (train.py:158)
     rng = split_key(rng, 0);
     act_keys[2 * t] = act.x; act_keys[2 * t + 1] = act.y;
-    rng = split_key(rng, 0);           // rng, step_rng = split(rng)     (train.py:163; the step keys are unused: deterministic env)
+    if (step_keys) { const U2 stp = split_key(rng, 1); step_keys[2 * t] = stp.x; step_keys[2 * t + 1] = stp.y; }
+    rng = split_key(rng, 0);           // rng, step_rng = split(rng)     (train.py:163; the step keys feed the reset noise, if there is any)
   }
   for (int e = 0; e < E; ++e) {
     U2 k = split_key(rng, 1);          // rng, _rng = split(rng)         (train.py:252)
@@ -114,8 +90,8 @@ int32_t threefry_bits(const unsigned* key2, size_t n, unsigned* out, int* iota, 
   MPPO_CHECK_LAUNCH("threefry_bits_kernel");
   return MPPO_OK;
 }
-int32_t threefry_chain(unsigned* rng2, int T, int E, int rounds, unsigned* act_keys, unsigned* sort_keys, hipStream_t s) {
-  hipLaunchKernelGGL(threefry_chain_kernel, dim3(1), dim3(64), 0, s, rng2, T, E, rounds, act_keys, sort_keys);
+int32_t threefry_chain(unsigned* rng2, int T, int E, int rounds, unsigned* act_keys, unsigned* sort_keys, unsigned* step_keys, hipStream_t s) {
+  hipLaunchKernelGGL(threefry_chain_kernel, dim3(1), dim3(64), 0, s, rng2, T, E, rounds, act_keys, sort_keys, step_keys);
   MPPO_CHECK_LAUNCH("threefry_chain_kernel");
   return MPPO_OK;
 }
@@ -136,5 +112,11 @@ extern "C" int32_t mppo_threefry_bits(const uint32_t* key2, size_t n, uint32_t* 
 
 extern "C" int32_t mppo_threefry_update_keys(uint32_t* rng2, int32_t T, int32_t E, int32_t rounds, uint32_t* act_keys, uint32_t* sort_keys, void* stream) {
   MPPO_REQUIRE(rng2 && act_keys && sort_keys && T >= 1 && E >= 1 && rounds >= 1, "mppo_threefry_update_keys: bad argument");
-  return threefry_chain(rng2, T, E, rounds, act_keys, sort_keys, static_cast<hipStream_t>(stream));
+  return threefry_chain(rng2, T, E, rounds, act_keys, sort_keys, nullptr, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int32_t mppo_threefry_update_keys_step(uint32_t* rng2, int32_t T, int32_t E, int32_t rounds, uint32_t* act_keys, uint32_t* sort_keys, uint32_t* step_keys,
+                                                  void* stream) {
+  MPPO_REQUIRE(rng2 && act_keys && sort_keys && step_keys && T >= 1 && E >= 1 && rounds >= 1, "mppo_threefry_update_keys_step: bad argument");
+  return threefry_chain(rng2, T, E, rounds, act_keys, sort_keys, step_keys, static_cast<hipStream_t>(stream));
 }

@@ -225,7 +225,7 @@ int32_t permutation_batch_ctr(unsigned long long seed, unsigned long long stream
 // k_rng.hip / k_perm.hip: jax.random-compatible streams (threefry2x32)
 int32_t threefry_normal(const unsigned* key2, size_t n, float* out, hipStream_t s);
 int32_t threefry_bits(const unsigned* key2, size_t n, unsigned* out, int* iota, hipStream_t s);
-int32_t threefry_chain(unsigned* rng2, int T, int E, int rounds, unsigned* act_keys, unsigned* sort_keys, hipStream_t s);
+int32_t threefry_chain(unsigned* rng2, int T, int E, int rounds, unsigned* act_keys, unsigned* sort_keys, unsigned* step_keys, hipStream_t s);
 // jax.random.permutation(key, B): `rounds` stable sorts by fresh random bits, sort_keys = [rounds][2] device words
 int32_t threefry_permutation(const unsigned* sort_keys, int rounds, int B, int* idx, void* ws, size_t ws_bytes, hipStream_t stream);
 inline int threefry_rounds(int B) { return B <= 1 ? 1 : (int)ceil(3.0 * log((double)B) / log(4294967295.0)); }

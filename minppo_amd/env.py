@@ -6,8 +6,12 @@ Keeps the surface of the reference's `minppo/env.py` (`HumanoidEnv(config)` with
 single-env function (`train.py:136,140`), every method here takes and returns `[N, ...]` torch CUDA tensors and runs the
 cooperative rigid-body kernel (`csrc/k_physics.hip`) through the C ABI (`mppo_env_reset` / `mppo_env_step`).
 
-`rng` arguments are accepted and ignored: `reset_noise_scale` is 0.0 in the reference (`env.py:87`), so its reset is
-deterministic and its step keys are unused (`env.py:117-119`).
+`reset_noise_scale` is 0.0 in the reference (`env.py:87`): its reset is deterministic and its step keys draw noise of width
+zero (`env.py:117-119`), so at scale 0 the `rng` arguments are accepted and ignored.  Above 0 (the attribute
+assigned as in any Brax humanoid, or `environment.reset_noise_scale`) they are the reference's keys: `reset(rng, num_envs)` takes an
+int seed or a `uint32[2]` key and splits it over the environments (`train.py:135`), `step(es, action, rng)` takes a `uint32[2]` key or
+the `[N, 2]` per-environment keys the reference passes (`train.py:164-165`), and an environment that is reset starts from
+`qpos0 + U(-s, s)`, `qvel = U(-s, s)` (`env.py:115-121`) in the conventions of `minppo_amd/jaxrng.py` (`mppo_env_reinit`).
 The debug viewer (`env.py:264-333`) is out of scope (needs the MuJoCo renderer and ffmpeg); `main` says so.
 """
 
@@ -84,6 +88,9 @@ class HumanoidEnv:
         # "Currently unused" in the reference as well (env.py:107-113)
         self.actuator_ctrlrange = torch.tensor(self.cm.t["act_ctrlrange"], dtype=torch.float32, device=self.device)
         self._reset_rec = torch.zeros(self.dims.rec_dim, dtype=torch.float32, device=self.device)
+        # `environment.reset_noise_scale` sets the attribute unless it was assigned directly (on the class, or on the instance later)
+        if type(self).reset_noise_scale == 0.0 and config.environment.reset_noise_scale > 0:
+            self.reset_noise_scale = float(config.environment.reset_noise_scale)
         self._have_reset = False
 
     # -- PipelineEnv attributes ------------------------------------------------
@@ -111,10 +118,33 @@ class HumanoidEnv:
     def _mstruct(m: EnvMetrics) -> nat.EnvMetrics:
         return nat.EnvMetrics(*[x.data_ptr() for x in m])
 
+    def _noise_keys(self, rng: Any, N: int, what: str):
+        """-> (rng_impl of mppo_env_reinit, device tensor of the key words) for a seed, a uint32[2] key or [N, 2] per-environment keys"""
+        t = self.torch
+        scale = float(self.reset_noise_scale)
+        if scale < 0:
+            raise ValueError(f"reset_noise_scale = {scale!r}: the half-width of the reset noise cannot be negative")
+        if rng is None:
+            raise ValueError(f"{what}: reset_noise_scale = {scale} needs `rng` (an int seed or a uint32[2] key" + (", or [N, 2] per-environment keys)" if what == "step" else ")"))
+        if isinstance(rng, (int, np.integer)):
+            from minppo_amd import jaxrng
+
+            key = jaxrng.prng_key(int(rng))
+        else:
+            key = (rng.detach().cpu().numpy() if hasattr(rng, "detach") else np.asarray(rng)).astype(np.uint32)
+        if key.shape == (2,):
+            impl = 1
+        elif what == "step" and key.shape == (N, 2):
+            impl = 2
+        else:
+            raise ValueError(f"{what}: rng must be an int seed or a uint32[2] key" + (f" or [{N}, 2] per-environment keys" if what == "step" else "") + f", got shape {key.shape}")
+        return impl, t.from_numpy(np.ascontiguousarray(key).view(np.int32)).to(self.device)
+
     # -- env.py:124-145 ---------------------------------------------------------
     def reset(self, rng: Any = None, num_envs: int = 1) -> EnvState:
         t = self.torch
         N = int(num_envs)
+        noise = self._noise_keys(rng, N, "reset") if self.reset_noise_scale != 0 else None  # (a missing key is refused before anything is launched)
         state = t.empty(N, self.dims.rec_dim, dtype=t.float32, device=self.device)
         obs = t.empty(N, self.dims.obs_pad, dtype=t.float32, device=self.device)
         reward, done = t.empty(N, dtype=t.float32, device=self.device), t.empty(N, dtype=t.uint8, device=self.device)
@@ -122,6 +152,11 @@ class HumanoidEnv:
         ms = self._mstruct(m)
         self.lib.env_reset(self._model, N, state.data_ptr(), self._reset_rec.data_ptr(), obs.data_ptr(), self.dims.obs_pad, reward.data_ptr(),
                            done.data_ptr(), C.byref(ms), self._stream())
+        if noise is not None:  # env.py:115-121: every environment from a state of its own, keyed by split(rng, num_envs) (train.py:135)
+            impl, keys = noise
+            self.lib.env_reinit(self._model, N, state.data_ptr(), obs.data_ptr(), self.dims.obs_pad, 0, float(self.reset_noise_scale), impl, 0, 0, keys.data_ptr(), 0, 0,
+                                self._stream())
+            self._noise_keep = keys  # (lives until the next call: the launch reads it; same-stream allocations are reused in stream order)
         self._have_reset = True
         return EnvState(state, obs[:, :self.observation_size], reward, done.bool(), m)
 
@@ -132,6 +167,7 @@ class HumanoidEnv:
             self.reset(num_envs=1)
         state = env_state.pipeline_state.clone()
         N = state.shape[0]
+        noise = self._noise_keys(rng, N, "step") if self.reset_noise_scale != 0 else None
         action = action.to(device=self.device, dtype=t.float32).contiguous()
         if action.shape != (N, self._action_size):
             raise ValueError(f"action must have shape ({N}, {self._action_size}), got {tuple(action.shape)}")
@@ -141,6 +177,11 @@ class HumanoidEnv:
         ms = self._mstruct(m)
         self.lib.env_step(self._model, N, self._n_frames, C.byref(self._rc), state.data_ptr(), self._reset_rec.data_ptr(), action.data_ptr(),
                           self._action_size, obs.data_ptr(), self.dims.obs_pad, reward.data_ptr(), done.data_ptr(), C.byref(ms), self._stream())
+        if noise is not None:  # env.py:166,179-180: the environments that ended restart from `_get_reset_state(rng)`, not from the constant record
+            impl, keys = noise
+            self.lib.env_reinit(self._model, N, state.data_ptr(), obs.data_ptr(), self.dims.obs_pad, done.data_ptr(), float(self.reset_noise_scale), impl, 0, 0,
+                                keys.data_ptr(), 0, 0, self._stream())
+            self._noise_keep = keys
         return EnvState(state, obs[:, :self.observation_size], reward, done.bool(), m)
 
     # -- env.py:245-261 / 238-242 / 199-235 on the state record (host-side views, for inspection) ------

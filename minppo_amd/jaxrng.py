@@ -10,6 +10,8 @@ This module restates, in NumPy, exactly the pieces the training loop uses, so th
   normal(key, n)                    jax.random.normal         (sqrt(2) erf_inv(uniform in (-1, 1)), XLA's float32 erf_inv polynomial)
   permutation(key, n)               jax.random.permutation    (ceil(3 ln n / ln(2^32 - 1)) rounds of a stable sort by fresh random bits)
   update_keys(rng, T, E)            the split tree of one `_update_step` (train.py:158,163,252)
+  update_keys_step(rng, T, E)       the same, with the T step keys (train.py:163)
+  reset_noise(key, N, nq, nv, s)    the noise of `_get_reset_state` for N environments keyed by split(key, N) (train.py:135,164; env.py:116-119)
 
 Conventions are those of jax 0.4.3x with its defaults (`jax_default_prng_impl = threefry2x32`, `jax_threefry_partitionable = False`),
 the versions the reference's un-pinned requirements resolved to in October 2024.  STATUS: written from the published algorithm and
@@ -116,20 +118,70 @@ def permutation(key, n: int) -> np.ndarray:
     return x
 
 
-def update_keys(rng, T: int, E: int, n_perm: int):
+def update_keys_step(rng, T: int, E: int, n_perm: int):
     """The split tree of one `_update_step` (reference train.py): per env step `rng, action_rng = split(rng)` (:158) and
-    `rng, step_rng = split(rng)` (:163; the per-env step keys are unused by the deterministic environment), per epoch
+    `rng, step_rng = split(rng)` (:163; the per-env keys split from it draw the reset noise, if there is any), per epoch
     `rng, _rng = split(rng)` (:252) followed by `_shuffle`'s `key, subkey = split(key)` per sort round.
-    Returns (new rng, action keys [T,2], sort keys [E, rounds, 2])."""
+    Returns (new rng, action keys [T,2], sort keys [E, rounds, 2], step keys [T,2])."""
     rng = np.asarray(rng, np.uint32)
     rounds = permutation_rounds(n_perm)
     act = np.zeros((T, 2), np.uint32)
+    step = np.zeros((T, 2), np.uint32)
     for t in range(T):
         rng, act[t] = split(rng)
-        rng, _step = split(rng)
+        rng, step[t] = split(rng)
     srt = np.zeros((E, rounds, 2), np.uint32)
     for e in range(E):
         rng, k = split(rng)
         for r in range(rounds):
             k, srt[e, r] = split(k)
-    return rng, act, srt
+    return rng, act, srt, step
+
+
+def update_keys(rng, T: int, E: int, n_perm: int):
+    """update_keys_step without the step keys: (new rng, action keys [T,2], sort keys [E, rounds, 2])."""
+    return update_keys_step(rng, T, E, n_perm)[:3]
+
+
+def reset_noise(key, num_envs: int, nq: int, nv: int, scale: float, env_keys=None):
+    """The noise `_get_reset_state` (env.py:115-121) adds for each of `num_envs` environments under `reset_fn` / `step_fn`'s keys
+    (train.py:135,164: `split(key, num_envs)`, or `env_keys` [N,2] given directly): `rng1, rng2 = split(key_n)`, qpos noise
+    `uniform(rng1, (nq,), -s, s)`, qvel noise `uniform(rng2, (nv,), -s, s)` -> float32 [N, nq], [N, nv]."""
+    keys = split(np.asarray(key, np.uint32), num_envs) if env_keys is None else np.asarray(env_keys, np.uint32).reshape(num_envs, 2)
+    dq, dv = np.zeros((num_envs, nq), np.float32), np.zeros((num_envs, nv), np.float32)
+    for n in range(num_envs):
+        r1, r2 = split(keys[n])
+        dq[n], dv[n] = uniform(r1, nq, -scale, scale), uniform(r2, nv, -scale, scale)
+    return dq, dv
+
+
+_RESET_STREAM = 0x5245534554 << 24  # "RESET": the engine's Philox stream of the reset noise (csrc/k_physics.hip kStreamReset)
+
+
+def _philox4x32(c0, c1, c2, c3, k0, k1):
+    """Philox4x32-10 (Salmon et al., SC'11) on NumPy arrays (the device code is csrc/philox.h)."""
+    c0, c1, c2, c3 = (np.asarray(x, np.uint64) for x in (c0, c1, c2, c3))
+    k0, k1 = np.uint64(k0), np.uint64(k1)
+    m32 = np.uint64(0xFFFFFFFF)
+    for _ in range(10):
+        p0, p1 = np.uint64(0xD2511F53) * c0, np.uint64(0xCD9E8D57) * c2
+        c0, c1, c2, c3 = (p1 >> np.uint64(32)) ^ c1 ^ k0, p1 & m32, (p0 >> np.uint64(32)) ^ c3 ^ k1, p0 & m32
+        k0, k1 = (k0 + np.uint64(0x9E3779B9)) & m32, (k1 + np.uint64(0xBB67AE85)) & m32
+    return c0, c1, c2, c3
+
+
+def reset_noise_philox(seed: int, rank: int, event: int, num_envs: int, nq: int, nv: int, scale: float):
+    """The same noise from the engine's own stream (`training.rng_impl=philox`): element i (qpos words, then qvel words) of local environment n at
+    event `event` is word i & 3 of philox(counter = (n, event, lo(S + (i >> 2)), hi(S)), key = seed), S = "RESET" << 24 + (rank << 16); bits become
+    a float as `uniform` makes one.  Events: 0 is the reset, step t of update u is u * T + 1 + t -> float32 [N, nq], [N, nv]."""
+    ne = nq + nv
+    nblk = (ne + 3) // 4
+    n = np.repeat(np.arange(num_envs, dtype=np.uint64), nblk)
+    st = np.uint64(_RESET_STREAM + (int(rank) << 16)) + np.tile(np.arange(nblk, dtype=np.uint64), num_envs)
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    z = np.stack(_philox4x32(n, np.full_like(n, int(event) & 0xFFFFFFFF), st & np.uint64(0xFFFFFFFF), st >> np.uint64(32), seed & 0xFFFFFFFF, seed >> 32), 1)
+    bits = z.reshape(num_envs, nblk * 4)[:, :ne].astype(np.uint32)
+    f = ((bits >> np.uint32(9)) | np.uint32(0x3F800000)).view(np.float32) - np.float32(1.0)
+    lo, hi = np.float32(-scale), np.float32(scale)
+    u = np.maximum(lo, f * (hi - lo) + lo).astype(np.float32)
+    return u[:, :nq].copy(), u[:, nq:].copy()

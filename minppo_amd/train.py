@@ -174,7 +174,7 @@ def tree_to_flat(tree: dict, O: int, A: int, H: int, L: int = 2) -> np.ndarray:
 
 _REGION_DTYPES = {
     "count": "int32", "done": "uint8", "perm": "int32", "adv_sums": "float64", "episode_lengths": "int32",
-    "returned_episode_lengths": "int32", "timestep": "int32", "returned_episode": "uint8", "jax_rng": "int32",
+    "returned_episode_lengths": "int32", "timestep": "int32", "returned_episode": "uint8", "jax_rng": "int32", "reset_rng": "int32",
 }
 
 
@@ -278,6 +278,10 @@ class Trainer:
             self.arena = raw[o:o + self.arena_bytes]
         self._engine = C.c_void_p()
         self.lib.engine_create(self._model, C.byref(self.ecfg), nat.ptr(self.arena), self.arena_bytes, C.byref(self._engine))
+        # environment.reset_noise_scale (env.py:87,115-121): 0 leaves the engine's launch sequence as it is
+        self.reset_noise_scale = float(config.environment.reset_noise_scale)  # (make_config refuses a negative one; so does the engine)
+        if self.reset_noise_scale > 0:
+            self.lib.engine_set_reset_noise(self._engine, self.reset_noise_scale)
         self.P = int(self.lib.param_count(C.byref(self.net)))
         self.updates_done = 0
         self._prepared = False
@@ -303,6 +307,18 @@ class Trainer:
         reg = self.region("jax_rng")
         vals = np.zeros(reg.shape[0], np.int32)
         vals[:2] = runner.view(np.int32)
+        self._write_region(reg, vals)
+
+    def _seed_reset_key(self) -> None:
+        """`reset_rng` of train.py:142 (the second key of the second split of PRNGKey(seed)) behind the step keys of region "reset_rng": what the
+        engine's noisy reset splits into the environments' keys (train.py:135)."""
+        from minppo_amd import jaxrng
+
+        rng = jaxrng.split(jaxrng.prng_key(self.seed))[0]
+        reset_key = jaxrng.split(rng)[1]
+        reg = self.region("reset_rng")
+        vals = np.zeros(reg.shape[0], np.int32)
+        vals[2 * self.T:2 * self.T + 2] = reset_key.view(np.int32)
         self._write_region(reg, vals)
 
     # -- arena views ----------------------------------------------------------
@@ -354,6 +370,7 @@ class Trainer:
     # uninterrupted run bit for bit (tests/test_train_surface.py).
     _CKPT_REGIONS = ("params", "adam_m", "adam_v", "count", "state", "episode_returns", "episode_lengths", "returned_episode_returns",
                      "returned_episode_lengths", "timestep", "returned_episode", "jax_rng")
+    _CKPT_OPTIONAL = ("reset_rng",)  # (regions younger than checkpoint version 2: written always, read when the file has them)
     _CKPT_VERSION = 2  # 2: 16-byte-aligned flat parameter layout
 
     def _ckpt_meta(self) -> Dict[str, Any]:
@@ -363,7 +380,7 @@ class Trainer:
 
     def save_checkpoint(self, path: str) -> None:
         self._sync()
-        arrays = {name: self._to_host(self.region(name)).copy() for name in self._CKPT_REGIONS}
+        arrays = {name: self._to_host(self.region(name)).copy() for name in self._CKPT_REGIONS + self._CKPT_OPTIONAL}
         arrays["last_obs"] = self._to_host(self.region("obs", (self.T + 1, self.N, self.OP))[0]).copy()
         meta = dict(self._ckpt_meta(), updates_done=int(self.updates_done))
         p = Path(path)
@@ -391,6 +408,9 @@ class Trainer:
             self._sync()
             for name in self._CKPT_REGIONS:
                 self._write_region(self.region(name), z[name])
+            for name in self._CKPT_OPTIONAL:  # (the reset noise's threefry keys: rewritten by every update and by reset(), so a file without them loses nothing)
+                if name in z.files:
+                    self._write_region(self.region(name), z[name])
             self._write_region(self.region("obs", (self.T + 1, self.N, self.OP))[0], z["last_obs"])
         self.updates_done = int(meta["updates_done"])
         self._hist_carry = None
@@ -631,6 +651,9 @@ class Trainer:
     # -- stepping ----------------------------------------------------------------
     def reset(self) -> None:
         self._hist_carry = None  # (the metric words change under the history's feet: re-read before the next update)
+        if self.ecfg.rng_impl == 1 and self.reset_noise_scale > 0:
+            self._sync()
+            self._seed_reset_key()  # (read by the engine's noisy reset)
         self.lib.engine_reset(self._engine, self._stream_ptr)
         if self.ecfg.rng_impl == 1:
             self._sync()

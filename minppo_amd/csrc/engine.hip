@@ -31,8 +31,8 @@ const ModelView& model_view(const mppo_model* m);
 size_t model_scratch_bytes(const mppo_model* m, int N);
 int32_t env_step_ws(const mppo_model_t* m, int32_t N, int32_t n_frames, const mppo_reward_cfg_t* rc, float* state, const float* reset_rec, const float* action,
                     int32_t act_ld, float* obs, int32_t obs_ld, float* reward, uint8_t* done, const mppo_env_metrics_t* metrics, float* ws, size_t ws_bytes, hipStream_t stream);
-int32_t env_reset_ws(const mppo_model_t* m, int32_t N, float* state, float* reset_rec, float* obs, int32_t obs_ld, const mppo_env_metrics_t* metrics, float* ws, size_t ws_bytes,
-                     hipStream_t stream);
+int32_t env_reset_ws(const mppo_model_t* m, int32_t N, float* state, float* reset_rec, float* obs, int32_t obs_ld, float* reward, uint8_t* done, const mppo_env_metrics_t* metrics,
+                     float* ws, size_t ws_bytes, hipStream_t stream);
 int32_t env_reinit_ws(const mppo_model_t* m, int32_t N, float* state, float* obs, int32_t obs_ld, const uint8_t* mask, float scale, int32_t rng_impl, uint64_t seed,
                       int32_t rank, const uint32_t* key2, const int32_t* counter, int32_t counter_mul, int32_t counter_add, float* ws, size_t ws_bytes, hipStream_t stream);
 
@@ -462,7 +462,7 @@ extern "C" int32_t mppo_engine_reset(mppo_engine_t* e, void* stream) {
   MPPO_CHECK_HIP(hipMemsetAsync(e->adam_v, 0, (size_t)e->P * 4, s));
   MPPO_CHECK_HIP(hipMemsetAsync(e->obs, 0, (size_t)(e->T + 1) * e->N * e->OP * 4, s));
   MPPO_TRY(permutation_batch_prepare(e->B, e->E, e->perm_ws, e->perm_ws_bytes, s));
-  MPPO_TRY(env_reset_ws(e->model, e->N, e->state, e->reset_rec, e->obs, e->OP, &e->met, e->env_ws, e->env_ws_bytes, static_cast<hipStream_t>(s)));  // train.py:142-144
+  MPPO_TRY(env_reset_ws(e->model, e->N, e->state, e->reset_rec, e->obs, e->OP, nullptr, nullptr, &e->met, e->env_ws, e->env_ws_bytes, static_cast<hipStream_t>(s)));  // train.py:142-144
   // reset noise: the plain reset above made the noise-free reset record and the zeroed metrics; every environment then starts from a state of its own
   // (event 0 of the Philox stream; the reset key behind the step keys of region "reset_rng" for threefry: the caller writes it before this call)
   if (e->reset_noise > 0.f)

@@ -16,16 +16,11 @@
 // are evaluated in closed form over ancestor / subtree bitmasks from the model blob, so they need no level-by-level
 // synchronisation.  HBM traffic per environment step: the state record in and out, the action in, the observation out (about
 // 2.9 KB at O = 225).  The kernel is bound by the instructions one wave issues, not by bandwidth.
-#include "model_view.h"
-#include "mppo_common.h"
+#include "env_kernel.h"
 #include "philox.h"
 #include "threefry.h"
 #include <wave_ops.h>
 
-#include <algorithm>
-#include <cstring>
-#include <vector>
-#include <initializer_list>
 #include <type_traits>
 #include <utility>
 
@@ -38,36 +33,7 @@ __device__ __forceinline__ void static_for_impl(F&& f, std::integer_sequence<int
 template <int N, class F>
 __device__ __forceinline__ void static_for(F&& f) { static_for_impl(f, std::make_integer_sequence<int, N>{}); }
 
-
-struct EnvArgs {
-  int N, mode, n_frames;  // mode 0: reset (pipeline_init), 1: step, 2: probe (one forward on given inputs)
-  float* state;
-  const float* reset_in;
-  float* reset_out;
-  const float* action;
-  int act_ld;
-  float* obs;
-  int obs_ld;
-  float* reward;
-  unsigned char* done;
-  mppo_env_metrics_t met;
-  mppo_reward_cfg_t rc;
-  const float *p_qpos, *p_qvel, *p_ctrl, *p_warm;
-  mppo_forward_probe_t probe;
-  float* scratch;  // per-environment records in global memory for the matrices a large robot keeps out of LDS (PhysLds::gwords floats each; null if none)
-  // mode 0 only - the reset from randomised states (env.py:115-121 with reset_noise_scale > 0): qpos = qpos0 + U(-s, s), qvel = U(-s, s), drawn in the
-  // kernel per environment and element.  Behind everything the step kernel reads, so that its argument offsets stay what they were.
-  const unsigned char* mask;    // [N], null: every environment; an environment whose byte is 0 is left alone (the engine passes a step's done[t])
-  float noise_scale;            // s; 0: the plain reset
-  int noise_impl;               // 0: the engine's Philox stream kStreamReset, 1: the reference's threefry tree (split(K, N)[n] -> split -> uniform), 2: the same from given key_n
-  const unsigned* noise_key;    // threefry: K, two words in device memory (the reset key, train.py:142, or a step key, :163); impl 2: the N keys split(K, N), [N][2]
-  unsigned long long noise_seed, noise_stream;  // philox: the key and the stream id (kStreamReset + (rank << 16))
-  const int* noise_ctr;         // philox: the event counter's word in device memory (null: 0) ...
-  int noise_ctr_mul, noise_ctr_add;  // ... event = word * mul + add: the engine's update index * T + 1 + t, so that a replayed graph draws fresh values
-};
-
 // The reset noise of element i (0 .. nq - 1: qpos, nq .. nq + nv - 1: qvel) of environment `env`; `r1`, `r2`: the environment's two threefry keys
-constexpr unsigned long long kStreamReset = 0x5245534554ull << 24;  // "RESET" (engine.hip: beside kStreamNoise / kStreamPerm)
 __device__ __forceinline__ float reset_noise(const EnvArgs& a, int env, unsigned event, U2 r1, U2 r2, int i, int nq, int nv) {
   unsigned bits;
   if (a.noise_impl != 0) {
@@ -709,9 +675,9 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerBlock) env_kernel(ModelView m
   constexpr bool kDims = SD::kStatic;
   // fixed-size kernel, up to 32 dofs: a lane's rows / columns of the Cholesky factors live in registers (see factor_m below)
   constexpr bool kRegChol = kDims && kSD.nv <= kRegCholMaxNv;
-  constexpr int kNefc = kSD.neq + kSD.nlimit + 4 * kSD.ncon;
-  constexpr int kSpill = kDims ? spill_for(kSD.nq, kSD.nv, kSD.nu, kSD.nbody, kSD.njnt, kSD.ncon, kNefc, kSD.nroot, kSD.ncvx, kRegChol, kSO.words, kSD.neq, kSD.nball) : 0;
-  constexpr PhysLds kSP = make_phys_lds(kSD.nq, kSD.nv, kSD.nu, kSD.nbody, kSD.njnt, kSD.ncon, kNefc, kSD.nroot, kSD.ncvx, kRegChol, kSpill, kSD.neq, kSD.nball);
+  constexpr int kNefc = nefc_of(kSD);
+  constexpr int kSpill = kDims ? spill_for(kSD, kRegChol, kSO.words) : 0;
+  constexpr PhysLds kSP = make_phys_lds(kSD, kRegChol, kSpill);
   const PhysLds P = SD::kStatic ? kSP : Prt;
   constexpr int NV = kDims ? kSD.nv : 0;
   constexpr int kDotU = dot_unroll(NV);
@@ -2275,9 +2241,7 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerBlock) env_kernel(ModelView m
 
 }  // namespace mppo
 
-// =================================================================================================
-// host side: model handle + launch wrappers (C ABI)
-// =================================================================================================
+// host side: the instantiations and their launch (the model handle and the C ABI: env_model.hip)
 namespace mppo {
 template <class SD>
 static int32_t launch_env_t(const ModelView& mv, const EnvArgs& a, const PhysLds& lds, int lds_bytes, int blocks, int waves, hipStream_t stream) {
@@ -2312,446 +2276,19 @@ static const SpecEntry kSpecs[] = {
 #undef MPPO_SPEC
 #undef MPPO_SPEC_EXTRA
 
-// MPPO_ENV_GENERIC=1 forces the run-time-sized kernel (A/B tests of the two instantiations); so does MPPO_ENV_SPILL, which only the
-// run-time-sized kernel can follow (a specialised kernel's choice is compiled in)
-static int env_spill_override() {
-  const char* e = getenv("MPPO_ENV_SPILL");
-  if (!e || !e[0]) return -1;
-  const int v = atoi(e);
-  return v == 0 ? 0 : v == 1 ? kSpillJ : (kSpillJ | kSpillM);
-}
-static int find_spec(const BlobDims& d) {
-  const char* e = getenv("MPPO_ENV_GENERIC");
-  if (e && e[0] == '1') return -1;
-  if (env_spill_override() >= 0) return -1;
-  for (int i = 0; kSpecs[i].launch; ++i) {
-    const BlobDims& s = kSpecs[i].d;
-    if (s.nq == d.nq && s.nv == d.nv && s.nu == d.nu && s.nbody == d.nbody && s.njnt == d.njnt && s.ncon == d.ncon && s.nlimit == d.nlimit &&
-        s.npair == d.npair && s.nlevel == d.nlevel && s.nroot == d.nroot && s.ncvx == d.ncvx && s.ncvxvert == d.ncvxvert && s.hull == d.hull && s.ncyl == d.ncyl &&
-        s.cparam == d.cparam && s.neq == d.neq && s.nball == d.nball)
-      return i;
-  }
+int find_spec(const BlobDims& d) {
+  for (int i = 0; kSpecs[i].launch; ++i) if (kSpecs[i].d == d) return i;
   return -1;
 }
-}  // namespace mppo
-
-struct mppo_model {
-  mppo::ModelView mv;
-  mppo::PhysLds lds;
-  int lds_bytes;
-  int waves;  // wavefronts per workgroup (mv.epw environments each: 4, fewer for a very large robot; one copy of the model tables per workgroup)
-  int spec;  // index into the table of model-specialised kernels (spec_dims.inc), -1: the run-time-sized kernel
-  // the records of the matrices a large robot keeps out of LDS (PhysLds::gwords floats per environment group of the grid), for launches
-  // through mppo_env_reset / _step / mppo_physics_forward: owned by the handle, grown on demand (the engine passes a region of its arena
-  // instead).  One stream at a time may launch through a handle that needs them.
-  mutable float* scratch = nullptr;
-  mutable size_t scratch_bytes = 0;
-  int canon_words = 0;  // the table part's length as it follows from the dims (what a specialised kernel's compile-time layout choice saw)
-  // a code object attached at run time (mppo_model_attach_kernel): the environment kernel compiled for exactly this robot's dimensions -
-  // what MPPO_SPECIALIZE does at build time, for a robot the library was not built for
-  bool jit = false;
-  int jit_regchol = 0;  // the MPPO_REGCHOL_MAX_NV the code object was compiled with (its LDS layout follows from it)
-  hipModule_t jit_module = nullptr;
-  hipFunction_t jit_fn[3] = {nullptr, nullptr, nullptr};
-  std::vector<char> jit_image;
-};
-
-namespace mppo {
-const ModelView& model_view(const mppo_model* m) { return m->mv; }
-// bytes of global memory the environment kernel needs beside the state for N environments (0 for a robot whose matrices fit LDS)
-size_t model_scratch_bytes(const mppo_model* m, int N) {
-  if (m->lds.gwords <= 0) return 0;
-  const int per_block = m->mv.epw * m->waves;
-  return (size_t)cdiv(N, per_block) * per_block * (size_t)m->lds.gwords * sizeof(float);
-}
-}
-
-namespace mppo {
-static int32_t launch_env(const mppo_model_t* m, EnvArgs a, hipStream_t stream, float* ws = nullptr, size_t ws_bytes = 0);
-
-// LDS layout, matrices in global memory, environments per wave and waves per workgroup of a model whose `spec` is decided
-static int32_t finalize_layout(mppo_model* m) {
-  ModelView& v = m->mv;
-  // (a model-specialised kernel of up to kRegCholMaxNv dofs keeps the inverse Cholesky factor in registers: no factor in its LDS layout; the
-  // matrices that leave LDS for global memory - spill_for - are a function of the dims that the specialised kernel evaluated at compile time)
-  // (MPPO_ENV_SPILL=0|1|3 overrides the choice - nothing, the Jacobian, the Jacobian and M in global memory - for A/B measurements and
-  // for the test that holds the two placements bit-equal)
-  auto lds_for = [&](bool li_regs) {
-    const int forced = env_spill_override();
-    return make_phys_lds(v.nq, v.nv, v.nu, v.nbody, v.njnt, v.ncon, v.nefc, v.nroot, v.ncvx, li_regs,
-                         forced >= 0 ? forced : spill_for(v.nq, v.nv, v.nu, v.nbody, v.njnt, v.ncon, v.nefc, v.nroot, v.ncvx, li_regs, m->canon_words, v.neq, v.nball), v.neq, v.nball);
-  };
-  const bool fixed = m->spec >= 0 || m->jit;
-  m->lds = lds_for(fixed && v.nv <= (m->jit ? m->jit_regchol : kRegCholMaxNv));
-  // waves per workgroup: whatever puts the most waves on a CU (160 KB of LDS; every workgroup holds one copy of the model tables and
-  // waves x 4 environments), the smaller workgroup on a tie.  MPPO_ENV_WAVES=1..4 overrides (measurements).
-  // A robot too large for four environments per wave even with its matrices outside LDS runs two or one per wave on the
-  // run-time-sized kernel - three quarters of the lanes idle, but it runs (round 5; before, it was refused).
-  v.epw = kEnvsPerWave;
-  if (fixed && ((long long)v.blob_words + (long long)m->lds.total * kEnvsPerWave) * 4 > 160 * 1024) {
-    // (a specialised kernel carries four environments per wave; a robot too large for that runs the run-time-sized kernel with fewer)
-    m->spec = -1;
-    m->jit = false;
-    m->lds = lds_for(false);
-  }
-  auto lds_of = [&](int w) { return (int)std::min<long long>(((long long)v.blob_words + (long long)m->lds.total * v.epw * w) * 4, 1 << 30); };
-  while (lds_of(1) > 160 * 1024 && m->spec < 0 && !m->jit && v.epw > 1) v.epw /= 2;
-  int best = 1, best_per_cu = 0;
-  for (int w = 1; w <= kMaxWavesPerBlock; ++w) {
-    const int per_cu = lds_of(w) <= 160 * 1024 ? (160 * 1024 / lds_of(w)) * w : 0;
-    if (per_cu > best_per_cu) { best = w; best_per_cu = per_cu; }
-  }
-  if (const char* e = getenv("MPPO_ENV_WAVES")) { const int w = atoi(e); if (w >= 1 && w <= kMaxWavesPerBlock) best = w; }
-  m->waves = best;
-  m->lds_bytes = lds_of(best);
-  if (m->lds_bytes > 160 * 1024) return fail(MPPO_EMODEL, "model needs %d bytes of LDS per workgroup for ONE environment (limit 163840)", m->lds_bytes);
-  return MPPO_OK;
-}
-
-// A kernel instantiation that MPPO_SPECIALIZE added to this build has never been compared with anything: before it is trusted, a reset and
-// four steps of 24 environments under pseudo-random controls must equal the run-time-sized kernel's bit for bit ON THIS DEVICE.  If they do
-// not (round 6: a 34-dof / 93-body robot's instantiation, 250 spilled registers, ended every episode at its first step on the GPU while the
-// same source was right on the emulator - a per-lane flag spilled inside divergent code: `bad_mid` in env_kernel says how it ended), the model runs the run-time-sized kernel and
-// says so on stderr.  A few milliseconds at mppo_model_open; the BASELINE instantiations are held to the same standard by the test suite.
-// Work on the device the model's tables are on, whatever the calling thread's current device is (restored on the way out)
-struct OnDeviceOf {
-  int cur = -1, dev = -1;
-  hipError_t err = hipSuccess;
-  explicit OnDeviceOf(const void* p) {
-#ifndef MPPO_EMU
-    hipPointerAttribute_t attr{};
-    err = hipGetDevice(&cur);
-    if (err == hipSuccess) err = hipPointerGetAttributes(&attr, p);
-    if (err == hipSuccess) { dev = attr.device; if (dev != cur) err = hipSetDevice(dev); }
+bool spec_is_extra(int spec) { return kSpecs[spec].extra; }
+int32_t launch_env_spec(int spec, const ModelView& mv, const EnvArgs& a, const PhysLds& lds, int lds_bytes, int blocks, int waves, hipStream_t stream) {
+#ifdef MPPO_JIT_ONLY  // (the device-side compile of minppo_amd/jit.py: one robot's instantiation and nothing else)
+  return kSpecs[0].launch(mv, a, lds, lds_bytes, blocks, waves, stream);
 #else
-    (void)p;
+  return (spec >= 0 ? kSpecs[spec].launch : mv.nball > 0 ? &launch_env_t<RuntimeBallModel> : &launch_env_t<RuntimeModel>)(mv, a, lds, lds_bytes, blocks, waves, stream);
 #endif
-  }
-  ~OnDeviceOf() {
-#ifndef MPPO_EMU
-    if (dev != cur && dev >= 0 && cur >= 0) (void)hipSetDevice(cur);
-#endif
-  }
-};
-static int32_t spec_self_check_on_device(mppo_model* m);
-static int32_t spec_self_check(mppo_model* m) {
-  OnDeviceOf where(m->mv.blob);
-  MPPO_CHECK_HIP(where.err);
-  return spec_self_check_on_device(m);
-}
-static int32_t spec_self_check_on_device(mppo_model* m) {
-  const ModelView& v = m->mv;
-  const int N = 24, steps = 4, nu = v.nu > 0 ? v.nu : 1;
-  const size_t nstate = (size_t)N * v.rec_dim, nobs = (size_t)N * v.obs_pad, nact = (size_t)N * nu;
-  const size_t words = nstate + v.rec_dim + nobs + (size_t)steps * nact + N + N;  // state, reset record, observation, controls, reward, done
-  float* dev = nullptr;
-  MPPO_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&dev), words * sizeof(float)));
-  std::vector<float> act((size_t)steps * nact), got[2];
-  unsigned lcg = 12345u;
-  for (float& x : act) { lcg = lcg * 1664525u + 1013904223u; x = ((lcg >> 8) & 0xffff) / 32768.f - 1.f; }
-  float *state = dev, *reset_rec = state + nstate, *obs = reset_rec + v.rec_dim, *actd = obs + nobs, *rew = actd + (size_t)steps * nact;
-  unsigned char* done = reinterpret_cast<unsigned char*>(rew + N);
-  mppo_reward_cfg_t rc{};
-  rc.height_min_z = -1e9f; rc.height_max_z = 1e9f;
-  mppo_model generic = *m;
-  generic.spec = -1; generic.jit = false; generic.scratch = nullptr; generic.scratch_bytes = 0;
-  int32_t st = finalize_layout(&generic);
-  for (int which = 0; which < 2 && st == MPPO_OK; ++which) {
-    const mppo_model* mm = which == 0 ? m : &generic;
-    hipError_t he = hipMemset(dev, 0, words * sizeof(float));
-    if (he == hipSuccess) he = hipMemcpy(actd, act.data(), act.size() * sizeof(float), hipMemcpyHostToDevice);
-    if (he != hipSuccess) { st = fail(MPPO_EHIP, "specialised-kernel self-check: %s", hipGetErrorString(he)); break; }
-    EnvArgs a{};
-    a.N = N; a.mode = 0; a.n_frames = 1; a.state = state; a.reset_out = reset_rec; a.obs = obs; a.obs_ld = v.obs_pad; a.reward = rew; a.done = done;
-    st = launch_env(mm, a, nullptr);
-    for (int t = 0; t < steps && st == MPPO_OK; ++t) {
-      EnvArgs b{};
-      b.N = N; b.mode = 1; b.n_frames = 1; b.state = state; b.reset_in = reset_rec; b.action = actd + (size_t)t * nact; b.act_ld = nu;
-      b.obs = obs; b.obs_ld = v.obs_pad; b.reward = rew; b.done = done; b.rc = rc;
-      st = launch_env(mm, b, nullptr);
-    }
-    if (st != MPPO_OK) break;
-    got[which].resize(words);
-    he = hipDeviceSynchronize();
-    if (he == hipSuccess) he = hipMemcpy(got[which].data(), dev, words * sizeof(float), hipMemcpyDeviceToHost);
-    if (he != hipSuccess) st = fail(MPPO_EHIP, "specialised-kernel self-check: %s", hipGetErrorString(he));
-  }
-  (void)hipFree(dev);
-  if (generic.scratch) (void)hipFree(generic.scratch);
-  if (st != MPPO_OK) return st;
-  // (the controls are the same bytes in both; everything else is the kernels' output)
-  if (memcmp(got[0].data(), got[1].data(), words * sizeof(float)) != 0) {
-    size_t bad = 0;
-    for (size_t i = 0; i < words; ++i) bad += memcmp(&got[0][i], &got[1][i], 4) != 0;
-    fprintf(stderr, "minppo_amd: the environment kernel specialised for this robot (nv %d, %d bodies, %d contact slots) differs from the run-time-sized kernel in %zu of %zu "
-                    "words after a reset and %d steps of %d environments on this device: NOT used - the run-time-sized kernel runs instead.  (DESIGN.md 3.3 has the one such kernel met so far; "
-                    "minppo_amd/build.py names the build variable that keeps a specialised kernel's factorisation out of registers.)\n", v.nv, v.nbody, v.ncon, bad, words, steps, N);
-    if (m->scratch) { (void)hipFree(m->scratch); m->scratch = nullptr; m->scratch_bytes = 0; }
-    m->spec = -1;
-    m->jit = false;
-    return finalize_layout(m);
-  }
-  return MPPO_OK;
 }
 }  // namespace mppo
-
-extern "C" int32_t mppo_model_open(const void* host_blob, size_t nbytes, const void* dev_blob, mppo_model_t** out) {
-  using namespace mppo;
-  if (!host_blob || !dev_blob || !out) return fail(MPPO_EINVAL, "mppo_model_open: null argument");
-  if (nbytes < 4 * (size_t)kBlobHeaderWords || (nbytes & 3)) return fail(MPPO_EMODEL, "model blob too small or not word-sized (%zu bytes)", nbytes);
-  if ((reinterpret_cast<uintptr_t>(dev_blob) & 15) != 0) return fail(MPPO_EINVAL, "device blob must be 16-byte aligned");
-  const uint32_t* w = static_cast<const uint32_t*>(host_blob);
-  const int32_t* wi = static_cast<const int32_t*>(host_blob);
-  const float* wf = static_cast<const float*>(host_blob);
-  if (w[0] != kBlobMagic) return fail(MPPO_EMODEL, "bad model blob magic 0x%08x", w[0]);
-  if (w[1] != kBlobVersion) return fail(MPPO_EMODEL, "unsupported model blob version %u", w[1]);
-  const size_t total = w[2], hull_words = w[35];  // table part + hull section (+ the contact-parameter section: below, once the dims are known)
-  if (wi[37] != 0 && wi[37] != 1) return fail(MPPO_EMODEL, "model blob: header word 37 (per-row contact parameters) is %d, not 0 or 1", wi[37]);
-  if (wi[38] < 0 || wi[38] > kMaxEqRows) return fail(MPPO_EMODEL, "model blob: header word 38 (equality rows) is %d, not in [0, %d]", wi[38], kMaxEqRows);
-  if ((total + hull_words) * 4 > nbytes || (wi[37] == 0 && wi[38] == 0 && (total + hull_words) * 4 != nbytes))
-    return fail(MPPO_EMODEL, "model blob size mismatch: header says %zu + %zu words, got %zu bytes", total, hull_words, nbytes);
-  if (wi[32] != BLOB_ARRAY_COUNT) return fail(MPPO_EMODEL, "model blob has %d arrays, engine expects %d", wi[32], (int)BLOB_ARRAY_COUNT);
-  mppo_model* m = new mppo_model();
-  ModelView& v = m->mv;
-  v.nq = wi[3]; v.nv = wi[4]; v.nu = wi[5]; v.nbody = wi[6]; v.njnt = wi[7]; v.ncon = wi[8]; v.nlimit = wi[9];
-  v.iterations = wi[10]; v.ls_iterations = wi[11]; v.nlevel = wi[12]; v.nroot = wi[13]; v.include_c = wi[14] ? 1 : 0; v.npair = wi[15];
-  v.ncvx = wi[33]; v.ncvxvert = wi[34];
-  // every header dimension inside a bound that keeps the size arithmetic below (and in blob_offsets) far from overflow, BEFORE any of it
-  // is computed (tests/test_blob_fuzz.py under UBSan: a dimension of INT_MAX overflowed `4 * ncon` here)
-  for (int d : {v.nq, v.nv, v.nu, v.nbody, v.njnt, v.ncon, v.nlimit, v.iterations, v.ls_iterations, v.nlevel, v.nroot, v.npair, v.ncvx, v.ncvxvert, wi[36]})
-    if (d < 0 || d > (1 << 16)) { delete m; return fail(MPPO_EMODEL, "model blob: header dimension %d out of range", d); }
-  v.neq = wi[38];
-  v.nefc = v.neq + v.nlimit + 4 * v.ncon;
-  v.cparam = wi[37];
-  const CParamView cpv = cparam_view(v.ncon, v.nlimit, v.ncvx);
-  // the equality section behind it: its element count is its first word (read only once the words before it are known to exist)
-  const size_t eq_at = total + hull_words + (v.cparam ? (size_t)cpv.words : 0);
-  int eq_nel = 0;
-  if (v.neq > 0) {
-    if ((eq_at + 4) * 4 > nbytes) { delete m; return fail(MPPO_EMODEL, "model blob size mismatch: no room for the equality section"); }
-    eq_nel = wi[eq_at];
-    if (eq_nel < 1 || eq_nel > v.neq) { delete m; return fail(MPPO_EMODEL, "model blob: equality section holds %d elements for %d rows", eq_nel, v.neq); }
-    const EqView ev = eq_view(v.neq, eq_nel);
-    if ((eq_at + (size_t)ev.words) * 4 != nbytes)
-      { delete m; return fail(MPPO_EMODEL, "model blob size mismatch: header says %zu + %d words (equality section), got %zu bytes", eq_at, ev.words, nbytes); }
-  }
-  if (v.neq == 0 && v.cparam && (total + hull_words + (size_t)cpv.words) * 4 != nbytes)
-    return fail(MPPO_EMODEL, "model blob size mismatch: header says %zu + %zu + %d words (contact-parameter section), got %zu bytes", total, hull_words, cpv.words, nbytes);
-  v.timestep = wf[16]; v.tolerance = wf[17]; v.ls_tolerance = wf[18]; v.impratio = wf[19]; v.plane_z = wf[20]; v.meaninertia = wf[21];
-  auto bad = [&](const char* what) { delete m; return fail(MPPO_EMODEL, "model blob: %s", what); };
-  if (v.nq < 1 || v.nv < 1 || v.nbody < 2 || v.nbody > 128 || v.nv > 128 || v.nq > 256 || v.nu < 0 || v.nu > v.nv || v.njnt < 1 ||
-      v.ncon < 0 || v.npair < 0 || v.npair > v.ncon || v.nlimit < 0 || v.nroot < 1 || v.nlevel < 1 || v.iterations < 0 || v.ls_iterations < 0 ||
-      v.ncvx < 0 || 4 * v.ncvx > v.ncon - v.npair || v.ncvxvert < 4 * v.ncvx || v.ncvxvert > 64 * 64)
-    return bad("dimension out of the supported range (nbody<=128, nv<=128, nq<=256)");
-  if (!(v.timestep > 0.f) || !(v.meaninertia > 0.f) || !(v.impratio > 0.f)) return bad("non-positive timestep / meaninertia / impratio");
-  const int32_t* dir = wi + kBlobHeaderWords;
-  BlobDims bd{v.nq, v.nv, v.nu, v.nbody, v.njnt, v.ncon, v.nlimit, v.npair, v.nlevel, v.nroot, v.ncvx, v.ncvxvert, 0, 0, 0, 0, 0};
-  const BlobOffsets canon = blob_offsets(bd);
-  const size_t dir_end = kBlobHeaderWords + 2 * (size_t)BLOB_ARRAY_COUNT;
-  if (dir_end > total) return bad("directory past the end");
-  for (int k = 0; k < BLOB_ARRAY_COUNT; ++k) {
-    const long off = dir[2 * k], cnt = dir[2 * k + 1];
-    if (off < (long)dir_end || cnt < 0 || (size_t)(off + cnt) > total || (off & 3)) return bad("array directory entry out of range");
-    if (cnt != blob_array_len(bd, k)) { delete m; return fail(MPPO_EMODEL, "model blob: array %d has %ld entries, expected %d", k, cnt, blob_array_len(bd, k)); }
-    if (off != canon.o[k]) { delete m; return fail(MPPO_EMODEL, "model blob: array %d sits at word %ld, canonical placement is %d", k, off, canon.o[k]); }
-  }
-  auto HI = [&](int k) { return wi + dir[2 * k]; };
-  // index tables are validated here so that the kernel never dereferences out of range
-  auto in_range = [&](int k, long lo, long hi_excl) {
-    const int32_t* p = HI(k);
-    for (long i = 0; i < dir[2 * k + 1]; ++i) if (p[i] < lo || p[i] >= hi_excl) return false;
-    return true;
-  };
-  if (!in_range(BI_body_parent, 0, v.nbody) || !in_range(BI_body_rootid, 0, v.nbody) || !in_range(BI_jnt_bodyid, 1, v.nbody) ||
-      !in_range(BI_jnt_qposadr, 0, v.nq) || !in_range(BI_jnt_dofadr, 0, v.nv) || !in_range(BI_dof_bodyid, 1, v.nbody) ||
-      !in_range(BI_dof_jntid, 0, v.njnt) || !in_range(BI_dof_parentid, -1, v.nv) || !in_range(BI_dof_qposadr, -1, v.nq) ||
-      !in_range(BI_act_dofid, 0, v.nv) || !in_range(BI_act_qposadr, 0, v.nq) || !in_range(BI_con_bodyid, 1, v.nbody) || !in_range(BI_pair_body, 1, v.nbody) ||
-      !in_range(BI_lim_jntid, 0, v.njnt) || !in_range(BI_level_adr, 0, v.nbody) || !in_range(BI_level_body, 1, v.nbody) ||
-      !in_range(BI_root_body, 1, v.nbody) || !in_range(BI_body_jntnum, 0, v.njnt + 1) || !in_range(BI_body_jntadr, -1, v.njnt) ||
-      !in_range(BI_con_cvx, -4, 4 * v.ncvx) || !in_range(BI_cvx_body, 1, v.nbody) || !in_range(BI_cvx_vadr, 0, v.ncvxvert + 1))
-    return bad("index table entry out of range");
-  {
-    const int32_t* va = HI(BI_cvx_vadr);
-    for (int k = 0; k < v.ncvx; ++k) if (va[k + 1] < va[k] + 4 || va[k + 1] - va[k] > 64) return bad("a convex geom needs 4 .. 64 hull vertices");
-    if (v.ncvx > 0 && (va[0] != 0 || va[v.ncvx] != v.ncvxvert)) return bad("cvx_vadr does not cover the vertex table");
-    // cylinders: slots -2, -3, -4 in a row among the ground contacts, a half-axis vector of non-zero length in the first
-    const int32_t* kind = HI(BI_con_cvx);
-    const float* cax = wf + dir[2 * BF_con_axis];
-    int ncyl = 0;
-    for (int c = 0; c < v.ncon; ++c) {
-      if (kind[c] > -2) continue;
-      if (c >= v.ncon - v.npair) return bad("a cylinder slot among the pair contacts");
-      if (kind[c] == -2) {
-        if (c + 2 >= v.ncon - v.npair || kind[c + 1] != -3 || kind[c + 2] != -4) return bad("a cylinder needs three consecutive ground-contact slots");
-        if (!(cax[3 * c] * cax[3 * c] + cax[3 * c + 1] * cax[3 * c + 1] + cax[3 * c + 2] * cax[3 * c + 2] > 0.f)) return bad("a cylinder with a zero half-axis");
-        ++ncyl;
-      } else if (c == 0 || kind[c - 1] != kind[c] + 1) return bad("a cylinder's second / third slot without its first");
-    }
-    if (ncyl != wi[36]) return bad("header ncyl does not match the contact table");
-    v.ncyl = ncyl;
-  }
-  {
-    // the hull section: every index the kernel follows from a pair row to a hull, its faces, their vertex lists and its edges
-    v.hull_words = (int)hull_words;
-    const int32_t* hs = wi + total;
-    HullView hv{};
-    if (hull_words > 0) {
-      if (hull_words < 8 || (hull_words & 3)) return bad("hull section too short");
-      if (hs[0] < 1 || hs[1] < 4 || hs[2] < 4 || hs[3] < 12 || hs[4] < 6 || hs[0] > 64 || hs[1] > 64 * 64 || hs[2] > 128 * 64 || hs[3] > 6 * 128 * 64 || hs[4] > 192 * 64)
-        return bad("hull section: dimension out of range");
-      if (hs[5] < 3 * hs[0] || hs[5] > hs[4]) return bad("hull section: number of edge directions out of range");
-      hv = hull_view(hs[0], hs[1], hs[2], hs[3], hs[4], hs[5]);
-      if ((size_t)hv.words != hull_words) return bad("hull section: length does not follow from its dimensions");
-      {
-        const int32_t* ua = hs + hv.udadr;
-        if (ua[0] != 0 || ua[hv.nhull] != hv.nudir) return bad("hull section: edge-direction ranges do not cover their array");
-        for (int h = 0; h < hv.nhull; ++h) if (ua[h + 1] < ua[h] + 3) return bad("a hull needs at least three edge directions");
-      }
-      const int32_t *va = hs + hv.vadr, *fa = hs + hv.fadr, *ea = hs + hv.eadr, *pa = hs + hv.face_adr, *fi = hs + hv.fidx, *ed = hs + hv.edge;
-      if (va[0] != 0 || fa[0] != 0 || ea[0] != 0 || pa[0] != 0 || va[hv.nhull] != hv.nvert || fa[hv.nhull] != hv.nface || ea[hv.nhull] != hv.nedge || pa[hv.nface] != hv.nfidx)
-        return bad("hull section: address tables do not cover their arrays");
-      for (int h = 0; h < hv.nhull; ++h) {
-        if (va[h + 1] < va[h] + 4 || va[h + 1] - va[h] > 64 || fa[h + 1] < fa[h] + 4 || ea[h + 1] < ea[h] + 6) return bad("a hull needs 4 .. 64 vertices, at least 4 faces and 6 edges");
-        for (int f = fa[h]; f < fa[h + 1]; ++f) {
-          if (pa[f + 1] < pa[f] + 3 || pa[f + 1] - pa[f] > 64) return bad("a hull face needs 3 .. 64 vertices");
-          for (int i = pa[f]; i < pa[f + 1]; ++i) if (fi[i] < va[h] || fi[i] >= va[h + 1]) return bad("hull face vertex out of its hull's range");
-        }
-        for (int e = 2 * ea[h]; e < 2 * ea[h + 1]; ++e) if (ed[e] < va[h] || ed[e] >= va[h + 1]) return bad("hull edge vertex out of its hull's range");
-      }
-    }
-    const float* pg = wf + dir[2 * BF_pair_geom];
-    auto v_pair_body = [&](int k) { const int32_t* pb = HI(BI_pair_body); return ((long long)pb[2 * k] << 32) | (long long)(unsigned)pb[2 * k + 1]; };
-    for (int k = 0; k < v.npair; ++k) {
-      const float* row = pg + 16 * k;
-      const float hid = row[7], slot = row[15];
-      // a hull pair (box / mesh against box / mesh, four slots): geom 1 carries no shape of its own and geom 2's radius word names geom 1's hull
-      const bool hullpair = hid != 0.f && row[14] != 0.f && row[3] == 0.f && row[4] == 0.f && row[5] == 0.f && row[6] == 0.f;
-      if (hid != (float)(int)hid || hid < 0.f || hid > (float)hv.nhull || slot != (float)(int)slot || slot < 0.f || slot > (hullpair ? 3.f : 1.f))
-        return bad("pair row: hull / slot tag out of range");
-      if (hullpair) {
-        const float h1 = row[14];
-        if (h1 != (float)(int)h1 || h1 < 1.f || h1 > (float)hv.nhull || h1 == hid) return bad("pair row: a hull pair's first hull out of range");
-        if (slot == 0.f && k + 3 >= v.npair) return bad("pair row: a hull pair needs four consecutive slots");
-        // (the manifold's candidates are kept four to a lane: faces of at most 16 vertices on either side)
-        const int32_t *fa = wi + total + hv.fadr, *pa = wi + total + hv.face_adr;
-        for (int hh : {(int)h1 - 1, (int)hid - 1})
-          for (int f = fa[hh]; f < fa[hh + 1]; ++f) if (pa[f + 1] - pa[f] > 16) return bad("a hull in a hull pair has a face of more than 16 vertices");
-      }
-      if (slot >= 1.f && (hid == 0.f || k == 0 || pg[16 * (k - 1) + 7] != hid || pg[16 * (k - 1) + 15] != slot - 1.f || pg[16 * (k - 1) + 14] != row[14] ||
-                          v_pair_body(k) != v_pair_body(k - 1)))
-        return bad("pair row: a later slot must follow its pair's previous one");
-    }
-  }
-  {
-    const int32_t *jt = HI(BI_jnt_type), *qa = HI(BI_jnt_qposadr), *da = HI(BI_jnt_dofadr), *jn = HI(BI_body_jntnum), *ja = HI(BI_body_jntadr),
-                  *par = HI(BI_body_parent), *dp = HI(BI_dof_parentid), *la = HI(BI_level_adr);
-    const int32_t *dj = HI(BI_dof_jntid), *jb = HI(BI_jnt_bodyid), *jl = HI(BI_jnt_limited), *lj = HI(BI_lim_jntid);
-    const float* jr = wf + dir[2 * BF_jnt_range];
-    v.nball = 0;
-    for (int j = 0; j < v.njnt; ++j) {
-      if (jt[j] != JNT_FREE && jt[j] != JNT_BALL && jt[j] != JNT_HINGE && jt[j] != JNT_SLIDE) return bad("unsupported joint type");
-      if (jt[j] == JNT_FREE && (qa[j] + 7 > v.nq || da[j] + 6 > v.nv)) return bad("free joint address out of range");
-      if (jt[j] == JNT_BALL) {
-        // a quaternion and three dofs of its own, alone in its body (its axes are the body's), a limit on the rotation angle: range = (0, max)
-        if (qa[j] + 4 > v.nq || da[j] + 3 > v.nv) return bad("ball joint address out of range");
-        for (int k = 0; k < 3; ++k) if (dj[da[j] + k] != j) return bad("ball joint: its three dofs must name it in dof_jntid");
-        if (jn[jb[j]] != 1 || ja[jb[j]] != j) return bad("a ball joint must be the only joint of its body");
-        bool limited = jl[j] != 0;
-        for (int r = 0; r < v.nlimit; ++r) limited = limited || lj[r] == j;
-        if (limited && !(jr[2 * j] == 0.f && jr[2 * j + 1] > 0.f)) return bad("a limited ball joint needs range = (0, max) with max > 0");
-        ++v.nball;
-      }
-    }
-    // (... and nobody else's: the kernel takes a ball dof's place among the three from its distance to the joint's first dof)
-    for (int d = 0; d < v.nv; ++d) if (jt[dj[d]] == JNT_BALL && (d < da[dj[d]] || d >= da[dj[d]] + 3)) return bad("ball joint: a dof outside its three names it in dof_jntid");
-    for (int b = 1; b < v.nbody; ++b) {
-      if (par[b] >= b) return bad("bodies are not topologically ordered");
-      if (jn[b] > 0 && (ja[b] < 0 || ja[b] + jn[b] > v.njnt)) return bad("body joint range out of bounds");
-    }
-    for (int d = 0; d < v.nv; ++d) if (dp[d] >= d) return bad("dof_parentid must point to an earlier dof");
-    for (int l = 0; l < v.nlevel; ++l) if (la[l + 1] < la[l] || la[l + 1] > v.nbody - 1) return bad("level_adr not monotone");
-    if (HI(BI_root_body)[0] != 1) return bad("body 1 must be the first tree root");
-  }
-  if (v.cparam) {
-    // the contact-parameter section: condim 1 or 3, finite values, solimp inside MuJoCo's clamps (dmin / dmax / mid in [mjMINIMP, mjMAXIMP], width > 0,
-    // power >= 1), a positive time constant / damping ratio in standard form, margins finite
-    const float* cf = wf + total + hull_words;
-    const int32_t* ci = wi + total + hull_words;
-    auto fin = [](float x) { return x == x && x - x == 0.f; };
-    auto good_ref = [&](const float* r) { return fin(r[0]) && fin(r[1]) && (r[0] <= 0.f || r[1] > 0.f) && (r[0] > 0.f || r[1] <= 0.f); };
-    auto good_imp = [&](const float* i) {
-      for (int k = 0; k < 5; ++k) if (!fin(i[k])) return false;
-      return i[0] >= MJ_MINIMP && i[0] <= MJ_MAXIMP && i[1] >= MJ_MINIMP && i[1] <= MJ_MAXIMP && i[2] > 0.f && i[3] >= MJ_MINIMP && i[3] <= MJ_MAXIMP && i[4] >= 1.f;
-    };
-    for (int c = 0; c < v.ncon; ++c) {
-      if (ci[cpv.con_condim + c] != 1 && ci[cpv.con_condim + c] != 3) return bad("contact-parameter section: condim must be 1 or 3");
-      if (!good_ref(cf + cpv.con_solref + 2 * c) || !good_imp(cf + cpv.con_solimp + 5 * c) || !fin(cf[cpv.con_margin + c]))
-        return bad("contact-parameter section: a contact slot's solref / solimp / margin is not finite or outside MuJoCo's ranges");
-    }
-    for (int r = 0; r < v.nlimit; ++r)
-      if (!good_ref(cf + cpv.lim_solref + 2 * r) || !good_imp(cf + cpv.lim_solimp + 5 * r) || !fin(cf[cpv.lim_margin + r]))
-        return bad("contact-parameter section: a joint limit's solref / solimp / margin is not finite or outside MuJoCo's ranges");
-    for (int k = 0; k < v.ncvx; ++k) if (!fin(cf[cpv.cvx_margin + k])) return bad("contact-parameter section: a convex geom's margin is not finite");
-  }
-  v.blob = static_cast<const int32_t*>(dev_blob);
-  v.blob_words = (int)((total + 3) & ~(size_t)3);
-  if ((size_t)v.blob_words != total) return bad("blob length must be a multiple of 4 words");
-  for (int k = 0; k < BLOB_ARRAY_COUNT; ++k) v.o[k] = dir[2 * k];
-  v.obs_dim = v.nq + 2 * v.nv + (v.include_c ? 16 * (v.nbody - 1) : 0);  // env.py:246-259
-  v.obs_pad = (v.obs_dim + 3) & ~3;
-  v.rec_dim = v.obs_pad + ((v.nv + 2 + 3) & ~3);
-  if (v.neq > 0) {
-    // the equality section: every element's kind, bodies / joints and rows, and finite parameters in MuJoCo's ranges - the kernel follows
-    // these ids into the tables without another check
-    const int32_t* es = wi + eq_at;
-    const float* ef = wf + eq_at;
-    const EqView ev = eq_view(v.neq, eq_nel);
-    auto fin = [](float x) { return x == x && x - x == 0.f; };
-    const int32_t* jtype = HI(BI_jnt_type);
-    int next_row = 0;
-    for (int e = 0; e < eq_nel; ++e) {
-      const int32_t* ri = es + ev.rec + kEqRecordWords * e;
-      const float* rf = ef + ev.rec + kEqRecordWords * e;
-      const int dim = ri[0] == EQ_CONNECT ? 3 : ri[0] == EQ_JOINT ? 1 : 0;
-      if (dim == 0) return bad("equality section: an element that is neither connect nor joint");
-      if (ri[3] != next_row || ri[3] + dim > v.neq) return bad("equality section: an element's rows are not the next ones");
-      for (int k = 0; k < dim; ++k) if (es[ev.row + ri[3] + k] != e) return bad("equality section: a row that is not its element's");
-      next_row += dim;
-      if (ri[0] == EQ_CONNECT) {
-        if (ri[1] < 1 || ri[1] >= v.nbody || ri[2] < 0 || ri[2] >= v.nbody || ri[1] == ri[2]) return bad("equality section: a connect's bodies out of range");
-      } else {
-        if (ri[1] < 0 || ri[1] >= v.njnt || ri[2] < -1 || ri[2] >= v.njnt || ri[1] == ri[2]) return bad("equality section: a joint equality's joints out of range");
-        if (jtype[ri[1]] == JNT_FREE || (ri[2] >= 0 && jtype[ri[2]] == JNT_FREE)) return bad("equality section: a joint equality on a free joint");
-        if (jtype[ri[1]] == JNT_BALL || (ri[2] >= 0 && jtype[ri[2]] == JNT_BALL)) return bad("equality section: a joint equality on a ball joint");
-      }
-      for (int k = 4; k < 23; ++k) if (!fin(rf[k])) return bad("equality section: a value is not finite");
-      const float* sr = rf + 15;
-      const float* si = rf + 17;
-      if ((sr[0] <= 0.f) != (sr[1] <= 0.f) || !(si[0] >= MJ_MINIMP && si[0] <= MJ_MAXIMP && si[1] >= MJ_MINIMP && si[1] <= MJ_MAXIMP && si[2] > 0.f &&
-                                                si[3] >= MJ_MINIMP && si[3] <= MJ_MAXIMP && si[4] >= 1.f))
-        return bad("equality section: solref / solimp outside MuJoCo's ranges");
-      if (!(rf[22] > 0.f)) return bad("equality section: invweight must be positive");
-    }
-    if (next_row != v.neq) return bad("equality section: the elements' rows do not add up to header word 38");
-  }
-  bd.hull = v.hull_words > 0 ? 1 : 0; bd.ncyl = v.ncyl; bd.cparam = v.cparam; bd.neq = v.neq; bd.nball = v.nball;
-  m->spec = find_spec(bd);
-  m->canon_words = canon.words;
-  if (int32_t rc = mppo::finalize_layout(m); rc != MPPO_OK) { delete m; return rc; }
-  // every specialised instantiation proves itself on the device it is about to run on (a few milliseconds): the ones a build adds (MPPO_SPECIALIZE) always,
-  // the default ones too on hardware - the test suite holds them bit-equal on the builder's toolchain, a user's compiler is another one (on the emulator the
-  // suite itself is the check)
-#ifdef MPPO_EMU
-  const bool check = m->spec >= 0 && kSpecs[m->spec].extra;
-#else
-  const bool check = m->spec >= 0;
-#endif
-  if (check) {
-    if (int32_t rc = mppo::spec_self_check(m); rc != MPPO_OK) { if (m->scratch) (void)hipFree(m->scratch); delete m; return rc; }
-  }
-  *out = m;
-  return MPPO_OK;
-}
 
 #ifdef MPPO_PHYS_TIMERS
 extern "C" int32_t mppo_debug_phys_timers(unsigned long long* out40) {
@@ -2760,210 +2297,4 @@ extern "C" int32_t mppo_debug_phys_timers(unsigned long long* out40) {
 }
 #endif
 
-extern "C" int32_t mppo_model_close(mppo_model_t* m) {
-  if (m && m->scratch) (void)hipFree(m->scratch);
-  if (m && m->jit_module) (void)hipModuleUnload(m->jit_module);
-  delete m;
-  return MPPO_OK;
-}
-
-// The tag a code object of this file carries (`mppo_env_kernel_tag`): the sizes of the three kernel-argument structs and the blob version -
-// what has to agree between the library and a code object compiled apart from it for a launch to mean anything.
-namespace mppo {
-constexpr unsigned kEnvKernelTag = (unsigned)sizeof(ModelView) * 2654435761u ^ (unsigned)sizeof(EnvArgs) * 40503u ^ (unsigned)sizeof(PhysLds) * 2246822519u ^ kBlobVersion * 3266489917u ^
-                                   (unsigned)kEnvsPerWave;
-}
-extern "C" __device__ __attribute__((used)) const unsigned mppo_env_kernel_tag = mppo::kEnvKernelTag;
-
-extern "C" int32_t mppo_model_attach_kernel(mppo_model_t* m, const void* image, size_t nbytes, const char* const* names, int32_t regchol_max_nv, int32_t* used) {
-  using namespace mppo;
-  if (!m || !image || !nbytes || !names || !names[0] || !names[1] || !names[2] || !used) return fail(MPPO_EINVAL, "mppo_model_attach_kernel: null argument");
-  *used = 0;
-  if (m->jit) return fail(MPPO_EINVAL, "mppo_model_attach_kernel: a code object is attached to this model already");
-  if (regchol_max_nv < 0 || regchol_max_nv > 64) return fail(MPPO_EINVAL, "mppo_model_attach_kernel: regchol_max_nv %d", regchol_max_nv);
-  if (m->spec >= 0) return MPPO_OK;  // (the library holds this robot's kernel itself)
-  {
-    const char* e = getenv("MPPO_ENV_GENERIC");
-    if ((e && e[0] == '1') || env_spill_override() >= 0) return MPPO_OK;  // (the switches that force the run-time-sized kernel)
-  }
-  // the kernels' names spell the dimensions they were compiled for: StaticModel<nq, nv, nu, nbody, njnt, ncon, nlimit, npair, nlevel, nroot, ncvx, ncvxvert, hull, ncyl, neq, nball, cparam>, MODE
-  const ModelView& v = m->mv;
-  const int dims[17] = {v.nq, v.nv, v.nu, v.nbody, v.njnt, v.ncon, v.nlimit, v.npair, v.nlevel, v.nroot, v.ncvx, v.ncvxvert, v.hull_words > 0 ? 1 : 0, v.ncyl, v.neq, v.nball, v.cparam};
-  char want[256];
-  int o = snprintf(want, sizeof want, "StaticModelI");
-  for (int d : dims) o += snprintf(want + o, sizeof want - o, "Li%dE", d);
-  for (int k = 0; k < 3; ++k) {
-    char mode[320];
-    snprintf(mode, sizeof mode, "%sEELi%dEEEv", want, k);
-    if (!strstr(names[k], "env_kernel") || !strstr(names[k], mode))
-      return fail(MPPO_EINVAL, "mppo_model_attach_kernel: kernel %d is named %s - not the environment kernel of this robot's dimensions and mode (%s)", k, names[k], mode);
-  }
-  OnDeviceOf where(m->mv.blob);  // (a module belongs to the device it was loaded on)
-  MPPO_CHECK_HIP(where.err);
-  m->jit_image.assign(static_cast<const char*>(image), static_cast<const char*>(image) + nbytes);
-  hipModule_t mod = nullptr;
-  hipError_t he = hipModuleLoadData(&mod, m->jit_image.data());
-  if (he != hipSuccess) { m->jit_image.clear(); return fail(MPPO_EHIP, "mppo_model_attach_kernel: the code object does not load (%s)", hipGetErrorString(he)); }
-  auto drop = [&](int32_t rc) { (void)hipModuleUnload(mod); m->jit_module = nullptr; m->jit = false; m->jit_image.clear(); m->jit_image.shrink_to_fit(); return rc; };
-  hipDeviceptr_t tag_ptr = nullptr;
-  size_t tag_bytes = 0;
-  unsigned tag = 0;
-  he = hipModuleGetGlobal(&tag_ptr, &tag_bytes, mod, "mppo_env_kernel_tag");
-  if (he == hipSuccess && tag_bytes == sizeof tag) he = hipMemcpy(&tag, tag_ptr, sizeof tag, hipMemcpyDeviceToHost);
-  if (he != hipSuccess || tag_bytes != sizeof tag) return drop(fail(MPPO_EINVAL, "mppo_model_attach_kernel: the code object carries no mppo_env_kernel_tag (%s)", hipGetErrorString(he)));
-  if (tag != kEnvKernelTag) return drop(fail(MPPO_EINVAL, "mppo_model_attach_kernel: the code object was compiled from other kernel sources than this library (tag %08x, library %08x)", tag, kEnvKernelTag));
-  for (int k = 0; k < 3; ++k) {
-    he = hipModuleGetFunction(&m->jit_fn[k], mod, names[k]);
-    if (he != hipSuccess) return drop(fail(MPPO_EINVAL, "mppo_model_attach_kernel: no kernel %s in the code object (%s)", names[k], hipGetErrorString(he)));
-  }
-  // the layout the specialised kernel computed for itself at compile time; then the same proof a build-time instantiation gives
-  m->jit_module = mod;
-  m->jit = true;
-  m->jit_regchol = regchol_max_nv;
-  if (m->scratch) { MPPO_CHECK_HIP(hipDeviceSynchronize()); (void)hipFree(m->scratch); m->scratch = nullptr; m->scratch_bytes = 0; }
-  int32_t rc = finalize_layout(m);
-  if (rc == MPPO_OK && m->jit) rc = spec_self_check(m);
-  if (rc != MPPO_OK) { m->jit = false; (void)finalize_layout(m); return drop(rc); }
-  if (!m->jit) return drop(MPPO_OK);  // (too large for four environments per wave, or it failed the check: the run-time-sized kernel stays)
-  *used = 1;
-  return MPPO_OK;
-}
-
-extern "C" int32_t mppo_model_scratch_bytes(const mppo_model_t* m, int32_t N, size_t* out) {
-  if (!m || !out || N < 1) return mppo::fail(MPPO_EINVAL, "mppo_model_scratch_bytes: null argument or N < 1");
-  *out = mppo::model_scratch_bytes(m, N);
-  return MPPO_OK;
-}
-
-extern "C" int32_t mppo_model_get_dims(const mppo_model_t* m, mppo_model_dims_t* o) {
-  if (!m || !o) return mppo::fail(MPPO_EINVAL, "mppo_model_get_dims: null argument");
-  const mppo::ModelView& v = m->mv;
-  o->nq = v.nq; o->nv = v.nv; o->nu = v.nu; o->nbody = v.nbody; o->njnt = v.njnt; o->ncon = v.ncon; o->nlimit = v.nlimit; o->nefc = v.nefc;
-  o->obs_dim = v.obs_dim; o->obs_pad = v.obs_pad; o->rec_dim = v.rec_dim; o->lds_bytes = m->lds_bytes; o->timestep = v.timestep;
-  return MPPO_OK;
-}
-
-namespace mppo {
-// `ws`: the caller's region for the out-of-LDS matrices (the engine's arena), or null: the handle's own allocation, grown on demand
-static int32_t launch_env(const mppo_model_t* m, EnvArgs a, hipStream_t stream, float* ws, size_t ws_bytes) {
-  const int blocks = cdiv(a.N, m->mv.epw * m->waves);
-  const size_t need = model_scratch_bytes(m, a.N);
-  if (need > 0) {
-    if (ws) {
-      if (ws_bytes < need) return fail(MPPO_EINVAL, "environment kernel: the caller's scratch region holds %zu bytes, %d environments need %zu", ws_bytes, a.N, need);
-      a.scratch = ws;
-    } else {
-      if (m->scratch_bytes < need) {
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        if (stream && hipStreamIsCapturing(stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
-          return fail(MPPO_EINVAL, "environment kernel: this robot keeps %zu bytes of matrices in global memory for %d environments and the handle's allocation would have to grow inside a stream capture: launch once outside the capture first", need, a.N);
-        if (m->scratch) { MPPO_CHECK_HIP(hipDeviceSynchronize()); (void)hipFree(m->scratch); m->scratch = nullptr; m->scratch_bytes = 0; }
-        MPPO_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&m->scratch), need));
-        m->scratch_bytes = need;
-      }
-      a.scratch = m->scratch;
-    }
-  }
-  if (m->jit) {
-    ModelView mv = m->mv;
-    PhysLds lds = m->lds;
-    void* params[] = {&mv, &a, &lds};
-    MPPO_CHECK_HIP(hipModuleLaunchKernel(m->jit_fn[a.mode], blocks, 1, 1, 64 * m->waves, 1, 1, m->lds_bytes, stream, params, nullptr));
-    return MPPO_OK;
-  }
-#ifdef MPPO_JIT_ONLY  // (the device-side compile of minppo_amd/jit.py: one robot's instantiation and nothing else)
-  return kSpecs[0].launch(m->mv, a, m->lds, m->lds_bytes, blocks, m->waves, stream);
-#else
-  return (m->spec >= 0 ? kSpecs[m->spec].launch : m->mv.nball > 0 ? &launch_env_t<RuntimeBallModel> : &launch_env_t<RuntimeModel>)(m->mv, a, m->lds, m->lds_bytes, blocks, m->waves, stream);
-#endif
-}
-// the engine's entry: mppo_env_step with the out-of-LDS matrices in a region of the engine's arena (hipGraph capture: nothing is allocated)
-int32_t env_step_ws(const mppo_model_t* m, int32_t N, int32_t n_frames, const mppo_reward_cfg_t* rc, float* state, const float* reset_rec, const float* action,
-                    int32_t act_ld, float* obs, int32_t obs_ld, float* reward, uint8_t* done, const mppo_env_metrics_t* metrics, float* ws, size_t ws_bytes, hipStream_t stream) {
-  EnvArgs a{};
-  a.N = N; a.mode = 1; a.n_frames = n_frames; a.state = state; a.reset_in = reset_rec; a.action = action; a.act_ld = act_ld;
-  a.obs = obs; a.obs_ld = obs_ld; a.reward = reward; a.done = done; a.rc = *rc;
-  if (metrics) a.met = *metrics;
-  return launch_env(m, a, stream, ws, ws_bytes);
-}
-int32_t env_reset_ws(const mppo_model_t* m, int32_t N, float* state, float* reset_rec, float* obs, int32_t obs_ld, const mppo_env_metrics_t* metrics, float* ws, size_t ws_bytes,
-                     hipStream_t stream) {
-  EnvArgs a{};
-  a.N = N; a.mode = 0; a.n_frames = 1; a.state = state; a.reset_out = reset_rec; a.obs = obs; a.obs_ld = obs_ld;
-  if (metrics) a.met = *metrics;
-  return launch_env(m, a, stream, ws, ws_bytes);
-}
-// the reset from randomised states over the environments `mask` names (null: all of them): the reset kernel with its noise fields set and nothing
-// but the state rows and the observation rows to write - reward, done and the metrics are the step's, the reset record stays the noise-free one
-int32_t env_reinit_ws(const mppo_model_t* m, int32_t N, float* state, float* obs, int32_t obs_ld, const uint8_t* mask, float scale, int32_t rng_impl, uint64_t seed,
-                      int32_t rank, const uint32_t* key2, const int32_t* counter, int32_t counter_mul, int32_t counter_add, float* ws, size_t ws_bytes, hipStream_t stream) {
-  // (the Philox stream numbers an environment's blocks of four elements in the 16 bits of the stream id below the rank)
-  MPPO_REQUIRE(m->mv.nq + m->mv.nv <= 4 * 65536, "reset noise: %d noise elements per environment", m->mv.nq + m->mv.nv);
-  EnvArgs a{};
-  a.N = N; a.mode = 0; a.n_frames = 1; a.state = state; a.obs = obs; a.obs_ld = obs_ld;
-  a.mask = mask; a.noise_scale = scale; a.noise_impl = rng_impl; a.noise_key = key2; a.noise_seed = seed;
-  a.noise_stream = kStreamReset + ((unsigned long long)rank << 16);
-  a.noise_ctr = counter; a.noise_ctr_mul = counter_mul; a.noise_ctr_add = counter_add;
-  return launch_env(m, a, stream, ws, ws_bytes);
-}
-}  // namespace mppo
-
-extern "C" int32_t mppo_model_is_specialized(const mppo_model_t* m, int32_t* out) {
-  if (!m || !out) return mppo::fail(MPPO_EINVAL, "mppo_model_is_specialized: null argument");
-  *out = m->spec >= 0 ? 1 : m->jit ? 2 : 0;
-  return MPPO_OK;
-}
-
-extern "C" int32_t mppo_env_reset(const mppo_model_t* m, int32_t N, float* state, float* reset_rec, float* obs, int32_t obs_ld,
-                                  float* reward, uint8_t* done, const mppo_env_metrics_t* metrics, void* stream) {
-  using namespace mppo;
-  MPPO_REQUIRE(m && state && reset_rec, "mppo_env_reset: null model / state / reset_rec");
-  MPPO_REQUIRE(N >= 1, "mppo_env_reset: N = %d", N);
-  MPPO_REQUIRE(m->mv.nq >= 3, "mppo_env_reset: the environment reads qpos[2] as the height (env.py:239); nq = %d", m->mv.nq);
-  MPPO_REQUIRE(!obs || obs_ld >= m->mv.obs_pad, "mppo_env_reset: obs_ld %d < padded observation width %d", obs_ld, m->mv.obs_pad);
-  EnvArgs a{};
-  a.N = N; a.mode = 0; a.n_frames = 1; a.state = state; a.reset_out = reset_rec; a.obs = obs; a.obs_ld = obs_ld; a.reward = reward; a.done = done;
-  if (metrics) a.met = *metrics;
-  return launch_env(m, a, static_cast<hipStream_t>(stream));
-}
-
-extern "C" int32_t mppo_env_reinit(const mppo_model_t* m, int32_t N, float* state, float* obs, int32_t obs_ld, const uint8_t* mask, float scale, int32_t rng_impl,
-                                   uint64_t seed, int32_t rank, const uint32_t* key2, const int32_t* counter, int32_t counter_offset, void* stream) {
-  using namespace mppo;
-  MPPO_REQUIRE(m && state, "mppo_env_reinit: null model / state");
-  MPPO_REQUIRE(N >= 1, "mppo_env_reinit: N = %d", N);
-  MPPO_REQUIRE(m->mv.nq >= 3, "mppo_env_reinit: the environment reads qpos[2] as the height (env.py:239); nq = %d", m->mv.nq);
-  MPPO_REQUIRE(!obs || obs_ld >= m->mv.obs_pad, "mppo_env_reinit: obs_ld %d < padded observation width %d", obs_ld, m->mv.obs_pad);
-  MPPO_REQUIRE(scale >= 0.f, "mppo_env_reinit: scale %g is negative (or not a number)", (double)scale);
-  MPPO_REQUIRE(rng_impl >= 0 && rng_impl <= 2, "mppo_env_reinit: rng_impl %d (0 philox, 1 threefry, 2 threefry from per-environment keys)", rng_impl);
-  MPPO_REQUIRE(rng_impl == 0 || scale == 0.f || key2, "mppo_env_reinit: the threefry stream needs a key (two words in device memory)");
-  MPPO_REQUIRE(rank >= 0 && rank < 256, "mppo_env_reinit: rank %d (0 .. 255)", rank);
-  return env_reinit_ws(m, N, state, obs, obs_ld, mask, scale, rng_impl, seed, rank, key2, counter, 1, counter_offset, nullptr, 0, static_cast<hipStream_t>(stream));
-}
-
-extern "C" int32_t mppo_env_step(const mppo_model_t* m, int32_t N, int32_t n_frames, const mppo_reward_cfg_t* rc, float* state,
-                                 const float* reset_rec, const float* action, int32_t act_ld, float* obs, int32_t obs_ld, float* reward,
-                                 uint8_t* done, const mppo_env_metrics_t* metrics, void* stream) {
-  using namespace mppo;
-  MPPO_REQUIRE(m && rc && state && reset_rec && action && obs && reward && done, "mppo_env_step: null argument");
-  MPPO_REQUIRE(N >= 1 && n_frames >= 1, "mppo_env_step: N = %d, n_frames = %d", N, n_frames);
-  MPPO_REQUIRE(m->mv.nq >= 3, "mppo_env_step: the environment reads qpos[2] as the height (env.py:239); nq = %d", m->mv.nq);
-  MPPO_REQUIRE(act_ld >= m->mv.nu, "mppo_env_step: act_ld %d < nu %d", act_ld, m->mv.nu);
-  MPPO_REQUIRE(obs_ld >= m->mv.obs_pad, "mppo_env_step: obs_ld %d < padded observation width %d", obs_ld, m->mv.obs_pad);
-  EnvArgs a{};
-  a.N = N; a.mode = 1; a.n_frames = n_frames; a.state = state; a.reset_in = reset_rec; a.action = action; a.act_ld = act_ld;
-  a.obs = obs; a.obs_ld = obs_ld; a.reward = reward; a.done = done; a.rc = *rc;
-  if (metrics) a.met = *metrics;
-  return launch_env(m, a, static_cast<hipStream_t>(stream));
-}
-
-extern "C" int32_t mppo_physics_forward(const mppo_model_t* m, int32_t N, const float* qpos, const float* qvel, const float* ctrl,
-                                        const float* qacc_warmstart, const mppo_forward_probe_t* out, void* stream) {
-  using namespace mppo;
-  MPPO_REQUIRE(m && qpos && qvel && qacc_warmstart && out, "mppo_physics_forward: null argument");
-  MPPO_REQUIRE(ctrl || m->mv.nu == 0, "mppo_physics_forward: ctrl is null but the model has actuators");
-  MPPO_REQUIRE(N >= 1, "mppo_physics_forward: N = %d", N);
-  EnvArgs a{};
-  a.N = N; a.mode = 2; a.n_frames = 1; a.p_qpos = qpos; a.p_qvel = qvel; a.p_ctrl = ctrl; a.p_warm = qacc_warmstart; a.probe = *out;
-  return launch_env(m, a, static_cast<hipStream_t>(stream));
-}
+extern "C" __device__ __attribute__((used)) const unsigned mppo_env_kernel_tag = mppo::kEnvKernelTag;  // the tag a code object of this file carries (env_kernel.h)

@@ -4,7 +4,10 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cstddef>
 #include <cstdint>
+#include <cstring>
+#include <type_traits>
 
 namespace mppo {
 
@@ -65,6 +68,15 @@ struct BlobDims { int nq, nv, nu, nbody, njnt, ncon, nlimit, npair, nlevel, nroo
                   int hull, ncyl, neq, nball, cparam; };  // (hull: 1 if the model has a hull section; ncyl: its cylinders; neq: equality rows; cparam: per-row contact
                                                           // parameters; nball: ball joints - they select code and size the LDS rows, not the table part)
 struct BlobOffsets { int o[BLOB_ARRAY_COUNT]; int words; };
+static_assert(std::has_unique_object_representations_v<BlobDims>, "ints only, no padding: two BlobDims are equal when their bytes are");
+inline bool operator==(const BlobDims& a, const BlobDims& b) { return memcmp(&a, &b, sizeof a) == 0; }
+__host__ __device__ constexpr inline int nefc_of(const BlobDims& d) { return d.neq + d.nlimit + 4 * d.ncon; }  // every constraint row: equalities, joint limits, contact pyramids
+inline BlobDims blob_dims_of(const ModelView& v) {  // (the one place that reads the dims from a filled view)
+  return BlobDims{v.nq, v.nv, v.nu, v.nbody, v.njnt, v.ncon, v.nlimit, v.npair, v.nlevel, v.nroot, v.ncvx, v.ncvxvert, v.hull_words > 0 ? 1 : 0, v.ncyl, v.neq, v.nball, v.cparam};
+}
+// The blob's validator (model_blob.hip: host arithmetic only, no HIP call): fills `view` from the `nbytes` bytes at `host_blob` - all of it but blob, epw and whatever
+// else needs the device (mppo_model_open, env_model.hip) -, the dims and the table part's canonical length.  MPPO_OK, or MPPO_EMODEL and the reason as the error text.
+int32_t parse_model_blob(const void* host_blob, size_t nbytes, ModelView* view, BlobDims* dims, int* canon_words);
 __host__ __device__ constexpr inline int blob_array_len(const BlobDims& d, int k) {
   switch (k) {
     case BI_body_parent: case BI_body_rootid: case BI_body_depth: case BI_body_jntadr: case BI_body_jntnum: case BI_body_dofadr: case BI_body_dofnum:
@@ -217,13 +229,11 @@ constexpr int kSpillJ = 1, kSpillM = 2;
 
 __host__ __device__ constexpr inline int imax_(int a, int b) { return a > b ? a : b; }
 
-// (nefc: every constraint row, the neq equality rows included)
-__host__ __device__ constexpr inline PhysLds make_phys_lds(int nq, int nv, int nu, int nbody, int njnt, int ncon, int nefc, int nroot, int ncvx = 0, bool li_regs = false, int spill = 0,
-                                                           int neq = 0, int nball = 0) {
+__host__ __device__ constexpr inline PhysLds make_phys_lds(const BlobDims& d, bool li_regs, int spill) {
+  const int nq = d.nq, nv = d.nv, nbody = d.nbody, njnt = d.njnt, ncon = d.ncon, nefc = nefc_of(d), nroot = d.nroot, ncvx = d.ncvx, neq = d.neq, nball = d.nball;
   PhysLds p{};
   int o = 0;
   auto take = [&](int n) { int r = o; o += (n + 3) & ~3; return r; };
-  (void)nu;  // (at most nv actuators: mppo_model_open)
   p.qpos = take(nq); p.qvel = take(nv); p.warm = take(nv);
   p.rootcom = take(3 * (nroot > 0 ? nroot : 1));
   p.ldm = nv + 1;  // odd row stride: a column read by 16 lanes hits 16 different banks
@@ -289,13 +299,12 @@ __host__ __device__ constexpr inline int waves_per_cu(long long blob_words, long
   }
   return best;
 }
-__host__ __device__ constexpr inline int spill_for(int nq, int nv, int nu, int nbody, int njnt, int ncon, int nefc, int nroot, int ncvx, bool li_regs, int blob_words, int neq = 0,
-                                                       int nball = 0) {
+__host__ __device__ constexpr inline int spill_for(const BlobDims& d, bool li_regs, int blob_words) {
   int best = 0, best_w = -1;
   const int opts[3] = {0, kSpillJ, kSpillJ | kSpillM};
   for (int t = 0; t < 3; ++t) {
     const int s = opts[t];
-    const int w = waves_per_cu(blob_words, make_phys_lds(nq, nv, nu, nbody, njnt, ncon, nefc, nroot, ncvx, li_regs, s, neq, nball).total, 4);
+    const int w = waves_per_cu(blob_words, make_phys_lds(d, li_regs, s).total, 4);
     const int wc = w > 4 ? 4 : w;
     if (wc > best_w) { best_w = wc; best = s; }
   }
@@ -303,10 +312,10 @@ __host__ __device__ constexpr inline int spill_for(int nq, int nv, int nu, int n
   // matrices stay in LDS while ONE environment with them fits; beyond that (a robot of about 100 dofs and more) the smallest set that leaves
   // LDS so that two environments per wave fit, else one.  A 128-dof robot with 123 contact slots and 614 constraint rows: 66 KB of M and
   // 254 KB of contact Jacobian per environment in LDS; both outside, two triangular factors of 33 KB each remain (tests/test_many_dofs.py).
-  if (best_w == 0 && waves_per_cu(blob_words, make_phys_lds(nq, nv, nu, nbody, njnt, ncon, nefc, nroot, ncvx, li_regs, 0, neq, nball).total, 1) == 0) {
+  if (best_w == 0 && waves_per_cu(blob_words, make_phys_lds(d, li_regs, 0).total, 1) == 0) {
     for (int epw = 2; epw >= 1; epw /= 2)
       for (int t = 1; t < 3; ++t)
-        if (waves_per_cu(blob_words, make_phys_lds(nq, nv, nu, nbody, njnt, ncon, nefc, nroot, ncvx, li_regs, opts[t], neq, nball).total, epw) > 0) return opts[t];
+        if (waves_per_cu(blob_words, make_phys_lds(d, li_regs, opts[t]).total, epw) > 0) return opts[t];
   }
   return best;
 }

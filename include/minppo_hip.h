@@ -420,6 +420,66 @@ int32_t mppo_engine_graph_active(const mppo_engine_t* e, int32_t* out);
 int32_t mppo_engine_rollout(mppo_engine_t* e, void* stream);
 int32_t mppo_engine_learn(mppo_engine_t* e, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Policy evaluation: K steps of N environments under a trained policy, episode statistics and an
+ * optional joint trajectory, as one call.  The reference has no counterpart (`minppo/infer.py:22-27`
+ * raises NotImplementedError) and no time limit (env.py:238-242 ends an episode on height only): a
+ * policy that stands never finishes an episode, so the result also counts the environments that
+ * never fell (`survivors`) and the returns they have collected so far.
+ *
+ * mppo_evaluate enqueues exactly this sequence on `stream` (launches only; no allocation,
+ * synchronisation or blocking copy - every buffer is a region of `ws`, a large robot's out-of-LDS
+ * matrices included), a composition of the entry points above that gives the same bits when the
+ * caller writes it out:
+ *   1. mppo_env_reset with zeroed metrics
+ *   2. reset_noise_scale > 0: mppo_env_reinit(mask NULL, rng_impl 0, seed, rank 0, counter NULL, counter_offset 0)
+ *   3. for t = 0 .. K - 1:
+ *        noise = deterministic ? zeros (then action == mean) : mppo_normal_fill(seed, stream_id = t, N * A)
+ *        mppo_policy_forward on the current observation; mppo_env_step with n_frames
+ *        reset_noise_scale > 0: mppo_env_reinit(mask = done, the same stream, counter_offset = t + 1)
+ *        mppo_eval_accumulate
+ *   4. mppo_eval_reduce
+ * `params`: the flat parameter vector of `net`.  `ws`: 256-byte aligned, >= mppo_eval_ws_bytes (0 for
+ * arguments mppo_evaluate refuses).  `result`: DEVICE memory, 8-byte aligned, valid once the stream
+ * has run; the same inputs give the same bytes on every run (fixed reduction order, no atomics).
+ * `traj` (device; may be NULL when record_envs = 0): [K + 1][R][W] floats, W = nq + nv + A + 2, of
+ * environments 0 .. R - 1: frame 0 = state[n, 0 : nq + nv] after the reset (and the initial reinit), the
+ * other columns zero; frame t + 1 = the state after step t (for an environment whose episode ended:
+ * its restart state) | that step's action [A] | reward | done (0 or 1).
+ * ---------------------------------------------------------------------------------------- */
+typedef struct mppo_eval_cfg {
+  int32_t N, K, n_frames, deterministic, record_envs /* R, 0 .. N */;
+  float reset_noise_scale;
+  uint64_t seed;
+  mppo_reward_cfg_t reward;
+} mppo_eval_cfg_t;
+typedef struct mppo_eval_result {  /* 8-byte fields in a fixed order */
+  int64_t episodes;   /* episodes that ended within the K steps                                        */
+  int64_t len_sum, len_min, len_max;   /* their lengths in env steps (0 when episodes = 0)             */
+  int64_t survivors;  /* environments none of whose episodes ended                                     */
+  int64_t steps;      /* K * N                                                                         */
+  double ret_sum, ret_sumsq, ret_min, ret_max;   /* the ended episodes' returns; +inf / -inf when episodes = 0 */
+  double survivor_ret_sum;   /* sum of the survivors' running episode_returns                          */
+  double reward_sum;         /* sum of all K * N rewards                                               */
+} mppo_eval_result_t;
+size_t mppo_eval_ws_bytes(const mppo_model_t* m, const mppo_net_t* net, const mppo_eval_cfg_t* cfg);
+int32_t mppo_evaluate(const mppo_model_t* m, const mppo_net_t* net, const float* params, const mppo_eval_cfg_t* cfg, void* ws,
+                      size_t ws_bytes, mppo_eval_result_t* result, float* traj, void* stream);
+/* The two statistics stages on caller-given arrays (as mppo_gae / mppo_adv_sums are stages of the update).
+ * `acc`: the per-environment accumulators, 10 * N 8-byte words in device memory, 8-byte aligned, slot-major (word n of
+ * slot k at 8 * (k * N + n)): int64 episodes, len_sum, len_min, len_max; double ret_sum, ret_sumsq, ret_min, ret_max,
+ * reward_sum, running episode_returns.  Every word has one writer; nothing is atomic.
+ *   mppo_eval_accumulate  one step: reads reward [N] (done [N] only for the trajectory row: may be NULL when R = 0) and the env kernel's own bookkeeping (metrics: returned_episode,
+ *                         returned_episode_returns, returned_episode_lengths, episode_returns as mppo_env_step left them -
+ *                         returns are not re-derived) and updates `acc`; first != 0: `acc` is empty (written, not read).
+ *                         R > 0 also writes one trajectory row [R][row_w + A + 2] = state[n, 0 : row_w] | action[n, 0 : A]
+ *                         (NULL: zeros) | reward[n] | done[n] into traj_row.
+ *   mppo_eval_reduce      the accumulators of N environments after K steps -> *result (device memory), one workgroup, fixed order. */
+int32_t mppo_eval_accumulate(int32_t N, int32_t first, const float* reward, const uint8_t* done, const mppo_env_metrics_t* metrics,
+                             void* acc, const float* state, int32_t state_ld, int32_t row_w, const float* action, int32_t act_ld,
+                             int32_t A, int32_t R, float* traj_row, void* stream);
+int32_t mppo_eval_reduce(int32_t N, int32_t K, const void* acc, mppo_eval_result_t* result, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -82,6 +82,18 @@ class EngineCfg(C.Structure):
                 ("seed", c_u64), ("use_graph", c_i32), ("external_random", c_i32), ("rng_impl", c_i32), ("reserved0", c_i32)]
 
 
+class EvalCfg(C.Structure):
+    _fields_ = [("N", c_i32), ("K", c_i32), ("n_frames", c_i32), ("deterministic", c_i32), ("record_envs", c_i32), ("reset_noise_scale", c_f),
+                ("seed", c_u64), ("reward", RewardCfg)]
+
+
+class EvalResultRaw(C.Structure):  # mppo_eval_result_t (minppo_amd.evaluate.EvalResult is what callers see)
+    _fields_ = [(n, C.c_int64) for n in ("episodes", "len_sum", "len_min", "len_max", "survivors", "steps")] + [
+        (n, C.c_double) for n in ("ret_sum", "ret_sumsq", "ret_min", "ret_max", "survivor_ret_sum", "reward_sum")]
+
+
+EVAL_ACC_SLOTS = 10  # include/minppo_hip.h: the accumulators of mppo_eval_accumulate / _reduce are 10 * N 8-byte words
+
 P = C.POINTER
 ABI_VERSION = 7  # include/minppo_hip.h: MPPO_ABI_VERSION
 
@@ -150,10 +162,14 @@ SIGNATURES = {
     "mppo_engine_graph_active": (c_i32, [c_vp, P(c_i32)]),
     "mppo_engine_rollout": (c_i32, [c_vp, c_vp]),
     "mppo_engine_learn": (c_i32, [c_vp, c_vp]),
+    "mppo_eval_ws_bytes": (c_sz, [c_vp, P(Net), P(EvalCfg)]),
+    "mppo_evaluate": (c_i32, [c_vp, P(Net), c_vp, P(EvalCfg), c_vp, c_sz, c_vp, c_vp, c_vp]),
+    "mppo_eval_accumulate": (c_i32, [c_i32, c_i32, c_vp, c_vp, P(EnvMetrics), c_vp, c_vp, c_i32, c_i32, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp]),
+    "mppo_eval_reduce": (c_i32, [c_i32, c_i32, c_vp, c_vp, c_vp]),
 }
 
 UNCHECKED = {"mppo_last_error", "mppo_abi_version", "mppo_param_count", "mppo_policy_ws_bytes", "mppo_grad_ws_bytes",
-             "mppo_adam_ws_bytes", "mppo_permutation_ws_bytes"}
+             "mppo_adam_ws_bytes", "mppo_permutation_ws_bytes", "mppo_eval_ws_bytes"}
 
 
 class Lib:

@@ -149,6 +149,20 @@ class InferenceConfig:
 
 
 @dataclass
+class EvaluationConfig:
+    # Extension (absent upstream, whose `infer` is a stub): `minppo evaluate` / `minppo_amd.evaluate.evaluate` run the model file
+    # `inference.model_path` for `num_steps` steps of `num_envs` environments (the reference has no time limit - env.py:238-242 - so the
+    # horizon is fixed here) under the mean action (`deterministic`) or a sample; seed: `training.seed`; frames per step, reset noise and
+    # the reward window: `environment` / `reward`.  `record_envs` > 0 keeps the joint trajectory of the first that many environments,
+    # `trajectory_path` writes it as an .npz (qpos, qvel, action, reward, done, dt, n_frames).
+    num_envs: int = field(default=256)
+    num_steps: int = field(default=1000)
+    deterministic: bool = field(default=True)
+    record_envs: int = field(default=0)
+    trajectory_path: str = field(default="")
+
+
+@dataclass
 class Config:
     kscale_id: str = field(default=MISSING)
     environment: EnvironmentConfig = field(default_factory=EnvironmentConfig)
@@ -159,6 +173,7 @@ class Config:
     rl: ReinforcementLearningConfig = field(default_factory=ReinforcementLearningConfig)
     training: TrainingConfig = field(default_factory=TrainingConfig)
     inference: InferenceConfig = field(default_factory=InferenceConfig)
+    evaluation: EvaluationConfig = field(default_factory=EvaluationConfig)
     debug: bool = field(default=True)
 
 

@@ -1,0 +1,128 @@
+// evaluator.hip - mppo_evaluate: K steps of N environments under a trained policy as ONE call, with episode statistics and an optional joint
+// trajectory.  What it replaces in the reference: nothing - minppo/infer.py:22-27 raises NotImplementedError; the loop below is the rollout of
+// train.py:150-179 without the learner, under the mean action (deterministic) or a sample of the engine's Philox stream.
+//
+// The sequence is a composition of the library's own entry points, so that a caller could write it themselves and get the same bits
+// (tests/test_evaluate.py does): mppo_env_reset, [mppo_env_reinit], then per step [mppo_normal_fill], mppo_policy_forward, mppo_env_step,
+// [mppo_env_reinit over done], and the two stages of k_eval.hip.  Launches only: no allocation, no synchronisation, no blocking copy - every
+// buffer is a region of the caller's workspace (a large robot's out-of-LDS matrices included), so the call can be captured into a hipGraph.
+#include "eval.h"
+#include "model_view.h"
+#include "ppo_layout.h"
+
+namespace mppo {
+const ModelView& model_view(const mppo_model* m);
+size_t model_scratch_bytes(const mppo_model* m, int N);
+int32_t env_step_ws(const mppo_model_t* m, int32_t N, int32_t n_frames, const mppo_reward_cfg_t* rc, float* state, const float* reset_rec, const float* action,
+                    int32_t act_ld, float* obs, int32_t obs_ld, float* reward, uint8_t* done, const mppo_env_metrics_t* metrics, float* ws, size_t ws_bytes, hipStream_t stream);
+int32_t env_reset_ws(const mppo_model_t* m, int32_t N, float* state, float* reset_rec, float* obs, int32_t obs_ld, float* reward, uint8_t* done, const mppo_env_metrics_t* metrics,
+                     float* ws, size_t ws_bytes, hipStream_t stream);
+int32_t env_reinit_ws(const mppo_model_t* m, int32_t N, float* state, float* obs, int32_t obs_ld, const uint8_t* mask, float scale, int32_t rng_impl, uint64_t seed,
+                      int32_t rank, const uint32_t* key2, const int32_t* counter, int32_t counter_mul, int32_t counter_add, float* ws, size_t ws_bytes, hipStream_t stream);
+
+struct EvalWs {
+  float *state, *reset_rec, *obs, *action, *log_prob, *value, *noise, *reward, *fwd_ws, *env_ws;
+  unsigned char* done;
+  mppo_env_metrics_t met;
+  void* acc;
+  size_t env_ws_bytes, total;
+};
+
+// the regions of the workspace, each on a 256-byte boundary (base = null: sizes only)
+static EvalWs carve_eval(const mppo_model* m, const mppo_net_t& net, int N, unsigned char* base) {
+  const ModelView& mv = model_view(m);
+  EvalWs w{};
+  size_t off = 0;
+  auto take = [&](size_t bytes) -> unsigned char* {
+    off = align_up(off, 256);
+    unsigned char* p = base ? base + off : nullptr;
+    off += bytes;
+    return p;
+  };
+  const size_t n = (size_t)N;
+  w.state = (float*)take(n * mv.rec_dim * 4);
+  w.reset_rec = (float*)take((size_t)mv.rec_dim * 4);
+  w.obs = (float*)take(n * mv.obs_pad * 4);
+  w.action = (float*)take(n * net.A * 4);
+  w.log_prob = (float*)take(n * 4);
+  w.value = (float*)take(n * 4);
+  w.noise = (float*)take(n * net.A * 4);
+  w.reward = (float*)take(n * 4);
+  w.done = take(n);
+  w.met.episode_returns = (float*)take(n * 4);
+  w.met.episode_lengths = (int32_t*)take(n * 4);
+  w.met.returned_episode_returns = (float*)take(n * 4);
+  w.met.returned_episode_lengths = (int32_t*)take(n * 4);
+  w.met.timestep = (int32_t*)take(n * 4);
+  w.met.returned_episode = (uint8_t*)take(n);
+  w.acc = take(eval_acc_bytes(N));
+  w.fwd_ws = (float*)take(fwd_bufs_floats(net, N) * 4);
+  w.env_ws_bytes = model_scratch_bytes(m, N);
+  w.env_ws = w.env_ws_bytes ? (float*)take(w.env_ws_bytes) : nullptr;
+  w.total = align_up(off, 256);
+  return w;
+}
+
+static int32_t check_eval(const char* who, const mppo_model_t* m, const mppo_net_t* net, const mppo_eval_cfg_t* c) {
+  MPPO_REQUIRE(m && net && c, "%s: null model / net / cfg", who);
+  MPPO_REQUIRE(c->N >= 1, "%s: N = %d environments", who, c->N);
+  MPPO_REQUIRE(c->K >= 1, "%s: K = %d steps", who, c->K);
+  MPPO_REQUIRE(c->n_frames >= 1, "%s: n_frames = %d", who, c->n_frames);
+  MPPO_REQUIRE(c->record_envs >= 0 && c->record_envs <= c->N, "%s: record_envs = %d of N = %d environments", who, c->record_envs, c->N);
+  MPPO_REQUIRE(c->reset_noise_scale >= 0.f, "%s: reset_noise_scale %g is negative (or not a number)", who, (double)c->reset_noise_scale);
+  const ModelView& mv = model_view(m);
+  MPPO_REQUIRE(mv.nq >= 3, "%s: the environment reads qpos[2] as the height (env.py:239); nq = %d", who, mv.nq);
+  MPPO_REQUIRE(net->O == mv.obs_dim && net->OP == mv.obs_pad, "%s: net O/OP (%d/%d) do not match the model's observation (%d/%d)", who, net->O, net->OP, mv.obs_dim, mv.obs_pad);
+  MPPO_REQUIRE(net->A == mv.nu, "%s: net A = %d but the model has %d actuators", who, net->A, mv.nu);
+  MPPO_REQUIRE(net->A >= 1 && net->A <= 63 && net->H >= 4 && net->H % 4 == 0, "%s: unsupported A / H (1 <= A <= 63, H a multiple of 4)", who);
+  MPPO_REQUIRE(net->num_layers >= 0 && net->num_layers <= kMaxHidden, "%s: num_layers = %d (1 .. %d hidden layers, 0 = 2)", who, net->num_layers, kMaxHidden);
+  MPPO_REQUIRE(!net->bf16 || (net_layers(*net) == 2 && net->H % 32 == 0 && net->H <= 256 && net->A <= 32),
+               "%s: bf16 products need the fused kernels (two hidden layers, hidden size a multiple of 32 up to 256, at most 32 actuators)", who);
+  return MPPO_OK;
+}
+
+}  // namespace mppo
+
+using namespace mppo;
+
+extern "C" size_t mppo_eval_ws_bytes(const mppo_model_t* m, const mppo_net_t* net, const mppo_eval_cfg_t* cfg) {
+  if (check_eval("mppo_eval_ws_bytes", m, net, cfg) != MPPO_OK) return 0;
+  return carve_eval(m, *net, cfg->N, nullptr).total;
+}
+
+extern "C" int32_t mppo_evaluate(const mppo_model_t* m, const mppo_net_t* net, const float* params, const mppo_eval_cfg_t* cfg, void* ws, size_t ws_bytes,
+                                 mppo_eval_result_t* result, float* traj, void* stream) {
+  MPPO_TRY(check_eval("mppo_evaluate", m, net, cfg));
+  MPPO_REQUIRE(params && ws && result, "mppo_evaluate: null params / workspace / result");
+  MPPO_REQUIRE(traj || cfg->record_envs == 0, "mppo_evaluate: null trajectory with record_envs = %d", cfg->record_envs);
+  MPPO_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 255) == 0, "mppo_evaluate: the workspace must be 256-byte aligned");
+  MPPO_REQUIRE((reinterpret_cast<uintptr_t>(result) & 7) == 0, "mppo_evaluate: the result must be 8-byte aligned");
+  const mppo_eval_cfg_t& c = *cfg;
+  const int N = c.N, K = c.K, R = c.record_envs, A = net->A;
+  const EvalWs w = carve_eval(m, *net, N, static_cast<unsigned char*>(ws));
+  MPPO_REQUIRE(ws_bytes >= w.total, "mppo_evaluate: workspace %zu < %zu bytes (mppo_eval_ws_bytes)", ws_bytes, w.total);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const ModelView& mv = model_view(m);
+  const int OP = mv.obs_pad, row_w = mv.nq + mv.nv;
+  const size_t frame = (size_t)R * (row_w + A + 2);
+  const bool noisy_reset = c.reset_noise_scale > 0.f;
+  const FwdBufs fb = carve_fwd(*net, N, w.fwd_ws);
+
+  // the reset zeroes the metrics; reward / done are the step's to write
+  MPPO_TRY(env_reset_ws(m, N, w.state, w.reset_rec, w.obs, OP, w.reward, w.done, &w.met, w.env_ws, w.env_ws_bytes, s));
+  if (noisy_reset)  // event 0 of the reset noise's Philox stream: every environment starts from a state of its own
+    MPPO_TRY(env_reinit_ws(m, N, w.state, w.obs, OP, nullptr, c.reset_noise_scale, 0, c.seed, 0, nullptr, nullptr, 1, 0, w.env_ws, w.env_ws_bytes, s));
+  if (c.deterministic) MPPO_TRY(eval_zero_launch(w.noise, (size_t)N * A, s));
+  // frame 0: the initial states, the action / reward / done columns zero
+  MPPO_TRY(eval_accumulate_launch(0, N, true, nullptr, nullptr, nullptr, nullptr, w.state, mv.rec_dim, row_w, nullptr, A, A, R, traj, s));
+  for (int t = 0; t < K; ++t) {
+    if (!c.deterministic) MPPO_TRY(normal_fill_ctr(c.seed, (unsigned long long)t, nullptr, (size_t)N * A, w.noise, s));
+    MPPO_TRY(policy_forward(*net, params, N, w.obs, OP, fb, w.noise, w.action, w.log_prob, w.value, nullptr, s));
+    MPPO_TRY(env_step_ws(m, N, c.n_frames, &c.reward, w.state, w.reset_rec, w.action, A, w.obs, OP, w.reward, w.done, &w.met, w.env_ws, w.env_ws_bytes, s));
+    if (noisy_reset)  // the environments whose episode ended restart from a randomised state (event t + 1), as in the engine's rollout
+      MPPO_TRY(env_reinit_ws(m, N, w.state, w.obs, OP, w.done, c.reset_noise_scale, 0, c.seed, 0, nullptr, nullptr, 1, t + 1, w.env_ws, w.env_ws_bytes, s));
+    MPPO_TRY(eval_accumulate_launch(N, N, t == 0, w.reward, w.done, &w.met, w.acc, w.state, mv.rec_dim, row_w, w.action, A, A, R,
+                                    R > 0 ? traj + (size_t)(t + 1) * frame : nullptr, s));
+  }
+  return eval_reduce_launch(N, K, w.acc, result, s);
+}

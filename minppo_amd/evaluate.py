@@ -1,0 +1,219 @@
+"""`minppo evaluate` - run a trained policy: deterministic (or sampled) rollouts, episode statistics, joint trajectories.
+
+The reference stops at a stub (`minppo/infer.py:22-27` raises NotImplementedError) and its environment has no time limit
+(`env.py:238-242` ends an episode on height only), so a policy that stands never finishes an episode.  `evaluate` therefore runs a
+fixed horizon - `evaluation.num_steps` steps of `evaluation.num_envs` environments - as ONE call into the engine (`mppo_evaluate`,
+csrc/evaluator.hip: policy forward, environment step, statistics and trajectory rows all on the device) and reports both the
+episodes that ended and the environments that never fell.
+
+    python -m minppo_amd.cli evaluate <config> inference.model_path=trained_model.pkl [evaluation.num_envs=256 ...]
+
+prints one JSON line with the statistics; `evaluation.trajectory_path=run.npz evaluation.record_envs=4` also writes the joint
+trajectory of the first four environments (`qpos`, `qvel`, `action`, `reward`, `done`, and `dt`, `n_frames`) for a viewer elsewhere.
+"""
+
+from __future__ import annotations
+
+import ctypes as C
+import json
+import logging
+import math
+import os
+import sys
+from dataclasses import asdict, dataclass
+from typing import Any, Dict, Optional, Sequence
+
+import numpy as np
+
+from minppo_amd import _native as nat
+from minppo_amd.config import Config, load_config_from_cli, require
+
+logger = logging.getLogger(__name__)
+
+_NAN = float("nan")
+
+
+@dataclass
+class EvalResult:
+    """Statistics of one evaluation, derived on the host from the engine's `mppo_eval_result_t`.  The episode fields describe the
+    episodes that ENDED within the horizon and are nan when none did; `survivors` counts the environments none of whose episodes
+    ended, `survivor_mean_return` is the mean of the returns they collected over the whole horizon."""
+
+    episodes: int
+    mean_return: float
+    std_return: float
+    min_return: float
+    max_return: float
+    mean_length: float
+    min_length: float
+    max_length: float
+    survivors: int
+    survivor_mean_return: float
+    mean_reward: float
+    steps: int
+    trajectory: Optional[Dict[str, np.ndarray]] = None
+    dt: float = _NAN      # seconds per environment step (the model's timestep x n_frames): what a viewer needs beside the trajectory
+    n_frames: int = 1
+
+    def stats(self) -> Dict[str, Any]:
+        """The statistics alone (what the command line prints)."""
+        d = asdict(self)
+        for k in ("trajectory", "dt", "n_frames"):
+            d.pop(k)
+        return d
+
+
+def result_from_struct(r: nat.EvalResultRaw, trajectory: Optional[Dict[str, np.ndarray]] = None) -> EvalResult:
+    n = int(r.episodes)
+    if n > 0:
+        mean = r.ret_sum / n
+        std = math.sqrt(max(r.ret_sumsq / n - mean * mean, 0.0))  # population standard deviation of the ended episodes' returns
+        ep = dict(mean_return=mean, std_return=std, min_return=float(r.ret_min), max_return=float(r.ret_max), mean_length=r.len_sum / n,
+                  min_length=float(r.len_min), max_length=float(r.len_max))
+    else:  # (the engine reports +inf / -inf and zeros there: nothing ended, nothing to average)
+        ep = dict(mean_return=_NAN, std_return=_NAN, min_return=_NAN, max_return=_NAN, mean_length=_NAN, min_length=_NAN, max_length=_NAN)
+    surv = int(r.survivors)
+    return EvalResult(episodes=n, survivors=surv, survivor_mean_return=r.survivor_ret_sum / surv if surv > 0 else _NAN,
+                      mean_reward=r.reward_sum / r.steps if r.steps > 0 else _NAN, steps=int(r.steps), trajectory=trajectory, **ep)
+
+
+def split_trajectory(traj: np.ndarray, nq: int, nv: int, A: int) -> Dict[str, np.ndarray]:
+    """[K + 1, R, nq + nv + A + 2] rows of `mppo_evaluate` -> named arrays (frame 0: the initial state, zero action / reward / done)."""
+    return dict(qpos=traj[..., :nq].copy(), qvel=traj[..., nq:nq + nv].copy(), action=traj[..., nq + nv:nq + nv + A].copy(),
+                reward=traj[..., nq + nv + A].copy(), done=traj[..., nq + nv + A + 1] != 0)
+
+
+def _flat_params(params: Any, O: int, A: int, H: int, L: int) -> np.ndarray:
+    from minppo_amd.train import param_slices, tree_to_flat
+
+    if isinstance(params, (str, os.PathLike)):
+        from minppo_amd.infer import load_model as load_pickle
+
+        params = load_pickle(os.fspath(params))
+    if isinstance(params, dict):
+        return tree_to_flat(params, O, A, H, L)
+    flat = np.ascontiguousarray(np.asarray(params), np.float32).reshape(-1)
+    want = param_slices(O, A, H, L)[1]
+    if flat.size != want:
+        raise ValueError(f"expected {want} parameters (O = {O}, A = {A}, hidden_size = {H}, num_layers = {L}), got {flat.size}")
+    return flat
+
+
+def eval_cfg(config: Config, **overrides: Any) -> nat.EvalCfg:
+    """`mppo_eval_cfg_t` of a config: sizes from `evaluation`, frames / reset noise from `environment`, the reward window from `reward`,
+    the seed from `training.seed`.  Overrides: num_envs, num_steps, deterministic, record_envs, seed."""
+    from minppo_amd.train import reward_cfg
+
+    ev = config.evaluation
+    unknown = set(overrides) - {"num_envs", "num_steps", "deterministic", "record_envs", "seed"}
+    if unknown:
+        raise TypeError(f"evaluate: unknown override(s) {sorted(unknown)}")
+    g = lambda k, d: d if overrides.get(k) is None else overrides[k]
+    return nat.EvalCfg(N=int(g("num_envs", ev.num_envs)), K=int(g("num_steps", ev.num_steps)), n_frames=int(config.environment.n_frames),
+                       deterministic=int(bool(g("deterministic", ev.deterministic))), record_envs=int(g("record_envs", ev.record_envs)),
+                       reset_noise_scale=float(config.environment.reset_noise_scale), seed=int(g("seed", config.training.seed)) & 0xFFFFFFFFFFFFFFFF,
+                       reward=reward_cfg(config))
+
+
+def run(lib: nat.Lib, xp: str, device: Any, stream: Any, model: C.c_void_p, dims: nat.ModelDims, net: nat.Net, params_dev: Any,
+        ecfg: nat.EvalCfg) -> EvalResult:
+    """One `mppo_evaluate` on an open model and parameters already in device memory (`Trainer.evaluate` comes in here)."""
+    need = int(lib.eval_ws_bytes(model, C.byref(net), C.byref(ecfg)))
+    if need == 0:  # the arguments are ones mppo_evaluate refuses: let it say why
+        lib.evaluate(model, C.byref(net), nat.ptr(params_dev), C.byref(ecfg), None, 0, None, None, None)
+    K, R, nq, nv, A = ecfg.K, ecfg.record_envs, dims.nq, dims.nv, net.A
+    W = nq + nv + A + 2
+    if xp == "torch":
+        import torch
+
+        def alloc(nbytes):
+            raw = torch.zeros(nbytes + 256, dtype=torch.uint8, device=device)
+            o = (-raw.data_ptr()) % 256
+            return raw[o:o + nbytes]
+
+        ws, res = alloc(need), alloc(C.sizeof(nat.EvalResultRaw))
+        traj = alloc((K + 1) * R * W * 4).view(torch.float32).reshape(K + 1, R, W) if R > 0 else None
+        with torch.cuda.device(device):
+            torch.cuda.synchronize(device)  # (the allocations were zeroed on torch's current stream)
+            lib.evaluate(model, C.byref(net), nat.ptr(params_dev), C.byref(ecfg), nat.ptr(ws), need, nat.ptr(res), nat.ptr(traj), stream.cuda_stream)
+            stream.synchronize()
+        res_host = res.cpu().numpy()
+        traj_host = traj.cpu().numpy() if traj is not None else None
+    else:  # NumPy "device" memory: the CPU emulator build of the test-suite
+
+        def alloc(nbytes):
+            raw = np.zeros(nbytes + 256, np.uint8)
+            o = (-raw.ctypes.data) % 256
+            return raw[o:o + nbytes]
+
+        ws, res_host = alloc(need), alloc(C.sizeof(nat.EvalResultRaw))
+        traj_host = alloc((K + 1) * R * W * 4).view(np.float32).reshape(K + 1, R, W) if R > 0 else None
+        lib.evaluate(model, C.byref(net), nat.ptr(params_dev), C.byref(ecfg), nat.ptr(ws), need, nat.ptr(res_host), nat.ptr(traj_host), None)
+    out = result_from_struct(nat.EvalResultRaw.from_buffer_copy(res_host.tobytes()), split_trajectory(traj_host, nq, nv, A) if traj_host is not None else None)
+    out.dt, out.n_frames = float(dims.timestep) * ecfg.n_frames, int(ecfg.n_frames)
+    return out
+
+
+def evaluate(config: Config, params: Any, *, lib: Optional[nat.Lib] = None, xp: str = "torch", device: Any = "cuda:0", **overrides: Any) -> EvalResult:
+    """Evaluates `params` - the nested tree of `save_model` / `Trainer.params`, a flat vector, or the path of a `save_model` pickle - on
+    the robot, network geometry, reward window and `evaluation` section of `config`.  `lib=` / `xp="numpy"` as in `Trainer`."""
+    from minppo_amd.train import open_model, resolve_model
+
+    lib = lib if lib is not None else nat.load()
+    if not 1 <= config.model.num_layers <= 4:
+        raise ValueError(f"model.num_layers = {config.model.num_layers}: the MI355X engine lays out 1 to 4 hidden layers")
+    ecfg = eval_cfg(config, **overrides)
+    cm = resolve_model(config)
+    torch, stream = None, None
+    if xp == "torch":
+        import torch
+
+        device = torch.device(device)
+        stream = torch.cuda.Stream(device=device)
+    model, blob_host, blob_dev = open_model(lib, config, cm, xp, device)  # (the blobs live as long as the handle)
+    try:
+        dims = nat.ModelDims()
+        lib.model_get_dims(model, C.byref(dims))
+        L = int(config.model.num_layers)
+        net = nat.Net(dims.obs_dim, dims.obs_pad, dims.nu, config.model.hidden_size, int(config.model.use_tanh), int(config.training.mlp_dtype == "bf16"), L)
+        flat = _flat_params(params, dims.obs_dim, dims.nu, config.model.hidden_size, L)
+        params_dev = torch.from_numpy(flat).to(device) if torch is not None else np.ascontiguousarray(flat)
+        return run(lib, xp, device, stream, model, dims, net, params_dev, ecfg)
+    finally:
+        if torch is not None:
+            torch.cuda.synchronize(device)
+        lib.model_close(model)
+
+
+def save_trajectory(path: str, result: EvalResult) -> None:
+    if result.trajectory is None:
+        raise ValueError("save_trajectory: the evaluation recorded no environment (evaluation.record_envs = 0)")
+    d = os.path.dirname(path)
+    if d:
+        os.makedirs(d, exist_ok=True)
+    with open(path, "wb") as f:  # (an open file: np.savez appends ".npz" to a bare name)
+        np.savez(f, dt=np.float64(result.dt), n_frames=np.int32(result.n_frames), **result.trajectory)
+
+
+def _json_value(v: Any) -> Any:
+    return None if isinstance(v, float) and not math.isfinite(v) else v
+
+
+def main(args: Sequence[str] | None = None) -> EvalResult:
+    """`minppo evaluate <config> [overrides]`: evaluates the model file `inference.model_path` (the reference's own key) and prints one
+    JSON line with the statistics (a statistic that does not exist - no episode ended - is null)."""
+    if args is None:
+        args = sys.argv[1:]
+    config = load_config_from_cli(args)
+    path = require(config.inference.model_path, "inference.model_path")
+    if config.evaluation.trajectory_path and config.evaluation.record_envs < 1:  # (before anything runs)
+        raise ValueError("evaluation.trajectory_path is set but evaluation.record_envs is 0: there would be no trajectory to write")
+    result = evaluate(config, path)
+    if config.evaluation.trajectory_path:
+        save_trajectory(config.evaluation.trajectory_path, result)
+    print(json.dumps({k: _json_value(v) for k, v in result.stats().items()}), flush=True)
+    return result
+
+
+if __name__ == "__main__":
+    main()

@@ -3,7 +3,10 @@ NotImplementedError; both are kept so that code written against the reference fi
 
 `load_model` reads what `minppo_amd.train.save_model` (and the reference's `save_model`, `train.py:86-89`) writes: the pickled
 nested parameter dict `{"params": {"MLP_0": {...}, "log_std": ..., "MLP_1": {...}}}`.  Unpickling executes whatever the file
-contains - load only model files you wrote yourself (the engine's own checkpoints are pickle-free: `Trainer.load_checkpoint`)."""
+contains - load only model files you wrote yourself (the engine's own checkpoints are pickle-free: `Trainer.load_checkpoint`).
+
+To RUN a trained policy - deterministic rollouts, episode statistics, joint trajectories - use `minppo_amd.evaluate` (`python -m
+minppo_amd.cli evaluate <config> inference.model_path=...`); `infer` stays the stub it is upstream."""
 
 from __future__ import annotations
 

@@ -194,6 +194,38 @@ def resolve_model(config: Config) -> CompiledModel:
     return load_model(name)
 
 
+def open_model(lib: nat.Lib, config: Config, cm: CompiledModel, xp: str, device: Any = None, verbose: bool = False):
+    """Opens `cm` on `lib`: -> (model handle, host blob, device blob); the two blobs must outlive the handle.  `xp` "torch": the device copy is a
+    tensor on `device`; "numpy": 256-byte aligned host memory (the CPU emulator build of the test-suite).  With `environment.jit_kernel` the
+    environment kernel is compiled for the robot before the handle is returned (minppo_amd/jit.py; the kernel's LDS / global-memory needs follow from it)."""
+    import contextlib
+
+    host = np.frombuffer(cm.to_blob(config.environment.include_c_vals), np.uint8).copy()
+    if xp == "torch":
+        import torch
+
+        dev = torch.from_numpy(host.copy()).to(device)
+        guard = lambda: torch.cuda.device(device)
+    else:
+        buf = np.zeros(host.size + 256, np.uint8)
+        o = (-buf.ctypes.data) % 256
+        dev = buf[o:o + host.size]
+        dev[:] = host
+        guard = contextlib.nullcontext
+    model = C.c_void_p()
+    with guard():  # (a specialised kernel is checked against the run-time-sized one on the device when the model is opened)
+        lib.model_open(host.ctypes.data, host.size, nat.ptr(dev), C.byref(model))
+        if config.environment.jit_kernel and xp == "torch":
+            from minppo_amd import jit
+
+            try:
+                jit.specialize(lib, model, cm, verbose=verbose)
+            except Exception:
+                lib.model_close(model)
+                raise
+    return model, host, dev
+
+
 class Trainer:
     """One rank of the engine: robot model, HBM arena, engine handle and tensor views of its regions."""
 
@@ -224,32 +256,18 @@ class Trainer:
         self.seed = tr.seed if seed is None else int(seed)
 
         self.cm = resolve_model(config)
-        blob = np.frombuffer(self.cm.to_blob(config.environment.include_c_vals), np.uint8)
-        self._blob_host = blob.copy()
         if xp == "torch":
             import torch
 
             self.torch = torch
             self.device = torch.device(device if device is not None else f"cuda:{torch.cuda.current_device()}")
-            self._blob_dev = torch.from_numpy(self._blob_host.copy()).to(self.device)
             self.stream = stream if stream is not None else torch.cuda.Stream(device=self.device)
             self._stream_ptr = self.stream.cuda_stream
         else:  # numpy "device" memory: the CPU emulator build used by the test-suite
             self.torch = None
             self.device = "cpu-emulator"
-            buf = np.zeros(blob.size + 256, np.uint8)
-            o = (-buf.ctypes.data) % 256
-            self._blob_dev = buf[o:o + blob.size]
-            self._blob_dev[:] = blob
             self.stream, self._stream_ptr = None, None
-        self._model = C.c_void_p()
-        with self._device_guard():  # (a specialised kernel is checked against the run-time-sized one on the device when the model is opened)
-            self.lib.model_open(self._blob_host.ctypes.data, self._blob_host.size, nat.ptr(self._blob_dev), C.byref(self._model))
-        if config.environment.jit_kernel and xp == "torch":  # (before the engine sizes its arena: the kernel's LDS / global-memory needs follow from it)
-            from minppo_amd import jit
-
-            with self._device_guard():
-                jit.specialize(self.lib, self._model, self.cm, verbose=rank == 0)
+        self._model, self._blob_host, self._blob_dev = open_model(self.lib, config, self.cm, xp, self.device, verbose=rank == 0)
         kind = C.c_int32(0)
         self.lib.model_is_specialized(self._model, C.byref(kind))
         self.env_kernel = ("run-time-sized", "library instantiation for this robot", "compiled for this robot at start-up")[kind.value]
@@ -792,6 +810,16 @@ class Trainer:
         else:
             obs[0] = obs[self.T]
         self.updates_done += 1
+
+    def evaluate(self, **overrides: Any):
+        """Evaluates the trainer's CURRENT parameters on its own library, device and robot (`minppo_amd.evaluate`): `evaluation.num_steps`
+        steps of `evaluation.num_envs` fresh environments, outside the training environments and their random streams.  Overrides:
+        num_envs, num_steps, deterministic, record_envs, seed (default: this trainer's seed).  Returns an `EvalResult`."""
+        from minppo_amd import evaluate as ev
+
+        overrides.setdefault("seed", self.seed)
+        # (on the trainer's own stream: behind the last enqueued update, whose parameters it reads)
+        return ev.run(self.lib, self.xp, self.device, self.stream, self._model, self.dims, self.net, self.region("params"), ev.eval_cfg(self.config, **overrides))
 
     def rollout_stats(self, reduce: bool = False) -> Dict[str, float]:
         """Device-side reduction of the last rollout's `EnvMetrics` history (`env.py:183-194`, `train.py:170,283`):

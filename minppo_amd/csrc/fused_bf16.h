@@ -1,6 +1,6 @@
 // fused_bf16.h — the training row pass of a bf16 network (BASELINE configs[3]), designed for bf16 instead of being the float kernel
-// with cheaper MFMAs.  Included by k_fused.hip (same translation unit: FusedArgs, the k-quad store helpers, the gather role and the
-// phase timers are shared); launched by fused_forward_backward for <bf16 network, W2^T / fragment shadow copies current, pre-gathered rows>.
+// with cheaper MFMAs.  FusedArgs, the k-quad store helpers, the gather role and the phase timers come from fused_common.h; launched by
+// fused_forward_backward (k_fused.hip) for <bf16 network, W2^T / fragment shadow copies current, pre-gathered rows>.
 //
 // Same decomposition as fused_mlp_kernel - one workgroup = 16 minibatch rows of ONE network, H / 32 waves, wave w owns hidden columns
 // [32 w, 32 w + 32) as two interleaved 16-column tiles - and the same arithmetic, rounding point for rounding point (oracle:
@@ -22,6 +22,9 @@
 //   * The loss block runs on wave 0 only (the emulator: every wave), its 16-row partial sums are 16-lane DPP sums instead of one
 //     thread's serial loop behind a barrier, and the x tile is brought in by the first half of the waves.
 #pragma once
+#include "fused_common.h"
+
+namespace mppo {
 
 // two floats -> the bits of two bf16 (round to nearest even) in one dword
 __device__ __forceinline__ float bf16x2_bits(float a, float b) { return bf16x4_bits(pack_bf16x4(a, b, 0.f, 0.f)).x; }
@@ -72,11 +75,11 @@ struct FragSlab {
 template <int OT, int NS1, bool EXACT>
 __global__ void __launch_bounds__(512, 2) bf16_rowpass_kernel(FusedArgs a) {
   constexpr int SD = 16 * OT, NSH = 8;
-  constexpr bool ROLLOUT = false;  // (the phase-timer macros of k_fused.hip test it)
+  constexpr bool ROLLOUT = false;  // (the phase-timer macros of fused_common.h test it)
   (void)ROLLOUT;
   FT(0);
   FTW(56);
-  if (blockIdx.y >= 2) {  // grid rows 2, 3: gather the NEXT step's rows (uniform per workgroup; see fused_mlp_kernel)
+  if (blockIdx.y >= 2) {  // grid rows 2, 3: gather the NEXT step's rows (uniform per workgroup; see rowpass_tile, k_fused.hip)
     gather_rows_tile<true>(a, (int)blockIdx.x, (int)blockIdx.y - 2);
     return;
   }
@@ -518,3 +521,5 @@ inline bool bf16_rowpass_supported(const mppo_net_t& net) {
   return net.bf16 && ((net.O + 31) & ~31) <= 32 * kBf16RowpassNS1 && net.H % 32 == 0 && net.H >= 32 && net.H <= 256 && net.A <= 32 &&
          bf16_rowpass_smem_bytes(net.O, net.A, net.H) <= 64 * 1024;
 }
+
+}  // namespace mppo

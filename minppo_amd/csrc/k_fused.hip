@@ -4,7 +4,7 @@
 //
 // One workgroup = 16 minibatch rows (gathered by permutation index) of ONE network (blockIdx.y: 0 actor, 1 critic);
 // H/32 waves, wave w owns hidden columns [32w, 32w+32) as two 16x16 MFMA tiles (v_mfma_f32_16x16x4_f32).  The 16-row
-// activation tiles (x, h1, h2, dZ2) live in LDS (row stride +4 floats: conflict-free ds_read_b128 of 4 consecutive k);
+// activation tiles (x, h1, h2, dZ2) live in LDS (FusedLds, fused_common.h: row stride +4 floats, conflict-free ds_read_b128 of 4 consecutive k);
 // weights stream from L2.  At mb = 1280 that is 160 workgroups of 8 waves: two waves per SIMD, whose dependent MFMA
 // chains interleave on the matrix pipe.  Replaces four launches (two GEMMs, the head/loss kernel, one backward GEMM) and
 // their ~4 us fixed cost each; what needs a reduction over rows (weight gradients) stays in the split-K GEMM that follows.
@@ -13,359 +13,19 @@
 // what a lane of this kernel holds in its accumulators and what a lane of k_wgrad.hip feeds to four MFMAs); loss partials.
 // Template arguments: BF16 (bf16-in / f32-accumulate MFMA, BASELINE configs[3]); ROLLOUT (forward + pi.sample + log_prob + value
 // on N rows, reference train.py:157-160,182: stops after the heads, writes no activations); OT (16-wide output tiles: A <= 16 / 32).
-// Weight stream: range-checked buffer loads through a branch-free three-deep register ring (see BStage / GemmPipe); the
+// Weight stream: range-checked buffer loads through a branch-free three-deep register ring (fused_pipes.h: BStage / GemmPipe / FragPipe); the
 // output-layer weights live in registers.  LDS per workgroup at O = 225, H = 256: 52 KB.
-#include <wave_ops.h>
-
+// Kernels of this file: fused_mlp_kernel (training row pass and rollout forward), gather_rows_kernel (the gather role alone) and, from
+// fused_bf16.h, bf16_rowpass_kernel (the training row pass of a bf16 network on pre-gathered rows).  What they share - FusedArgs, the LDS
+// layout, the k-quad stores, gather_rows_tile, the phase timers - is fused_common.h.  Every instantiation the library launches is a row of
+// kRowKernels below: the launchers look their kernel up there and the dynamic-LDS attribute is set from the same rows.
 #include <cstdlib>
 
-#include "mppo_common.h"
-#include "ppo_layout.h"
-#include "wgrad.h"
+#include "fused_bf16.h"
+#include "fused_common.h"
+#include "fused_pipes.h"
 
 namespace mppo {
-
-// Phase timers (profiling builds only, -DMPPO_FUSED_TIMERS: tools/fused_phases.py): wave 0 of the first training workgroup stamps
-// s_memtime at the phase boundaries into a device array that mppo_debug_fused_timers() copies out.
-#ifdef MPPO_FUSED_TIMERS
-__device__ unsigned long long g_fused_t[24 + 64];
-#define FT(k) do { if (!ROLLOUT && blockIdx.x == 40 && blockIdx.y == 0 && threadIdx.x == 0) g_fused_t[k] = __builtin_amdgcn_s_memtime(); } while (0)
-#define FTW(k) do { if (!ROLLOUT && blockIdx.x == 40 && blockIdx.y == 0 && (threadIdx.x & 63) == 0) g_fused_t[(k) + (threadIdx.x >> 6)] = __builtin_amdgcn_s_memtime(); } while (0)
-#else
-#define FT(k) do { } while (0)
-#define FTW(k) do { } while (0)
-#endif
-
-constexpr float kLog2PiF = 1.8378770664093453f;
-constexpr int FRT = 16;  // rows per workgroup
-#ifndef MPPO_ROLLOUT_WAVES
-#define MPPO_ROLLOUT_WAVES 4
-#endif
-#ifndef MPPO_TRAIN_WAVES
-#define MPPO_TRAIN_WAVES 2
-#endif
-
-__device__ __forceinline__ float fused_tanh(float x) {
-  const float e = __expf(2.f * x);
-  return 1.f - __fdividef(2.f, e + 1.f);
-}
-
-struct FusedArgs {
-  int mb, O, OP, A, AP, DP, H, use_tanh;
-  const float* params;
-  ParamLayout L;
-  mppo_batch_t b;
-  const int* idx;
-  const float* adv_stat;
-  float inv_count;
-  mppo_loss_cfg_t lc;
-  float *h1[2], *h2[2], *dz2[2], *dz1[2];
-  float *dout, *xmb, *partial;
-  const float* w2t[2];  // W2^T shadow copies (W2T = true instantiations)
-  const unsigned short* frag[2];  // bf16 fragment-order copies per network: W1 (KP x H) | W2 | W2^T (BF16 && W2T instantiations)
-  // rollout mode (ROLLOUT = true): forward + pi.sample + pi.log_prob (train.py:157-160); rows are not gathered
-  const float* noise;
-  float *action, *log_prob, *value, *mean_out;
-  int net0;  // first network of the launch: 0 = actor + critic, 1 = critic only (bootstrap value, train.py:182)
-  // engine minibatch loop (PRE = true instantiations, ppo_layout.h XPre): this step's rows, already gathered, in k-quad layout; the
-  // workgroups with blockIdx.y >= 2 gather the NEXT step's rows (idx_next) into xnext while the others compute.  They are
-  // the LAST rows of the grid: workgroups are dispatched in linear order, so the gather fills the CUs the row tiles leave idle
-  // (96 of 256 at the headline shape) and never delays a row tile (it did, by 2 us, as columns of the grid at 8192 environments)
-  const float* xpre;
-  float* xnext;
-  const int* idx_next;
-  int skip;  // timing experiments only (MPPO_FUSED_SKIP bit mask): 1 L1, 2 L2, 4 heads, 8 dZ2, 16 dZ1, 32 activation stores, 64 gather
-};
-
-// One 16-row x 32-column slab of A_tile . op(W) on the 16x16x4 f32 MFMA (A_tile in LDS with row stride AS, K a multiple
-// of 32, zero beyond Kvalid).  The wave's 32 columns are two INTERLEAVED 16-column tiles: tile tau holds columns
-// n0 + 2j + tau (j = lane&15), so that one float2 load feeds both tiles.
-//   NT = false: W stored [K][H] (forward):   lane (j, kq) loads W[k][n0+2j .. +1] for its 8 k's of the stage
-//   NT = true : W stored [H][K] (backward):  B(k,n) = W[n*K + k], lane loads float4 W[n][k..k+3] for both of its columns
-// Stage = 32 k = 16 MFMAs; stage S+1's B fragment is fetched while stage S computes (copy-free ping-pong), so with two
-// waves per SIMD a load has about 1000 cycles before its first use.  k inside a stage: 32S + 16g + 4kq + c.
-// Loads are BRANCH-FREE on purpose: a conditional around a prefetch splits the loop body into basic blocks, and the
-// compiler's s_waitcnt insertion then has to assume the shorter of the two histories at the join - it waited for vmcnt(0)
-// before a stage whose operands had been requested two stages earlier, i.e. the ring degenerated to depth one.
-template <bool NT>
-struct BStage {
-  float x0[8], x1[8];
-  // NT = false: `wb` is a range-checked view of W[0 .. Kvalid) x H: rows of the zero-padded K tail read as 0
-  __device__ __forceinline__ void load(const float* W, const BufView& wb, int H, int K, int S, int n0, int j, int kq) {
-    if (NT) {
-      // buffer loads like the forward pipe: the per-lane part of the address is fixed for the whole GEMM, the stage advances a
-      // scalar offset (flat loads recomputed a 64-bit address per load: VALU work in the MFMA stream)
-      const int lane_off = ((n0 + 2 * j) * K + 4 * kq) * 4;
-#pragma unroll
-      for (int g = 0; g < 2; ++g) {
-#ifdef MPPO_FUSED_NT_FLAT
-        const float4 q0 = *reinterpret_cast<const float4*>(W + (size_t)(n0 + 2 * j) * K + 32 * S + 16 * g + 4 * kq);
-        const float4 q1 = *reinterpret_cast<const float4*>(W + (size_t)(n0 + 2 * j + 1) * K + 32 * S + 16 * g + 4 * kq);
-#else
-        const float4 q0 = buf_load_f4(wb, lane_off, (32 * S + 16 * g) * 4);
-        const float4 q1 = buf_load_f4(wb, lane_off + K * 4, (32 * S + 16 * g) * 4);
-#endif
-        x0[4 * g] = q0.x; x0[4 * g + 1] = q0.y; x0[4 * g + 2] = q0.z; x0[4 * g + 3] = q0.w;
-        x1[4 * g] = q1.x; x1[4 * g + 1] = q1.y; x1[4 * g + 2] = q1.z; x1[4 * g + 3] = q1.w;
-      }
-    } else {
-      const int lane_off = (4 * kq * H + n0 + 2 * j) * 4;  // bytes; the only per-lane part of the address
-#pragma unroll
-      for (int g = 0; g < 2; ++g)
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-          const float2 q = buf_load_f2(wb, lane_off, (32 * S + 16 * g + c) * H * 4);
-          x0[4 * g + c] = q.x; x1[4 * g + c] = q.y;
-        }
-    }
-  }
-};
-
-// BF16: a lane's four consecutive k's (the float4 it already holds) are one operand of v_mfma_f32_16x16x16_bf16: the same
-// registers, rounded to bf16, feed 4 MFMAs instead of 16 (f32 accumulate).
-template <bool BF16>
-__device__ __forceinline__ void stage_mfma(const float* arow, int S, const float (&x0)[8], const float (&x1)[8], f32x4& acc0, f32x4& acc1) {
-  const float4 a0 = *reinterpret_cast<const float4*>(arow + 32 * S);
-  const float4 a1 = *reinterpret_cast<const float4*>(arow + 32 * S + 16);
-  if (BF16) {
-    const bf16x4 A0 = pack_bf16x4(a0.x, a0.y, a0.z, a0.w), A1 = pack_bf16x4(a1.x, a1.y, a1.z, a1.w);
-    mfma_bf16_16x16x16(A0, pack_bf16x4(x0[0], x0[1], x0[2], x0[3]), acc0);
-    mfma_bf16_16x16x16(A0, pack_bf16x4(x1[0], x1[1], x1[2], x1[3]), acc1);
-    mfma_bf16_16x16x16(A1, pack_bf16x4(x0[4], x0[5], x0[6], x0[7]), acc0);
-    mfma_bf16_16x16x16(A1, pack_bf16x4(x1[4], x1[5], x1[6], x1[7]), acc1);
-    return;
-  }
-  mfma_f32_16x16x4(a0.x, x0[0], acc0); mfma_f32_16x16x4(a0.x, x1[0], acc1);
-  mfma_f32_16x16x4(a0.y, x0[1], acc0); mfma_f32_16x16x4(a0.y, x1[1], acc1);
-  mfma_f32_16x16x4(a0.z, x0[2], acc0); mfma_f32_16x16x4(a0.z, x1[2], acc1);
-  mfma_f32_16x16x4(a0.w, x0[3], acc0); mfma_f32_16x16x4(a0.w, x1[3], acc1);
-  mfma_f32_16x16x4(a1.x, x0[4], acc0); mfma_f32_16x16x4(a1.x, x1[4], acc1);
-  mfma_f32_16x16x4(a1.y, x0[5], acc0); mfma_f32_16x16x4(a1.y, x1[5], acc1);
-  mfma_f32_16x16x4(a1.z, x0[6], acc0); mfma_f32_16x16x4(a1.z, x1[6], acc1);
-  mfma_f32_16x16x4(a1.w, x0[7], acc0); mfma_f32_16x16x4(a1.w, x1[7], acc1);
-}
-
-// Three-deep register ring over the K stages: stage S+2 is fetched while stage S computes, so a weight fragment has two
-// full MFMA blocks (about 2000 cycles with two waves per SIMD) to arrive from L2.  The first two stages are requested by
-// prefetch(), which the kernel calls one phase EARLY (weights depend on nothing computed here): the fill latency of each
-// GEMM phase hides under the barrier / epilogue / loss code of the phase before it.
-template <bool NT>
-struct GemmPipe {
-  BStage<NT> b0, b1;
-  BufView wb;
-  __device__ __forceinline__ void prefetch(int K, int Kvalid, const float* W, int H, int n0, int lane) {
-    const int j = lane & 15, kq = lane >> 4;
-    const int last = K / 32 - 1;
-    wb = make_buf(W, (unsigned)Kvalid * (unsigned)H * 4u);
-    b0.load(W, wb, H, K, 0, n0, j, kq);
-    b1.load(W, wb, H, K, last < 1 ? last : 1, n0, j, kq);
-  }
-  // invariant at the loop top: b0 = stage S, b1 = stage S+1.  Stage indices past the end are clamped to the last stage
-  // (a redundant, harmless load) instead of being skipped: straight-line code, exact vmcnt bookkeeping.
-  template <bool BF16>
-  __device__ __forceinline__ void run(const float* At, int AS, int K, const float* W, int H, int n0, int lane, f32x4& acc0, f32x4& acc1) {
-    const int j = lane & 15, kq = lane >> 4;
-    const float* arow = At + j * AS + 4 * kq;
-    const int nst = K / 32, last = nst - 1;
-    BStage<NT> b2;
-    int S = 0;
-    // MPPO_SCHED_FENCE: the machine scheduler otherwise sinks a stage's loads down to their first use (it minimises
-    // register pressure), which is exactly the latency exposure the ring exists to avoid
-    for (; S + 2 < nst; S += 3) {
-      b2.load(W, wb, H, K, S + 2, n0, j, kq);
-      MPPO_SCHED_FENCE();
-      stage_mfma<BF16>(arow, S, b0.x0, b0.x1, acc0, acc1);
-      MPPO_SCHED_FENCE();
-      b0.load(W, wb, H, K, S + 3 < last ? S + 3 : last, n0, j, kq);
-      MPPO_SCHED_FENCE();
-      stage_mfma<BF16>(arow, S + 1, b1.x0, b1.x1, acc0, acc1);
-      MPPO_SCHED_FENCE();
-      b1.load(W, wb, H, K, S + 4 < last ? S + 4 : last, n0, j, kq);
-      MPPO_SCHED_FENCE();
-      stage_mfma<BF16>(arow, S + 2, b2.x0, b2.x1, acc0, acc1);
-      MPPO_SCHED_FENCE();
-    }
-    if (S < nst) stage_mfma<BF16>(arow, S, b0.x0, b0.x1, acc0, acc1);
-    if (S + 1 < nst) stage_mfma<BF16>(arow, S + 1, b1.x0, b1.x1, acc0, acc1);
-  }
-  // Two 16-row tiles per workgroup (RT = 2: rows j and j + 16 of a 32-row activation tile): every weight stage is fetched ONCE and
-  // multiplied into both tiles - twice the MFMAs per byte streamed, the same ring otherwise.
-  __device__ __forceinline__ void run2(const float* At, int AS, int K, const float* W, int H, int n0, int lane, f32x4 (&acc)[2][2]) {
-    const int j = lane & 15, kq = lane >> 4;
-    const float* arow = At + j * AS + 4 * kq;
-    const float* arow2 = arow + 16 * AS;
-    const int nst = K / 32, last = nst - 1;
-    BStage<NT> b2;
-    int S = 0;
-    for (; S + 2 < nst; S += 3) {
-      b2.load(W, wb, H, K, S + 2, n0, j, kq);
-      MPPO_SCHED_FENCE();
-      stage_mfma<false>(arow, S, b0.x0, b0.x1, acc[0][0], acc[0][1]);
-      stage_mfma<false>(arow2, S, b0.x0, b0.x1, acc[1][0], acc[1][1]);
-      MPPO_SCHED_FENCE();
-      b0.load(W, wb, H, K, S + 3 < last ? S + 3 : last, n0, j, kq);
-      MPPO_SCHED_FENCE();
-      stage_mfma<false>(arow, S + 1, b1.x0, b1.x1, acc[0][0], acc[0][1]);
-      stage_mfma<false>(arow2, S + 1, b1.x0, b1.x1, acc[1][0], acc[1][1]);
-      MPPO_SCHED_FENCE();
-      b1.load(W, wb, H, K, S + 4 < last ? S + 4 : last, n0, j, kq);
-      MPPO_SCHED_FENCE();
-      stage_mfma<false>(arow, S + 2, b2.x0, b2.x1, acc[0][0], acc[0][1]);
-      stage_mfma<false>(arow2, S + 2, b2.x0, b2.x1, acc[1][0], acc[1][1]);
-      MPPO_SCHED_FENCE();
-    }
-    if (S < nst) { stage_mfma<false>(arow, S, b0.x0, b0.x1, acc[0][0], acc[0][1]); stage_mfma<false>(arow2, S, b0.x0, b0.x1, acc[1][0], acc[1][1]); }
-    if (S + 1 < nst) { stage_mfma<false>(arow, S + 1, b1.x0, b1.x1, acc[0][0], acc[0][1]); stage_mfma<false>(arow2, S + 1, b1.x0, b1.x1, acc[1][0], acc[1][1]); }
-  }
-};
-
-// The same ring for a bf16 network with shadow copies: the B operand comes from the fragment-order bf16 copy of the weight
-// (ppo_layout.h frag_index): a lane's eight values of a column tile and stage are 16 contiguous bytes (two 16-byte buffer loads instead of eight
-// 8-byte ones, half the bytes, and no float -> bf16 conversion of weights in the loop).  `W` = fragment base of the matrix.
-struct FragStage {
-  float4 q0, q1;  // raw bits: q0 = tile 0 (k 0..3 of group 0 | group 1), q1 = tile 1
-  __device__ __forceinline__ void load(const BufView& wb, int S, int nwaves, int wave, int lane) {
-    const int uni = ((S * nwaves + wave_uniform(wave)) * 64) * 32;  // bytes: (stage, wave slab) block of 2 KB; the wave index in a scalar register (else: a waterfall loop around every load)
-    q0 = buf_load_f4(wb, lane * (2 * kFragLaneElems), uni);
-    q1 = buf_load_f4(wb, lane * (2 * kFragLaneElems) + 2 * kFragTileElems, uni);
-  }
-};
-__device__ __forceinline__ void frag_mfma(const float* arow, int S, const FragStage& b, f32x4& acc0, f32x4& acc1) {
-  const float4 a0 = *reinterpret_cast<const float4*>(arow + 32 * S);
-  const float4 a1 = *reinterpret_cast<const float4*>(arow + 32 * S + 16);
-  const bf16x4 A0 = pack_bf16x4(a0.x, a0.y, a0.z, a0.w), A1 = pack_bf16x4(a1.x, a1.y, a1.z, a1.w);
-  const bf16x4 t0g0 = bf16x4_from_bits(b.q0.x, b.q0.y), t0g1 = bf16x4_from_bits(b.q0.z, b.q0.w);
-  const bf16x4 t1g0 = bf16x4_from_bits(b.q1.x, b.q1.y), t1g1 = bf16x4_from_bits(b.q1.z, b.q1.w);
-  mfma_bf16_16x16x16(A0, t0g0, acc0);
-  mfma_bf16_16x16x16(A0, t1g0, acc1);
-  mfma_bf16_16x16x16(A1, t0g1, acc0);
-  mfma_bf16_16x16x16(A1, t1g1, acc1);
-}
-struct FragPipe {
-  FragStage b0, b1;
-  BufView wb;
-  int nw;
-  // same interface as GemmPipe (K = padded depth, H = columns, n0 = 32 * wave); Kvalid is implicit (the copy is zero-padded)
-  __device__ __forceinline__ void prefetch(int K, int, const float* W, int H, int n0, int lane) {
-    const int last = K / 32 - 1;
-    nw = H / 32;
-    wb = make_buf(W, (unsigned)K * (unsigned)H * 2u);
-    b0.load(wb, 0, nw, n0 >> 5, lane);
-    b1.load(wb, last < 1 ? last : 1, nw, n0 >> 5, lane);
-  }
-  template <bool BF16>
-  __device__ __forceinline__ void run(const float* At, int AS, int K, const float*, int, int n0, int lane, f32x4& acc0, f32x4& acc1) {
-    const int j = lane & 15, kq = lane >> 4, wv = n0 >> 5;
-    const float* arow = At + j * AS + 4 * kq;
-    const int nst = K / 32, last = nst - 1;
-    FragStage b2;
-    int S = 0;
-    for (; S + 2 < nst; S += 3) {
-      b2.load(wb, S + 2, nw, wv, lane);
-      MPPO_SCHED_FENCE();
-      frag_mfma(arow, S, b0, acc0, acc1);
-      MPPO_SCHED_FENCE();
-      b0.load(wb, S + 3 < last ? S + 3 : last, nw, wv, lane);
-      MPPO_SCHED_FENCE();
-      frag_mfma(arow, S + 1, b1, acc0, acc1);
-      MPPO_SCHED_FENCE();
-      b1.load(wb, S + 4 < last ? S + 4 : last, nw, wv, lane);
-      MPPO_SCHED_FENCE();
-      frag_mfma(arow, S + 2, b2, acc0, acc1);
-      MPPO_SCHED_FENCE();
-    }
-    if (S < nst) frag_mfma(arow, S, b0, acc0, acc1);
-    if (S + 1 < nst) frag_mfma(arow, S + 1, b1, acc0, acc1);
-  }
-  __device__ __forceinline__ void run2(const float*, int, int, const float*, int, int, int, f32x4 (&)[2][2]) {}  // (32-row tiles are a float-network form)
-};
-template <bool FRAG, bool NT> struct PipeSel { typedef GemmPipe<NT> type; };
-template <bool NT> struct PipeSel<true, NT> { typedef FragPipe type; };
-
-template <int LRW>
-__device__ __forceinline__ float row32_sum(float x) {
-  x = group16_sum(x);
-  x += __shfl_xor(x, 16);
-  return x;
-}
-
-// K-quad operands of the weight-gradient kernel.  Float network: one float4 per (quad of rows, column).  bf16 network (BF16 = true):
-// the weight-gradient MFMAs round their operands to bf16 anyway, so the row pass stores them ROUNDED - 8 bytes per quad, the same
-// index (quad_index) in units of bf16: half the bytes written here and read there, no conversion in the consumer, same results.
-template <bool BF16>
-__device__ __forceinline__ void store_quad(float* base, size_t qi, const float (&q)[4]) {
-  if (BF16) stream_store(base + (qi >> 1), bf16x4_bits(pack_bf16x4(q[0], q[1], q[2], q[3])));
-  else wt_store(base, qi, make_float4(q[0], q[1], q[2], q[3]));
-}
-// two adjacent columns (c0 even): 32 bytes as two float4, or 16 bytes of bf16
-// WT: write-through (sc0 sc1) stores - the bytes leave this XCD's L2 while the kernel is still computing instead of waiting, dirty, for the
-// end-of-kernel flush, and the weight-gradient launch finds them in memory: 13.9 -> 12.6 us there.  The row pass itself pays 0.9 us for it
-// (a wave retires when its write-through stores are acknowledged); net 6.59 -> 6.555 ms per update.  All four operand stores or none:
-// write-through for h1 / h2 / dZ2 and a streaming store for the last one (dZ1) measured 6.82 ms.
-// float networks: SPLIT-PAIR column order inside a quad row (wgrad.h) - the even column of the lane's pair at qi, the odd one at qi2, half
-// a quad row further: each of the two store instructions then writes whole lines across the lanes
-template <bool BF16, bool WT = true>
-__device__ __forceinline__ void store_quad2(float* base, size_t qi, size_t qi2, const float (&q0)[4], const float (&q1)[4]) {
-  if (BF16) {
-    const float2 a = bf16x4_bits(pack_bf16x4(q0[0], q0[1], q0[2], q0[3])), b = bf16x4_bits(pack_bf16x4(q1[0], q1[1], q1[2], q1[3]));
-    if (WT) wt_store(base, qi >> 1, make_float4(a.x, a.y, b.x, b.y));
-    else stream_store(base + (qi >> 1), make_float4(a.x, a.y, b.x, b.y));
-  } else if (WT) {
-    wt_store(base, qi, make_float4(q0[0], q0[1], q0[2], q0[3]));
-    wt_store(base, qi2, make_float4(q1[0], q1[1], q1[2], q1[3]));
-  } else {
-    stream_store(base + qi, make_float4(q0[0], q0[1], q0[2], q0[3]));
-    stream_store(base + qi2, make_float4(q1[0], q1[1], q1[2], q1[3]));
-  }
-}
-// positions of the column pair (c0, c0 + 1), c0 even, of quad row `row` in an operand of `cols` columns: plain order for a bf16 network
-// (one 16-byte store holds both), split-pair order for a float network
-template <bool BF16>
-__device__ __forceinline__ void pair_index(size_t row, size_t c0, size_t cols, size_t& qi, size_t& qi2) {
-  if (BF16) { qi = quad_index(row, c0, cols); qi2 = qi + 4; }
-  else { qi = ((row >> 2) * cols + (c0 >> 1)) * 4; qi2 = qi + (cols >> 1) * 4; }
-}
-
-// Gather role of a PRE launch: 16 rows of the NEXT minibatch (half = blockIdx.y picks two of the tile's four quads) from the
-// trajectory into the k-quad buffer; rows past the minibatch are written as zeros (the buffer is an operand of the weight-gradient
-// product and of the first layer).  Depends on the permutation only - it runs beside the workgroups that compute this step.
-template <bool BF16>
-__device__ __forceinline__ void gather_rows_tile(const FusedArgs& a, int tile, int half) {
-  const int OP = a.OP, row0 = tile * FRT;
-  for (int e = threadIdx.x; e < 2 * OP; e += blockDim.x) {
-    const int qd = 2 * half + e / OP, c = e % OP;
-    long ix[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int r = row0 + 4 * qd + j;
-      ix[j] = a.idx_next[r < a.mb ? r : a.mb - 1];
-    }
-    float v[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const float x = a.b.obs[ix[j] * a.b.obs_ld + c];
-      v[j] = row0 + 4 * qd + j < a.mb ? x : 0.f;
-    }
-    store_quad<BF16>(a.xnext, quad_index(row0 + 4 * qd, c, OP), v);
-  }
-  // the same rows' scalars of the loss, behind the observation quads (ppo_layout.h xquad_floats): float4 = one column of four rows
-  if (a.b.action) {
-    const int A = a.A, SC = A + 4;
-    float* sq = a.xnext + xquad_obs_floats(OP, a.mb);
-    for (int e = threadIdx.x; e < 2 * SC; e += blockDim.x) {
-      const int qd = 2 * half + e / SC, c = e % SC;
-      float v[4];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int r = row0 + 4 * qd + j;
-        const long ix = a.idx_next[r < a.mb ? r : a.mb - 1];
-        const float x = c < A ? a.b.action[ix * a.b.act_ld + c] : c == A ? a.b.log_prob[ix] : c == A + 1 ? a.b.adv[ix] : c == A + 2 ? a.b.value[ix] : a.b.target[ix];
-        v[j] = r < a.mb ? x : 0.f;
-      }
-      *reinterpret_cast<float4*>(sq + ((size_t)((row0 >> 2) + qd) * SC + c) * 4) = make_float4(v[0], v[1], v[2], v[3]);
-    }
-  }
-}
 
 // rollout launches have 2 x N/16 workgroups (512 at N = 4096): two per CU must be co-resident = 4 waves per SIMD (the second
 // __launch_bounds__ argument is HIP's minimum waves per execution unit), i.e. at most 128 VGPRs
@@ -379,36 +39,31 @@ __device__ __forceinline__ void gather_rows_tile(const FusedArgs& a, int tile, i
 template <bool BF16, bool ROLLOUT, int OT, bool W2T = false, bool PRE = false, int RT = 1>
 __global__ void __launch_bounds__(512, ROLLOUT ? MPPO_ROLLOUT_WAVES : MPPO_TRAIN_WAVES) fused_mlp_kernel(FusedArgs a) {
   static_assert(RT == 1 || (RT == 2 && PRE && !BF16 && !ROLLOUT), "32-row tiles: float training row pass on pre-gathered rows");
+  static_assert(!(ROLLOUT && PRE), "the rollout forward reads its rows in place (the gather role alone is gather_rows_kernel)");
   constexpr int SD = 16 * OT;  // row stride of the per-row output-space tiles
   constexpr int ROWS = FRT * RT;
   FT(0);
   FTW(56);
   // The role is decided from the launch geometry alone (grid rows 0, 1: the two networks; rows 2, 3: gather), not from a kernel
   // argument: a scalar load ahead of this branch would put one more (cold) trip to the argument segment in front of every row tile.
-  // <ROLLOUT, PRE> together name the gather-ONLY launch (fused_gather_rows): every workgroup gathers.
-  if (PRE && (ROLLOUT || blockIdx.y >= 2)) {  // uniform per workgroup
+  // (The gather role alone - the first optimizer step of an update - is gather_rows_kernel below.)
+  if (PRE && blockIdx.y >= 2) {  // uniform per workgroup
     if (RT == 2) {  // grid row 2 / 3: the first / second 16-row tile of this 32-row block, both halves
       gather_rows_tile<BF16>(a, 2 * (int)blockIdx.x + (int)blockIdx.y - 2, 0);
       gather_rows_tile<BF16>(a, 2 * (int)blockIdx.x + (int)blockIdx.y - 2, 1);
       return;
     }
-    gather_rows_tile<BF16>(a, (int)blockIdx.x, ROLLOUT ? (int)blockIdx.y : (int)blockIdx.y - 2);
+    gather_rows_tile<BF16>(a, (int)blockIdx.x, (int)blockIdx.y - 2);
     return;
   }
   MPPO_DYN_SMEM(smem_raw);
   float* sm = reinterpret_cast<float*>(smem_raw);
   const int H = a.H, O = a.O, OP = a.OP, A = a.A, AP = a.AP;
   const int net = blockIdx.y + (ROLLOUT ? a.net0 : 0);  // 0 actor, 1 critic
-  const int KP = (O + 31) & ~31;  // first-layer K padded to whole 32-k stages (x tile zero-padded)
-  const int XS = KP + 4, HS = H + 4;
-  const int R0 = ROWS * (XS > HS ? XS : HS);
-  float* xt = sm;            // [ROWS][XS]  then dZ2 tile [ROWS][HS]
-  float* h1t = sm + R0;      // [ROWS][HS]
-  float* h2t = h1t + ROWS * HS;
-  float* s_do = h2t + ROWS * HS;        // [ROWS][SD]  d mean (cols < A, zero beyond) | critic: col 0 = d value
-  float* s_red = s_do + ROWS * SD;      // [ROWS][SD]  d log_std terms
-  float* s_l = s_red + ROWS * SD;       // [ROWS]      per-row loss term
-  float* s_hp = xt;                     // [H/32 waves][RT][OT][64 lanes][4]  partial head tiles: over the x tile, dead between layer 1 and dZ2
+  const FusedLds lds(O, H, OT, RT);  // the layout the host sized the launch from (fused_common.h)
+  const int KP = lds.KP;  // first-layer K padded to whole 32-k stages (x tile zero-padded)
+  const int XS = lds.XS, HS = lds.HS;
+  float *xt = lds.xt(sm), *h1t = lds.h1t(sm), *h2t = lds.h2t(sm), *s_do = lds.s_do(sm), *s_red = lds.s_red(sm), *s_l = lds.s_l(sm), *s_hp = lds.s_hp(sm);
   const int t = threadIdx.x, nthr = blockDim.x, lane = t & 63, wave = t >> 6;
   const int row0 = blockIdx.x * ROWS;
   const bool tanh_act = net == 0 && a.use_tanh;
@@ -622,13 +277,13 @@ __global__ void __launch_bounds__(512, ROLLOUT ? MPPO_ROLLOUT_WAVES : MPPO_TRAIN
     if (!ROLLOUT && blockIdx.x == 40 && blockIdx.y == 0 && lane == 0) g_fused_t[24 + 16 * layer + wave] = __builtin_amdgcn_s_memtime();
 #endif
     if (layer == 0) {
-      if (RT == 2) pipe1.run2(xt, XS, KP, F1, H, n0, lane, accr);
+      if constexpr (RT == 2) pipe1.run2(xt, XS, KP, F1, H, n0, lane, accr);
       else if (!(a.skip & 1)) pipe1.template run<BF16>(xt, XS, KP, F1, H, n0, lane, acc0, acc1);
       if (!ROLLOUT) pipe2.prefetch(H, H, F2, H, n0, lane);  // arrives during the epilogue + barrier below
     } else {
       // rollout: 4 waves per SIMD hide the fill latency, and the 128-VGPR budget has no room for a cross-phase prefetch
       if (ROLLOUT) pipe2.prefetch(H, H, F2, H, n0, lane);
-      if (RT == 2) pipe2.run2(h1t, HS, H, F2, H, n0, lane, accr);
+      if constexpr (RT == 2) pipe2.run2(h1t, HS, H, F2, H, n0, lane, accr);
       else if (!(a.skip & 2)) pipe2.template run<BF16>(h1t, HS, H, F2, H, n0, lane, acc0, acc1);
       if (!ROLLOUT) pipe5.prefetch(H, H, W2back, H, n0, lane);  // W2^T fragments of the backward product: hidden under heads / loss / dZ2
     }
@@ -885,7 +540,7 @@ __global__ void __launch_bounds__(512, ROLLOUT ? MPPO_ROLLOUT_WAVES : MPPO_TRAIN
     f32x4 acc0, acc1;
     f32x4 accr[2][2];
     for (int r = 0; r < 4; ++r) { acc0[r] = 0.f; acc1[r] = 0.f; accr[0][0][r] = accr[0][1][r] = accr[1][0][r] = accr[1][1][r] = 0.f; }
-    if (RT == 2) pipe5.run2(dzt, HS, H, W2back, H, n0, lane, accr);
+    if constexpr (RT == 2) pipe5.run2(dzt, HS, H, W2back, H, n0, lane, accr);
     else if (!(a.skip & 16)) pipe5.template run<BF16>(dzt, HS, H, W2back, H, n0, lane, acc0, acc1);
     FT(13);
     const int c0 = n0 + 2 * cj;
@@ -912,6 +567,13 @@ __global__ void __launch_bounds__(512, ROLLOUT ? MPPO_ROLLOUT_WAVES : MPPO_TRAIN
   FT(14);
 }
 
+// The gather role alone, grid (mb / 16 tiles, 2 halves): the first optimizer step of an update has no previous launch to gather its rows.
+template <bool BF16>
+__global__ void __launch_bounds__(256) gather_rows_kernel(FusedArgs a) {
+  gather_rows_tile<BF16>(a, (int)blockIdx.x, (int)blockIdx.y);
+}
+
+
 #ifdef MPPO_FUSED_TIMERS
 }  // namespace mppo
 extern "C" int32_t mppo_debug_fused_timers(unsigned long long* out24) {
@@ -921,14 +583,7 @@ extern "C" int32_t mppo_debug_fused_timers(unsigned long long* out24) {
 namespace mppo {
 #endif
 
-#include "fused_bf16.h"  // bf16_rowpass_kernel: the training row pass of a bf16 network (BASELINE configs[3])
-
-size_t fused_smem_bytes(int O, int A, int H, int RT) {
-  const int KP = (O + 31) & ~31, XS = KP + 4, HS = H + 4, OT = A > 16 ? 2 : 1;
-  const size_t rows = (size_t)FRT * RT, R0 = rows * (XS > HS ? XS : HS);
-  // x tile (later: partial head tiles, then the dZ2 tile) | h1 | h2 | dOut, d log_std terms | per-row loss
-  return sizeof(float) * (R0 + 2 * rows * HS + 2 * rows * 16 * OT + rows);
-}
+size_t fused_smem_bytes(int O, int A, int H, int RT) { return sizeof(float) * FusedLds(O, H, A > 16 ? 2 : 1, RT).floats(); }
 size_t fused_smem_bytes(int O, int A, int H) { return fused_smem_bytes(O, A, H, 1); }
 
 // Rows per workgroup of the training row pass for this launch: 32 (two 16-row tiles sharing every weight stage) when the 16-row tiling
@@ -960,24 +615,48 @@ bool fused_rollout_supported(const mppo_net_t& net, const float* obs, int obs_ld
          fused_smem_bytes(net.O, net.A, net.H) <= 160 * 1024;
 }
 
+// ---- every instantiation of the row-pass kernels that the library launches.  The launchers below find their kernel here (a combination
+// without a row is an error, not a fall-back) and fused_set_smem raises the dynamic-LDS limit of exactly these rows. ----
+enum RowRole { kRoleTrain, kRoleRollout, kRoleBf16Train };
+using RowKernelFn = void (*)(FusedArgs);
+struct RowKernel {
+  RowRole role;
+  bool bf16;
+  int ot;
+  bool w2t, pre;
+  int rt;
+  bool exact;  // (bf16_rowpass_kernel only)
+  RowKernelFn fn;
+};
+#define MPPO_FUSED(B, R, T, W, P, RT) {(R) ? kRoleRollout : kRoleTrain, B, T, W, P, RT, false, fused_mlp_kernel<B, R, T, W, P, RT>}
+#define MPPO_BF16_ROWPASS(T, E) {kRoleBf16Train, true, T, true, true, 1, E, bf16_rowpass_kernel<T, kBf16RowpassNS1, E>}
+static const RowKernel kRowKernels[] = {
+    // training, rows gathered by index: plain weights | shadow copies current (W2T)
+    MPPO_FUSED(false, false, 1, false, false, 1), MPPO_FUSED(true, false, 1, false, false, 1), MPPO_FUSED(false, false, 2, false, false, 1), MPPO_FUSED(true, false, 2, false, false, 1),
+    MPPO_FUSED(false, false, 1, true, false, 1), MPPO_FUSED(true, false, 1, true, false, 1), MPPO_FUSED(false, false, 2, true, false, 1), MPPO_FUSED(true, false, 2, true, false, 1),
+    // training, pre-gathered rows (the engine's minibatch loop): 16-row tiles | 32-row tiles (float networks)
+    MPPO_FUSED(false, false, 1, true, true, 1), MPPO_FUSED(true, false, 1, true, true, 1), MPPO_FUSED(false, false, 2, true, true, 1), MPPO_FUSED(true, false, 2, true, true, 1),
+    MPPO_FUSED(false, false, 1, true, true, 2), MPPO_FUSED(false, false, 2, true, true, 2),
+    // rollout forward: float | bf16 from the float weights | bf16 from the fragment copies (W2T)
+    MPPO_FUSED(false, true, 1, false, false, 1), MPPO_FUSED(false, true, 2, false, false, 1), MPPO_FUSED(true, true, 1, false, false, 1), MPPO_FUSED(true, true, 2, false, false, 1),
+    MPPO_FUSED(true, true, 1, true, false, 1), MPPO_FUSED(true, true, 2, true, false, 1),
+    // training row pass of a bf16 network on pre-gathered rows (fused_bf16.h): general | exact geometry
+    MPPO_BF16_ROWPASS(1, false), MPPO_BF16_ROWPASS(1, true), MPPO_BF16_ROWPASS(2, false), MPPO_BF16_ROWPASS(2, true),
+};
+#undef MPPO_FUSED
+#undef MPPO_BF16_ROWPASS
+
+static RowKernelFn row_kernel(RowRole role, bool bf16, int A, bool w2t, bool pre, int rt, bool exact = false) {
+  const int ot = A > 16 ? 2 : 1;
+  for (const RowKernel& k : kRowKernels)
+    if (k.role == role && k.bf16 == bf16 && k.ot == ot && k.w2t == w2t && k.pre == pre && k.rt == rt && k.exact == exact) return k.fn;
+  return nullptr;
+}
+
+// `smem` bytes of dynamic LDS for every row of the table (a launch above 64 KB needs the attribute); the 32-row form's own limit is fixed
 static int32_t fused_set_smem(size_t smem) {
-#define MPPO_FUSED_ATTR(B, R, T) \
-  MPPO_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(fused_mlp_kernel<B, R, T>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem))
-  MPPO_FUSED_ATTR(false, false, 1); MPPO_FUSED_ATTR(true, false, 1); MPPO_FUSED_ATTR(false, true, 1); MPPO_FUSED_ATTR(true, true, 1);
-  MPPO_FUSED_ATTR(false, false, 2); MPPO_FUSED_ATTR(true, false, 2); MPPO_FUSED_ATTR(false, true, 2); MPPO_FUSED_ATTR(true, true, 2);
-#undef MPPO_FUSED_ATTR
-#define MPPO_FUSED_ATTR(B, T) \
-  MPPO_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(fused_mlp_kernel<B, false, T, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem))
-  MPPO_FUSED_ATTR(false, 1); MPPO_FUSED_ATTR(true, 1); MPPO_FUSED_ATTR(false, 2); MPPO_FUSED_ATTR(true, 2);
-#undef MPPO_FUSED_ATTR
-#define MPPO_FUSED_ATTR(B, T) \
-  MPPO_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(fused_mlp_kernel<B, false, T, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem))
-  MPPO_FUSED_ATTR(false, 1); MPPO_FUSED_ATTR(true, 1); MPPO_FUSED_ATTR(false, 2); MPPO_FUSED_ATTR(true, 2);
-#undef MPPO_FUSED_ATTR
-  MPPO_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(fused_mlp_kernel<false, false, 1, true, true, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  MPPO_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(fused_mlp_kernel<false, false, 2, true, true, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  MPPO_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(fused_mlp_kernel<true, true, 1, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-  MPPO_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(fused_mlp_kernel<true, true, 2, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+  for (const RowKernel& k : kRowKernels)
+    MPPO_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k.fn), hipFuncAttributeMaxDynamicSharedMemorySize, k.rt == 2 ? 160 * 1024 : (int)smem));
   return MPPO_OK;
 }
 
@@ -997,7 +676,7 @@ int32_t fused_forward_backward(const mppo_net_t& net, const float* params, const
 #else
   a.skip = 0;
 #endif
-  const size_t smem = fused_smem_bytes(net.O, net.A, net.H);
+  size_t smem = fused_smem_bytes(net.O, net.A, net.H);
   static thread_local size_t attr_for = 0;
   if (smem > 64 * 1024 && attr_for < smem) {
     MPPO_TRY(fused_set_smem(smem));
@@ -1005,54 +684,40 @@ int32_t fused_forward_backward(const mppo_net_t& net, const float* params, const
   }
   MPPO_REQUIRE(!pre || (w2t && idx), "fused_forward_backward: pre-gathered rows need the shadow copies and a permutation");
   if (pre) { a.xpre = pre->cur; a.xnext = pre->next; a.idx_next = pre->idx_next; }
-  if (fused_rows_per_workgroup(net, mb, pre != nullptr) == 2 * FRT) {  // 32-row tiles: one round of workgroups instead of two
-    const size_t smem2 = fused_smem_bytes(net.O, net.A, net.H, 2);
+  const int rt = fused_rows_per_workgroup(net, mb, pre != nullptr) / FRT;  // 2: 32-row tiles, one round of workgroups instead of two
+  const dim3 grid(cdiv(mb, rt * FRT), pre && pre->idx_next ? 4 : 2), block(2 * net.H);
+  RowKernelFn fn;
+  const char* what = "fused_mlp_kernel";
+  if (rt == 2) {
     if (attr_for < smem) { MPPO_TRY(fused_set_smem(smem)); attr_for = smem; }  // (sets the 32-row instantiations' limit too)
-    const dim3 grid2(cdiv(mb, 2 * FRT), pre->idx_next ? 4 : 2), block2(2 * net.H);
-    if (net.A > 16) hipLaunchKernelGGL((fused_mlp_kernel<false, false, 2, true, true, 2>), grid2, block2, smem2, stream, a);
-    else hipLaunchKernelGGL((fused_mlp_kernel<false, false, 1, true, true, 2>), grid2, block2, smem2, stream, a);
-    MPPO_CHECK_LAUNCH("fused_mlp_kernel<32 rows>");
-    return MPPO_OK;
-  }
-  const dim3 grid(cdiv(mb, FRT), pre && pre->idx_next ? 4 : 2), block(2 * net.H);
-  if (pre && g.frag && bf16_rowpass_supported(net)) {  // the engine's minibatch loop of a bf16 network: the kernel designed for it (fused_bf16.h)
-    const size_t sb = bf16_rowpass_smem_bytes(net.O, net.A, net.H);
+    smem = fused_smem_bytes(net.O, net.A, net.H, 2);
+    fn = row_kernel(kRoleTrain, false, net.A, true, true, 2);
+    what = "fused_mlp_kernel<32 rows>";
+  } else if (pre && g.frag && bf16_rowpass_supported(net)) {  // the engine's minibatch loop of a bf16 network: the kernel designed for it (fused_bf16.h)
+    smem = bf16_rowpass_smem_bytes(net.O, net.A, net.H);
 #ifdef MPPO_TRACE_BF16
     fprintf(stderr, "[trace] bf16_rowpass_kernel mb=%d\n", mb);
 #endif
     const bool exact = ((net.O + 31) & ~31) == 32 * kBf16RowpassNS1 && net.H == 256;  // the registers are filled exactly: no zero stages, no selects
-    if (net.A > 16) {
-      if (exact) hipLaunchKernelGGL((bf16_rowpass_kernel<2, kBf16RowpassNS1, true>), grid, block, sb, stream, a);
-      else hipLaunchKernelGGL((bf16_rowpass_kernel<2, kBf16RowpassNS1, false>), grid, block, sb, stream, a);
-    } else {
-      if (exact) hipLaunchKernelGGL((bf16_rowpass_kernel<1, kBf16RowpassNS1, true>), grid, block, sb, stream, a);
-      else hipLaunchKernelGGL((bf16_rowpass_kernel<1, kBf16RowpassNS1, false>), grid, block, sb, stream, a);
-    }
-    MPPO_CHECK_LAUNCH("bf16_rowpass_kernel");
-    return MPPO_OK;
-  }
-#define MPPO_FUSED_GO(B, T) do { if (pre) hipLaunchKernelGGL((fused_mlp_kernel<B, false, T, true, true>), grid, block, smem, stream, a); \
-                                else if (w2t) hipLaunchKernelGGL((fused_mlp_kernel<B, false, T, true>), grid, block, smem, stream, a); \
-                                else hipLaunchKernelGGL((fused_mlp_kernel<B, false, T, false>), grid, block, smem, stream, a); } while (0)
-  if (net.A > 16) {
-    if (net.bf16) MPPO_FUSED_GO(true, 2); else MPPO_FUSED_GO(false, 2);
+    fn = row_kernel(kRoleBf16Train, true, net.A, true, true, 1, exact);
+    what = "bf16_rowpass_kernel";
   } else {
-    if (net.bf16) MPPO_FUSED_GO(true, 1); else MPPO_FUSED_GO(false, 1);
+    fn = row_kernel(kRoleTrain, net.bf16, net.A, w2t, pre != nullptr, 1);
   }
-#undef MPPO_FUSED_GO
-  MPPO_CHECK_LAUNCH("fused_mlp_kernel");
+  MPPO_REQUIRE(fn, "fused_forward_backward: no %s instantiation for this launch", what);
+  hipLaunchKernelGGL(fn, grid, block, smem, stream, a);
+  MPPO_CHECK_LAUNCH(what);
   return MPPO_OK;
 }
 
-// The first optimizer step of an update has no previous launch to gather its rows: the gather role alone (every workgroup of a PRE
-// <ROLLOUT, PRE> instantiation).
+// The first optimizer step of an update has no previous launch to gather its rows: the gather role alone.
 int32_t fused_gather_rows(const mppo_net_t& net, const mppo_batch_t& batch, const int* idx, int mb, float* dst, hipStream_t stream) {
   MPPO_REQUIRE(idx && dst && batch.obs, "fused_gather_rows: null argument");
   FusedArgs a{};
   a.mb = mb; a.O = net.O; a.OP = net.OP; a.A = net.A; a.H = net.H; a.b = batch; a.idx_next = idx; a.xnext = dst;
-  if (net.bf16) hipLaunchKernelGGL((fused_mlp_kernel<true, true, 1, true, true>), dim3(cdiv(mb, FRT), 2), dim3(256), 0, stream, a);  // (bf16 quads)
-  else hipLaunchKernelGGL((fused_mlp_kernel<false, true, 1, true, true>), dim3(cdiv(mb, FRT), 2), dim3(256), 0, stream, a);
-  MPPO_CHECK_LAUNCH("fused_mlp_kernel<gather>");
+  const RowKernelFn fn = net.bf16 ? gather_rows_kernel<true> : gather_rows_kernel<false>;  // (bf16 network: 8-byte quads)
+  hipLaunchKernelGGL(fn, dim3(cdiv(mb, FRT), 2), dim3(256), 0, stream, a);
+  MPPO_CHECK_LAUNCH("gather_rows_kernel");
   return MPPO_OK;
 }
 
@@ -1076,15 +741,9 @@ int32_t fused_policy_forward(const mppo_net_t& net, const float* params, int n, 
   }
   const dim3 grid(cdiv(n, FRT), noise && value ? 2 : 1);  // (noise without value: the actor alone)
   const dim3 block(2 * net.H);
-  if (net.A > 16) {
-    if (use_frag) hipLaunchKernelGGL((fused_mlp_kernel<true, true, 2, true>), grid, block, smem, stream, a);
-    else if (net.bf16) hipLaunchKernelGGL((fused_mlp_kernel<true, true, 2>), grid, block, smem, stream, a);
-    else hipLaunchKernelGGL((fused_mlp_kernel<false, true, 2>), grid, block, smem, stream, a);
-  } else {
-    if (use_frag) hipLaunchKernelGGL((fused_mlp_kernel<true, true, 1, true>), grid, block, smem, stream, a);
-    else if (net.bf16) hipLaunchKernelGGL((fused_mlp_kernel<true, true, 1>), grid, block, smem, stream, a);
-    else hipLaunchKernelGGL((fused_mlp_kernel<false, true, 1>), grid, block, smem, stream, a);
-  }
+  const RowKernelFn fn = row_kernel(kRoleRollout, net.bf16, net.A, use_frag, false, 1);
+  MPPO_REQUIRE(fn, "fused_policy_forward: no fused_mlp_kernel<rollout> instantiation for this launch");
+  hipLaunchKernelGGL(fn, grid, block, smem, stream, a);
   MPPO_CHECK_LAUNCH("fused_mlp_kernel<rollout>");
   return MPPO_OK;
 }

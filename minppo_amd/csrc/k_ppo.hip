@@ -877,24 +877,34 @@ extern "C" int32_t mppo_minibatch_path(const mppo_net_t* net, const mppo_batch_t
 
 extern "C" size_t mppo_grad_ws_bytes(const mppo_net_t* net, int32_t mb) { return net ? grad_bufs_floats(*net, mb) * sizeof(float) : 0; }
 
+// Argument checks shared by mppo_minibatch_rowpass / _grad and their _shadow forms (`who` names the entry point in every message; the gradient
+// entries - `grad_entry` - additionally need the gradient buffer and every batch field); on success *gb is the carved workspace.
+static int32_t minibatch_args(const char* who, bool grad_entry, bool shadow, const mppo_net_t* net, const float* params, const mppo_batch_t* batch, int32_t mb,
+                              const float* adv_stat, const mppo_loss_cfg_t* lc, const float* grad, void* ws, size_t ws_bytes, GradBufs* gb) {
+  MPPO_TRY(check_net(net));
+  MPPO_REQUIRE(params && batch && adv_stat && lc && (grad || !grad_entry) && ws && mb >= 1, "%s: null argument or mb < 1", who);
+  if (grad_entry) {
+    MPPO_REQUIRE(batch->obs && batch->action && batch->value && batch->log_prob && batch->adv && batch->target, "%s: null batch field", who);
+    MPPO_REQUIRE(batch->obs_ld >= net->O && batch->act_ld >= net->A, "%s: leading dimensions too small", who);
+  }
+  if (ws_bytes < mppo_grad_ws_bytes(net, mb)) return fail(MPPO_ENOMEM, "%s: workspace %zu < %zu bytes", who, ws_bytes, mppo_grad_ws_bytes(net, mb));
+  *gb = carve_grad(*net, mb, static_cast<float*>(ws));
+  gb->w2t_valid = shadow;
+  return MPPO_OK;
+}
+
 extern "C" int32_t mppo_minibatch_grad(const mppo_net_t* net, const float* params, const mppo_batch_t* batch, const int32_t* idx, int32_t mb,
                                        const float* adv_stat, float inv_count, const mppo_loss_cfg_t* lc, float* grad, float* loss4, void* ws,
                                        size_t ws_bytes, void* stream) {
-  MPPO_TRY(check_net(net));
-  MPPO_REQUIRE(params && batch && adv_stat && lc && grad && ws && mb >= 1, "mppo_minibatch_grad: null argument or mb < 1");
-  MPPO_REQUIRE(batch->obs && batch->action && batch->value && batch->log_prob && batch->adv && batch->target, "mppo_minibatch_grad: null batch field");
-  MPPO_REQUIRE(batch->obs_ld >= net->O && batch->act_ld >= net->A, "mppo_minibatch_grad: leading dimensions too small");
-  if (ws_bytes < mppo_grad_ws_bytes(net, mb)) return fail(MPPO_ENOMEM, "mppo_minibatch_grad: workspace %zu < %zu bytes", ws_bytes, mppo_grad_ws_bytes(net, mb));
-  const GradBufs gb = carve_grad(*net, mb, static_cast<float*>(ws));
+  GradBufs gb;
+  MPPO_TRY(minibatch_args("mppo_minibatch_grad", true, false, net, params, batch, mb, adv_stat, lc, grad, ws, ws_bytes, &gb));
   return minibatch_grad(*net, params, *batch, idx, mb, adv_stat, inv_count, *lc, grad, loss4, nullptr, gb, static_cast<hipStream_t>(stream));
 }
 
 extern "C" int32_t mppo_minibatch_rowpass(const mppo_net_t* net, const float* params, const mppo_batch_t* batch, const int32_t* idx, int32_t mb,
                                           const float* adv_stat, float inv_count, const mppo_loss_cfg_t* lc, void* ws, size_t ws_bytes, void* stream) {
-  MPPO_TRY(check_net(net));
-  MPPO_REQUIRE(params && batch && adv_stat && lc && ws && mb >= 1, "mppo_minibatch_rowpass: null argument or mb < 1");
-  if (ws_bytes < mppo_grad_ws_bytes(net, mb)) return fail(MPPO_ENOMEM, "mppo_minibatch_rowpass: workspace %zu < %zu bytes", ws_bytes, mppo_grad_ws_bytes(net, mb));
-  const GradBufs gb = carve_grad(*net, mb, static_cast<float*>(ws));
+  GradBufs gb;
+  MPPO_TRY(minibatch_args("mppo_minibatch_rowpass", false, false, net, params, batch, mb, adv_stat, lc, nullptr, ws, ws_bytes, &gb));
   int nblk = 0;
   return minibatch_rowpass(*net, params, *batch, idx, mb, adv_stat, inv_count, *lc, gb, &nblk, nullptr, static_cast<hipStream_t>(stream));
 }
@@ -933,11 +943,8 @@ extern "C" int32_t mppo_shadow_refresh(const mppo_net_t* net, const float* param
 
 extern "C" int32_t mppo_minibatch_rowpass_shadow(const mppo_net_t* net, const float* params, const mppo_batch_t* batch, const int32_t* idx, int32_t mb,
                                                  const float* adv_stat, float inv_count, const mppo_loss_cfg_t* lc, void* ws, size_t ws_bytes, void* stream) {
-  MPPO_TRY(check_net(net));
-  MPPO_REQUIRE(params && batch && adv_stat && lc && ws && mb >= 1, "mppo_minibatch_rowpass_shadow: null argument or mb < 1");
-  if (ws_bytes < mppo_grad_ws_bytes(net, mb)) return fail(MPPO_ENOMEM, "mppo_minibatch_rowpass_shadow: workspace %zu < %zu bytes", ws_bytes, mppo_grad_ws_bytes(net, mb));
-  GradBufs gb = carve_grad(*net, mb, static_cast<float*>(ws));
-  gb.w2t_valid = true;
+  GradBufs gb;
+  MPPO_TRY(minibatch_args("mppo_minibatch_rowpass_shadow", false, true, net, params, batch, mb, adv_stat, lc, nullptr, ws, ws_bytes, &gb));
   int nblk = 0;
   return minibatch_rowpass(*net, params, *batch, idx, mb, adv_stat, inv_count, *lc, gb, &nblk, nullptr, static_cast<hipStream_t>(stream));
 }
@@ -945,13 +952,8 @@ extern "C" int32_t mppo_minibatch_rowpass_shadow(const mppo_net_t* net, const fl
 extern "C" int32_t mppo_minibatch_grad_shadow(const mppo_net_t* net, const float* params, const mppo_batch_t* batch, const int32_t* idx, int32_t mb,
                                               const float* adv_stat, float inv_count, const mppo_loss_cfg_t* lc, float* grad, float* loss4, void* ws,
                                               size_t ws_bytes, void* stream) {
-  MPPO_TRY(check_net(net));
-  MPPO_REQUIRE(params && batch && adv_stat && lc && grad && ws && mb >= 1, "mppo_minibatch_grad_shadow: null argument or mb < 1");
-  MPPO_REQUIRE(batch->obs && batch->action && batch->value && batch->log_prob && batch->adv && batch->target, "mppo_minibatch_grad_shadow: null batch field");
-  MPPO_REQUIRE(batch->obs_ld >= net->O && batch->act_ld >= net->A, "mppo_minibatch_grad_shadow: leading dimensions too small");
-  if (ws_bytes < mppo_grad_ws_bytes(net, mb)) return fail(MPPO_ENOMEM, "mppo_minibatch_grad_shadow: workspace %zu < %zu bytes", ws_bytes, mppo_grad_ws_bytes(net, mb));
-  GradBufs gb = carve_grad(*net, mb, static_cast<float*>(ws));
-  gb.w2t_valid = true;
+  GradBufs gb;
+  MPPO_TRY(minibatch_args("mppo_minibatch_grad_shadow", true, true, net, params, batch, mb, adv_stat, lc, grad, ws, ws_bytes, &gb));
   return minibatch_grad(*net, params, *batch, idx, mb, adv_stat, inv_count, *lc, grad, loss4, nullptr, gb, static_cast<hipStream_t>(stream));
 }
 

@@ -97,7 +97,7 @@ struct GradBufs {
   float *dza[kMaxHidden], *dzc[kMaxHidden];                    // d loss / d pre-activation of every hidden layer
   float* xmb;  // [mb, OP]: the minibatch observations, laid out contiguously by the first forward GEMM
   // Second observation buffer (k-quad layout like xmb in the fused path): the engine's row pass of optimizer step s gathers the
-  // rows of step s + 1 on workgroups of its own launch (k_fused.hip, XPre) - they depend on the permutation only, not on the
+  // rows of step s + 1 on workgroups of its own launch (k_fused.hip rowpass_tile, XPre) - they depend on the permutation only, not on the
   // parameters - so that step s + 1 starts from a contiguous tile instead of the index -> row chain; xmb and xmb2 alternate.
   float* xmb2;
   // Shadow copy of the second-layer weights, transposed: w2t[net][n][k] = W2_net[k][n] (net 0 actor, 1 critic).  The backward
@@ -117,7 +117,7 @@ struct GradBufs {
 };
 // one pre-gathered minibatch (xmb / xmb2): the observation rows in k-quad layout [mbp / 4][OP][4], and behind them the per-row scalars of the
 // loss in the same layout, [mbp / 4][A + 4][4]: columns 0 .. A - 1 the action, A old log_prob, A + 1 advantage, A + 2 old value, A + 3 target
-// (k_fused.hip: gathered by the same workgroups as the rows, read by the next step's row tiles as whole float4s - no index -> row chain)
+// (fused_common.h gather_rows_tile: gathered by the same workgroups as the rows, read by the next step's row tiles as whole float4s - no index -> row chain)
 __host__ __device__ inline size_t xquad_obs_floats(int OP, int mb) { return pad4(pad16((size_t)mb) * OP); }
 inline size_t xquad_floats(const mppo_net_t& net, int mb) { return xquad_obs_floats(net.OP, mb) + pad4(pad16((size_t)mb) * (net.A + 4)); }
 inline size_t grad_bufs_floats(const mppo_net_t& net, int mb) {
@@ -202,7 +202,8 @@ inline ShadowRef make_shadow_ref(const mppo_net_t& net, const GradBufs& g) {
 }
 int32_t gae_launch(int T, int N, float gamma, float lam, const float* reward, const float* value, const unsigned char* done, const float* last_val, float* adv,
                    float* target, hipStream_t stream);
-// k_fused.hip: row-local forward + backward of one minibatch in a single launch (falls back to the layer-wise path when unsupported)
+// k_fused.hip: row-local forward + backward of one minibatch in a single launch (falls back to the layer-wise path when unsupported);
+// the LDS layout behind fused_smem_bytes is FusedLds (fused_common.h)
 bool fused_supported(const mppo_net_t& net, const mppo_batch_t& b);
 int fused_rows_per_workgroup(const mppo_net_t& net, int mb, bool pre);  // 16, or 32 where that turns two rounds of workgroups into one (k_fused.hip)
 bool fused_rollout_supported(const mppo_net_t& net, const float* obs, int obs_ld);

@@ -447,14 +447,14 @@ def test_gemm_batch_variants(be):
     np.testing.assert_allclose(s[Min], dZ.sum(0), atol=2e-5)
 
 
-@pytest.mark.parametrize("bf16", [0, 1])
-def test_shadow_copies_change_nothing_but_the_layout_of_one_operand(be, bf16):
-    """(bf16 = 1: additionally the bf16 fragment-order copies of W1, W2, W2^T that the bf16 row pass then reads instead of
+@pytest.mark.parametrize("bf16,A", [pytest.param(0, 5, id="0"), pytest.param(1, 5, id="1"), pytest.param(0, 20, id="0-A20"), pytest.param(1, 20, id="1-A20")])
+def test_shadow_copies_change_nothing_but_the_layout_of_one_operand(be, bf16, A):
+    """(A = 20: the instantiations with two 16-wide output tiles.)  (bf16 = 1: additionally the bf16 fragment-order copies of W1, W2, W2^T that the bf16 row pass then reads instead of
     converting the float weights in its GEMM loops - same rounding, same values, same MFMAs.)
     The W2^T shadow copies inside the gradient workspace (include/minppo_hip.h): mppo_minibatch_grad_shadow == mppo_minibatch_grad
     bit for bit (the backward product issues the same MFMAs on the same values), mppo_clip_adam_shadow == mppo_clip_adam bit
     for bit on params / m / v, and after it the copies equal a fresh mppo_shadow_refresh of the new parameters."""
-    O, A, H, B, mb = 37, 5, 64, 96, 48
+    O, H, B, mb = 37, 64, 96, 48
     OP = (O + 3) // 4 * 4
     rng = np.random.default_rng(5)
     net = nat.Net(O, OP, A, H, 1, bf16)
@@ -532,13 +532,14 @@ def test_shadow_copies_change_nothing_but_the_layout_of_one_operand(be, bf16):
             assert frag[per_net + KP * H + H * H + frag_index(k2, n2, H)] == bf16_bits(W2c[n2, k2])
 
 
-@pytest.mark.parametrize("bf16,mb", [(0, 48), (0, 42), (1, 42)])
-def test_pregathered_rows_change_nothing(be, bf16, mb):
+@pytest.mark.parametrize("bf16,mb,A", [pytest.param(0, 48, 5, id="0-48"), pytest.param(0, 42, 5, id="0-42"), pytest.param(1, 42, 5, id="1-42"),
+                                       pytest.param(0, 42, 20, id="0-42-A20"), pytest.param(1, 42, 20, id="1-42-A20")])
+def test_pregathered_rows_change_nothing(be, bf16, mb, A):
     """The engine's minibatch loop (include/minppo_hip.h, "Pre-gathered rows"): the row pass of one step gathers the next step's
     observation rows on extra workgroups of its own launch.  mppo_minibatch_grad_pre == mppo_minibatch_grad bit for bit, for a step
     whose rows were gathered by mppo_gather_rows and for the following step whose rows were gathered inside the first step's
-    launch; minibatch sizes that are not a multiple of the 16-row tile (zero rows behind the minibatch) included."""
-    O, A, H, B = 37, 5, 64, 96
+    launch; minibatch sizes that are not a multiple of the 16-row tile (zero rows behind the minibatch) and A = 20 (two 16-wide output tiles) included."""
+    O, H, B = 37, 64, 96
     OP = (O + 3) // 4 * 4
     rng = np.random.default_rng(11)
     net = nat.Net(O, OP, A, H, 1, bf16)

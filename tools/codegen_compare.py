@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
-"""tools/codegen_compare.py <dir of tree A> <dir of tree B> - env_kernel instantiations of k_physics.hip in two trees, function by function: the
-instruction streams (comments dropped, local labels renumbered) and the compiler's resource remarks.  Each directory holds `k_physics.s` and
-`remarks.txt` of one tree:
+"""tools/codegen_compare.py <dir of tree A> <dir of tree B> [<source stem> [<kernel-name pattern>]] - kernel instantiations of one source file in
+two trees, function by function: the instruction streams (comments dropped, local labels renumbered) and the compiler's resource remarks.
+<source stem> defaults to k_physics and <kernel-name pattern> (a regular expression over the kernels' unqualified names) to env_kernel; e.g.
+`k_fused 'fused_mlp_kernel|bf16_rowpass_kernel|gather_rows_kernel'` compares the row-pass kernels (with that file's build flags, -ffp-contract=fast,
+in the command below).  Each directory holds `<source stem>.s` and `remarks.txt` of one tree:
 
     hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -I<tree>/minppo_amd/csrc -I<tree>/include -Rpass-analysis=kernel-resource-usage \\
           --cuda-device-only -S <tree>/minppo_amd/csrc/k_physics.hip -o <dir>/k_physics.s 2> <dir>/remarks.txt
@@ -9,15 +11,23 @@ instruction streams (comments dropped, local labels renumbered) and the compiler
 (cross-compiles: no GPU needed).  Kernels are matched by name; where tree B's specialised kernels carry one template argument more than tree A's (16 -> 17:
 the number of ball joints in front of cparam), an instantiation of A is matched with the one of B that has a 0 there.  A stream that differs only in the
 offsets of kernel-argument loads and the kernel-argument size (the argument struct grew: what lies behind it moved) is reported as such.
-profiles/ball_joints_codegen.txt and profiles/reset_noise_codegen.txt are its output."""
+Other kernels are labelled by their demangled names (c++filt) and matched by name, or through RENAMED below.
+profiles/ball_joints_codegen.txt, profiles/reset_noise_codegen.txt and profiles/rowpass_split_codegen.txt are its output."""
 import re
+import subprocess
 import sys
+
+SOURCE = sys.argv[3] if len(sys.argv) > 3 else "k_physics"
+KERNELS = sys.argv[4] if len(sys.argv) > 4 else "env_kernel"
+# kernels of tree A that tree B has under another name: the gather-only launch used to be the <ROLLOUT, PRE> instantiations of fused_mlp_kernel
+RENAMED = {"_ZN4mppo16fused_mlp_kernelILb0ELb1ELi1ELb1ELb1ELi1EEEvNS_9FusedArgsE": "_ZN4mppo18gather_rows_kernelILb0EEEvNS_9FusedArgsE",
+           "_ZN4mppo16fused_mlp_kernelILb1ELb1ELi1ELb1ELb1ELi1EEEvNS_9FusedArgsE": "_ZN4mppo18gather_rows_kernelILb1EEEvNS_9FusedArgsE"}
 
 
 def funcs(path):
     out, cur, body = {}, None, []
     for line in open(path):
-        m = re.match(r"^(_ZN4mppo10env_kernelI\S+):\s", line)
+        m = re.match(r"^(_ZN4mppo\d+(?:" + KERNELS + r")I\S+):\s", line)
         if m:
             cur, body = m.group(1), []
             continue
@@ -63,7 +73,14 @@ def label(name):
     if d:
         return f"StaticModel{d[0]} mode {d[1]}"
     m = re.search(r"(Runtime\w*Model)ELi(\d)E", name)
-    return f"{m.group(1)} mode {m.group(2)}" if m else name
+    return f"{m.group(1)} mode {m.group(2)}" if m else demangled(name)
+
+
+def demangled(name):
+    try:
+        return subprocess.run(["c++filt", name], capture_output=True, text=True).stdout.strip().replace("void mppo::", "").replace("(mppo::FusedArgs)", "") or name
+    except FileNotFoundError:
+        return name
 
 
 def verdict(a, b):
@@ -78,19 +95,21 @@ def verdict(a, b):
     return "DIFFER", False
 
 
-old, new = funcs(sys.argv[1] + "/k_physics.s"), funcs(sys.argv[2] + "/k_physics.s")
+old, new = funcs(f"{sys.argv[1]}/{SOURCE}.s"), funcs(f"{sys.argv[2]}/{SOURCE}.s")
 ro, rn = remarks(sys.argv[1] + "/remarks.txt"), remarks(sys.argv[2] + "/remarks.txt")
 keys = ("VGPRs", "AGPRs", "TotalSGPRs", "ScratchSize [bytes/lane]", "LDS Size [bytes/block]", "Occupancy [waves/SIMD]", "VGPRs Spill", "SGPRs Spill")
 short = lambda r: " ".join(f"{k.split(' [')[0].replace(' ', '')}={r.get(k, '?')}" for k in keys)
 newby = {dims(n): n for n in new if dims(n)}
-print("# env_kernel instantiations of k_physics.hip, parent commit against this tree: hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off")
+env = KERNELS == "env_kernel"
+flags = "-ffp-contract=off" if env else "-ffp-contract=fast"
+print(f"# {KERNELS.replace('|', ', ')} instantiations of {SOURCE}.hip, parent commit against this tree: hipcc --offload-arch=gfx950 -O3 -std=c++17 {flags}")
 print("# --cuda-device-only -S -Rpass-analysis=kernel-resource-usage; instruction streams compared line by line after dropping comments and")
 print("# renumbering local labels.")
 same = {0: [0, 0], 1: [0, 0], 2: [0, 0]}
 matched = set()
 for n in sorted(old, key=label):
     d = dims(n)
-    nn = n if n in new else None
+    nn = n if n in new else RENAMED.get(n) if RENAMED.get(n) in new else None
     if nn is None and d is not None and len(d[0]) == 16:  # (tree B's names carry the number of ball joints)
         nn = newby.get((d[0][:15] + (0,) + d[0][15:], d[1]))
     if nn is None:
@@ -98,13 +117,16 @@ for n in sorted(old, key=label):
         continue
     matched.add(nn)
     what, eq = verdict(old[n], new[nn])
-    mode = int(label(n)[-1])
+    mode = int(label(n)[-1]) if env else 0
     same[mode][0] += eq
     same[mode][1] += 1
-    print(f"{label(n)}\n   parent: {len(old[n])} instructions/directives  {short(ro.get(n, {}))}\n   new   : {len(new[nn])} instructions/directives  {short(rn.get(nn, {}))}\n"
+    print(f"{label(n)}{'' if nn == n else ' -> ' + label(nn)}\n   parent: {len(old[n])} instructions/directives  {short(ro.get(n, {}))}\n   new   : {len(new[nn])} instructions/directives  {short(rn.get(nn, {}))}\n"
           f"   instruction streams {what}")
 for n in sorted(set(new) - matched, key=label):
     print(f"{label(n)} (new)\n   new   : {len(new[n])} instructions/directives  {short(rn.get(n, {}))}")
-for mode, (s, t) in same.items():
-    print(f"# mode {mode} ({('reset', 'step', 'probe')[mode]}): {s} of {t} instantiations identical to the parent's (kernel-argument offsets aside)")
-print("# scratch bytes per lane, every env_kernel of the new tree:", sorted({rn[n].get("ScratchSize [bytes/lane]") for n in rn if "env_kernel" in n}))
+if env:
+    for mode, (s, t) in same.items():
+        print(f"# mode {mode} ({('reset', 'step', 'probe')[mode]}): {s} of {t} instantiations identical to the parent's (kernel-argument offsets aside)")
+    print("# scratch bytes per lane, every env_kernel of the new tree:", sorted({rn[n].get("ScratchSize [bytes/lane]") for n in rn if "env_kernel" in n}))
+else:
+    print(f"# {same[0][0]} of {same[0][1]} instantiations identical to the parent's (kernel-argument offsets aside)")

@@ -480,6 +480,34 @@ int32_t mppo_eval_accumulate(int32_t N, int32_t first, const float* reward, cons
                              int32_t A, int32_t R, float* traj_row, void* stream);
 int32_t mppo_eval_reduce(int32_t N, int32_t K, const void* acc, mppo_eval_result_t* result, void* stream);
 
+/* ---- rendering --------------------------------------------------------------------------------------------------------------
+ * Frames of a rollout as images, ray-cast on the device (csrc/k_render.hip): what the reference leaves to MuJoCo's renderer
+ * (env.render, minppo/env.py:264-333).  A scene is opened from the scene blob of minppo_amd/render.py (scene_blob: the kinematic
+ * tree, the visuals, hull face planes, the ground plane, the cameras; layout in csrc/render.h), given in host memory (validated
+ * there: a malformed blob is MPPO_EMODEL with a message) and in device memory (what the kernels read; it must outlive the handle).
+ *
+ * mppo_render draws F frames with one camera: two launches on `stream` (the visuals' and the camera's world poses from qpos,
+ * then one ray per pixel), no synchronisation; the scratch for the poses belongs to the handle and grows on demand (a device
+ * allocation on the first call and when a later call needs more: one render at a time per handle).  `qpos` is device memory,
+ * frame f at qpos + f * q_ld: q_ld = nq for packed joint positions, q_ld = rec_dim to draw straight from state records or an
+ * evaluation's trajectory rows (qpos is at offset 0 of both).  Outputs are device memory; any may be NULL.
+ * The image: MuJoCo's camera convention (looks along -z, +x right, +y up, vertical fovy), row 0 at the top, one ray through every
+ * pixel centre, no anti-aliasing; Lambert shading from one fixed directional light plus ambient, hard shadows, a two-tone 1 m
+ * checker on the ground plane, a constant sky; meshes are drawn as their convex hulls. */
+typedef struct mppo_scene mppo_scene_t;
+typedef struct mppo_scene_dims { int32_t nq, nbody, ngeom, ncam, has_plane; } mppo_scene_dims_t;
+int32_t mppo_scene_open(const void* host_blob, size_t nbytes, const void* dev_blob, mppo_scene_t** out);
+int32_t mppo_scene_close(mppo_scene_t* s);
+int32_t mppo_scene_get_dims(const mppo_scene_t* s, mppo_scene_dims_t* out);
+typedef struct mppo_render_out {   /* any pointer may be NULL */
+  uint8_t* rgb;      /* [F, H, W, 3] */
+  float*   depth;    /* [F, H, W] distance along the unit ray; +inf on a miss */
+  int32_t* geom_id;  /* [F, H, W] visual index; ngeom = ground plane; -1 = miss */
+  float*   geom_pose;/* [F, ngeom, 12] world position + row-major rotation of every visual */
+} mppo_render_out_t;
+int32_t mppo_render(const mppo_scene_t* s, int32_t F, const float* qpos, int32_t q_ld, int32_t camera, int32_t width, int32_t height,
+                    const mppo_render_out_t* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

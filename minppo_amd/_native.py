@@ -92,6 +92,14 @@ class EvalResultRaw(C.Structure):  # mppo_eval_result_t (minppo_amd.evaluate.Eva
         (n, C.c_double) for n in ("ret_sum", "ret_sumsq", "ret_min", "ret_max", "survivor_ret_sum", "reward_sum")]
 
 
+class SceneDims(C.Structure):
+    _fields_ = [(n, c_i32) for n in ("nq", "nbody", "ngeom", "ncam", "has_plane")]
+
+
+class RenderOut(C.Structure):  # mppo_render_out_t: device pointers, any may be null
+    _fields_ = [(n, c_vp) for n in ("rgb", "depth", "geom_id", "geom_pose")]
+
+
 EVAL_ACC_SLOTS = 10  # include/minppo_hip.h: the accumulators of mppo_eval_accumulate / _reduce are 10 * N 8-byte words
 
 P = C.POINTER
@@ -166,6 +174,10 @@ SIGNATURES = {
     "mppo_evaluate": (c_i32, [c_vp, P(Net), c_vp, P(EvalCfg), c_vp, c_sz, c_vp, c_vp, c_vp]),
     "mppo_eval_accumulate": (c_i32, [c_i32, c_i32, c_vp, c_vp, P(EnvMetrics), c_vp, c_vp, c_i32, c_i32, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp]),
     "mppo_eval_reduce": (c_i32, [c_i32, c_i32, c_vp, c_vp, c_vp]),
+    "mppo_scene_open": (c_i32, [c_vp, c_sz, c_vp, P(c_vp)]),
+    "mppo_scene_close": (c_i32, [c_vp]),
+    "mppo_scene_get_dims": (c_i32, [c_vp, P(SceneDims)]),
+    "mppo_render": (c_i32, [c_vp, c_i32, c_vp, c_i32, c_i32, c_i32, c_i32, P(RenderOut), c_vp]),
 }
 
 UNCHECKED = {"mppo_last_error", "mppo_abi_version", "mppo_param_count", "mppo_policy_ws_bytes", "mppo_grad_ws_bytes",

@@ -160,6 +160,9 @@ class EvaluationConfig:
     deterministic: bool = field(default=True)
     record_envs: int = field(default=0)
     trajectory_path: str = field(default="")
+    # `video_path` renders recorded environment 0's trajectory (camera and image size: `visualization`) and writes it as a video
+    # (.npz / .avi / .mp4: minppo_amd.render.write_video) - train, then watch it.  Needs record_envs >= 1.
+    video_path: str = field(default="")
 
 
 @dataclass

@@ -12,7 +12,8 @@ assigned as in any Brax humanoid, or `environment.reset_noise_scale`) they are t
 int seed or a `uint32[2]` key and splits it over the environments (`train.py:135`), `step(es, action, rng)` takes a `uint32[2]` key or
 the `[N, 2]` per-environment keys the reference passes (`train.py:164-165`), and an environment that is reset starts from
 `qpos0 + U(-s, s)`, `qvel = U(-s, s)` (`env.py:115-121`) in the conventions of `minppo_amd/jaxrng.py` (`mppo_env_reinit`).
-The debug viewer (`env.py:264-333`) is out of scope (needs the MuJoCo renderer and ffmpeg); `main` says so.
+`render(states, camera, width, height)` is Brax's `env.render` with the engine's own ray caster behind it (minppo_amd/render.py), and `main` is
+the reference's debug viewer (`env.py:264-333`): a random-action rollout of one environment, rendered and written as a video.
 """
 
 from __future__ import annotations
@@ -24,7 +25,7 @@ from typing import Any, NamedTuple, Optional, Sequence
 import numpy as np
 
 from minppo_amd import _native as nat
-from minppo_amd.config import Config, load_config_from_cli
+from minppo_amd.config import Config, load_config_from_cli, require
 from minppo_amd.model import CompiledModel, load_model
 from minppo_amd.train import resolve_model, reward_cfg
 
@@ -92,6 +93,8 @@ class HumanoidEnv:
         if type(self).reset_noise_scale == 0.0 and config.environment.reset_noise_scale > 0:
             self.reset_noise_scale = float(config.environment.reset_noise_scale)
         self._have_reset = False
+        self._camera_name = config.visualization.camera_name
+        self._renderer = None
 
     # -- PipelineEnv attributes ------------------------------------------------
     @property
@@ -205,29 +208,93 @@ class HumanoidEnv:
         vel = (next_state[:, OP + nv] - state[:, OP + nv]) / self.dt
         return r.weights_ctrl_cost * ctrl + r.weights_original_pos_reward * pos_r + r.weights_velocity * vel + r.weights_is_healthy * healthy
 
+    # -- Brax's env.render(trajectory, camera, width, height) (what env.py:322-329 calls) ------------------------------------
+    def render(self, states: Any, camera: Optional[str] = None, width: int = 640, height: int = 480, env_index: int = 0) -> np.ndarray:
+        """Frames of a rollout, uint8 [F, H, W, 3], ray-cast on the device (minppo_amd/render.py).  `states`: a [F, nq] or [F, rec_dim]
+        tensor / array (joint positions, or state records - qpos leads a record), a sequence of `EnvState`s, or a sequence of
+        `pipeline_state` tensors [N, rec_dim]; of a batched state the environment `env_index` is drawn.  `camera=None`: the config's
+        `visualization.camera_name`."""
+        from minppo_amd.render import Renderer
+
+        t = self.torch
+        if camera is None:
+            camera = require(self._camera_name, "visualization.camera_name")
+        if isinstance(states, (list, tuple)):
+            if not states:
+                raise ValueError("render: no states")
+            rows = []
+            for s in states:
+                ps = s.pipeline_state if isinstance(s, EnvState) else s
+                ps = ps if hasattr(ps, "data_ptr") else t.as_tensor(np.asarray(ps, np.float32))
+                if ps.ndim == 2:
+                    if not 0 <= env_index < ps.shape[0]:
+                        raise ValueError(f"render: env_index {env_index} of {ps.shape[0]} environments")
+                    ps = ps[env_index]
+                rows.append(ps.to(device=self.device, dtype=t.float32))
+            q = t.stack(rows)
+        else:
+            q = states if hasattr(states, "data_ptr") else t.as_tensor(np.asarray(states, np.float32))
+            q = q.to(device=self.device, dtype=t.float32)
+        if q.ndim != 2 or q.shape[1] not in (self.cm.nq, self.dims.rec_dim):
+            raise ValueError(f"render: states must be [F, {self.cm.nq}] joint positions or [F, {self.dims.rec_dim}] state records, got {tuple(q.shape)}")
+        if self._renderer is None:  # (opened on the first render)
+            self._renderer = Renderer(self.cm, lib=self.lib, device=self.device)
+        return self._renderer.render(q, camera, width, height)
+
     def close(self) -> None:
+        if getattr(self, "_renderer", None) is not None:
+            self._renderer.close()
+            self._renderer = None
         if getattr(self, "_model", None):
             self.lib.model_close(self._model)
             self._model = None
 
 
 def main(args: Sequence[str] | None = None) -> None:
-    """The reference's `minppo env` renders a video with the MuJoCo renderer + ffmpeg (`env.py:264-333`); that viewer is
-    outside the training hot path and is not provided.  This entry point runs a short random-action rollout instead."""
+    """The reference's `minppo env` (`env.py:264-333`): runs `visualization.num_episodes` episodes of at most `max_steps` steps of one
+    environment under actions drawn from U(0, 1), collects the states of the first `video_length * fps` steps (fps = int(1 / env.dt)),
+    renders every `render_every`-th of them with `visualization.camera_name / width / height` and writes `video_save_path`.  As in the
+    reference, the video's fps is NOT divided by `render_every`."""
     import sys
 
     import torch
 
+    from minppo_amd.render import write_video
+
     logging.basicConfig(level=logging.INFO)
     config = load_config_from_cli(sys.argv[1:] if args is None else args)
+    vis = config.visualization
     env = HumanoidEnv(config)
-    logger.info("Initialized environment with action size %d (rendering is not available in this build)", env.action_size)
-    es = env.reset(num_envs=4)
-    total = torch.zeros(4, device=env.device)
-    for _ in range(int(config.visualization.max_steps)):
-        es = env.step(es, torch.rand(4, env.action_size, device=env.device))
-        total += es.reward
-    logger.info("random-action rollout: mean return %.3f over %d steps", float(total.mean()), int(config.visualization.max_steps))
+    try:
+        logger.info("Initialized environment with action size %d", env.action_size)
+        gen = torch.Generator(device="cpu").manual_seed(int(config.training.seed))
+        fps = int(1 / env.dt)
+        max_frames = int(vis.video_length * fps)
+        rollout = []
+        for episode in range(int(vis.num_episodes)):
+            seed = int(torch.randint(0, 2**31 - 1, (1,), generator=gen))
+            es = env.reset(seed if env.reset_noise_scale != 0 else None, num_envs=1)
+            total = 0.0
+            for _ in range(int(vis.max_steps)):
+                if len(rollout) < vis.video_length * fps:
+                    rollout.append(es.pipeline_state[0].clone())
+                action = torch.rand(1, env.action_size, generator=gen).to(env.device)
+                step_seed = int(torch.randint(0, 2**31 - 1, (1,), generator=gen))
+                es = env.step(es, action, step_seed if env.reset_noise_scale != 0 else None)
+                total += float(es.reward[0])
+                if bool(es.done[0]):
+                    break
+            logger.info("Episode %d total reward: %f", episode + 1, total)
+            if len(rollout) >= max_frames:
+                break
+        if not rollout:
+            raise ValueError(f"visualization.video_length = {vis.video_length} and max_steps = {vis.max_steps} leave no frame to render")
+        logger.info("Rendering video with %d frames at %d fps", len(rollout), fps)
+        images = env.render(torch.stack(rollout[::max(1, int(vis.render_every))]), camera=vis.camera_name, width=vis.width, height=vis.height)
+        write_video(vis.video_save_path, images, fps=fps)
+        logger.info("Video saved to %s", vis.video_save_path)
+    finally:
+        env.close()
 
 
 if __name__ == "__main__":

@@ -9,7 +9,9 @@ episodes that ended and the environments that never fell.
     python -m minppo_amd.cli evaluate <config> inference.model_path=trained_model.pkl [evaluation.num_envs=256 ...]
 
 prints one JSON line with the statistics; `evaluation.trajectory_path=run.npz evaluation.record_envs=4` also writes the joint
-trajectory of the first four environments (`qpos`, `qvel`, `action`, `reward`, `done`, and `dt`, `n_frames`) for a viewer elsewhere.
+trajectory of the first four environments (`qpos`, `qvel`, `action`, `reward`, `done`, and `dt`, `n_frames`); `evaluation.video_path=policy.avi`
+(with `record_envs >= 1`) renders recorded environment 0 - one frame per step, camera and size from `visualization` - and writes the video
+(minppo_amd/render.py: train, then watch it).
 """
 
 from __future__ import annotations
@@ -163,6 +165,8 @@ def evaluate(config: Config, params: Any, *, lib: Optional[nat.Lib] = None, xp: 
     if not 1 <= config.model.num_layers <= 4:
         raise ValueError(f"model.num_layers = {config.model.num_layers}: the MI355X engine lays out 1 to 4 hidden layers")
     ecfg = eval_cfg(config, **overrides)
+    if config.evaluation.video_path and ecfg.record_envs < 1:  # (before anything runs)
+        raise ValueError("evaluation.video_path is set but evaluation.record_envs is 0: there would be no trajectory to render")
     cm = resolve_model(config)
     torch, stream = None, None
     if xp == "torch":
@@ -178,11 +182,14 @@ def evaluate(config: Config, params: Any, *, lib: Optional[nat.Lib] = None, xp: 
         net = nat.Net(dims.obs_dim, dims.obs_pad, dims.nu, config.model.hidden_size, int(config.model.use_tanh), int(config.training.mlp_dtype == "bf16"), L)
         flat = _flat_params(params, dims.obs_dim, dims.nu, config.model.hidden_size, L)
         params_dev = torch.from_numpy(flat).to(device) if torch is not None else np.ascontiguousarray(flat)
-        return run(lib, xp, device, stream, model, dims, net, params_dev, ecfg)
+        result = run(lib, xp, device, stream, model, dims, net, params_dev, ecfg)
     finally:
         if torch is not None:
             torch.cuda.synchronize(device)
         lib.model_close(model)
+    if config.evaluation.video_path:
+        save_video(config.evaluation.video_path, config, result, lib=lib, xp=xp, device=device)
+    return result
 
 
 def save_trajectory(path: str, result: EvalResult) -> None:
@@ -193,6 +200,21 @@ def save_trajectory(path: str, result: EvalResult) -> None:
         os.makedirs(d, exist_ok=True)
     with open(path, "wb") as f:  # (an open file: np.savez appends ".npz" to a bare name)
         np.savez(f, dt=np.float64(result.dt), n_frames=np.int32(result.n_frames), **result.trajectory)
+
+
+def save_video(path: str, config: Config, result: EvalResult, *, lib: Optional[nat.Lib] = None, xp: str = "torch", device: Any = "cuda:0") -> None:
+    """Renders recorded environment 0's trajectory with `visualization.camera_name / width / height` and writes it to `path`
+    (minppo_amd.render.write_video), at the frame rate of the environment step."""
+    from minppo_amd.render import render, write_video
+    from minppo_amd.train import resolve_model
+
+    if result.trajectory is None:
+        raise ValueError("save_video: the evaluation recorded no environment (evaluation.record_envs = 0)")
+    vis = config.visualization
+    # one frame per step: the state every step STARTED from (trajectory rows 0 .. K - 1; as env.py:302-303 collects a state before it steps)
+    frames = render(resolve_model(config), result.trajectory["qpos"][:-1, 0], require(vis.camera_name, "visualization.camera_name"), vis.width, vis.height, lib=lib, xp=xp,
+                    device=device)
+    write_video(path, frames, fps=1.0 / result.dt)
 
 
 def _json_value(v: Any) -> Any:
@@ -208,6 +230,8 @@ def main(args: Sequence[str] | None = None) -> EvalResult:
     path = require(config.inference.model_path, "inference.model_path")
     if config.evaluation.trajectory_path and config.evaluation.record_envs < 1:  # (before anything runs)
         raise ValueError("evaluation.trajectory_path is set but evaluation.record_envs is 0: there would be no trajectory to write")
+    if config.evaluation.video_path and config.evaluation.record_envs < 1:
+        raise ValueError("evaluation.video_path is set but evaluation.record_envs is 0: there would be no trajectory to render")
     result = evaluate(config, path)
     if config.evaluation.trajectory_path:
         save_trajectory(config.evaluation.trajectory_path, result)

@@ -68,8 +68,8 @@ from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from minppo_amd.model import (GEOM_BOX, GEOM_CAPSULE, GEOM_CYLINDER, GEOM_MESH, GEOM_SPHERE, JNT_BALL, JNT_FREE, JNT_HINGE, JNT_SLIDE, MAX_CONVEX_VERTS, ActuatorSpec, BodySpec, EqualitySpec,
-                              GeomSpec, JointSpec, ModelSpec, _normalize, _qmat, _qmul, mix_contact_params)
+from minppo_amd.model import (DEFAULT_RGBA, GEOM_BOX, GEOM_CAPSULE, GEOM_CYLINDER, GEOM_ELLIPSOID, GEOM_MESH, GEOM_SPHERE, JNT_BALL, JNT_FREE, JNT_HINGE, JNT_SLIDE, MAX_CONVEX_VERTS, ActuatorSpec,
+                              BodySpec, CameraSpec, EqualitySpec, GeomSpec, JointSpec, ModelSpec, VisualSpec, _normalize, _qmat, _qmul, mix_contact_params)
 
 logger = logging.getLogger(__name__)
 
@@ -464,6 +464,56 @@ def parse_mjcf(xml: str, name: str = "mjcf", base_dir: Optional[Path] = None) ->
                 raise ValueError(f"mesh {mname}: refpos / refquat are not supported")
             meshes[mname] = pts * scale[None, :]
 
+    # what the renderer draws (minppo_amd/render.py): colours and cameras.  Nothing here raises or logs - a file that parsed before this
+    # existed parses exactly as it did; what cannot be resolved is recorded in the visual and surfaces when a scene is built
+    materials: Dict[str, Tuple[float, ...]] = {}
+    for asset in root.findall("asset"):
+        for ma in asset.findall("material"):
+            try:
+                materials[ma.get("name", "")] = tuple(_floats(ma.get("rgba", "1 1 1 1"), 4))
+            except ValueError:
+                pass
+    cameras: List[CameraSpec] = []
+    world_visuals: List[VisualSpec] = []
+
+    def visual_of(a: Dict[str, str], own: Dict[str, str], gs: Optional[GeomSpec]) -> VisualSpec:
+        """The drawn form of a geom from its resolved attributes `a` (`own`: the element's own, which win over its class's)."""
+        try:
+            rgba = DEFAULT_RGBA
+            for src in (a, own):  # (the element's own rgba / material last)
+                if "material" in src and src["material"] in materials:
+                    rgba = materials[src["material"]]
+                if "rgba" in src:
+                    rgba = tuple(_floats(src["rgba"], 4))
+            if gs is not None:  # a collider: drawn as the shape that collides
+                return VisualSpec(gs.type, tuple(gs.size), tuple(gs.pos), tuple(gs.quat), tuple(rgba), gs.vertices)
+            gtype = "mesh" if ("mesh" in a and "type" not in a) else a.get("type", "sphere")
+            quat = comp.orientation(a, "geom")
+            pos = np.array(_floats(a.get("pos", "0 0 0"), 3))
+            size = _floats(a["size"]) if "size" in a else []
+            if "fromto" in a:
+                ft = np.array(_floats(a["fromto"], 6))
+                pos, quat = 0.5 * (ft[:3] + ft[3:]), _z_to(ft[3:] - ft[:3])
+                if gtype in ("capsule", "cylinder"):
+                    size = [size[0], 0.5 * float(np.linalg.norm(ft[3:] - ft[:3]))]
+            if gtype == "mesh":
+                if a.get("mesh") not in meshes:
+                    return VisualSpec(GEOM_MESH, rgba=tuple(rgba), problem=f"mesh {a.get('mesh')!r} is not defined under <asset>")
+                return VisualSpec(GEOM_MESH, (), tuple(pos), tuple(quat), tuple(rgba), meshes[a["mesh"]])
+            kinds = {"sphere": (GEOM_SPHERE, 1), "capsule": (GEOM_CAPSULE, 2), "cylinder": (GEOM_CYLINDER, 2), "box": (GEOM_BOX, 3), "ellipsoid": (GEOM_ELLIPSOID, 3)}
+            if gtype not in kinds or len(size) < kinds[gtype][1]:
+                return VisualSpec(GEOM_SPHERE, rgba=tuple(rgba), problem=f"a {gtype} geom with size {size} cannot be drawn")
+            return VisualSpec(kinds[gtype][0], tuple(size[:kinds[gtype][1]]), tuple(pos), tuple(quat), tuple(rgba))
+        except Exception as exc:  # noqa: BLE001 - a malformed number in a purely visual attribute
+            return VisualSpec(GEOM_SPHERE, problem=str(exc))
+
+    def camera_of(el: ET.Element, body: str) -> None:
+        try:
+            cameras.append(CameraSpec(el.get("name", f"camera{len(cameras)}"), body, el.get("mode", "fixed"), tuple(_floats(el.get("pos", "0 0 0"), 3)),
+                                      tuple(comp.orientation(el.attrib, "camera")), float(el.get("fovy", "45"))))
+        except Exception:  # noqa: BLE001 - a camera that cannot be read is one the file does not have
+            pass
+
     world = _merged(root, "worldbody")
     if world is None:
         raise ValueError("MJCF has no <worldbody>")
@@ -556,6 +606,7 @@ def parse_mjcf(xml: str, name: str = "mjcf", base_dir: Optional[Path] = None) ->
         quat = comp.orientation(el.attrib, f"body {bname}")
         joints: List[JointSpec] = []
         geoms: List[GeomSpec] = []
+        visuals: List[VisualSpec] = []
         parts = []
         inertial = None
         for ch in el:
@@ -636,9 +687,11 @@ def parse_mjcf(xml: str, name: str = "mjcf", base_dir: Optional[Path] = None) ->
                 if jt == JNT_BALL:
                     joints[-1].springref = None  # (qpos_spring of a ball joint is the identity quaternion)
             elif ch.tag == "geom":
-                kind, gs, part = geom_spec(dfl.resolve("geom", ch, cc), what)
+                ga = dfl.resolve("geom", ch, cc)
+                kind, gs, part = geom_spec(ga, what)
                 if kind == "plane":
                     raise ValueError(f"{what}: a plane belongs to the worldbody")
+                visuals.append(visual_of(ga, ch.attrib, gs))
                 if gs is not None:
                     geoms.append(gs)
                 if part is not None:
@@ -646,7 +699,8 @@ def parse_mjcf(xml: str, name: str = "mjcf", base_dir: Optional[Path] = None) ->
             elif ch.tag == "body":
                 pass
             elif ch.tag in ("site", "camera", "light"):
-                pass
+                if ch.tag == "camera":
+                    camera_of(ch, bname)
             else:
                 raise ValueError(f"{what} is outside the supported MJCF subset")
         use_geoms = comp.inertiafromgeom == "true" or (comp.inertiafromgeom == "auto" and inertial is None)
@@ -675,16 +729,18 @@ def parse_mjcf(xml: str, name: str = "mjcf", base_dir: Optional[Path] = None) ->
         inertia_ = [max(x, comp.boundinertia) for x in inertia_]
         inertial = (mass_, inertial[1], inertial[2], tuple(inertia_))
         bodies.append(BodySpec(bname, parent, pos=pos, quat=tuple(quat), mass=inertial[0], inertia=inertial[3], ipos=inertial[1], iquat=inertial[2],
-                               joints=joints, geoms=geoms))
+                               joints=joints, geoms=geoms, visuals=visuals))
         for ch in el.findall("body"):
             walk(ch, bname, cc)
 
     for ch in world:
         if ch.tag == "geom":
-            kind, info, _ = geom_spec(dfl.resolve("geom", ch, None), "<geom> in worldbody")
+            wa = dfl.resolve("geom", ch, None)
+            kind, info, _ = geom_spec(wa, "<geom> in worldbody")
             if kind != "plane":
                 if (int(ch.get("contype", "1")) | int(ch.get("conaffinity", "1"))) != 0:
                     raise ValueError("worldbody geoms other than one ground plane must be non-colliding")
+                world_visuals.append(visual_of(wa, ch.attrib, None))
                 continue
             if plane is not None:
                 raise ValueError("more than one ground plane")
@@ -694,6 +750,8 @@ def parse_mjcf(xml: str, name: str = "mjcf", base_dir: Optional[Path] = None) ->
         elif ch.tag == "body":
             walk(ch, "world", None)
         elif ch.tag in ("light", "camera", "site"):
+            if ch.tag == "camera":
+                camera_of(ch, "world")
             continue
         else:
             raise ValueError(f"<{ch.tag}> in worldbody is outside the supported MJCF subset")
@@ -840,7 +898,7 @@ def parse_mjcf(xml: str, name: str = "mjcf", base_dir: Optional[Path] = None) ->
     eqs = _parse_equality(root, dfl)
     if eqs:
         spec_kw["equalities"] = eqs
-    return ModelSpec(name=name, bodies=bodies, actuators=acts, free_root_z=free_root_z, **spec_kw)
+    return ModelSpec(name=name, bodies=bodies, actuators=acts, free_root_z=free_root_z, world_visuals=world_visuals, cameras=cameras, **spec_kw)
 
 
 _EQ_ATTRS = {"connect": {"name", "class", "body1", "body2", "anchor", "active", "solref", "solimp"},

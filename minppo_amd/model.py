@@ -37,6 +37,8 @@ import numpy as np
 
 JNT_FREE, JNT_BALL, JNT_HINGE, JNT_SLIDE = 0, 1, 2, 3  # MuJoCo's mjtJoint numbering
 GEOM_SPHERE, GEOM_CAPSULE, GEOM_CYLINDER, GEOM_BOX, GEOM_MESH = 2, 3, 5, 6, 7  # MuJoCo's mjtGeom numbering
+GEOM_ELLIPSOID = 4  # (visuals only: the renderer draws it, nothing collides as one)
+DEFAULT_RGBA = (0.5, 0.5, 0.5, 1.0)  # MuJoCo's default geom colour
 
 MJ_MINVAL = 1e-15
 MAX_CONVEX_VERTS = 64  # hull vertices of one mesh collider (the kernel scans them five times per step)
@@ -98,6 +100,34 @@ class GeomSpec:
 
 
 @dataclass
+class VisualSpec:
+    """What the renderer draws of one geom (minppo_amd/render.py): every geom of an MJCF body, colliding or not.  `size` as in GeomSpec
+    (an ellipsoid: its three radii); a mesh is drawn as its convex hull: `vertices` are points whose hull it is.  `problem` names what
+    could not be resolved at parse time (the visual is then skipped, with one warning, when a scene is built)."""
+    type: int
+    size: Sequence[float] = ()
+    pos: Sequence[float] = (0.0, 0.0, 0.0)
+    quat: Sequence[float] = (1.0, 0.0, 0.0, 0.0)
+    rgba: Sequence[float] = DEFAULT_RGBA
+    vertices: Optional[object] = None
+    problem: str = ""
+
+
+@dataclass
+class CameraSpec:
+    """An MJCF <camera>: `pos` / `quat` in the frame of `body` ("world" or a body name).  MuJoCo's convention: the camera looks along its
+    -z axis, +x is right, +y is up; `fovy` is the vertical field of view in degrees.  `mode` is kept as written; the renderer draws
+    "fixed" and "track" and refuses the others when a render with that camera is requested."""
+    name: str
+    body: str = "world"
+    mode: str = "fixed"
+    pos: Sequence[float] = (0.0, 0.0, 0.0)
+    quat: Sequence[float] = (1.0, 0.0, 0.0, 0.0)
+    fovy: float = 45.0
+    bodyid: int = -1  # (filled by compile_model)
+
+
+@dataclass
 class BodySpec:
     name: str
     parent: str  # "world" or a body name
@@ -109,6 +139,7 @@ class BodySpec:
     iquat: Sequence[float] = (1.0, 0.0, 0.0, 0.0)
     joints: List[JointSpec] = field(default_factory=list)
     geoms: List[GeomSpec] = field(default_factory=list)
+    visuals: Optional[List[VisualSpec]] = None  # None: the geoms are the visuals, in MuJoCo's default colour (the built-in robots)
 
 
 @dataclass
@@ -182,6 +213,8 @@ class ModelSpec:
     plane_margin: float = 0.0
     plane_gap: float = 0.0
     equalities: List[EqualitySpec] = field(default_factory=list)  # MJCF <equality><connect> / <joint> (active ones only)
+    world_visuals: List[VisualSpec] = field(default_factory=list)  # the worldbody's geoms other than the ground plane (drawn, never colliding)
+    cameras: List[CameraSpec] = field(default_factory=list)  # (compile_model adds the implicit tracking camera "track")
 
 
 # ---------------------------------------------------------------------------
@@ -235,6 +268,10 @@ class CompiledModel:
     body_names: List[str]
     joint_names: List[str]
     meaninertia_override: Optional[float] = None
+    # what the renderer needs beside the tables (minppo_amd/render.py); none of it reaches `t` or the model blob
+    visuals: List[Tuple[int, VisualSpec]] = field(default_factory=list)  # (body id, visual) in document order
+    cameras: List[CameraSpec] = field(default_factory=list)
+    has_plane: bool = True
 
     # -- dims -------------------------------------------------------------
     @property
@@ -975,6 +1012,18 @@ def compile_model(spec: ModelSpec) -> CompiledModel:
         put("nball", sum(1 for x in jnt_type if x == JNT_BALL), np.int32)
 
     cm = CompiledModel(spec.name, t, names, joint_names, spec.meaninertia)
+    cm.has_plane = bool(spec.has_plane)
+    cm.visuals = [(0, v) for v in spec.world_visuals]
+    for bi, b in enumerate(spec.bodies, start=1):
+        vis = b.visuals if b.visuals is not None else [VisualSpec(g.type, tuple(g.size), tuple(g.pos), tuple(g.quat), DEFAULT_RGBA, g.vertices) for g in b.geoms]
+        cm.visuals += [(bi, v) for v in vis]
+    for c in spec.cameras:
+        cm.cameras.append(CameraSpec(c.name, c.body, c.mode, tuple(c.pos), tuple(c.quat), float(c.fovy), names.index(c.body) if c.body in names else -1))
+    if not any(c.name == "track" for c in cm.cameras):
+        # the classic humanoid tracking camera: four metres in front of the root, looking along +y (a model without a free joint: its first body)
+        free = [int(b) for j, b in enumerate(jnt_bodyid) if jnt_type[j] == JNT_FREE]
+        root = free[0] if free else 1
+        cm.cameras.append(CameraSpec("track", names[root], "track", (0.0, -4.0, 0.0), (0.70710678118654757, 0.70710678118654757, 0.0, 0.0), 45.0, root))
     _set_const(cm)
     if spec.equalities:
         _compile_equalities(cm, spec.equalities)

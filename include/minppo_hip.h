@@ -318,6 +318,27 @@ int32_t mppo_threefry_update_keys_step(uint32_t* rng2, int32_t T, int32_t E, int
                                        uint32_t* step_keys, void* stream);
 int32_t mppo_threefry_permutation(const uint32_t* sort_keys, int32_t rounds, int32_t B, int32_t* idx, void* ws, size_t ws_bytes, void* stream);
 
+/* Running observation normalisation (csrc/k_obsnorm.hip).  The reference feeds the raw observation to the network (train.py:157); this is what
+ * Brax's `ppo.train(normalize_observations=True)` and gym's `NormalizeObservation` do, as two stages.  Per column c < O the running statistics
+ * are float64: `stats` [1 + 2 O] = count n | mean[O] | M2[O] (sum of squared deviations).  The float32 `table` [2][table_ld] is what gets applied:
+ * row 0 mean32 = (float)mean, row 1 inv_std32 = (float)(1 / sqrt(M2 / n + eps)); while n = 0 it is exactly 0 / 1, the identity.
+ *   mppo_obs_norm_partials  G, the workgroups (= partial sums) of one apply launch over N rows: ceil(N / 128)
+ *   mppo_obs_norm_apply     in place on obs[n, 0:O] (row stride obs_ld): y = (x - mean32[c]) * inv_std32[c] in float32 in that order, clamped to
+ *                           [-clip, clip] when clip > 0.  Columns O .. obs_ld - 1 are not written.  partial != NULL ([G][2][O] float64): workgroup g
+ *                           also writes S1 = sum d and S2 = sum d^2, d = (double)x - (double)mean32[c] of the RAW x, over its rows 128 g .. 128 g + 127
+ *                           below N: each group of 8 rows (one wave) summed in row order, then the 16 groups' sums added in row order (one writer per
+ *                           word, no atomics, nothing that depends on timing).  16-byte loads and stores when obs is 16-byte aligned and obs_ld a
+ *                           multiple of 4.
+ *   mppo_obs_norm_update    one small launch, one thread per column: sums the n_partials x [2][O] partials in index order, then merges the k = `rows`
+ *                           rows they hold (Chan): b = mean32 + S1/k, M2b = max(S2 - S1^2/k, 0), delta = b - mean, n' = n + k, mean' = mean + delta k/n',
+ *                           M2' = M2 + M2b + delta^2 n k/n' (mean32: the table as it stands, which the partials were taken against); then rewrites
+ *                           the table, columns O .. table_ld - 1 as 0 / 1.  rows = 0 (then n_partials = 0, partial may be NULL): the table from the
+ *                           statistics alone.  The same inputs give the same bytes on every run. */
+int32_t mppo_obs_norm_partials(int32_t N);
+int32_t mppo_obs_norm_apply(int32_t N, int32_t O, float* obs, int32_t obs_ld, const float* table, int32_t table_ld, float clip, double* partial, void* stream);
+int32_t mppo_obs_norm_update(int32_t O, int32_t n_partials, int64_t rows, const double* partial, double* stats, float eps, float* table, int32_t table_ld,
+                             void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Engine: the whole `_update_step` (train.py:146-283) as one call, launches enqueued from
  * C++ (optionally replayed from a hipGraph), gradients summed over ranks with RCCL.
@@ -350,7 +371,8 @@ typedef struct mppo_engine_cfg {
  * located with mppo_engine_region (offset in bytes, size in bytes) to view them as tensors:
  * "params" "adam_m" "adam_v" "grad" "count" "state" "reset_rec" "obs" "action" "value" "reward"
  * "log_prob" "done" "last_val" "adv" "target" "noise" "perm" "adv_stats" "losses" "rollout_stats" "jax_rng" "reset_rng"
- * (8 floats: sum reward, episodes ended, sum of their returns, sum of their lengths, the two means, 0, 0) ... */
+ * "obs_norm_stats" (float64) "obs_norm_table" "obs_norm_partials" (float64)
+ * ("rollout_stats": 8 floats: sum reward, episodes ended, sum of their returns, sum of their lengths, the two means, 0, 0) ... */
 int32_t mppo_engine_arena_bytes(const mppo_model_t* m, const mppo_engine_cfg_t* cfg, size_t* out);
 int32_t mppo_engine_create(const mppo_model_t* m, const mppo_engine_cfg_t* cfg, void* arena, size_t arena_bytes,
                            mppo_engine_t** out);
@@ -406,6 +428,16 @@ int32_t mppo_engine_reset(mppo_engine_t* e, void* stream);
  * device's update index "count"[1].  Call before mppo_engine_reset: after it (with another scale than the one the reset ran with: the environments hold that
  * scale's initial states), after mppo_engine_prepare or after the first mppo_engine_update it returns MPPO_ESTATE. */
 int32_t mppo_engine_set_reset_noise(mppo_engine_t* e, float scale);
+/* Observation normalisation (mppo_obs_norm_* above; enabled = 0, the default: the engine enqueues exactly the launches it enqueues without this call).
+ * enabled != 0: every rollout step is followed by one mppo_obs_norm_apply on the rows it wrote - observation slot t + 1, after the step and after the
+ * reset-noise reinit where that is on - with the table of arena region "obs_norm_table" ([2][OP]) and the partials of step t in "obs_norm_partials"
+ * ([T][G][2][O]); the rollout ends with one mppo_obs_norm_update over the T * G partials (rows = T * N) into "obs_norm_stats" ([1 + 2 O] float64) and
+ * the table: T + 1 launches more per update, inside the captured graph too.  So the table is frozen within an update, every observation is stored
+ * normalised with the table of the moment it was collected (the learn phase reads what the rollout's forward read), and the count is updates * T * N.
+ * mppo_engine_reset zeroes the statistics and writes the identity table; the observation it makes (slot 0) stays raw.  The three regions lie behind
+ * every other one and exist whether or not the option is on.  Call before mppo_engine_reset, mppo_engine_prepare and the first mppo_engine_update:
+ * afterwards it returns MPPO_ESTATE.  MPPO_EINVAL: a negative (or NaN) clip / eps; enabled with world_size > 1 (the statistics are not summed over ranks). */
+int32_t mppo_engine_set_obs_norm(mppo_engine_t* e, int32_t enabled, float clip, float eps);
 /* one full update: T rollout steps, bootstrap value, GAE, E epochs x M minibatches */
 int32_t mppo_engine_update(mppo_engine_t* e, void* stream);
 /* what mppo_engine_update does before it enqueues anything: the one-time capture of the update into a hipGraph (no device work).
@@ -465,6 +497,11 @@ typedef struct mppo_eval_result {  /* 8-byte fields in a fixed order */
 size_t mppo_eval_ws_bytes(const mppo_model_t* m, const mppo_net_t* net, const mppo_eval_cfg_t* cfg);
 int32_t mppo_evaluate(const mppo_model_t* m, const mppo_net_t* net, const float* params, const mppo_eval_cfg_t* cfg, void* ws,
                       size_t ws_bytes, mppo_eval_result_t* result, float* traj, void* stream);
+/* mppo_evaluate for a policy trained on normalised observations: the same sequence with mppo_obs_norm_apply(N, O, obs, OP, obs_table, O, clip, NULL)
+ * on the observation after every step (behind the reinit where there is one, in front of mppo_eval_accumulate); the observation after the reset is left
+ * alone, as in the engine.  obs_table: DEVICE memory, [2][O] floats (mean32 | inv_std32, row stride O); NULL: exactly mppo_evaluate.  Same workspace. */
+int32_t mppo_evaluate_obs_norm(const mppo_model_t* m, const mppo_net_t* net, const float* params, const mppo_eval_cfg_t* cfg, void* ws, size_t ws_bytes,
+                               const float* obs_table, float clip, mppo_eval_result_t* result, float* traj, void* stream);
 /* The two statistics stages on caller-given arrays (as mppo_gae / mppo_adv_sums are stages of the update).
  * `acc`: the per-environment accumulators, 10 * N 8-byte words in device memory, 8-byte aligned, slot-major (word n of
  * slot k at 8 * (k * N + n)): int64 episodes, len_sum, len_min, len_max; double ret_sum, ret_sumsq, ret_min, ret_max,

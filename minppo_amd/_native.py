@@ -150,6 +150,9 @@ SIGNATURES = {
     "mppo_threefry_update_keys": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
     "mppo_threefry_update_keys_step": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
     "mppo_threefry_permutation": (c_i32, [c_vp, c_i32, c_i32, c_vp, c_vp, c_sz, c_vp]),
+    "mppo_obs_norm_partials": (c_i32, [c_i32]),
+    "mppo_obs_norm_apply": (c_i32, [c_i32, c_i32, c_vp, c_i32, c_vp, c_i32, c_f, c_vp, c_vp]),
+    "mppo_obs_norm_update": (c_i32, [c_i32, c_i32, C.c_int64, c_vp, c_vp, c_f, c_vp, c_i32, c_vp]),
     "mppo_engine_arena_bytes": (c_i32, [c_vp, P(EngineCfg), P(c_sz)]),
     "mppo_engine_create": (c_i32, [c_vp, P(EngineCfg), c_vp, c_sz, P(c_vp)]),
     "mppo_engine_destroy": (c_i32, [c_vp]),
@@ -165,6 +168,7 @@ SIGNATURES = {
     "mppo_engine_peer_disable": (c_i32, [c_vp]),
     "mppo_engine_reset": (c_i32, [c_vp, c_vp]),
     "mppo_engine_set_reset_noise": (c_i32, [c_vp, c_f]),
+    "mppo_engine_set_obs_norm": (c_i32, [c_vp, c_i32, c_f, c_f]),
     "mppo_engine_update": (c_i32, [c_vp, c_vp]),
     "mppo_engine_prepare": (c_i32, [c_vp, c_vp]),
     "mppo_engine_graph_active": (c_i32, [c_vp, P(c_i32)]),
@@ -172,6 +176,7 @@ SIGNATURES = {
     "mppo_engine_learn": (c_i32, [c_vp, c_vp]),
     "mppo_eval_ws_bytes": (c_sz, [c_vp, P(Net), P(EvalCfg)]),
     "mppo_evaluate": (c_i32, [c_vp, P(Net), c_vp, P(EvalCfg), c_vp, c_sz, c_vp, c_vp, c_vp]),
+    "mppo_evaluate_obs_norm": (c_i32, [c_vp, P(Net), c_vp, P(EvalCfg), c_vp, c_sz, c_vp, c_f, c_vp, c_vp, c_vp]),
     "mppo_eval_accumulate": (c_i32, [c_i32, c_i32, c_vp, c_vp, P(EnvMetrics), c_vp, c_vp, c_i32, c_i32, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp]),
     "mppo_eval_reduce": (c_i32, [c_i32, c_i32, c_vp, c_vp, c_vp]),
     "mppo_scene_open": (c_i32, [c_vp, c_sz, c_vp, P(c_vp)]),
@@ -181,7 +186,7 @@ SIGNATURES = {
 }
 
 UNCHECKED = {"mppo_last_error", "mppo_abi_version", "mppo_param_count", "mppo_policy_ws_bytes", "mppo_grad_ws_bytes",
-             "mppo_adam_ws_bytes", "mppo_permutation_ws_bytes", "mppo_eval_ws_bytes"}
+             "mppo_adam_ws_bytes", "mppo_permutation_ws_bytes", "mppo_eval_ws_bytes", "mppo_obs_norm_partials"}
 
 
 class Lib:

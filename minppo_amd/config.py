@@ -138,6 +138,12 @@ class TrainingConfig:
     # every update, [num_updates, T, N] each) instead of the per-update device-side reductions.  Small runs only: every update then
     # synchronises and copies its [T, N] reward / done arrays out; refused above 1 GiB of history.
     keep_metrics_history: bool = field(default=False)
+    # Extension (absent upstream; Brax `normalize_observations`, gym `NormalizeObservation`): running mean / standard deviation per observation
+    # column, collected from the rollout's own rows, applied in place before the network sees them.  `obs_norm_clip` clamps the
+    # normalised value to [-clip, clip] (0 = no clamp); `obs_norm_eps` is added to the variance.  Off: nothing changes.  Single rank only.
+    normalize_observations: bool = field(default=False)
+    obs_norm_clip: float = field(default=10.0)
+    obs_norm_eps: float = field(default=1e-8)
     checkpoint_path: str = field(default="")
     checkpoint_every: int = field(default=0)
     resume_from: str = field(default="")
@@ -274,6 +280,9 @@ def make_config(yaml_dict: dict | None = None, overrides: Sequence[str] = ()) ->
         _merge_into(cfg, _dotlist_to_dict(overrides))
     if not cfg.environment.reset_noise_scale >= 0.0:
         raise ValueError(f"environment.reset_noise_scale = {cfg.environment.reset_noise_scale!r}: the half-width of the reset noise cannot be negative")
+    for key in ("obs_norm_clip", "obs_norm_eps"):
+        if not getattr(cfg.training, key) >= 0.0:
+            raise ValueError(f"training.{key} = {getattr(cfg.training, key)!r} cannot be negative")
     return cfg
 
 

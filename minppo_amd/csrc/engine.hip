@@ -19,6 +19,7 @@
 #include "ppo_layout.h"
 #include "platform.h"
 #include "peer.h"
+#include "obsnorm.h"
 
 #include <cmath>
 #include <cstdlib>
@@ -138,6 +139,12 @@ struct mppo_engine {
   float reset_noise;
   unsigned* reset_rng;   // [T][2] this update's step keys (train.py:163) | [2] the reset key (train.py:142): the threefry stream's keys (rng_impl = 1)
   bool prepared;         // an update has been prepared (captured or not): the launch sequence is fixed
+  // observation normalisation (mppo_engine_set_obs_norm; off: nothing below is used and no launch is added)
+  bool obs_norm;
+  float obs_norm_clip, obs_norm_eps;
+  double* obs_norm_stats;     // [1 + 2 O] count | mean | M2
+  float* obs_norm_table;      // [2][OP] mean32 | inv_std32: what this update's rollout applies
+  double* obs_norm_partials;  // [T][G][2][O] the apply launches' sums of this update
 };
 
 namespace mppo {
@@ -199,6 +206,10 @@ static size_t layout(mppo_engine* e, bool assign) {
   e->env_ws = e->env_ws_bytes ? (float*)take("env_scratch", e->env_ws_bytes) : nullptr;
   // the keys of the reset noise's threefry stream: behind everything else, so that every other region is where it was ("jax_rng" keeps its size and meaning)
   e->reset_rng = (unsigned*)take("reset_rng", (2 * T + 2) * 4);
+  // observation normalisation: behind those again, present whether or not the option is on
+  e->obs_norm_stats = (double*)take("obs_norm_stats", (1 + 2 * (size_t)e->O) * 8);
+  e->obs_norm_table = (float*)take("obs_norm_table", 2 * OP * 4);
+  e->obs_norm_partials = (double*)take("obs_norm_partials", T * obs_norm_partial_doubles((int)N, e->O) * 8);
   return align_up(off, 256);
 }
 
@@ -289,6 +300,11 @@ static int32_t do_rollout(mppo_engine* e, hipStream_t s) {
     if (e->reset_noise > 0.f)
       MPPO_TRY(env_reinit_ws(e->model, e->N, e->state, e->obs + (size_t)(t + 1) * N * OP, e->OP, e->done + t * N, e->reset_noise, c.rng_impl, c.seed, c.rank,
                              e->reset_rng + 2 * t, e->count + 1, e->T, 1 + t, e->env_ws, e->env_ws_bytes, s));
+    // observation normalisation: the new rows are stored normalised with this update's table (the next forward and the learn phase read them so);
+    // their raw values go into this step's partial sums first
+    if (e->obs_norm)
+      MPPO_TRY(obs_norm_apply_launch(e->N, e->O, e->obs + (size_t)(t + 1) * N * OP, e->OP, e->obs_norm_table, e->OP, e->obs_norm_clip,
+                                     e->obs_norm_partials + (size_t)t * obs_norm_partial_doubles(e->N, e->O), s));
   }
   if (defer_critic)  // value[t] of all T steps and the bootstrap value in ONE critic launch over the [T + 1][N] observation rows (nothing before GAE reads them)
     MPPO_TRY(policy_forward(c.net, e->params, (e->T + 1) * e->N, e->obs, e->OP, fb, nullptr, nullptr, nullptr, e->value, nullptr, s));
@@ -297,6 +313,9 @@ static int32_t do_rollout(mppo_engine* e, hipStream_t s) {
   MPPO_TRY(gae_launch(e->T, e->N, c.gamma, c.gae_lambda, e->reward, e->value, e->done, e->last_val, e->adv, e->target, s));
   hipLaunchKernelGGL(rollout_stats_kernel, dim3(1), dim3(kStatsThreads), 0, s, e->T, e->N, e->reward, e->done, e->stat_ret_in, e->stat_len_in, e->stats);
   MPPO_CHECK_LAUNCH("rollout_stats_kernel");
+  if (e->obs_norm)  // the T steps' rows join the running statistics; the table is rewritten for the next update (nothing of this one applies it any more)
+    MPPO_TRY(obs_norm_update_launch(e->O, e->T * obs_norm_partials(e->N), (long long)e->T * e->N, e->obs_norm_partials, e->obs_norm_stats, e->obs_norm_eps, e->obs_norm_table,
+                                    e->OP, s));
   return MPPO_OK;
 }
 
@@ -415,6 +434,7 @@ extern "C" int32_t mppo_engine_create(const mppo_model_t* m, const mppo_engine_c
   if (arena_bytes < need) { delete e; return fail(MPPO_ENOMEM, "mppo_engine_create: arena %zu < %zu bytes", arena_bytes, need); }
   e->comm = nullptr; e->peer = nullptr; e->graph = nullptr; e->graph_failed = false; e->was_reset = false; e->graph_agreed = false;
   e->reset_noise = 0.f; e->prepared = false;
+  e->obs_norm = false; e->obs_norm_clip = 0.f; e->obs_norm_eps = 0.f;
   *out = e;
   return MPPO_OK;
 }
@@ -468,7 +488,27 @@ extern "C" int32_t mppo_engine_reset(mppo_engine_t* e, void* stream) {
   if (e->reset_noise > 0.f)
     MPPO_TRY(env_reinit_ws(e->model, e->N, e->state, e->obs, e->OP, nullptr, e->reset_noise, e->cfg.rng_impl, e->cfg.seed, e->cfg.rank, e->reset_rng + 2 * e->T, nullptr, 0, 0,
                            e->env_ws, e->env_ws_bytes, s));
+  if (e->obs_norm) {  // nothing counted, the identity table (pad columns included); obs[0] above stays raw
+    MPPO_CHECK_HIP(hipMemsetAsync(e->obs_norm_stats, 0, (1 + 2 * (size_t)e->O) * 8, s));
+    MPPO_TRY(obs_norm_update_launch(e->O, 0, 0, nullptr, e->obs_norm_stats, e->obs_norm_eps, e->obs_norm_table, e->OP, s));
+  }
   e->was_reset = true;
+  return MPPO_OK;
+}
+
+extern "C" int32_t mppo_engine_set_obs_norm(mppo_engine_t* e, int32_t enabled, float clip, float eps) {
+  MPPO_REQUIRE(e, "mppo_engine_set_obs_norm: null engine");
+  MPPO_REQUIRE(clip >= 0.f && eps >= 0.f, "mppo_engine_set_obs_norm: clip %g / eps %g is negative (or not a number)", (double)clip, (double)eps);
+  MPPO_REQUIRE(!enabled || e->cfg.world_size == 1, "mppo_engine_set_obs_norm: world_size = %d ranks - the running statistics are not summed over ranks, observation "
+               "normalisation runs on a single rank only", e->cfg.world_size);
+  if (e->graph || e->prepared)
+    return fail(MPPO_ESTATE, "mppo_engine_set_obs_norm: the update has been prepared already (its launch sequence is fixed, a captured graph holds it): "
+                             "call it before mppo_engine_reset, mppo_engine_prepare and the first mppo_engine_update");
+  if (e->was_reset)
+    return fail(MPPO_ESTATE, "mppo_engine_set_obs_norm: mppo_engine_reset has run already (it zeroes the statistics and writes the identity table): call it before the reset");
+  e->obs_norm = enabled != 0;
+  e->obs_norm_clip = clip;
+  e->obs_norm_eps = eps;
   return MPPO_OK;
 }
 

@@ -8,6 +8,7 @@
 // buffer is a region of the caller's workspace (a large robot's out-of-LDS matrices included), so the call can be captured into a hipGraph.
 #include "eval.h"
 #include "model_view.h"
+#include "obsnorm.h"
 #include "ppo_layout.h"
 
 namespace mppo {
@@ -90,17 +91,19 @@ extern "C" size_t mppo_eval_ws_bytes(const mppo_model_t* m, const mppo_net_t* ne
   return carve_eval(m, *net, cfg->N, nullptr).total;
 }
 
-extern "C" int32_t mppo_evaluate(const mppo_model_t* m, const mppo_net_t* net, const float* params, const mppo_eval_cfg_t* cfg, void* ws, size_t ws_bytes,
-                                 mppo_eval_result_t* result, float* traj, void* stream) {
-  MPPO_TRY(check_eval("mppo_evaluate", m, net, cfg));
-  MPPO_REQUIRE(params && ws && result, "mppo_evaluate: null params / workspace / result");
-  MPPO_REQUIRE(traj || cfg->record_envs == 0, "mppo_evaluate: null trajectory with record_envs = %d", cfg->record_envs);
-  MPPO_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 255) == 0, "mppo_evaluate: the workspace must be 256-byte aligned");
-  MPPO_REQUIRE((reinterpret_cast<uintptr_t>(result) & 7) == 0, "mppo_evaluate: the result must be 8-byte aligned");
+// obs_table (may be null: the plain evaluation, not one launch more): [2][O] mean32 | inv_std32 of a policy trained on normalised observations
+static int32_t evaluate_impl(const char* who, const mppo_model_t* m, const mppo_net_t* net, const float* params, const mppo_eval_cfg_t* cfg, void* ws, size_t ws_bytes,
+                             const float* obs_table, float clip, mppo_eval_result_t* result, float* traj, void* stream) {
+  MPPO_TRY(check_eval(who, m, net, cfg));
+  MPPO_REQUIRE(params && ws && result, "%s: null params / workspace / result", who);
+  MPPO_REQUIRE(traj || cfg->record_envs == 0, "%s: null trajectory with record_envs = %d", who, cfg->record_envs);
+  MPPO_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 255) == 0, "%s: the workspace must be 256-byte aligned", who);
+  MPPO_REQUIRE((reinterpret_cast<uintptr_t>(result) & 7) == 0, "%s: the result must be 8-byte aligned", who);
+  MPPO_REQUIRE(clip >= 0.f, "%s: clip %g is negative (or not a number)", who, (double)clip);
   const mppo_eval_cfg_t& c = *cfg;
   const int N = c.N, K = c.K, R = c.record_envs, A = net->A;
   const EvalWs w = carve_eval(m, *net, N, static_cast<unsigned char*>(ws));
-  MPPO_REQUIRE(ws_bytes >= w.total, "mppo_evaluate: workspace %zu < %zu bytes (mppo_eval_ws_bytes)", ws_bytes, w.total);
+  MPPO_REQUIRE(ws_bytes >= w.total, "%s: workspace %zu < %zu bytes (mppo_eval_ws_bytes)", who, ws_bytes, w.total);
   hipStream_t s = static_cast<hipStream_t>(stream);
   const ModelView& mv = model_view(m);
   const int OP = mv.obs_pad, row_w = mv.nq + mv.nv;
@@ -121,8 +124,20 @@ extern "C" int32_t mppo_evaluate(const mppo_model_t* m, const mppo_net_t* net, c
     MPPO_TRY(env_step_ws(m, N, c.n_frames, &c.reward, w.state, w.reset_rec, w.action, A, w.obs, OP, w.reward, w.done, &w.met, w.env_ws, w.env_ws_bytes, s));
     if (noisy_reset)  // the environments whose episode ended restart from a randomised state (event t + 1), as in the engine's rollout
       MPPO_TRY(env_reinit_ws(m, N, w.state, w.obs, OP, w.done, c.reset_noise_scale, 0, c.seed, 0, nullptr, nullptr, 1, t + 1, w.env_ws, w.env_ws_bytes, s));
+    if (obs_table)  // the next forward reads what the policy was trained on; the observation after the reset stays raw, as in the engine (the state rows are raw throughout)
+      MPPO_TRY(obs_norm_apply_launch(N, net->O, w.obs, OP, obs_table, net->O, clip, nullptr, s));
     MPPO_TRY(eval_accumulate_launch(N, N, t == 0, w.reward, w.done, &w.met, w.acc, w.state, mv.rec_dim, row_w, w.action, A, A, R,
                                     R > 0 ? traj + (size_t)(t + 1) * frame : nullptr, s));
   }
   return eval_reduce_launch(N, K, w.acc, result, s);
+}
+
+extern "C" int32_t mppo_evaluate(const mppo_model_t* m, const mppo_net_t* net, const float* params, const mppo_eval_cfg_t* cfg, void* ws, size_t ws_bytes,
+                                 mppo_eval_result_t* result, float* traj, void* stream) {
+  return evaluate_impl("mppo_evaluate", m, net, params, cfg, ws, ws_bytes, nullptr, 0.f, result, traj, stream);
+}
+
+extern "C" int32_t mppo_evaluate_obs_norm(const mppo_model_t* m, const mppo_net_t* net, const float* params, const mppo_eval_cfg_t* cfg, void* ws, size_t ws_bytes,
+                                          const float* obs_table, float clip, mppo_eval_result_t* result, float* traj, void* stream) {
+  return evaluate_impl("mppo_evaluate_obs_norm", m, net, params, cfg, ws, ws_bytes, obs_table, clip, result, traj, stream);
 }

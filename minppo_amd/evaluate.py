@@ -101,6 +101,19 @@ def _flat_params(params: Any, O: int, A: int, H: int, L: int) -> np.ndarray:
     return flat
 
 
+def obs_norm_table(obs_norm: Optional[Dict[str, Any]], O: int):
+    """The "obs_norm" entry of a model file (`Trainer.params` with `training.normalize_observations`) -> (float32 [2, O] table, clip); (None, 0.0) for None."""
+    if obs_norm is None:
+        return None, 0.0
+    table = np.stack([np.asarray(obs_norm["mean"], np.float32).reshape(-1), np.asarray(obs_norm["inv_std"], np.float32).reshape(-1)])
+    clip = float(obs_norm.get("clip", 0.0))
+    if table.shape != (2, O):
+        raise ValueError(f"obs_norm: mean / inv_std of {table.shape[1]} columns, the robot's observation has {O}")
+    if not clip >= 0.0:
+        raise ValueError(f"obs_norm: clip = {clip!r} cannot be negative")
+    return np.ascontiguousarray(table), clip
+
+
 def eval_cfg(config: Config, **overrides: Any) -> nat.EvalCfg:
     """`mppo_eval_cfg_t` of a config: sizes from `evaluation`, frames / reset noise from `environment`, the reward window from `reward`,
     the seed from `training.seed`.  Overrides: num_envs, num_steps, deterministic, record_envs, seed."""
@@ -118,8 +131,17 @@ def eval_cfg(config: Config, **overrides: Any) -> nat.EvalCfg:
 
 
 def run(lib: nat.Lib, xp: str, device: Any, stream: Any, model: C.c_void_p, dims: nat.ModelDims, net: nat.Net, params_dev: Any,
-        ecfg: nat.EvalCfg) -> EvalResult:
-    """One `mppo_evaluate` on an open model and parameters already in device memory (`Trainer.evaluate` comes in here)."""
+        ecfg: nat.EvalCfg, obs_norm: Optional[Dict[str, Any]] = None) -> EvalResult:
+    """One `mppo_evaluate` on an open model and parameters already in device memory (`Trainer.evaluate` comes in here); with `obs_norm`
+    ({"mean", "inv_std", "clip"}) one `mppo_evaluate_obs_norm`: the policy reads observations normalised with that table."""
+    table, clip = obs_norm_table(obs_norm, dims.obs_dim)
+
+    def call(ws, res, traj, s):
+        if table is None:
+            lib.evaluate(model, C.byref(net), nat.ptr(params_dev), C.byref(ecfg), nat.ptr(ws), need, nat.ptr(res), nat.ptr(traj), s)
+        else:
+            lib.evaluate_obs_norm(model, C.byref(net), nat.ptr(params_dev), C.byref(ecfg), nat.ptr(ws), need, nat.ptr(table_dev), clip, nat.ptr(res), nat.ptr(traj), s)
+
     need = int(lib.eval_ws_bytes(model, C.byref(net), C.byref(ecfg)))
     if need == 0:  # the arguments are ones mppo_evaluate refuses: let it say why
         lib.evaluate(model, C.byref(net), nat.ptr(params_dev), C.byref(ecfg), None, 0, None, None, None)
@@ -134,10 +156,11 @@ def run(lib: nat.Lib, xp: str, device: Any, stream: Any, model: C.c_void_p, dims
             return raw[o:o + nbytes]
 
         ws, res = alloc(need), alloc(C.sizeof(nat.EvalResultRaw))
+        table_dev = torch.from_numpy(table).to(device) if table is not None else None
         traj = alloc((K + 1) * R * W * 4).view(torch.float32).reshape(K + 1, R, W) if R > 0 else None
         with torch.cuda.device(device):
             torch.cuda.synchronize(device)  # (the allocations were zeroed on torch's current stream)
-            lib.evaluate(model, C.byref(net), nat.ptr(params_dev), C.byref(ecfg), nat.ptr(ws), need, nat.ptr(res), nat.ptr(traj), stream.cuda_stream)
+            call(ws, res, traj, stream.cuda_stream)
             stream.synchronize()
         res_host = res.cpu().numpy()
         traj_host = traj.cpu().numpy() if traj is not None else None
@@ -150,15 +173,19 @@ def run(lib: nat.Lib, xp: str, device: Any, stream: Any, model: C.c_void_p, dims
 
         ws, res_host = alloc(need), alloc(C.sizeof(nat.EvalResultRaw))
         traj_host = alloc((K + 1) * R * W * 4).view(np.float32).reshape(K + 1, R, W) if R > 0 else None
-        lib.evaluate(model, C.byref(net), nat.ptr(params_dev), C.byref(ecfg), nat.ptr(ws), need, nat.ptr(res_host), nat.ptr(traj_host), None)
+        table_dev = table
+        call(ws, res_host, traj_host, None)
     out = result_from_struct(nat.EvalResultRaw.from_buffer_copy(res_host.tobytes()), split_trajectory(traj_host, nq, nv, A) if traj_host is not None else None)
     out.dt, out.n_frames = float(dims.timestep) * ecfg.n_frames, int(ecfg.n_frames)
     return out
 
 
-def evaluate(config: Config, params: Any, *, lib: Optional[nat.Lib] = None, xp: str = "torch", device: Any = "cuda:0", **overrides: Any) -> EvalResult:
+def evaluate(config: Config, params: Any, *, lib: Optional[nat.Lib] = None, xp: str = "torch", device: Any = "cuda:0", obs_norm: Optional[Dict[str, Any]] = None,
+             **overrides: Any) -> EvalResult:
     """Evaluates `params` - the nested tree of `save_model` / `Trainer.params`, a flat vector, or the path of a `save_model` pickle - on
-    the robot, network geometry, reward window and `evaluation` section of `config`.  `lib=` / `xp="numpy"` as in `Trainer`."""
+    the robot, network geometry, reward window and `evaluation` section of `config`.  `lib=` / `xp="numpy"` as in `Trainer`.
+    A tree or pickle with an "obs_norm" entry (a policy trained with `training.normalize_observations`) is evaluated on observations normalised
+    with it; `obs_norm=` ({"mean", "inv_std", "clip"}) supplies the entry for a flat vector or overrides the tree's.  A flat vector without it: none."""
     from minppo_amd.train import open_model, resolve_model
 
     lib = lib if lib is not None else nat.load()
@@ -180,9 +207,15 @@ def evaluate(config: Config, params: Any, *, lib: Optional[nat.Lib] = None, xp: 
         lib.model_get_dims(model, C.byref(dims))
         L = int(config.model.num_layers)
         net = nat.Net(dims.obs_dim, dims.obs_pad, dims.nu, config.model.hidden_size, int(config.model.use_tanh), int(config.training.mlp_dtype == "bf16"), L)
+        if isinstance(params, (str, os.PathLike)):
+            from minppo_amd.infer import load_model as load_pickle
+
+            params = load_pickle(os.fspath(params))
+        if obs_norm is None and isinstance(params, dict):
+            obs_norm = params.get("obs_norm")
         flat = _flat_params(params, dims.obs_dim, dims.nu, config.model.hidden_size, L)
         params_dev = torch.from_numpy(flat).to(device) if torch is not None else np.ascontiguousarray(flat)
-        result = run(lib, xp, device, stream, model, dims, net, params_dev, ecfg)
+        result = run(lib, xp, device, stream, model, dims, net, params_dev, ecfg, obs_norm=obs_norm)
     finally:
         if torch is not None:
             torch.cuda.synchronize(device)

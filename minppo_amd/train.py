@@ -58,6 +58,9 @@ class TrainState(NamedTuple):
 
 
 class RunnerState(NamedTuple):
+    """`last_obs` is the row as the engine stores it: with `training.normalize_observations` the NORMALISED observation (the table of the update
+    that collected it; what the network reads), otherwise the raw one.  `HumanoidEnv` returns raw observations either way."""
+
     train_state: TrainState
     env_state: Any
     last_obs: Any
@@ -175,6 +178,7 @@ def tree_to_flat(tree: dict, O: int, A: int, H: int, L: int = 2) -> np.ndarray:
 _REGION_DTYPES = {
     "count": "int32", "done": "uint8", "perm": "int32", "adv_sums": "float64", "episode_lengths": "int32",
     "returned_episode_lengths": "int32", "timestep": "int32", "returned_episode": "uint8", "jax_rng": "int32", "reset_rng": "int32",
+    "obs_norm_stats": "float64", "obs_norm_partials": "float64",
 }
 
 
@@ -243,6 +247,9 @@ class Trainer:
         if not 1 <= config.model.num_layers <= 4:
             raise ValueError(f"model.num_layers = {config.model.num_layers}: the MI355X engine lays out 1 to 4 hidden layers (reference default 2, config.py:53)")
         self.L = int(config.model.num_layers)
+        self.obs_norm_on = bool(tr.normalize_observations)
+        if self.obs_norm_on and world_size > 1:  # (the engine refuses it too; here before anything is created)
+            raise ValueError(f"training.normalize_observations with {world_size} ranks: the running statistics are not summed over ranks (single rank only)")
         if tr.num_envs % world_size != 0:
             raise ValueError(f"training.num_envs ({tr.num_envs}) must be divisible by the number of ranks ({world_size})")
         self.num_envs_global = tr.num_envs
@@ -300,6 +307,10 @@ class Trainer:
         self.reset_noise_scale = float(config.environment.reset_noise_scale)  # (make_config refuses a negative one; so does the engine)
         if self.reset_noise_scale > 0:
             self.lib.engine_set_reset_noise(self._engine, self.reset_noise_scale)
+        # training.normalize_observations: off leaves the engine's launch sequence as it is
+        self.obs_norm_clip, self.obs_norm_eps = float(tr.obs_norm_clip), float(tr.obs_norm_eps)
+        if self.obs_norm_on:
+            self.lib.engine_set_obs_norm(self._engine, 1, self.obs_norm_clip, self.obs_norm_eps)
         self.P = int(self.lib.param_count(C.byref(self.net)))
         self.updates_done = 0
         self._prepared = False
@@ -388,13 +399,13 @@ class Trainer:
     # uninterrupted run bit for bit (tests/test_train_surface.py).
     _CKPT_REGIONS = ("params", "adam_m", "adam_v", "count", "state", "episode_returns", "episode_lengths", "returned_episode_returns",
                      "returned_episode_lengths", "timestep", "returned_episode", "jax_rng")
-    _CKPT_OPTIONAL = ("reset_rng",)  # (regions younger than checkpoint version 2: written always, read when the file has them)
+    _CKPT_OPTIONAL = ("reset_rng", "obs_norm_stats", "obs_norm_table")  # (regions younger than checkpoint version 2: written always, read when the file has them)
     _CKPT_VERSION = 2  # 2: 16-byte-aligned flat parameter layout
 
     def _ckpt_meta(self) -> Dict[str, Any]:
         return dict(version=self._CKPT_VERSION, model=self.cm.name, num_envs=self.N, num_steps=self.T, obs_dim=self.O, act_dim=self.A, hidden=self.H,
                     params=self.P, rec_dim=int(self.dims.rec_dim), seed=int(self.seed), rank=self.rank, world_size=self.world_size,
-                    rng_impl="threefry" if self.ecfg.rng_impl == 1 else "philox")
+                    rng_impl="threefry" if self.ecfg.rng_impl == 1 else "philox", normalize_observations=self.obs_norm_on)
 
     def save_checkpoint(self, path: str) -> None:
         self._sync()
@@ -419,6 +430,11 @@ class Trainer:
             # the seed keys the engine's Philox streams: only the same seed continues the same noise / permutation sequence
             meta.setdefault("rng_impl", "philox")  # (files written before the field existed: the engine's own streams)
             # rng_impl: a philox checkpoint carries an all-zero "jax_rng" region; continued with threefry it would silently draw from key (0, 0)
+            meta.setdefault("normalize_observations", False)  # (files written before the option existed)
+            if meta["normalize_observations"] != want["normalize_observations"]:
+                # the stored observations, the parameters and the table belong together: a policy trained on normalised rows reads raw ones as noise
+                raise ValueError(f"checkpoint {path}: written with training.normalize_observations={str(meta['normalize_observations']).lower()}, this run has "
+                                 f"training.normalize_observations={str(want['normalize_observations']).lower()}")
             for k in ("version", "model", "num_envs", "num_steps", "obs_dim", "act_dim", "hidden", "params", "rec_dim", "world_size", "rank", "seed", "rng_impl"):
                 if meta.get(k) != want[k]:
                     raise ValueError(f"checkpoint {path}: {k} = {meta.get(k)!r} does not match this run ({want[k]!r})")
@@ -444,7 +460,24 @@ class Trainer:
 
     @property
     def params(self) -> dict:
-        return flat_to_tree(self.params_flat(), self.O, self.A, self.H, self.L)
+        """The model file's tree.  With `training.normalize_observations` it carries, beside "params", what the policy's inputs went through:
+        "obs_norm" = {"mean" f32[O], "inv_std" f32[O], "clip", "count"} - the table the NEXT rollout would apply (`evaluate` reads it)."""
+        tree = flat_to_tree(self.params_flat(), self.O, self.A, self.H, self.L)
+        if self.obs_norm_on:
+            on = self.obs_norm()
+            tree["obs_norm"] = {"mean": on["table"][0].copy(), "inv_std": on["table"][1].copy(), "clip": float(on["clip"]), "count": float(on["count"])}
+        return tree
+
+    def obs_norm(self) -> Dict[str, Any]:
+        """The running observation statistics on the host: "count" (rows seen = updates x T x N), "mean" / "var" (float64 [O], var = M2 / count),
+        "table" (float32 [2, O]: mean32 | inv_std32, what the next rollout applies), "clip", "eps".  Identity table and zero count when the option is off."""
+        self._sync()
+        st = self._to_host(self.region("obs_norm_stats")).astype(np.float64)
+        O, n = self.O, float(st[0])
+        table = self._to_host(self.region("obs_norm_table", (2, self.OP)))[:, :O].astype(np.float32).copy()
+        if not self.obs_norm_on:
+            n, st, table = 0.0, np.zeros_like(st), np.stack([np.zeros(O, np.float32), np.ones(O, np.float32)])
+        return dict(count=n, mean=st[1:1 + O].copy(), var=st[1 + O:1 + 2 * O] / n if n > 0 else np.zeros(O), table=table, clip=self.obs_norm_clip, eps=self.obs_norm_eps)
 
     # -- multi-GPU ---------------------------------------------------------------
     def init_comm(self, mode: Optional[str] = None) -> str:
@@ -818,8 +851,10 @@ class Trainer:
         from minppo_amd import evaluate as ev
 
         overrides.setdefault("seed", self.seed)
+        on = self.obs_norm() if self.obs_norm_on else None  # (the table the next rollout would apply: what these parameters were last trained towards)
         # (on the trainer's own stream: behind the last enqueued update, whose parameters it reads)
-        return ev.run(self.lib, self.xp, self.device, self.stream, self._model, self.dims, self.net, self.region("params"), ev.eval_cfg(self.config, **overrides))
+        return ev.run(self.lib, self.xp, self.device, self.stream, self._model, self.dims, self.net, self.region("params"), ev.eval_cfg(self.config, **overrides),
+                      obs_norm=None if on is None else {"mean": on["table"][0], "inv_std": on["table"][1], "clip": on["clip"]})
 
     def rollout_stats(self, reduce: bool = False) -> Dict[str, float]:
         """Device-side reduction of the last rollout's `EnvMetrics` history (`env.py:183-194`, `train.py:170,283`):

@@ -339,6 +339,24 @@ int32_t mppo_obs_norm_apply(int32_t N, int32_t O, float* obs, int32_t obs_ld, co
 int32_t mppo_obs_norm_update(int32_t O, int32_t n_partials, int64_t rows, const double* partial, double* stats, float eps, float* table, int32_t table_ld,
                              void* stream);
 
+/* Reward scaling (csrc/k_rewnorm.hip).  The reference's GAE reads the raw reward (train.py:185-205); this is what gym's `NormalizeReward`, SB3's
+ * `VecNormalize(norm_reward=True)` and Brax's `reward_scaling` do: the rewards of a rollout divided by the running standard deviation of the
+ * discounted return.  `table` [2] = mean32 | inv_std32 and `stats` [3] = count n | mean | M2 are those of mppo_obs_norm_update with O = 1, table_ld = 1.
+ *   mppo_reward_norm_partials  G, the workgroups (= partial sums) of one apply launch over N environments: ceil(N / 256)
+ *   mppo_reward_norm_apply     one thread per environment n, forward over t = 0 .. T - 1 from ret = carry[n]: ret = ret * gamma + reward[t][n] in float32
+ *                              (a multiply, then an add: two roundings); d = (double)ret - (double)table[0] is summed into S1 = sum d, S2 = sum d^2;
+ *                              scaled[t][n] = reward[t][n] * table[1] in float32, clamped to [-clip, clip] when clip > 0 (a NaN stays a NaN); then, where
+ *                              done[t][n], ret = 0 (the return that ends an episode is counted, then the carry restarts); at the end carry[n] = ret.
+ *                              Rewards are scaled, never centred: the mean only shifts the sums.  `scaled` may be `reward`.  partial != NULL ([G][2]
+ *                              float64): workgroup g writes (S1, S2) over its environments 256 g .. 256 g + 255 below N - a thread's steps in t order,
+ *                              then the 64 lanes of a wave, then the four waves in wave order; no atomics, the same inputs give the same bytes.
+ *                              MPPO_EINVAL: non-positive T / N, a null pointer (partial excepted), a negative (or NaN) clip, pointers not 4-byte
+ *                              (partial: 8-byte) aligned.
+ * The merge is mppo_obs_norm_update(1, G, T * N, partial, stats, eps, table, 1, stream). */
+int32_t mppo_reward_norm_partials(int32_t N);
+int32_t mppo_reward_norm_apply(int32_t T, int32_t N, float gamma, const float* reward, const uint8_t* done, float* carry, const float* table, float clip,
+                               float* scaled, double* partial, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Engine: the whole `_update_step` (train.py:146-283) as one call, launches enqueued from
  * C++ (optionally replayed from a hipGraph), gradients summed over ranks with RCCL.
@@ -372,6 +390,7 @@ typedef struct mppo_engine_cfg {
  * "params" "adam_m" "adam_v" "grad" "count" "state" "reset_rec" "obs" "action" "value" "reward"
  * "log_prob" "done" "last_val" "adv" "target" "noise" "perm" "adv_stats" "losses" "rollout_stats" "jax_rng" "reset_rng"
  * "obs_norm_stats" (float64) "obs_norm_table" "obs_norm_partials" (float64)
+ * "reward_norm_stats" (float64 [3]) "reward_norm_table" ([2]) "reward_norm_carry" ([N]) "reward_norm_partials" (float64 [G][2]) "reward_scaled" ([T][N])
  * ("rollout_stats": 8 floats: sum reward, episodes ended, sum of their returns, sum of their lengths, the two means, 0, 0) ... */
 int32_t mppo_engine_arena_bytes(const mppo_model_t* m, const mppo_engine_cfg_t* cfg, size_t* out);
 int32_t mppo_engine_create(const mppo_model_t* m, const mppo_engine_cfg_t* cfg, void* arena, size_t arena_bytes,
@@ -438,6 +457,17 @@ int32_t mppo_engine_set_reset_noise(mppo_engine_t* e, float scale);
  * every other one and exist whether or not the option is on.  Call before mppo_engine_reset, mppo_engine_prepare and the first mppo_engine_update:
  * afterwards it returns MPPO_ESTATE.  MPPO_EINVAL: a negative (or NaN) clip / eps; enabled with world_size > 1 (the statistics are not summed over ranks). */
 int32_t mppo_engine_set_obs_norm(mppo_engine_t* e, int32_t enabled, float clip, float eps);
+/* Reward scaling (mppo_reward_norm_* above; enabled = 0, the default: the engine enqueues exactly the launches it enqueues without this call).
+ * enabled != 0: behind the rollout's bootstrap critic forward, one mppo_reward_norm_apply over the T steps reads arena region "reward" and writes
+ * "reward_scaled" ([T][N]) with the table of "reward_norm_table" ([2]), the carried discounted return of "reward_norm_carry" ([N]) and the partials
+ * in "reward_norm_partials" ([G][2]); GAE then reads "reward_scaled"; behind GAE one mppo_obs_norm_update(1, G, T * N, ...) merges the partials into
+ * "reward_norm_stats" ([3] float64) and rewrites the table: 2 launches more per update, inside the captured graph too.  So the scale is frozen within
+ * an update - update u divides by the deviation collected through update u - 1, the first by 1 - and the count is updates * T * N.  "reward",
+ * "rollout_stats" and the environment's metrics stay raw: users see real returns.  mppo_engine_reset zeroes the statistics and the carry and writes the
+ * identity table 0 | 1.  The five regions lie behind every other one and exist whether or not the option is on.  Call before mppo_engine_reset,
+ * mppo_engine_prepare and the first mppo_engine_update: afterwards it returns MPPO_ESTATE.  MPPO_EINVAL: a negative (or NaN) clip / eps; enabled with
+ * world_size > 1 (the sums are not exchanged between ranks; switching it off is never refused for the rank count). */
+int32_t mppo_engine_set_reward_norm(mppo_engine_t* e, int32_t enabled, float clip, float eps);
 /* one full update: T rollout steps, bootstrap value, GAE, E epochs x M minibatches */
 int32_t mppo_engine_update(mppo_engine_t* e, void* stream);
 /* what mppo_engine_update does before it enqueues anything: the one-time capture of the update into a hipGraph (no device work).

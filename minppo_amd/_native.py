@@ -153,6 +153,8 @@ SIGNATURES = {
     "mppo_obs_norm_partials": (c_i32, [c_i32]),
     "mppo_obs_norm_apply": (c_i32, [c_i32, c_i32, c_vp, c_i32, c_vp, c_i32, c_f, c_vp, c_vp]),
     "mppo_obs_norm_update": (c_i32, [c_i32, c_i32, C.c_int64, c_vp, c_vp, c_f, c_vp, c_i32, c_vp]),
+    "mppo_reward_norm_partials": (c_i32, [c_i32]),
+    "mppo_reward_norm_apply": (c_i32, [c_i32, c_i32, c_f, c_vp, c_vp, c_vp, c_vp, c_f, c_vp, c_vp, c_vp]),
     "mppo_engine_arena_bytes": (c_i32, [c_vp, P(EngineCfg), P(c_sz)]),
     "mppo_engine_create": (c_i32, [c_vp, P(EngineCfg), c_vp, c_sz, P(c_vp)]),
     "mppo_engine_destroy": (c_i32, [c_vp]),
@@ -169,6 +171,7 @@ SIGNATURES = {
     "mppo_engine_reset": (c_i32, [c_vp, c_vp]),
     "mppo_engine_set_reset_noise": (c_i32, [c_vp, c_f]),
     "mppo_engine_set_obs_norm": (c_i32, [c_vp, c_i32, c_f, c_f]),
+    "mppo_engine_set_reward_norm": (c_i32, [c_vp, c_i32, c_f, c_f]),
     "mppo_engine_update": (c_i32, [c_vp, c_vp]),
     "mppo_engine_prepare": (c_i32, [c_vp, c_vp]),
     "mppo_engine_graph_active": (c_i32, [c_vp, P(c_i32)]),
@@ -186,7 +189,8 @@ SIGNATURES = {
 }
 
 UNCHECKED = {"mppo_last_error", "mppo_abi_version", "mppo_param_count", "mppo_policy_ws_bytes", "mppo_grad_ws_bytes",
-             "mppo_adam_ws_bytes", "mppo_permutation_ws_bytes", "mppo_eval_ws_bytes", "mppo_obs_norm_partials"}
+             "mppo_adam_ws_bytes", "mppo_permutation_ws_bytes", "mppo_eval_ws_bytes", "mppo_obs_norm_partials",
+             "mppo_reward_norm_partials"}
 
 
 class Lib:

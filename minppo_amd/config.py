@@ -144,6 +144,13 @@ class TrainingConfig:
     normalize_observations: bool = field(default=False)
     obs_norm_clip: float = field(default=10.0)
     obs_norm_eps: float = field(default=1e-8)
+    # Extension (absent upstream; gym `NormalizeReward`, SB3 `VecNormalize(norm_reward=True)`, Brax `reward_scaling`): the rewards GAE reads are divided
+    # by the running standard deviation of the discounted return, collected on the device from the rollout's own rewards.  Scaled, never
+    # centred; the scale is frozen within an update.  `reward_norm_clip` clamps the scaled reward to [-clip, clip] (0 = no clamp); `reward_norm_eps` is
+    # added to the variance.  Metrics and `evaluate` report raw returns.  Off: nothing changes.  Single rank only.
+    normalize_rewards: bool = field(default=False)
+    reward_norm_clip: float = field(default=10.0)
+    reward_norm_eps: float = field(default=1e-8)
     checkpoint_path: str = field(default="")
     checkpoint_every: int = field(default=0)
     resume_from: str = field(default="")
@@ -280,7 +287,7 @@ def make_config(yaml_dict: dict | None = None, overrides: Sequence[str] = ()) ->
         _merge_into(cfg, _dotlist_to_dict(overrides))
     if not cfg.environment.reset_noise_scale >= 0.0:
         raise ValueError(f"environment.reset_noise_scale = {cfg.environment.reset_noise_scale!r}: the half-width of the reset noise cannot be negative")
-    for key in ("obs_norm_clip", "obs_norm_eps"):
+    for key in ("obs_norm_clip", "obs_norm_eps", "reward_norm_clip", "reward_norm_eps"):
         if not getattr(cfg.training, key) >= 0.0:
             raise ValueError(f"training.{key} = {getattr(cfg.training, key)!r} cannot be negative")
     return cfg

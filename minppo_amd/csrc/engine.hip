@@ -20,6 +20,7 @@
 #include "platform.h"
 #include "peer.h"
 #include "obsnorm.h"
+#include "rewnorm.h"
 
 #include <cmath>
 #include <cstdlib>
@@ -145,6 +146,14 @@ struct mppo_engine {
   double* obs_norm_stats;     // [1 + 2 O] count | mean | M2
   float* obs_norm_table;      // [2][OP] mean32 | inv_std32: what this update's rollout applies
   double* obs_norm_partials;  // [T][G][2][O] the apply launches' sums of this update
+  // reward scaling (mppo_engine_set_reward_norm; off: nothing below is used and no launch is added)
+  bool reward_norm;
+  float reward_norm_clip, reward_norm_eps;
+  double* reward_norm_stats;     // [3] count | mean | M2 of the discounted return
+  float* reward_norm_table;      // [2] mean32 | inv_std32: the scale this update's rollout applies
+  float* reward_norm_carry;      // [N] the discounted return carried from one update to the next
+  double* reward_norm_partials;  // [G][2] the apply launch's sums of this update
+  float* reward_scaled;          // [T][N] what GAE reads; "reward" stays raw
 };
 
 namespace mppo {
@@ -210,6 +219,12 @@ static size_t layout(mppo_engine* e, bool assign) {
   e->obs_norm_stats = (double*)take("obs_norm_stats", (1 + 2 * (size_t)e->O) * 8);
   e->obs_norm_table = (float*)take("obs_norm_table", 2 * OP * 4);
   e->obs_norm_partials = (double*)take("obs_norm_partials", T * obs_norm_partial_doubles((int)N, e->O) * 8);
+  // reward scaling: behind those again, present whether or not the option is on
+  e->reward_norm_stats = (double*)take("reward_norm_stats", 3 * 8);
+  e->reward_norm_table = (float*)take("reward_norm_table", 2 * 4);
+  e->reward_norm_carry = (float*)take("reward_norm_carry", N * 4);
+  e->reward_norm_partials = (double*)take("reward_norm_partials", (size_t)reward_norm_partials((int)N) * 2 * 8);
+  e->reward_scaled = (float*)take("reward_scaled", B * 4);
   return align_up(off, 256);
 }
 
@@ -310,12 +325,20 @@ static int32_t do_rollout(mppo_engine* e, hipStream_t s) {
     MPPO_TRY(policy_forward(c.net, e->params, (e->T + 1) * e->N, e->obs, e->OP, fb, nullptr, nullptr, nullptr, e->value, nullptr, s));
   else
     MPPO_TRY(policy_forward(c.net, e->params, e->N, e->obs + (size_t)e->T * N * OP, e->OP, fb, nullptr, nullptr, nullptr, e->last_val, nullptr, s));  // train.py:182
-  MPPO_TRY(gae_launch(e->T, e->N, c.gamma, c.gae_lambda, e->reward, e->value, e->done, e->last_val, e->adv, e->target, s));
+  // reward scaling: GAE reads the rewards divided by the return deviation collected through the previous update (the scale is frozen within an update);
+  // the statistics kernel below, the metrics and the history go on reading the raw rewards
+  if (e->reward_norm)
+    MPPO_TRY(reward_norm_apply_launch(e->T, e->N, c.gamma, e->reward, e->done, e->reward_norm_carry, e->reward_norm_table, e->reward_norm_clip, e->reward_scaled,
+                                      e->reward_norm_partials, s));
+  MPPO_TRY(gae_launch(e->T, e->N, c.gamma, c.gae_lambda, e->reward_norm ? e->reward_scaled : e->reward, e->value, e->done, e->last_val, e->adv, e->target, s));
   hipLaunchKernelGGL(rollout_stats_kernel, dim3(1), dim3(kStatsThreads), 0, s, e->T, e->N, e->reward, e->done, e->stat_ret_in, e->stat_len_in, e->stats);
   MPPO_CHECK_LAUNCH("rollout_stats_kernel");
   if (e->obs_norm)  // the T steps' rows join the running statistics; the table is rewritten for the next update (nothing of this one applies it any more)
     MPPO_TRY(obs_norm_update_launch(e->O, e->T * obs_norm_partials(e->N), (long long)e->T * e->N, e->obs_norm_partials, e->obs_norm_stats, e->obs_norm_eps, e->obs_norm_table,
                                     e->OP, s));
+  if (e->reward_norm)  // this update's T N returns join the running statistics; the scale is rewritten for the next update
+    MPPO_TRY(obs_norm_update_launch(1, reward_norm_partials(e->N), (long long)e->T * e->N, e->reward_norm_partials, e->reward_norm_stats, e->reward_norm_eps,
+                                    e->reward_norm_table, 1, s));
   return MPPO_OK;
 }
 
@@ -435,6 +458,7 @@ extern "C" int32_t mppo_engine_create(const mppo_model_t* m, const mppo_engine_c
   e->comm = nullptr; e->peer = nullptr; e->graph = nullptr; e->graph_failed = false; e->was_reset = false; e->graph_agreed = false;
   e->reset_noise = 0.f; e->prepared = false;
   e->obs_norm = false; e->obs_norm_clip = 0.f; e->obs_norm_eps = 0.f;
+  e->reward_norm = false; e->reward_norm_clip = 0.f; e->reward_norm_eps = 0.f;
   *out = e;
   return MPPO_OK;
 }
@@ -492,6 +516,11 @@ extern "C" int32_t mppo_engine_reset(mppo_engine_t* e, void* stream) {
     MPPO_CHECK_HIP(hipMemsetAsync(e->obs_norm_stats, 0, (1 + 2 * (size_t)e->O) * 8, s));
     MPPO_TRY(obs_norm_update_launch(e->O, 0, 0, nullptr, e->obs_norm_stats, e->obs_norm_eps, e->obs_norm_table, e->OP, s));
   }
+  if (e->reward_norm) {  // nothing counted, no return carried, the identity table: the first update's rewards are multiplied by 1
+    MPPO_CHECK_HIP(hipMemsetAsync(e->reward_norm_stats, 0, 3 * 8, s));
+    MPPO_CHECK_HIP(hipMemsetAsync(e->reward_norm_carry, 0, (size_t)e->N * 4, s));
+    MPPO_TRY(obs_norm_update_launch(1, 0, 0, nullptr, e->reward_norm_stats, e->reward_norm_eps, e->reward_norm_table, 1, s));
+  }
   e->was_reset = true;
   return MPPO_OK;
 }
@@ -509,6 +538,23 @@ extern "C" int32_t mppo_engine_set_obs_norm(mppo_engine_t* e, int32_t enabled, f
   e->obs_norm = enabled != 0;
   e->obs_norm_clip = clip;
   e->obs_norm_eps = eps;
+  return MPPO_OK;
+}
+
+extern "C" int32_t mppo_engine_set_reward_norm(mppo_engine_t* e, int32_t enabled, float clip, float eps) {
+  MPPO_REQUIRE(e, "mppo_engine_set_reward_norm: null engine");
+  MPPO_REQUIRE(clip >= 0.f && eps >= 0.f, "mppo_engine_set_reward_norm: clip %g / eps %g is negative (or not a number)", (double)clip, (double)eps);
+  MPPO_REQUIRE(!enabled || e->cfg.world_size == 1, "mppo_engine_set_reward_norm: world_size = %d ranks - the running statistics are not summed over ranks, reward "
+               "scaling runs on a single rank only", e->cfg.world_size);
+  if (e->graph || e->prepared)
+    return fail(MPPO_ESTATE, "mppo_engine_set_reward_norm: the update has been prepared already (its launch sequence is fixed, a captured graph holds it): "
+                             "call it before mppo_engine_reset, mppo_engine_prepare and the first mppo_engine_update");
+  if (e->was_reset)
+    return fail(MPPO_ESTATE, "mppo_engine_set_reward_norm: mppo_engine_reset has run already (it zeroes the statistics and the carry and writes the identity table): "
+                             "call it before the reset");
+  e->reward_norm = enabled != 0;
+  e->reward_norm_clip = clip;
+  e->reward_norm_eps = eps;
   return MPPO_OK;
 }
 

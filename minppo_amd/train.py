@@ -178,7 +178,7 @@ def tree_to_flat(tree: dict, O: int, A: int, H: int, L: int = 2) -> np.ndarray:
 _REGION_DTYPES = {
     "count": "int32", "done": "uint8", "perm": "int32", "adv_sums": "float64", "episode_lengths": "int32",
     "returned_episode_lengths": "int32", "timestep": "int32", "returned_episode": "uint8", "jax_rng": "int32", "reset_rng": "int32",
-    "obs_norm_stats": "float64", "obs_norm_partials": "float64",
+    "obs_norm_stats": "float64", "obs_norm_partials": "float64", "reward_norm_stats": "float64", "reward_norm_partials": "float64",
 }
 
 
@@ -250,6 +250,9 @@ class Trainer:
         self.obs_norm_on = bool(tr.normalize_observations)
         if self.obs_norm_on and world_size > 1:  # (the engine refuses it too; here before anything is created)
             raise ValueError(f"training.normalize_observations with {world_size} ranks: the running statistics are not summed over ranks (single rank only)")
+        self.reward_norm_on = bool(tr.normalize_rewards)
+        if self.reward_norm_on and world_size > 1:  # (the engine refuses it too; here before anything is created)
+            raise ValueError(f"training.normalize_rewards with {world_size} ranks: the running return statistics are not summed over ranks (single rank only)")
         if tr.num_envs % world_size != 0:
             raise ValueError(f"training.num_envs ({tr.num_envs}) must be divisible by the number of ranks ({world_size})")
         self.num_envs_global = tr.num_envs
@@ -311,6 +314,10 @@ class Trainer:
         self.obs_norm_clip, self.obs_norm_eps = float(tr.obs_norm_clip), float(tr.obs_norm_eps)
         if self.obs_norm_on:
             self.lib.engine_set_obs_norm(self._engine, 1, self.obs_norm_clip, self.obs_norm_eps)
+        # training.normalize_rewards: likewise
+        self.reward_norm_clip, self.reward_norm_eps = float(tr.reward_norm_clip), float(tr.reward_norm_eps)
+        if self.reward_norm_on:
+            self.lib.engine_set_reward_norm(self._engine, 1, self.reward_norm_clip, self.reward_norm_eps)
         self.P = int(self.lib.param_count(C.byref(self.net)))
         self.updates_done = 0
         self._prepared = False
@@ -399,13 +406,14 @@ class Trainer:
     # uninterrupted run bit for bit (tests/test_train_surface.py).
     _CKPT_REGIONS = ("params", "adam_m", "adam_v", "count", "state", "episode_returns", "episode_lengths", "returned_episode_returns",
                      "returned_episode_lengths", "timestep", "returned_episode", "jax_rng")
-    _CKPT_OPTIONAL = ("reset_rng", "obs_norm_stats", "obs_norm_table")  # (regions younger than checkpoint version 2: written always, read when the file has them)
+    _CKPT_OPTIONAL = ("reset_rng", "obs_norm_stats", "obs_norm_table", "reward_norm_stats", "reward_norm_table", "reward_norm_carry")  # (regions younger than checkpoint version 2: written always, read when the file has them)
     _CKPT_VERSION = 2  # 2: 16-byte-aligned flat parameter layout
 
     def _ckpt_meta(self) -> Dict[str, Any]:
         return dict(version=self._CKPT_VERSION, model=self.cm.name, num_envs=self.N, num_steps=self.T, obs_dim=self.O, act_dim=self.A, hidden=self.H,
                     params=self.P, rec_dim=int(self.dims.rec_dim), seed=int(self.seed), rank=self.rank, world_size=self.world_size,
-                    rng_impl="threefry" if self.ecfg.rng_impl == 1 else "philox", normalize_observations=self.obs_norm_on)
+                    rng_impl="threefry" if self.ecfg.rng_impl == 1 else "philox", normalize_observations=self.obs_norm_on,
+                    normalize_rewards=self.reward_norm_on)
 
     def save_checkpoint(self, path: str) -> None:
         self._sync()
@@ -435,6 +443,11 @@ class Trainer:
                 # the stored observations, the parameters and the table belong together: a policy trained on normalised rows reads raw ones as noise
                 raise ValueError(f"checkpoint {path}: written with training.normalize_observations={str(meta['normalize_observations']).lower()}, this run has "
                                  f"training.normalize_observations={str(want['normalize_observations']).lower()}")
+            meta.setdefault("normalize_rewards", False)  # (likewise)
+            if meta["normalize_rewards"] != want["normalize_rewards"]:
+                # the critic's targets are in units of the scale: a value head trained on scaled returns is off by that factor on raw ones, and back
+                raise ValueError(f"checkpoint {path}: written with training.normalize_rewards={str(meta['normalize_rewards']).lower()}, this run has "
+                                 f"training.normalize_rewards={str(want['normalize_rewards']).lower()}")
             for k in ("version", "model", "num_envs", "num_steps", "obs_dim", "act_dim", "hidden", "params", "rec_dim", "world_size", "rank", "seed", "rng_impl"):
                 if meta.get(k) != want[k]:
                     raise ValueError(f"checkpoint {path}: {k} = {meta.get(k)!r} does not match this run ({want[k]!r})")
@@ -478,6 +491,17 @@ class Trainer:
         if not self.obs_norm_on:
             n, st, table = 0.0, np.zeros_like(st), np.stack([np.zeros(O, np.float32), np.ones(O, np.float32)])
         return dict(count=n, mean=st[1:1 + O].copy(), var=st[1 + O:1 + 2 * O] / n if n > 0 else np.zeros(O), table=table, clip=self.obs_norm_clip, eps=self.obs_norm_eps)
+
+    def reward_norm(self) -> Dict[str, Any]:
+        """The running statistics of the discounted return on the host: "count" (steps seen = updates x T x N), "mean" / "var" (float64, var = M2 / count),
+        "scale" (the float32 inv_std the next rollout multiplies the rewards with; rewards are never centred), "clip", "eps".  Zero count and scale 1
+        when the option is off."""
+        self._sync()
+        st = self._to_host(self.region("reward_norm_stats")).astype(np.float64)
+        n, scale = float(st[0]), float(self._to_host(self.region("reward_norm_table"))[1])
+        if not self.reward_norm_on:
+            n, st, scale = 0.0, np.zeros_like(st), 1.0
+        return dict(count=n, mean=float(st[1]), var=float(st[2] / n) if n > 0 else 0.0, scale=scale, clip=self.reward_norm_clip, eps=self.reward_norm_eps)
 
     # -- multi-GPU ---------------------------------------------------------------
     def init_comm(self, mode: Optional[str] = None) -> str:

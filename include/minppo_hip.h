@@ -79,7 +79,8 @@ int32_t mppo_model_is_specialized(const mppo_model_t* m, int32_t* out);
  * csrc/k_physics.hip with a one-robot list, cached by the hash of the kernel sources and the dimensions).  What it replaces in the
  * reference: `jax.jit` of the environment step (env.py:123,147 `@partial(jax.jit, ...)` on reset / step, train.py:133,138,306: XLA
  * compiles them for the loaded robot's shapes at start-up).  `names[0..2]`: the symbols of the kernel's three modes (reset, step, probe) - their mangled names must
- * spell this model's dimensions; `regchol_max_nv`: the MPPO_REGCHOL_MAX_NV the object was compiled with (48 by default: its LDS layout
+ * spell this model's dimensions (the step's and the probe's instantiations under an external wrench, mppo_env_step_xfrc below, are looked up in the same object
+ * under those two names with the mode's digit 1 / 2 replaced by 3 / 4: an object without them is refused); `regchol_max_nv`: the MPPO_REGCHOL_MAX_NV the object was compiled with (48 by default: its LDS layout
  * follows from it).  The object must carry the library's `mppo_env_kernel_tag` (argument-struct sizes, blob version).  Before it is
  * used, a reset and four steps of 24 environments must equal the run-time-sized kernel's bit for bit on this device.  *used = 1: the
  * model now runs the attached kernel (mppo_model_is_specialized reports 2); *used = 0 with MPPO_OK: it does not - the library has an
@@ -158,6 +159,46 @@ typedef struct mppo_forward_probe {
 } mppo_forward_probe_t;
 int32_t mppo_physics_forward(const mppo_model_t* m, int32_t N, const float* qpos, const float* qvel, const float* ctrl,
                              const float* qacc_warmstart, const mppo_forward_probe_t* out, void* stream);
+
+/* ---- random pushes: an external wrench on one body --------------------------------------------------------------------------
+ * What MJX calls `xfrc_applied` (Brax: `pipeline_state.xfrc_applied` before `pipeline_step`), for ONE body per launch: a force and a torque in
+ * world axes acting at the body's centre of mass `xipos[body]`, added to qfrc_smooth as `support.xfrc_accumulate` adds it inside
+ * `forward.fwd_acceleration`:
+ *     qfrc_smooth[d] += cdof[d] . (torque + (xipos[body] - subtree_com[root(body)]) x force, force)
+ * for every dof d of `body` and of its ancestors, and for no other dof.  The wrench is constant over the n_frames frames of an env step.  It
+ * changes qfrc_smooth and what follows from it (qacc_smooth, the solver's input, the Euler solve); qfrc_actuator, the observation of the
+ * pre-step state, the reward's control cost and the NaN guard see it only through the state it produces.  The reset is never pushed.
+ *
+ * mppo_env_step_xfrc : mppo_env_step with `xfrc` [N][6] floats in DEVICE memory - per environment force (3) then torque (3) - acting on `body`
+ *                   (1 .. nbody - 1; MPPO_EINVAL otherwise).  xfrc = NULL: exactly mppo_env_step, launch and bits (`body` is then not read); an
+ *                   all-zero row leaves its environment's bits what the unpushed step gives.
+ * mppo_physics_forward_xfrc : the probe mppo_physics_forward with the same two arguments: qacc_smooth, efc_aref, qacc and qacc_euler are those
+ *                   under the wrench; qM, qfrc_bias, qfrc_passive, qfrc_actuator, the poses and cinert / cvel do not depend on it. */
+int32_t mppo_env_step_xfrc(const mppo_model_t* m, int32_t N, int32_t n_frames, const mppo_reward_cfg_t* rc, float* state,
+                           const float* reset_rec, const float* action, int32_t act_ld, float* obs, int32_t obs_ld,
+                           float* reward, uint8_t* done, const mppo_env_metrics_t* metrics, int32_t body, const float* xfrc, void* stream);
+int32_t mppo_physics_forward_xfrc(const mppo_model_t* m, int32_t N, const float* qpos, const float* qvel, const float* ctrl,
+                                  const float* qacc_warmstart, const mppo_forward_probe_t* out, int32_t body, const float* xfrc, void* stream);
+/* The random draw (csrc/push.h; host statement minppo_amd/jaxrng.py push_wrench_philox).  Stateless - a function of (seed, rank, environment,
+ * step) alone, so nothing is added to the state record or to a checkpoint.  With S = ("PUSH" << 24) + (rank << 16), for local environment n:
+ *     phase_n = word 0 of philox(counter = {n, 0xFFFFFFFF, lo(S), hi(S)}, key = seed) mod interval
+ *     pushed at step s  iff  (s + phase_n) mod interval < duration;   window k = (s + phase_n) / interval      (uint32 arithmetic)
+ *     fx, fy = uniform(word 0 / word 1 of philox({n, k, lo(S), hi(S)}, seed), -force, force);   fz = 0, torque = 0
+ * bits -> float as in mppo_env_reinit.  Every environment is pushed on exactly `duration` of any `interval` consecutive steps, out of phase
+ * with the others, by a horizontal force uniform on a square that holds for the whole window - across an episode's auto-reset too.  An
+ * environment that is not pushed gets exact zeros.  The stream is the engine's Philox under both rng_impl values (the reference has no pushes).
+ * Refused (MPPO_EINVAL): a negative or NaN force, interval < 1, duration outside 1 .. interval, rank outside 0 .. 255, and - wherever a model
+ * is at hand - a body outside 1 .. nbody - 1.  force = 0 is "off" everywhere, and then nothing else of the configuration is read or refused.
+ *
+ * mppo_push_fill  : writes xfrc [N][6] (device) of step s = (counter ? *counter : 0) * counter_mul + counter_add, `counter` a word in DEVICE
+ *                   memory (NULL: 0) read when the launch runs.  `body` is not read.  One launch, no workspace. */
+typedef struct mppo_push_cfg {
+  int32_t body, interval, duration, rank;
+  float force;
+  uint64_t seed;
+} mppo_push_cfg_t;
+int32_t mppo_push_fill(const mppo_push_cfg_t* cfg, int32_t N, const int32_t* counter, int32_t counter_mul, int32_t counter_add, float* xfrc,
+                       void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * PPO stages
@@ -468,6 +509,15 @@ int32_t mppo_engine_set_obs_norm(mppo_engine_t* e, int32_t enabled, float clip, 
  * mppo_engine_prepare and the first mppo_engine_update: afterwards it returns MPPO_ESTATE.  MPPO_EINVAL: a negative (or NaN) clip / eps; enabled with
  * world_size > 1 (the sums are not exchanged between ranks; switching it off is never refused for the rank count). */
 int32_t mppo_engine_set_reward_norm(mppo_engine_t* e, int32_t enabled, float clip, float eps);
+/* Random pushes during training (mppo_push_cfg_t above; NULL or force = 0, the default: the engine enqueues exactly the launches, with exactly the
+ * arguments, it enqueues without this call).  force > 0: every rollout step's environment launch draws its wrench inside the kernel - no launch more,
+ * no [N][6] array, no arena region - at step s = u * T + t, u the device's update index "count"[1] read when the launch runs, so a replayed captured
+ * graph draws fresh pushes and a resumed run continues the sequence (checkpoints already carry the counter; nothing else is state).  `seed` and `rank`
+ * of the configuration are NOT read: the engine configuration's are used, so every rank pushes its own environments from its own stream and nothing
+ * crosses ranks - any world_size is allowed.  The same bits as mppo_push_fill(counter = "count" + 1, counter_mul = T, counter_add = t) followed by
+ * mppo_env_step_xfrc.  Call before mppo_engine_reset, mppo_engine_prepare and the first mppo_engine_update: afterwards it returns MPPO_ESTATE.
+ * MPPO_EINVAL: the refusals listed at mppo_push_cfg_t. */
+int32_t mppo_engine_set_push(mppo_engine_t* e, const mppo_push_cfg_t* push);
 /* one full update: T rollout steps, bootstrap value, GAE, E epochs x M minibatches */
 int32_t mppo_engine_update(mppo_engine_t* e, void* stream);
 /* what mppo_engine_update does before it enqueues anything: the one-time capture of the update into a hipGraph (no device work).
@@ -532,6 +582,14 @@ int32_t mppo_evaluate(const mppo_model_t* m, const mppo_net_t* net, const float*
  * alone, as in the engine.  obs_table: DEVICE memory, [2][O] floats (mean32 | inv_std32, row stride O); NULL: exactly mppo_evaluate.  Same workspace. */
 int32_t mppo_evaluate_obs_norm(const mppo_model_t* m, const mppo_net_t* net, const float* params, const mppo_eval_cfg_t* cfg, void* ws, size_t ws_bytes,
                                const float* obs_table, float clip, mppo_eval_result_t* result, float* traj, void* stream);
+/* mppo_evaluate_obs_norm under random pushes - the robustness test: `survivors` of `steps / N` pushed steps is the figure two standing policies are
+ * compared by.  push = NULL or force = 0: exactly mppo_evaluate_obs_norm (obs_table may be NULL as there).  Otherwise the documented sequence with
+ *        mppo_push_fill(push with rank 0 and seed = cfg->seed, N, NULL, 0, t, xfrc) + mppo_env_step_xfrc(..., push->body, xfrc)
+ * in place of step t's mppo_env_step - the same bits when the caller writes it out - except that the wrench is drawn inside the environment kernel:
+ * no launch more and no wrench array, so the workspace is mppo_eval_ws_bytes' as before.  `seed` and `rank` of the configuration are not read.  A push
+ * keeps running across an episode's restart.  MPPO_EINVAL: the refusals listed at mppo_push_cfg_t. */
+int32_t mppo_evaluate_push(const mppo_model_t* m, const mppo_net_t* net, const float* params, const mppo_eval_cfg_t* cfg, void* ws, size_t ws_bytes,
+                           const float* obs_table, float clip, const mppo_push_cfg_t* push, mppo_eval_result_t* result, float* traj, void* stream);
 /* The two statistics stages on caller-given arrays (as mppo_gae / mppo_adv_sums are stages of the update).
  * `acc`: the per-environment accumulators, 10 * N 8-byte words in device memory, 8-byte aligned, slot-major (word n of
  * slot k at 8 * (k * N + n)): int64 episodes, len_sum, len_min, len_max; double ret_sum, ret_sumsq, ret_min, ret_max,

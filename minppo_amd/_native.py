@@ -92,6 +92,10 @@ class EvalResultRaw(C.Structure):  # mppo_eval_result_t (minppo_amd.evaluate.Eva
         (n, C.c_double) for n in ("ret_sum", "ret_sumsq", "ret_min", "ret_max", "survivor_ret_sum", "reward_sum")]
 
 
+class PushCfg(C.Structure):  # mppo_push_cfg_t: random pushes (force 0: off)
+    _fields_ = [("body", c_i32), ("interval", c_i32), ("duration", c_i32), ("rank", c_i32), ("force", c_f), ("seed", c_u64)]
+
+
 class SceneDims(C.Structure):
     _fields_ = [(n, c_i32) for n in ("nq", "nbody", "ngeom", "ncam", "has_plane")]
 
@@ -120,6 +124,10 @@ SIGNATURES = {
                               P(EnvMetrics), c_vp]),
     "mppo_env_reinit": (c_i32, [c_vp, c_i32, c_vp, c_vp, c_i32, c_vp, c_f, c_i32, c_u64, c_i32, c_vp, c_vp, c_i32, c_vp]),
     "mppo_physics_forward": (c_i32, [c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, P(ForwardProbe), c_vp]),
+    "mppo_env_step_xfrc": (c_i32, [c_vp, c_i32, c_i32, P(RewardCfg), c_vp, c_vp, c_vp, c_i32, c_vp, c_i32, c_vp, c_vp,
+                                   P(EnvMetrics), c_i32, c_vp, c_vp]),
+    "mppo_physics_forward_xfrc": (c_i32, [c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, P(ForwardProbe), c_i32, c_vp, c_vp]),
+    "mppo_push_fill": (c_i32, [P(PushCfg), c_i32, c_vp, c_i32, c_i32, c_vp, c_vp]),
     "mppo_param_count": (c_sz, [P(Net)]),
     "mppo_policy_ws_bytes": (c_sz, [P(Net), c_i32]),
     "mppo_policy_forward": (c_i32, [P(Net), c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
@@ -172,6 +180,7 @@ SIGNATURES = {
     "mppo_engine_set_reset_noise": (c_i32, [c_vp, c_f]),
     "mppo_engine_set_obs_norm": (c_i32, [c_vp, c_i32, c_f, c_f]),
     "mppo_engine_set_reward_norm": (c_i32, [c_vp, c_i32, c_f, c_f]),
+    "mppo_engine_set_push": (c_i32, [c_vp, P(PushCfg)]),
     "mppo_engine_update": (c_i32, [c_vp, c_vp]),
     "mppo_engine_prepare": (c_i32, [c_vp, c_vp]),
     "mppo_engine_graph_active": (c_i32, [c_vp, P(c_i32)]),
@@ -180,6 +189,7 @@ SIGNATURES = {
     "mppo_eval_ws_bytes": (c_sz, [c_vp, P(Net), P(EvalCfg)]),
     "mppo_evaluate": (c_i32, [c_vp, P(Net), c_vp, P(EvalCfg), c_vp, c_sz, c_vp, c_vp, c_vp]),
     "mppo_evaluate_obs_norm": (c_i32, [c_vp, P(Net), c_vp, P(EvalCfg), c_vp, c_sz, c_vp, c_f, c_vp, c_vp, c_vp]),
+    "mppo_evaluate_push": (c_i32, [c_vp, P(Net), c_vp, P(EvalCfg), c_vp, c_sz, c_vp, c_f, P(PushCfg), c_vp, c_vp, c_vp]),
     "mppo_eval_accumulate": (c_i32, [c_i32, c_i32, c_vp, c_vp, P(EnvMetrics), c_vp, c_vp, c_i32, c_i32, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp]),
     "mppo_eval_reduce": (c_i32, [c_i32, c_i32, c_vp, c_vp, c_vp]),
     "mppo_scene_open": (c_i32, [c_vp, c_sz, c_vp, P(c_vp)]),

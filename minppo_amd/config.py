@@ -63,6 +63,15 @@ class EnvironmentConfig:
     # the environment kernel from the stream `training.rng_impl` names (threefry: the reference's own keys, train.py:135,142,163-165).  0: every
     # environment restarts from the one constant state, as before.  Negative: ValueError.
     reset_noise_scale: float = field(default=0.0)
+    # Extension (absent upstream; legged_gym `push_robots`, MuJoCo Playground's push perturbation): random pushes.  Above 0, every environment is shoved
+    # for `push_duration` of every `push_interval` env steps - out of phase with the others - by a horizontal force on `push_body` (a body name of the
+    # model; "": body 1, the first root), each component uniform in [-push_force, push_force] newtons and constant for the shove (at the
+    # built-in robots' 2 ms step the defaults are a 0.1 s shove every 2 s).  In training, in `evaluate` - whose `survivors` is then a robustness figure -
+    # and in the `env` rollout.  The other three keys are read only when push_force > 0.  0: nothing changes.
+    push_force: float = field(default=0.0)
+    push_interval: int = field(default=1000)
+    push_duration: int = field(default=50)
+    push_body: str = field(default="")
 
 
 @dataclass
@@ -287,6 +296,12 @@ def make_config(yaml_dict: dict | None = None, overrides: Sequence[str] = ()) ->
         _merge_into(cfg, _dotlist_to_dict(overrides))
     if not cfg.environment.reset_noise_scale >= 0.0:
         raise ValueError(f"environment.reset_noise_scale = {cfg.environment.reset_noise_scale!r}: the half-width of the reset noise cannot be negative")
+    env = cfg.environment
+    if not env.push_force >= 0.0:
+        raise ValueError(f"environment.push_force = {env.push_force!r}: the size of the random pushes cannot be negative")
+    if env.push_force > 0.0 and not (env.push_interval >= 1 and 1 <= env.push_duration <= env.push_interval):
+        raise ValueError(f"environment.push_interval = {env.push_interval!r} / push_duration = {env.push_duration!r}: the interval is at least one env step and "
+                         "the duration lies in 1 .. push_interval")
     for key in ("obs_norm_clip", "obs_norm_eps", "reward_norm_clip", "reward_norm_eps"):
         if not getattr(cfg.training, key) >= 0.0:
             raise ValueError(f"training.{key} = {getattr(cfg.training, key)!r} cannot be negative")

@@ -21,6 +21,7 @@
 #include "peer.h"
 #include "obsnorm.h"
 #include "rewnorm.h"
+#include "push.h"
 
 #include <cmath>
 #include <cstdlib>
@@ -154,6 +155,8 @@ struct mppo_engine {
   float* reward_norm_carry;      // [N] the discounted return carried from one update to the next
   double* reward_norm_partials;  // [G][2] the apply launch's sums of this update
   float* reward_scaled;          // [T][N] what GAE reads; "reward" stays raw
+  // random pushes (mppo_engine_set_push; body 0: off - the rollout's step launches are the unpushed ones)
+  mppo::EnvPush push;
 };
 
 namespace mppo {
@@ -308,8 +311,11 @@ static int32_t do_rollout(mppo_engine* e, hipStream_t s) {
     const float* obs_t = e->obs + (size_t)t * N * OP;
     MPPO_TRY(policy_forward(c.net, e->params, e->N, obs_t, e->OP, fb, e->noise + t * N * A, e->action + t * N * A, e->log_prob + t * N,
                             defer_critic ? nullptr : e->value + (size_t)t * N, nullptr, s));                          // train.py:157-160
-    MPPO_TRY(env_step_ws(e->model, e->N, c.n_frames, &c.reward, e->state, e->reset_rec, e->action + t * N * A, e->A, e->obs + (size_t)(t + 1) * N * OP,
-                         e->OP, e->reward + t * N, e->done + t * N, &e->met, e->env_ws, e->env_ws_bytes, static_cast<hipStream_t>(s)));                                  // :165
+    // (random pushes: the wrench of step u * T + t, u the device's update index, is drawn inside this launch - a replayed graph draws fresh ones; off: the plain step)
+    EnvPush push = e->push;
+    push.add = t;
+    MPPO_TRY(env_step_push_ws(e->model, e->N, c.n_frames, &c.reward, e->state, e->reset_rec, e->action + t * N * A, e->A, e->obs + (size_t)(t + 1) * N * OP,
+                              e->OP, e->reward + t * N, e->done + t * N, &e->met, push, e->env_ws, e->env_ws_bytes, static_cast<hipStream_t>(s)));                       // :165
     // reset noise: the environments whose episode ended at this step restart from a randomised state instead of the constant record the step kernel
     // gave them (env.py:166,179-180) - one masked launch of the reset kernel over done[t]; a workgroup without an ended episode leaves at once
     if (e->reset_noise > 0.f)
@@ -459,6 +465,7 @@ extern "C" int32_t mppo_engine_create(const mppo_model_t* m, const mppo_engine_c
   e->reset_noise = 0.f; e->prepared = false;
   e->obs_norm = false; e->obs_norm_clip = 0.f; e->obs_norm_eps = 0.f;
   e->reward_norm = false; e->reward_norm_clip = 0.f; e->reward_norm_eps = 0.f;
+  e->push = EnvPush{};
   *out = e;
   return MPPO_OK;
 }
@@ -568,6 +575,26 @@ extern "C" int32_t mppo_engine_set_reset_noise(mppo_engine_t* e, float scale) {
     return fail(MPPO_ESTATE, "mppo_engine_set_reset_noise: mppo_engine_reset has run already (the environments hold the initial states of scale %g): set the scale before it",
                 (double)e->reset_noise);
   e->reset_noise = scale;
+  return MPPO_OK;
+}
+
+extern "C" int32_t mppo_engine_set_push(mppo_engine_t* e, const mppo_push_cfg_t* push) {
+  MPPO_REQUIRE(e, "mppo_engine_set_push: null engine");
+  if (push) MPPO_TRY(check_push_cfg("mppo_engine_set_push", push));
+  const bool on = push && push->force > 0.f;
+  if (on) MPPO_TRY(check_push_body("mppo_engine_set_push", e->model, push->body));
+  if (e->graph || e->prepared)
+    return fail(MPPO_ESTATE, "mppo_engine_set_push: the update has been prepared already (its launch sequence is fixed, a captured graph holds it): "
+                             "set the pushes before mppo_engine_prepare and the first mppo_engine_update");
+  if (e->was_reset)
+    return fail(MPPO_ESTATE, "mppo_engine_set_push: mppo_engine_reset has run already: set the pushes before it");
+  e->push = EnvPush{};
+  if (on) {
+    mppo_push_cfg_t pc = *push;
+    pc.seed = e->cfg.seed; pc.rank = e->cfg.rank;  // (the engine's own: one stream per rank, as the action noise and the reset noise have)
+    MPPO_TRY(check_push_cfg("mppo_engine_set_push", &pc));  // (the rank that is used - the engine configuration's - fits the stream id's eight bits)
+    e->push.body = pc.body; e->push.draw = push_draw_of(pc); e->push.ctr = e->count + 1; e->push.mul = e->T;
+  }
   return MPPO_OK;
 }
 

@@ -3,6 +3,7 @@
 #pragma once
 #include "model_view.h"
 #include "mppo_common.h"
+#include "push.h"
 
 namespace mppo {
 
@@ -31,7 +32,19 @@ struct EnvArgs {
   unsigned long long noise_seed, noise_stream;  // philox: the key and the stream id (kStreamReset + (rank << 16))
   const int* noise_ctr;         // philox: the event counter's word in device memory (null: 0) ...
   int noise_ctr_mul, noise_ctr_add;  // ... event = word * mul + add: the engine's update index * T + 1 + t, so that a replayed graph draws fresh values
+  // modes 1 and 2 only - an external wrench on one body (MJX xfrc_applied: world axes, at the body's centre of mass), constant over the frames of the step.
+  // A launch is pushed (push_body > 0: the host sets it when xfrc is given or push.force > 0) or it is not; a pushed launch runs a kernel instantiation of its
+  // own (env_kernel_index below), an unpushed one reads nothing of what follows.  Behind everything else, by the rule above.
+  int push_body;                // 1 .. nbody - 1; 0: the launch is not pushed
+  const float* xfrc;            // [N][6] force | torque; null: the wrench is drawn in the kernel (push.h) if push.force > 0, else there is none
+  PushDraw push;                // the draw's parameters (force 0: off)
+  const int* push_ctr;          // the step index's word in device memory (null: 0) ...
+  int push_ctr_mul, push_ctr_add;  // ... step = word * mul + add: the engine's update index * T + t
 };
+
+// the kernel a launch runs (env_kernel's KMODE): its mode, and for a pushed step / probe the instantiation that holds the wrench's code
+constexpr int kEnvKernels = 5;
+inline int env_kernel_index(const EnvArgs& a) { return a.mode >= 1 && a.push_body > 0 ? a.mode + 2 : a.mode; }
 
 constexpr unsigned long long kStreamReset = 0x5245534554ull << 24;  // "RESET" (engine.hip: beside kStreamNoise / kStreamPerm)
 

@@ -3,6 +3,7 @@
 
 #include <algorithm>
 #include <memory>
+#include <string>
 #include <vector>
 
 struct mppo_model {
@@ -22,7 +23,7 @@ struct mppo_model {
   bool jit = false;
   int jit_regchol = 0;  // the MPPO_REGCHOL_MAX_NV the code object was compiled with (its LDS layout follows from it)
   hipModule_t jit_module = nullptr;
-  hipFunction_t jit_fn[3] = {nullptr, nullptr, nullptr};
+  hipFunction_t jit_fn[mppo::kEnvKernels] = {};  // reset, step, probe, pushed step, pushed probe (env_kernel_index)
   std::vector<char> jit_image;
 };
 
@@ -59,7 +60,7 @@ static int32_t launch_env(const mppo_model_t* m, EnvArgs a, hipStream_t stream, 
     ModelView mv = m->mv;
     PhysLds lds = m->lds;
     void* params[] = {&mv, &a, &lds};
-    MPPO_CHECK_HIP(hipModuleLaunchKernel(m->jit_fn[a.mode], blocks, 1, 1, 64 * m->waves, 1, 1, m->lds_bytes, stream, params, nullptr));
+    MPPO_CHECK_HIP(hipModuleLaunchKernel(m->jit_fn[env_kernel_index(a)], blocks, 1, 1, 64 * m->waves, 1, 1, m->lds_bytes, stream, params, nullptr));
     return MPPO_OK;
   }
   return launch_env_spec(m->spec, m->mv, a, m->lds, m->lds_bytes, blocks, m->waves, stream);
@@ -71,6 +72,37 @@ int32_t env_step_ws(const mppo_model_t* m, int32_t N, int32_t n_frames, const mp
   a.N = N; a.mode = 1; a.n_frames = n_frames; a.state = state; a.reset_in = reset_rec; a.action = action; a.act_ld = act_ld;
   a.obs = obs; a.obs_ld = obs_ld; a.reward = reward; a.done = done; a.rc = *rc;
   if (metrics) a.met = *metrics;
+  return launch_env(m, a, stream, ws, ws_bytes);
+}
+// Random pushes.  What every entry point that takes a push configuration refuses (the body is checked against the model by the callers that have one)
+int32_t check_push_cfg(const char* who, const mppo_push_cfg_t* p) {
+  MPPO_REQUIRE(p->force >= 0.f, "%s: push force %g is negative (or not a number)", who, (double)p->force);
+  if (p->force == 0.f) return MPPO_OK;  // off: nothing else is read
+  MPPO_REQUIRE(p->interval >= 1, "%s: push interval %d (at least 1 env step)", who, p->interval);
+  MPPO_REQUIRE(p->duration >= 1 && p->duration <= p->interval, "%s: push duration %d outside 1 .. interval = %d", who, p->duration, p->interval);
+  MPPO_REQUIRE(p->rank >= 0 && p->rank < 256, "%s: rank %d (0 .. 255)", who, p->rank);
+  return MPPO_OK;
+}
+int32_t check_push_body(const char* who, const mppo_model_t* m, int32_t body) {
+  MPPO_REQUIRE(body >= 1 && body < m->mv.nbody, "%s: push body %d outside 1 .. nbody - 1 = %d (0 is the world)", who, body, m->mv.nbody - 1);
+  return MPPO_OK;
+}
+PushDraw push_draw_of(const mppo_push_cfg_t& p) {
+  return PushDraw{p.force, p.interval, p.duration, p.seed, kStreamPush + ((unsigned long long)p.rank << 16)};
+}
+// env_step_ws under an external wrench (push.xfrc given, or drawn in the kernel when push.draw.force > 0; neither: exactly env_step_ws)
+int32_t env_step_push_ws(const mppo_model_t* m, int32_t N, int32_t n_frames, const mppo_reward_cfg_t* rc, float* state, const float* reset_rec, const float* action,
+                         int32_t act_ld, float* obs, int32_t obs_ld, float* reward, uint8_t* done, const mppo_env_metrics_t* metrics, const EnvPush& push, float* ws,
+                         size_t ws_bytes, hipStream_t stream) {
+  EnvArgs a{};
+  a.N = N; a.mode = 1; a.n_frames = n_frames; a.state = state; a.reset_in = reset_rec; a.action = action; a.act_ld = act_ld;
+  a.obs = obs; a.obs_ld = obs_ld; a.reward = reward; a.done = done; a.rc = *rc;
+  if (metrics) a.met = *metrics;
+  if (push.xfrc || push.draw.force > 0.f) {
+    MPPO_TRY(check_push_body("environment step", m, push.body));
+    a.push_body = push.body; a.xfrc = push.xfrc;
+    if (!push.xfrc) { a.push = push.draw; a.push_ctr = push.ctr; a.push_ctr_mul = push.mul; a.push_ctr_add = push.add; }
+  }
   return launch_env(m, a, stream, ws, ws_bytes);
 }
 int32_t env_reset_ws(const mppo_model_t* m, int32_t N, float* state, float* reset_rec, float* obs, int32_t obs_ld, float* reward, uint8_t* done, const mppo_env_metrics_t* metrics,
@@ -288,6 +320,18 @@ extern "C" int32_t mppo_model_attach_kernel(mppo_model_t* m, const void* image, 
     he = hipModuleGetFunction(&m->jit_fn[k], mod, names[k]);
     if (he != hipSuccess) return drop(fail(MPPO_EINVAL, "mppo_model_attach_kernel: no kernel %s in the code object (%s)", names[k], hipGetErrorString(he)));
   }
+  // the pushed step and the pushed probe (KMODE 3, 4): the step's and the probe's symbols with the mode's digit replaced - a code object of these sources holds them
+  for (int k = 1; k <= 2; ++k) {
+    std::string name(names[k]);
+    char from[16], to[16];
+    snprintf(from, sizeof from, "EELi%dEEEv", k);
+    snprintf(to, sizeof to, "EELi%dEEEv", k + 2);
+    const size_t at = name.rfind(from);
+    if (at == std::string::npos) return drop(fail(MPPO_EINVAL, "mppo_model_attach_kernel: kernel %d is named %s", k, names[k]));
+    name.replace(at, strlen(from), to);
+    he = hipModuleGetFunction(&m->jit_fn[k + 2], mod, name.c_str());
+    if (he != hipSuccess) return drop(fail(MPPO_EINVAL, "mppo_model_attach_kernel: no kernel %s in the code object (%s)", name.c_str(), hipGetErrorString(he)));
+  }
   // the layout the specialised kernel computed for itself at compile time; then the same proof a build-time instantiation gives
   m->jit_module = mod;
   m->jit = true;
@@ -365,5 +409,33 @@ extern "C" int32_t mppo_physics_forward(const mppo_model_t* m, int32_t N, const 
   MPPO_REQUIRE(N >= 1, "mppo_physics_forward: N = %d", N);
   EnvArgs a{};
   a.N = N; a.mode = 2; a.n_frames = 1; a.p_qpos = qpos; a.p_qvel = qvel; a.p_ctrl = ctrl; a.p_warm = qacc_warmstart; a.probe = *out;
+  return launch_env(m, a, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int32_t mppo_env_step_xfrc(const mppo_model_t* m, int32_t N, int32_t n_frames, const mppo_reward_cfg_t* rc, float* state,
+                                      const float* reset_rec, const float* action, int32_t act_ld, float* obs, int32_t obs_ld, float* reward,
+                                      uint8_t* done, const mppo_env_metrics_t* metrics, int32_t body, const float* xfrc, void* stream) {
+  using namespace mppo;
+  MPPO_REQUIRE(m && rc && state && reset_rec && action && obs && reward && done, "mppo_env_step_xfrc: null argument");
+  MPPO_REQUIRE(N >= 1 && n_frames >= 1, "mppo_env_step_xfrc: N = %d, n_frames = %d", N, n_frames);
+  MPPO_REQUIRE(m->mv.nq >= 3, "mppo_env_step_xfrc: the environment reads qpos[2] as the height (env.py:239); nq = %d", m->mv.nq);
+  MPPO_REQUIRE(act_ld >= m->mv.nu, "mppo_env_step_xfrc: act_ld %d < nu %d", act_ld, m->mv.nu);
+  MPPO_REQUIRE(obs_ld >= m->mv.obs_pad, "mppo_env_step_xfrc: obs_ld %d < padded observation width %d", obs_ld, m->mv.obs_pad);
+  if (xfrc) MPPO_TRY(check_push_body("mppo_env_step_xfrc", m, body));
+  EnvPush push{};
+  push.body = body; push.xfrc = xfrc;
+  return env_step_push_ws(m, N, n_frames, rc, state, reset_rec, action, act_ld, obs, obs_ld, reward, done, metrics, push, nullptr, 0, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int32_t mppo_physics_forward_xfrc(const mppo_model_t* m, int32_t N, const float* qpos, const float* qvel, const float* ctrl,
+                                             const float* qacc_warmstart, const mppo_forward_probe_t* out, int32_t body, const float* xfrc, void* stream) {
+  using namespace mppo;
+  MPPO_REQUIRE(m && qpos && qvel && qacc_warmstart && out, "mppo_physics_forward_xfrc: null argument");
+  MPPO_REQUIRE(ctrl || m->mv.nu == 0, "mppo_physics_forward_xfrc: ctrl is null but the model has actuators");
+  MPPO_REQUIRE(N >= 1, "mppo_physics_forward_xfrc: N = %d", N);
+  if (xfrc) MPPO_TRY(check_push_body("mppo_physics_forward_xfrc", m, body));
+  EnvArgs a{};
+  a.N = N; a.mode = 2; a.n_frames = 1; a.p_qpos = qpos; a.p_qvel = qvel; a.p_ctrl = ctrl; a.p_warm = qacc_warmstart; a.probe = *out;
+  if (xfrc) { a.push_body = body; a.xfrc = xfrc; }
   return launch_env(m, a, static_cast<hipStream_t>(stream));
 }

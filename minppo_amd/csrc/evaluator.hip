@@ -10,6 +10,7 @@
 #include "model_view.h"
 #include "obsnorm.h"
 #include "ppo_layout.h"
+#include "push.h"
 
 namespace mppo {
 const ModelView& model_view(const mppo_model* m);
@@ -93,8 +94,19 @@ extern "C" size_t mppo_eval_ws_bytes(const mppo_model_t* m, const mppo_net_t* ne
 
 // obs_table (may be null: the plain evaluation, not one launch more): [2][O] mean32 | inv_std32 of a policy trained on normalised observations
 static int32_t evaluate_impl(const char* who, const mppo_model_t* m, const mppo_net_t* net, const float* params, const mppo_eval_cfg_t* cfg, void* ws, size_t ws_bytes,
-                             const float* obs_table, float clip, mppo_eval_result_t* result, float* traj, void* stream) {
+                             const float* obs_table, float clip, const mppo_push_cfg_t* push, mppo_eval_result_t* result, float* traj, void* stream) {
   MPPO_TRY(check_eval(who, m, net, cfg));
+  // random pushes (may be null, or of force 0: the unpushed evaluation, launch for launch): drawn inside the step's kernel at step t of rank 0 under the evaluation's seed
+  EnvPush ep{};
+  if (push) {
+    MPPO_TRY(check_push_cfg(who, push));
+    if (push->force > 0.f) {
+      MPPO_TRY(check_push_body(who, m, push->body));
+      mppo_push_cfg_t pc = *push;
+      pc.rank = 0; pc.seed = cfg->seed;  // (rank 0: within the stream id's eight bits whatever the configuration held)
+      ep.body = pc.body; ep.draw = push_draw_of(pc); ep.mul = 0;
+    }
+  }
   MPPO_REQUIRE(params && ws && result, "%s: null params / workspace / result", who);
   MPPO_REQUIRE(traj || cfg->record_envs == 0, "%s: null trajectory with record_envs = %d", who, cfg->record_envs);
   MPPO_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 255) == 0, "%s: the workspace must be 256-byte aligned", who);
@@ -121,7 +133,8 @@ static int32_t evaluate_impl(const char* who, const mppo_model_t* m, const mppo_
   for (int t = 0; t < K; ++t) {
     if (!c.deterministic) MPPO_TRY(normal_fill_ctr(c.seed, (unsigned long long)t, nullptr, (size_t)N * A, w.noise, s));
     MPPO_TRY(policy_forward(*net, params, N, w.obs, OP, fb, w.noise, w.action, w.log_prob, w.value, nullptr, s));
-    MPPO_TRY(env_step_ws(m, N, c.n_frames, &c.reward, w.state, w.reset_rec, w.action, A, w.obs, OP, w.reward, w.done, &w.met, w.env_ws, w.env_ws_bytes, s));
+    ep.add = t;
+    MPPO_TRY(env_step_push_ws(m, N, c.n_frames, &c.reward, w.state, w.reset_rec, w.action, A, w.obs, OP, w.reward, w.done, &w.met, ep, w.env_ws, w.env_ws_bytes, s));
     if (noisy_reset)  // the environments whose episode ended restart from a randomised state (event t + 1), as in the engine's rollout
       MPPO_TRY(env_reinit_ws(m, N, w.state, w.obs, OP, w.done, c.reset_noise_scale, 0, c.seed, 0, nullptr, nullptr, 1, t + 1, w.env_ws, w.env_ws_bytes, s));
     if (obs_table)  // the next forward reads what the policy was trained on; the observation after the reset stays raw, as in the engine (the state rows are raw throughout)
@@ -134,10 +147,15 @@ static int32_t evaluate_impl(const char* who, const mppo_model_t* m, const mppo_
 
 extern "C" int32_t mppo_evaluate(const mppo_model_t* m, const mppo_net_t* net, const float* params, const mppo_eval_cfg_t* cfg, void* ws, size_t ws_bytes,
                                  mppo_eval_result_t* result, float* traj, void* stream) {
-  return evaluate_impl("mppo_evaluate", m, net, params, cfg, ws, ws_bytes, nullptr, 0.f, result, traj, stream);
+  return evaluate_impl("mppo_evaluate", m, net, params, cfg, ws, ws_bytes, nullptr, 0.f, nullptr, result, traj, stream);
 }
 
 extern "C" int32_t mppo_evaluate_obs_norm(const mppo_model_t* m, const mppo_net_t* net, const float* params, const mppo_eval_cfg_t* cfg, void* ws, size_t ws_bytes,
                                           const float* obs_table, float clip, mppo_eval_result_t* result, float* traj, void* stream) {
-  return evaluate_impl("mppo_evaluate_obs_norm", m, net, params, cfg, ws, ws_bytes, obs_table, clip, result, traj, stream);
+  return evaluate_impl("mppo_evaluate_obs_norm", m, net, params, cfg, ws, ws_bytes, obs_table, clip, nullptr, result, traj, stream);
+}
+
+extern "C" int32_t mppo_evaluate_push(const mppo_model_t* m, const mppo_net_t* net, const float* params, const mppo_eval_cfg_t* cfg, void* ws, size_t ws_bytes,
+                                      const float* obs_table, float clip, const mppo_push_cfg_t* push, mppo_eval_result_t* result, float* traj, void* stream) {
+  return evaluate_impl("mppo_evaluate_push", m, net, params, cfg, ws, ws_bytes, obs_table, clip, push, result, traj, stream);
 }

@@ -668,8 +668,12 @@ struct StaticModel {
   static constexpr BlobDims dims() { return BlobDims{NQ, NV, NU, NBODY, NJNT, NCON, NLIMIT, NPAIR, NLEVEL, NROOT, NCVX, NCVXVERT, HULL, NCYL, NEQ, NBALL, CPARAM}; }
 };
 // MODE (EnvArgs::mode) is a template parameter too: the step kernel carries neither the probe's 17 output pointers nor its stores.
-template <class SD, int MODE>
+// KMODE: 0 reset, 1 step, 2 probe; 3 / 4: the step / the probe under an external wrench (EnvArgs::push_body > 0) - instantiations of their own, so that the kernels
+// 0 .. 2 hold no instruction of the wrench's and are, but for the offsets behind the grown EnvArgs, the kernels they were before it existed
+template <class SD, int KMODE>
 __global__ void __launch_bounds__(64 * kMaxWavesPerBlock) env_kernel(ModelView mv, EnvArgs a, PhysLds Prt) {
+  constexpr int MODE = KMODE >= 3 ? KMODE - 2 : KMODE;
+  constexpr bool pushed = KMODE >= 3;
   constexpr BlobDims kSD = SD::dims();
   constexpr BlobOffsets kSO = blob_offsets(kSD);
   constexpr bool kDims = SD::kStatic;
@@ -1175,6 +1179,41 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerBlock) env_kernel(ModelView m
     if (spM) { for (int w = g; w < nvq * nv; w += kGroupLanes) Mq[w] = make_float4(0.f, 0.f, 0.f, 0.f); }
     else FOR_G(i, nv) for (int k = 0; k < nv; ++k) M[i * ldm + k] = 0.f;
     if (spM) GSYNC(); else SYNC();
+    if (pushed) {
+      // ---- the external wrench (MJX support.xfrc_accumulate in fwd_acceleration): its generalised force per dof -----------------
+      // qfrc[d] = cdof[d] . (torque + (xipos[b] - subtree_com[root(b)]) x force, force) for the dofs of body b and of its ancestors, 0 for every other.
+      // Formed HERE, where the poses of region A1 and cdof are both alive (the factorisation's work copy takes A1 next), and parked in qfs, which is
+      // dead from the end of the previous frame's solver until qfrc_smooth is written into it below - by the same lane, which adds what it finds.
+      // Nothing is carried in registers across the factorisation and no array is added.  The draw (push.h) is repeated by every frame: it is a
+      // function of the step, the same in all of them.  (`pushed` is a compile-time constant: KMODE 3 / 4.)
+      const int pb = a.push_body;
+      float w6[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};  // torque about the tree's centre of mass | force
+      // (the wrench does not depend on the frame, so the compiler computes it in front of the frame loop and keeps it in vector registers across the whole step -
+      // in the instantiation that spills, the export biped's, 20 more bytes of scratch per lane than its unpushed step.  The environment's index made opaque HERE
+      // keeps the draw where it is used: that kernel then has the unpushed step's 328 bytes)
+      int envp = env;
+#ifndef MPPO_EMU
+      asm volatile("" : "+v"(envp));
+#endif
+      if (a.xfrc) {
+        const float* x = a.xfrc + (size_t)envp * 6;
+        w6[3] = x[0]; w6[4] = x[1]; w6[5] = x[2]; w6[0] = x[3]; w6[1] = x[4]; w6[2] = x[5];
+      } else {
+        const unsigned step = (a.push_ctr ? (unsigned)a.push_ctr[0] : 0u) * (unsigned)a.push_ctr_mul + (unsigned)a.push_ctr_add;  // (modulo 2^32: no signed overflow)
+        (void)push_draw(a.push, (unsigned)envp, step, &w6[3], &w6[4]);
+      }
+      int ri = 0;
+      for (int r = 0; r < nroot; ++r) if (TI(root_body)[r] == TI(body_rootid)[pb]) ri = r;
+      const V3 arm = sub3(ld3(xipos + 3 * pb), ld3(rootcom + 3 * ri)), mo = cross3(arm, {w6[3], w6[4], w6[5]});
+      w6[0] += mo.x; w6[1] += mo.y; w6[2] += mo.z;
+      FOR_G(d, nv) {
+        // (the subtree set of the dof's body: word pb >> 6 of two beyond 64 bodies - a 64-bit shift uses the low six bits of its amount)
+        const u64 sub = TU(body_subtree_mask)[(nb > 64 ? (pb >> 6) * nb : 0) + TI(dof_bodyid)[d]];
+        const float* cd = cdof + 6 * d;
+        const float q = cd[0] * w6[0] + cd[1] * w6[1] + cd[2] * w6[2] + cd[3] * w6[3] + cd[4] * w6[4] + cd[5] * w6[5];
+        qfs[d] = ((sub >> (pb & 63)) & 1ull) ? q : 0.f;
+      }
+    }
     PT(4);
     // ---- crb: composite inertia over the subtree mask, dense M ------------------------------------
     FOR_G(i, nv) {
@@ -1492,7 +1531,9 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerBlock) env_kernel(ModelView m
         const float lo = TF(dof_actfrcrange)[2 * d], hi = TF(dof_actfrcrange)[2 * d + 1];
         act = act < lo ? lo : (act > hi ? hi : act);
       }
-      qfs[d] = passive - bias + act;
+      float smooth = passive - bias + act;
+      if (pushed) { const float w = qfs[d]; if (w != 0.f) smooth += w; }  // (this lane left the wrench's share there, above; a zero of either sign changes no bit)
+      qfs[d] = smooth;
       // qfrc_actuator is part of the new record / observation (env.py:252) and of the NaN guard, not of the solver: it leaves here
       bad_lane |= (int)isnan(act);
       if (MODE != 2 && frame == frames - 1 && valid) {
@@ -2245,12 +2286,13 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerBlock) env_kernel(ModelView m
 namespace mppo {
 template <class SD>
 static int32_t launch_env_t(const ModelView& mv, const EnvArgs& a, const PhysLds& lds, int lds_bytes, int blocks, int waves, hipStream_t stream) {
-  void (*kern)(ModelView, EnvArgs, PhysLds) = a.mode == 0 ? &env_kernel<SD, 0> : a.mode == 1 ? &env_kernel<SD, 1> : &env_kernel<SD, 2>;
+  const int k = env_kernel_index(a);  // (a pushed step / probe is a kernel of its own: env_kernel's KMODE)
+  void (*kern)(ModelView, EnvArgs, PhysLds) = k == 0 ? &env_kernel<SD, 0> : k == 1 ? &env_kernel<SD, 1> : k == 2 ? &env_kernel<SD, 2> : k == 3 ? &env_kernel<SD, 3> : &env_kernel<SD, 4>;
   // (the run-time-sized instantiation serves robots of different sizes: the limit follows the largest one seen)
-  static thread_local int attr_lds[3] = {64 * 1024, 64 * 1024, 64 * 1024};
-  if (lds_bytes > attr_lds[a.mode]) {
+  static thread_local int attr_lds[kEnvKernels] = {64 * 1024, 64 * 1024, 64 * 1024, 64 * 1024, 64 * 1024};
+  if (lds_bytes > attr_lds[k]) {
     MPPO_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes));
-    attr_lds[a.mode] = lds_bytes;
+    attr_lds[k] = lds_bytes;
   }
   hipLaunchKernelGGL(kern, dim3(blocks), dim3(64 * waves), lds_bytes, stream, mv, a, lds);
   MPPO_CHECK_LAUNCH("env_kernel");

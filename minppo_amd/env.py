@@ -27,7 +27,7 @@ import numpy as np
 from minppo_amd import _native as nat
 from minppo_amd.config import Config, load_config_from_cli, require
 from minppo_amd.model import CompiledModel, load_model
-from minppo_amd.train import resolve_model, reward_cfg
+from minppo_amd.train import push_body_id, push_cfg, resolve_model, reward_cfg
 
 logger = logging.getLogger(__name__)
 
@@ -69,6 +69,9 @@ class HumanoidEnv:
         self._include_c_vals = config.environment.include_c_vals
         self._kscale_id = config.kscale_id
         self.cm = resolve_model(config)
+        # the body `step(..., xfrc=)` acts on: the name is resolved - and an unknown one refused, before anything is opened - even at push_force = 0
+        # (an explicit wrench needs no random draw)
+        self._push_body = push_body_id(config, self.cm, always=True)
         self._n_frames = config.environment.n_frames
         self._blob_host = np.frombuffer(self.cm.to_blob(self._include_c_vals), np.uint8).copy()
         self._blob_dev = torch.from_numpy(self._blob_host.copy()).to(self.device)
@@ -92,6 +95,8 @@ class HumanoidEnv:
         # `environment.reset_noise_scale` sets the attribute unless it was assigned directly (on the class, or on the instance later)
         if type(self).reset_noise_scale == 0.0 and config.environment.reset_noise_scale > 0:
             self.reset_noise_scale = float(config.environment.reset_noise_scale)
+        # random pushes (`environment.push_*`): what `push_wrench` draws (None: push_force = 0)
+        self._push = push_cfg(config, self.cm, config.training.seed)
         self._have_reset = False
         self._camera_name = config.visualization.camera_name
         self._renderer = None
@@ -164,7 +169,10 @@ class HumanoidEnv:
         return EnvState(state, obs[:, :self.observation_size], reward, done.bool(), m)
 
     # -- env.py:148-196 -----------------------------------------------------------
-    def step(self, env_state: EnvState, action: Any, rng: Any = None) -> EnvState:
+    def step(self, env_state: EnvState, action: Any, rng: Any = None, *, xfrc: Any = None) -> EnvState:
+        """`xfrc` (extension; Brax: `pipeline_state.xfrc_applied`): [N, 6] external wrench per environment - force, then torque, world axes, at the
+        centre of mass of the body `environment.push_body` (default: body 1, the first root; read whatever `environment.push_force` is) - held for the
+        whole step (`mppo_env_step_xfrc`)."""
         t = self.torch
         if not self._have_reset:
             self.reset(num_envs=1)
@@ -178,14 +186,36 @@ class HumanoidEnv:
         reward, done = t.empty(N, dtype=t.float32, device=self.device), t.empty(N, dtype=t.uint8, device=self.device)
         m = EnvMetrics(*[x.clone() if x.dtype != t.bool else x.to(t.uint8) for x in env_state.metrics])
         ms = self._mstruct(m)
-        self.lib.env_step(self._model, N, self._n_frames, C.byref(self._rc), state.data_ptr(), self._reset_rec.data_ptr(), action.data_ptr(),
-                          self._action_size, obs.data_ptr(), self.dims.obs_pad, reward.data_ptr(), done.data_ptr(), C.byref(ms), self._stream())
+        if xfrc is not None:
+            xfrc = (xfrc if hasattr(xfrc, "data_ptr") else t.as_tensor(np.asarray(xfrc, np.float32))).to(device=self.device, dtype=t.float32).contiguous()
+            if xfrc.shape != (N, 6):
+                raise ValueError(f"xfrc must have shape ({N}, 6) - force, then torque, per environment - got {tuple(xfrc.shape)}")
+            self.lib.env_step_xfrc(self._model, N, self._n_frames, C.byref(self._rc), state.data_ptr(), self._reset_rec.data_ptr(), action.data_ptr(),
+                                   self._action_size, obs.data_ptr(), self.dims.obs_pad, reward.data_ptr(), done.data_ptr(), C.byref(ms), self._push_body,
+                                   xfrc.data_ptr(), self._stream())
+            self._xfrc_keep = xfrc  # (lives until the next call: the launch reads it)
+        else:
+            self.lib.env_step(self._model, N, self._n_frames, C.byref(self._rc), state.data_ptr(), self._reset_rec.data_ptr(), action.data_ptr(),
+                              self._action_size, obs.data_ptr(), self.dims.obs_pad, reward.data_ptr(), done.data_ptr(), C.byref(ms), self._stream())
         if noise is not None:  # env.py:166,179-180: the environments that ended restart from `_get_reset_state(rng)`, not from the constant record
             impl, keys = noise
             self.lib.env_reinit(self._model, N, state.data_ptr(), obs.data_ptr(), self.dims.obs_pad, done.data_ptr(), float(self.reset_noise_scale), impl, 0, 0,
                                 keys.data_ptr(), 0, 0, self._stream())
             self._noise_keep = keys
         return EnvState(state, obs[:, :self.observation_size], reward, done.bool(), m)
+
+    def push_wrench(self, step: int, num_envs: int, seed: Optional[int] = None) -> Any:
+        """The wrench [num_envs, 6] the random pushes of `environment.push_force / push_interval / push_duration` put on the environments at env step
+        `step` (`mppo_push_fill`; rank 0; seed: `training.seed`), to be handed to `step(..., xfrc=)`; `jaxrng.push_wrench_philox` is its host statement."""
+        if self._push is None:
+            raise ValueError("push_wrench: environment.push_force is 0 - there are no pushes to draw")
+        t = self.torch
+        p = nat.PushCfg.from_buffer_copy(self._push)
+        if seed is not None:
+            p.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        out = t.empty(int(num_envs), 6, dtype=t.float32, device=self.device)
+        self.lib.push_fill(C.byref(p), int(num_envs), None, 0, int(step) & 0x7FFFFFFF, out.data_ptr(), self._stream())
+        return out
 
     # -- env.py:245-261 / 238-242 / 199-235 on the state record (host-side views, for inspection) ------
     def get_obs(self, data: Any, action: Any = None) -> Any:
@@ -271,16 +301,19 @@ def main(args: Sequence[str] | None = None) -> None:
         fps = int(1 / env.dt)
         max_frames = int(vis.video_length * fps)
         rollout = []
+        n_steps = 0  # (env steps so far, over all episodes: the pushes' step index - a push keeps running across a restart)
         for episode in range(int(vis.num_episodes)):
             seed = int(torch.randint(0, 2**31 - 1, (1,), generator=gen))
             es = env.reset(seed if env.reset_noise_scale != 0 else None, num_envs=1)
             total = 0.0
+            pushed = config.environment.push_force > 0  # (random pushes: the rollout is shoved as a training environment is, so a push can be watched)
             for _ in range(int(vis.max_steps)):
                 if len(rollout) < vis.video_length * fps:
                     rollout.append(es.pipeline_state[0].clone())
                 action = torch.rand(1, env.action_size, generator=gen).to(env.device)
                 step_seed = int(torch.randint(0, 2**31 - 1, (1,), generator=gen))
-                es = env.step(es, action, step_seed if env.reset_noise_scale != 0 else None)
+                es = env.step(es, action, step_seed if env.reset_noise_scale != 0 else None, xfrc=env.push_wrench(n_steps, 1) if pushed else None)
+                n_steps += 1
                 total += float(es.reward[0])
                 if bool(es.done[0]):
                     break

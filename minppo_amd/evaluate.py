@@ -12,6 +12,12 @@ prints one JSON line with the statistics; `evaluation.trajectory_path=run.npz ev
 trajectory of the first four environments (`qpos`, `qvel`, `action`, `reward`, `done`, and `dt`, `n_frames`); `evaluation.video_path=policy.avi`
 (with `record_envs >= 1`) renders recorded environment 0 - one frame per step, camera and size from `visualization` - and writes the video
 (minppo_amd/render.py: train, then watch it).
+
+Under random pushes (`environment.push_force` > 0 with `push_interval`, `push_duration`, `push_body`) the same call goes through
+`mppo_evaluate_push`: every environment is shoved on `push_duration` of every `push_interval` steps, and `survivors` of `num_envs` - the
+environments that never fell - is the robustness figure two standing policies are compared by.  The wrench of any (environment, step) is
+`minppo_amd.jaxrng.push_wrench_philox(seed, 0, step, num_envs, push_force, push_interval, push_duration)[environment]`.  The result, its JSON line
+and the trajectory file are what they are without pushes.
 """
 
 from __future__ import annotations
@@ -131,13 +137,17 @@ def eval_cfg(config: Config, **overrides: Any) -> nat.EvalCfg:
 
 
 def run(lib: nat.Lib, xp: str, device: Any, stream: Any, model: C.c_void_p, dims: nat.ModelDims, net: nat.Net, params_dev: Any,
-        ecfg: nat.EvalCfg, obs_norm: Optional[Dict[str, Any]] = None) -> EvalResult:
+        ecfg: nat.EvalCfg, obs_norm: Optional[Dict[str, Any]] = None, push: Optional[nat.PushCfg] = None) -> EvalResult:
     """One `mppo_evaluate` on an open model and parameters already in device memory (`Trainer.evaluate` comes in here); with `obs_norm`
-    ({"mean", "inv_std", "clip"}) one `mppo_evaluate_obs_norm`: the policy reads observations normalised with that table."""
+    ({"mean", "inv_std", "clip"}) one `mppo_evaluate_obs_norm`: the policy reads observations normalised with that table; with `push`
+    (`train.push_cfg`: random pushes, with or without a table) one `mppo_evaluate_push`."""
     table, clip = obs_norm_table(obs_norm, dims.obs_dim)
 
     def call(ws, res, traj, s):
-        if table is None:
+        if push is not None:
+            lib.evaluate_push(model, C.byref(net), nat.ptr(params_dev), C.byref(ecfg), nat.ptr(ws), need, nat.ptr(table_dev), clip, C.byref(push), nat.ptr(res),
+                              nat.ptr(traj), s)
+        elif table is None:
             lib.evaluate(model, C.byref(net), nat.ptr(params_dev), C.byref(ecfg), nat.ptr(ws), need, nat.ptr(res), nat.ptr(traj), s)
         else:
             lib.evaluate_obs_norm(model, C.byref(net), nat.ptr(params_dev), C.byref(ecfg), nat.ptr(ws), need, nat.ptr(table_dev), clip, nat.ptr(res), nat.ptr(traj), s)
@@ -186,7 +196,7 @@ def evaluate(config: Config, params: Any, *, lib: Optional[nat.Lib] = None, xp: 
     the robot, network geometry, reward window and `evaluation` section of `config`.  `lib=` / `xp="numpy"` as in `Trainer`.
     A tree or pickle with an "obs_norm" entry (a policy trained with `training.normalize_observations`) is evaluated on observations normalised
     with it; `obs_norm=` ({"mean", "inv_std", "clip"}) supplies the entry for a flat vector or overrides the tree's.  A flat vector without it: none."""
-    from minppo_amd.train import open_model, resolve_model
+    from minppo_amd.train import open_model, push_cfg, resolve_model
 
     lib = lib if lib is not None else nat.load()
     if not 1 <= config.model.num_layers <= 4:
@@ -215,7 +225,7 @@ def evaluate(config: Config, params: Any, *, lib: Optional[nat.Lib] = None, xp: 
             obs_norm = params.get("obs_norm")
         flat = _flat_params(params, dims.obs_dim, dims.nu, config.model.hidden_size, L)
         params_dev = torch.from_numpy(flat).to(device) if torch is not None else np.ascontiguousarray(flat)
-        result = run(lib, xp, device, stream, model, dims, net, params_dev, ecfg, obs_norm=obs_norm)
+        result = run(lib, xp, device, stream, model, dims, net, params_dev, ecfg, obs_norm=obs_norm, push=push_cfg(config, cm, ecfg.seed))
     finally:
         if torch is not None:
             torch.cuda.synchronize(device)

@@ -185,3 +185,31 @@ def reset_noise_philox(seed: int, rank: int, event: int, num_envs: int, nq: int,
     lo, hi = np.float32(-scale), np.float32(scale)
     u = np.maximum(lo, f * (hi - lo) + lo).astype(np.float32)
     return u[:, :nq].copy(), u[:, nq:].copy()
+
+
+_PUSH_STREAM = 0x50555348 << 24  # "PUSH": the Philox stream of the random pushes (csrc/push.h kStreamPush)
+
+
+def push_wrench_philox(seed: int, rank: int, step: int, num_envs: int, force: float, interval: int, duration: int) -> np.ndarray:
+    """The wrench (force xyz, torque xyz) the random pushes put on every local environment at env step `step` (csrc/push.h, bit for bit what
+    `mppo_push_fill` writes and the environment kernel draws): with S = "PUSH" << 24 + (rank << 16), environment n has the phase
+    word0(philox((n, 0xFFFFFFFF, lo(S), hi(S)), seed)) mod interval, is pushed iff (step + phase) mod interval < duration, and then gets
+    fx, fy = uniform(word0 / word1 of philox((n, (step + phase) // interval, lo(S), hi(S)), seed), -force, force); everything else is an exact zero.
+    Steps: the engine's step t of update u is u * T + t, the evaluator's is t (seed: the evaluation's, rank 0) -> float32 [N, 6]."""
+    if not (force >= 0 and interval >= 1 and 1 <= duration <= interval):
+        raise ValueError(f"push: force {force} / interval {interval} / duration {duration}")
+    n = np.arange(num_envs, dtype=np.uint64)
+    st = _PUSH_STREAM + (int(rank) << 16)
+    s0, s1 = np.full_like(n, st & 0xFFFFFFFF), np.full_like(n, st >> 32)
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    k0, k1 = seed & 0xFFFFFFFF, seed >> 32
+    phase = _philox4x32(n, np.full_like(n, 0xFFFFFFFF), s0, s1, k0, k1)[0] % np.uint64(interval)
+    at = (np.uint64(int(step) & 0xFFFFFFFF) + phase) & np.uint64(0xFFFFFFFF)
+    on = at % np.uint64(interval) < np.uint64(duration)
+    z = _philox4x32(n, at // np.uint64(interval), s0, s1, k0, k1)
+    bits = np.stack(z[:2], 1).astype(np.uint32)
+    f = ((bits >> np.uint32(9)) | np.uint32(0x3F800000)).view(np.float32) - np.float32(1.0)
+    lo, hi = np.float32(-force), np.float32(force)
+    out = np.zeros((num_envs, 6), np.float32)
+    out[:, :2] = np.where(on[:, None], np.maximum(lo, f * (hi - lo) + lo).astype(np.float32), np.float32(0.0))
+    return out

@@ -195,7 +195,30 @@ def resolve_model(config: Config) -> CompiledModel:
     if config.environment.backend != "mjx":
         raise ValueError(f"environment.backend={config.environment.backend!r}: only the MJX pipeline ('mjx', the reference's default) exists in this engine")
     name = config.environment.model or require(config.kscale_id, "kscale_id")
-    return load_model(name)
+    cm = load_model(name)
+    push_body_id(config, cm)  # (an unknown environment.push_body is refused here, where the model's names are first at hand)
+    return cm
+
+
+def push_body_id(config: Config, cm: CompiledModel, always: bool = False) -> int:
+    """The body id of `environment.push_body` in `cm` ("": body 1, the first root).  Read - and an unknown name refused - only when pushes are on, or
+    `always` (`HumanoidEnv`, whose `step(..., xfrc=)` acts on the named body whether or not the random draw is switched on)."""
+    name = config.environment.push_body
+    if not (always or config.environment.push_force > 0) or not name:
+        return 1
+    names = list(cm.body_names)
+    if name not in names[1:]:
+        raise ValueError(f"environment.push_body = {name!r}: no such body in the model; its bodies are {names[1:]}")
+    return names.index(name)
+
+
+def push_cfg(config: Config, cm: CompiledModel, seed: int = 0, rank: int = 0) -> Optional[nat.PushCfg]:
+    """`mppo_push_cfg_t` of a config's `environment.push_*` keys; None when pushes are off (push_force = 0)."""
+    env = config.environment
+    if not env.push_force > 0:
+        return None
+    return nat.PushCfg(body=push_body_id(config, cm), interval=int(env.push_interval), duration=int(env.push_duration), rank=int(rank), force=float(env.push_force),
+                       seed=int(seed) & 0xFFFFFFFFFFFFFFFF)
 
 
 def open_model(lib: nat.Lib, config: Config, cm: CompiledModel, xp: str, device: Any = None, verbose: bool = False):
@@ -310,6 +333,11 @@ class Trainer:
         self.reset_noise_scale = float(config.environment.reset_noise_scale)  # (make_config refuses a negative one; so does the engine)
         if self.reset_noise_scale > 0:
             self.lib.engine_set_reset_noise(self._engine, self.reset_noise_scale)
+        # environment.push_force (random pushes): 0 leaves every launch as it is.  The draw is a function of (seed, rank, environment,
+        # update index * T + t) and the update index is the device counter "count"[1] that checkpoints already carry: checkpoint / resume needs nothing new
+        self.push = push_cfg(config, self.cm, self.seed, rank)  # (seed and rank are the engine configuration's: the engine reads its own)
+        if self.push is not None:
+            self.lib.engine_set_push(self._engine, C.byref(self.push))
         # training.normalize_observations: off leaves the engine's launch sequence as it is
         self.obs_norm_clip, self.obs_norm_eps = float(tr.obs_norm_clip), float(tr.obs_norm_eps)
         if self.obs_norm_on:
@@ -877,8 +905,10 @@ class Trainer:
         overrides.setdefault("seed", self.seed)
         on = self.obs_norm() if self.obs_norm_on else None  # (the table the next rollout would apply: what these parameters were last trained towards)
         # (on the trainer's own stream: behind the last enqueued update, whose parameters it reads)
-        return ev.run(self.lib, self.xp, self.device, self.stream, self._model, self.dims, self.net, self.region("params"), ev.eval_cfg(self.config, **overrides),
-                      obs_norm=None if on is None else {"mean": on["table"][0], "inv_std": on["table"][1], "clip": on["clip"]})
+        ecfg = ev.eval_cfg(self.config, **overrides)
+        return ev.run(self.lib, self.xp, self.device, self.stream, self._model, self.dims, self.net, self.region("params"), ecfg,
+                      obs_norm=None if on is None else {"mean": on["table"][0], "inv_std": on["table"][1], "clip": on["clip"]},
+                      push=push_cfg(self.config, self.cm, ecfg.seed))  # (environment.push_force > 0: the evaluation is pushed as the training was)
 
     def rollout_stats(self, reduce: bool = False) -> Dict[str, float]:
         """Device-side reduction of the last rollout's `EnvMetrics` history (`env.py:183-194`, `train.py:170,283`):

@@ -200,6 +200,31 @@ typedef struct mppo_push_cfg {
 int32_t mppo_push_fill(const mppo_push_cfg_t* cfg, int32_t N, const int32_t* counter, int32_t counter_mul, int32_t counter_add, float* xfrc,
                        void* stream);
 
+/* ---- episode time limit: truncation --------------------------------------------------------------------------------------------
+ * The reference has none (env.py:238-242 ends an episode on height only), so a policy that stands never finishes an episode: the episode statistics
+ * dry up exactly when training succeeds, and randomised starts (reset noise, pushes) are seen once.  Brax's `EpisodeWrapper(episode_length)`,
+ * legged_gym and MuJoCo Playground train with a limit and treat reaching it as a TRUNCATION, not a failure; so does this (csrc/limit.h, k_limit.hip).
+ *
+ * mppo_env_time_limit : one launch behind mppo_env_step (no change to the step kernel).  Environment n is truncated iff its episode did not end in that
+ *     step (done[n] == 0) and either metrics->episode_lengths[n] (post-step) >= length, or `stagger` is set, metrics->timestep[n] == episode_lengths[n]
+ *     (still its first episode since the reset) and episode_lengths[n] == first_n, where
+ *         first_n = 1 + (word 0 of philox(counter = {n, 0xFFFFFFFE, lo(S), hi(S)}, key = seed) mod length),   S = ("LIMIT" << 24) + (rank << 16)
+ *     in uint32 arithmetic (host statement: minppo_amd/jaxrng.py time_limit_first_philox).  Stagger shortens only the first episode of each environment,
+ *     so that a batch does not reach the limit in the same step for ever (legged_gym randomises episode_length_buf for the same reason); the draw is
+ *     stateless, nothing is added to the state record or to a checkpoint.  A truncated environment gets exactly what the step kernel writes for an ended
+ *     episode: done = 1, truncated = 1, returned_episode_returns = episode_returns, returned_episode_lengths = episode_lengths, returned_episode = 1,
+ *     episode_returns = 0, episode_lengths = 0, its state row = reset_rec (rec_dim words) and - obs may be NULL - its observation row = the record's first
+ *     OP words.  reward and timestep stay.  Every other environment keeps every bit, and its `truncated` byte is written 0.  An environment that fell in
+ *     exactly that step is a termination: its lengths are 0 already.  Fixed order, no atomics, one writer per word.
+ *     MPPO_EINVAL: length < 1 (0 means "no limit" wherever a configuration is stored: there is then nothing to launch), rank outside 0 .. 255,
+ *     metrics without the five episode arrays (and `timestep` under stagger), obs_ld below the padded observation width. */
+typedef struct mppo_time_limit_cfg {
+  int32_t length, stagger, rank, reserved;
+  uint64_t seed;
+} mppo_time_limit_cfg_t;
+int32_t mppo_env_time_limit(const mppo_model_t* m, int32_t N, const mppo_time_limit_cfg_t* cfg, float* state, const float* reset_rec, float* obs, int32_t obs_ld,
+                            uint8_t* done, uint8_t* truncated, const mppo_env_metrics_t* metrics, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * PPO stages
  * ---------------------------------------------------------------------------------------- */
@@ -243,6 +268,12 @@ int32_t mppo_gemm_batch(const mppo_gemm_desc_t* probs, int32_t count, int32_t va
 /* `_calculate_gae` (train.py:185-205): reverse scan over T, independent per env. */
 int32_t mppo_gae(int32_t T, int32_t N, float gamma, float lam, const float* reward, const float* value,
                  const uint8_t* done, const float* last_val, float* adv, float* target, void* stream);
+/* mppo_gae under an episode time limit (Brax's compute_gae with its truncation mask): `truncated` [T][N] marks the samples mppo_env_time_limit cut (a
+ * subset of `done`).  In the reverse scan, at such a sample: adv = 0, target = value (the same bits), the carried gae becomes 0 and next_value this
+ * sample's value as always - the value of the observation after the reset is never used as the truncated state's successor.  Every other sample's
+ * arithmetic is mppo_gae's: with an all-zero `truncated` the output bits are its bits; truncated = NULL is exactly mppo_gae, launch and bits. */
+int32_t mppo_gae_truncated(int32_t T, int32_t N, float gamma, float lam, const float* reward, const float* value, const uint8_t* done,
+                           const uint8_t* truncated, const float* last_val, float* adv, float* target, void* stream);
 
 /* One `_update_minibatch` gradient (train.py:213-247): gathers rows idx[0..mb) of the flat
  * [B,...] batch, forward, clipped-PPO loss with the given advantage statistics
@@ -432,7 +463,8 @@ typedef struct mppo_engine_cfg {
  * "log_prob" "done" "last_val" "adv" "target" "noise" "perm" "adv_stats" "losses" "rollout_stats" "jax_rng" "reset_rng"
  * "obs_norm_stats" (float64) "obs_norm_table" "obs_norm_partials" (float64)
  * "reward_norm_stats" (float64 [3]) "reward_norm_table" ([2]) "reward_norm_carry" ([N]) "reward_norm_partials" (float64 [G][2]) "reward_scaled" ([T][N])
- * ("rollout_stats": 8 floats: sum reward, episodes ended, sum of their returns, sum of their lengths, the two means, 0, 0) ... */
+ * "truncated" (bytes [T][N]: the samples an episode time limit cut, mppo_engine_set_time_limit)
+ * ("rollout_stats": 8 floats: sum reward, episodes ended, sum of their returns, sum of their lengths, the two means, truncations (0 without a time limit), 0) ... */
 int32_t mppo_engine_arena_bytes(const mppo_model_t* m, const mppo_engine_cfg_t* cfg, size_t* out);
 int32_t mppo_engine_create(const mppo_model_t* m, const mppo_engine_cfg_t* cfg, void* arena, size_t arena_bytes,
                            mppo_engine_t** out);
@@ -518,6 +550,14 @@ int32_t mppo_engine_set_reward_norm(mppo_engine_t* e, int32_t enabled, float cli
  * mppo_env_step_xfrc.  Call before mppo_engine_reset, mppo_engine_prepare and the first mppo_engine_update: afterwards it returns MPPO_ESTATE.
  * MPPO_EINVAL: the refusals listed at mppo_push_cfg_t. */
 int32_t mppo_engine_set_push(mppo_engine_t* e, const mppo_push_cfg_t* push);
+/* An episode time limit during training (mppo_env_time_limit above; length = 0, the default: the engine enqueues exactly the launches, with exactly the
+ * arguments, it enqueues without this call - the plain GAE included).  length > 0: every rollout step becomes step -> mppo_env_time_limit (seed and rank:
+ * the engine configuration's; any world_size - nothing crosses ranks) -> the masked mppo_env_reinit where reset noise is on (its mask done[t] now includes
+ * the truncations) -> the observation normalisation's apply, in the captured graph too; the step's `truncated` bytes are row t of the arena region
+ * "truncated" [T][N] (behind every other region; it exists whether or not a limit is set), GAE is mppo_gae_truncated over it, and "rollout_stats"[6] is
+ * the number of truncations of the rollout (0 without a limit).  Reward scaling needs nothing: its carry restarts behind every `done`.  Call before
+ * mppo_engine_reset, mppo_engine_prepare and the first mppo_engine_update: afterwards it returns MPPO_ESTATE.  MPPO_EINVAL: a negative length. */
+int32_t mppo_engine_set_time_limit(mppo_engine_t* e, int32_t length, int32_t stagger);
 /* one full update: T rollout steps, bootstrap value, GAE, E epochs x M minibatches */
 int32_t mppo_engine_update(mppo_engine_t* e, void* stream);
 /* what mppo_engine_update does before it enqueues anything: the one-time capture of the update into a hipGraph (no device work).
@@ -604,6 +644,29 @@ int32_t mppo_eval_accumulate(int32_t N, int32_t first, const float* reward, cons
                              void* acc, const float* state, int32_t state_ld, int32_t row_w, const float* action, int32_t act_ld,
                              int32_t A, int32_t R, float* traj_row, void* stream);
 int32_t mppo_eval_reduce(int32_t N, int32_t K, const void* acc, mppo_eval_result_t* result, void* stream);
+/* mppo_evaluate_push under an episode time limit (no stagger, rank 0): with episode_length > 0 the documented sequence with
+ *        mppo_env_time_limit({episode_length, 0, 0, 0, cfg->seed}, ..., done, truncated, metrics)
+ * behind every step's mppo_env_step (in front of the masked reinit, whose mask then includes the truncations, the observation normalisation and
+ * mppo_eval_accumulate, which therefore counts a truncated episode as an episode, with its return and length), one mppo_eval_limit_count behind
+ * mppo_eval_accumulate and one mppo_eval_limit_reduce at the end - the same bits when the caller writes it out.  The trajectory's `done` column
+ * includes the truncations.  *result keeps its documented meaning (`survivors`: the environments none of whose episodes ended - under a limit
+ * shorter than K that is none of them); *extra (DEVICE memory, 8-byte aligned) says why the episodes ended:
+ *        truncated_episodes  the episodes the limit cut;  fallen_envs  the environments with at least one termination (N - fallen_envs never fell).
+ * episode_length = 0: exactly mppo_evaluate_push, bytes and launches; *extra is not written (it may be NULL).  MPPO_EINVAL: a negative length.
+ * `ws`: >= mppo_eval_limit_ws_bytes (mppo_eval_ws_bytes' regions, then truncated [N] and the counters), whatever episode_length is.
+ *   mppo_eval_limit_count   one step: `acc` (2 * N int64 in device memory, 8-byte aligned: truncations [N] | terminations [N]) gains this step's
+ *                           truncated[n] and done[n] && !truncated[n]; first != 0: `acc` is empty (written, not read).
+ *   mppo_eval_limit_reduce  those counters -> *result (device memory): the first row's sum and the number of non-zero words of the second. */
+typedef struct mppo_eval_limit_result {
+  int64_t truncated_episodes;
+  int64_t fallen_envs;
+} mppo_eval_limit_result_t;
+size_t mppo_eval_limit_ws_bytes(const mppo_model_t* m, const mppo_net_t* net, const mppo_eval_cfg_t* cfg);
+int32_t mppo_evaluate_limit(const mppo_model_t* m, const mppo_net_t* net, const float* params, const mppo_eval_cfg_t* cfg, void* ws, size_t ws_bytes,
+                            const float* obs_table, float clip, const mppo_push_cfg_t* push, int32_t episode_length, mppo_eval_result_t* result,
+                            mppo_eval_limit_result_t* extra, float* traj, void* stream);
+int32_t mppo_eval_limit_count(int32_t N, int32_t first, const uint8_t* done, const uint8_t* truncated, void* acc, void* stream);
+int32_t mppo_eval_limit_reduce(int32_t N, const void* acc, mppo_eval_limit_result_t* result, void* stream);
 
 /* ---- rendering --------------------------------------------------------------------------------------------------------------
  * Frames of a rollout as images, ray-cast on the device (csrc/k_render.hip): what the reference leaves to MuJoCo's renderer

@@ -96,6 +96,14 @@ class PushCfg(C.Structure):  # mppo_push_cfg_t: random pushes (force 0: off)
     _fields_ = [("body", c_i32), ("interval", c_i32), ("duration", c_i32), ("rank", c_i32), ("force", c_f), ("seed", c_u64)]
 
 
+class TimeLimitCfg(C.Structure):  # mppo_time_limit_cfg_t: the episode time limit of one mppo_env_time_limit launch (length >= 1)
+    _fields_ = [("length", c_i32), ("stagger", c_i32), ("rank", c_i32), ("reserved", c_i32), ("seed", c_u64)]
+
+
+class EvalLimitResultRaw(C.Structure):  # mppo_eval_limit_result_t
+    _fields_ = [("truncated_episodes", C.c_int64), ("fallen_envs", C.c_int64)]
+
+
 class SceneDims(C.Structure):
     _fields_ = [(n, c_i32) for n in ("nq", "nbody", "ngeom", "ncam", "has_plane")]
 
@@ -128,6 +136,8 @@ SIGNATURES = {
                                    P(EnvMetrics), c_i32, c_vp, c_vp]),
     "mppo_physics_forward_xfrc": (c_i32, [c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, P(ForwardProbe), c_i32, c_vp, c_vp]),
     "mppo_push_fill": (c_i32, [P(PushCfg), c_i32, c_vp, c_i32, c_i32, c_vp, c_vp]),
+    "mppo_env_time_limit": (c_i32, [c_vp, c_i32, P(TimeLimitCfg), c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, P(EnvMetrics), c_vp]),
+    "mppo_gae_truncated": (c_i32, [c_i32, c_i32, c_f, c_f, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "mppo_param_count": (c_sz, [P(Net)]),
     "mppo_policy_ws_bytes": (c_sz, [P(Net), c_i32]),
     "mppo_policy_forward": (c_i32, [P(Net), c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
@@ -181,6 +191,7 @@ SIGNATURES = {
     "mppo_engine_set_obs_norm": (c_i32, [c_vp, c_i32, c_f, c_f]),
     "mppo_engine_set_reward_norm": (c_i32, [c_vp, c_i32, c_f, c_f]),
     "mppo_engine_set_push": (c_i32, [c_vp, P(PushCfg)]),
+    "mppo_engine_set_time_limit": (c_i32, [c_vp, c_i32, c_i32]),
     "mppo_engine_update": (c_i32, [c_vp, c_vp]),
     "mppo_engine_prepare": (c_i32, [c_vp, c_vp]),
     "mppo_engine_graph_active": (c_i32, [c_vp, P(c_i32)]),
@@ -192,6 +203,10 @@ SIGNATURES = {
     "mppo_evaluate_push": (c_i32, [c_vp, P(Net), c_vp, P(EvalCfg), c_vp, c_sz, c_vp, c_f, P(PushCfg), c_vp, c_vp, c_vp]),
     "mppo_eval_accumulate": (c_i32, [c_i32, c_i32, c_vp, c_vp, P(EnvMetrics), c_vp, c_vp, c_i32, c_i32, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp]),
     "mppo_eval_reduce": (c_i32, [c_i32, c_i32, c_vp, c_vp, c_vp]),
+    "mppo_eval_limit_ws_bytes": (c_sz, [c_vp, P(Net), P(EvalCfg)]),
+    "mppo_evaluate_limit": (c_i32, [c_vp, P(Net), c_vp, P(EvalCfg), c_vp, c_sz, c_vp, c_f, P(PushCfg), c_i32, c_vp, c_vp, c_vp, c_vp]),
+    "mppo_eval_limit_count": (c_i32, [c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
+    "mppo_eval_limit_reduce": (c_i32, [c_i32, c_vp, c_vp, c_vp]),
     "mppo_scene_open": (c_i32, [c_vp, c_sz, c_vp, P(c_vp)]),
     "mppo_scene_close": (c_i32, [c_vp]),
     "mppo_scene_get_dims": (c_i32, [c_vp, P(SceneDims)]),
@@ -199,7 +214,7 @@ SIGNATURES = {
 }
 
 UNCHECKED = {"mppo_last_error", "mppo_abi_version", "mppo_param_count", "mppo_policy_ws_bytes", "mppo_grad_ws_bytes",
-             "mppo_adam_ws_bytes", "mppo_permutation_ws_bytes", "mppo_eval_ws_bytes", "mppo_obs_norm_partials",
+             "mppo_adam_ws_bytes", "mppo_permutation_ws_bytes", "mppo_eval_ws_bytes", "mppo_eval_limit_ws_bytes", "mppo_obs_norm_partials",
              "mppo_reward_norm_partials"}
 
 

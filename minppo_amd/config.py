@@ -72,6 +72,14 @@ class EnvironmentConfig:
     push_interval: int = field(default=1000)
     push_duration: int = field(default=50)
     push_body: str = field(default="")
+    # Extension (absent upstream: env.py:238-242 ends an episode on height only; Brax `EpisodeWrapper(episode_length=1000)`, legged_gym, MuJoCo Playground):
+    # an episode time limit in env steps.  An environment whose episode reaches it is TRUNCATED - restarted as a fallen one is, counted as an episode with its
+    # return and length, and cut out of GAE (advantage 0, target = value: reaching the limit is no failure) - so a standing policy keeps producing episode
+    # statistics and keeps seeing randomised starts.  In training, in `evaluate` and in `HumanoidEnv.step` / the `env` rollout.
+    # `episode_length_stagger` (read only when episode_length > 0; training only): every environment's FIRST episode is cut at a length of its own, drawn in
+    # 1 .. episode_length, so that the batch does not reach the limit in the same step for ever.  0: no limit, nothing changes.  Negative: ValueError.
+    episode_length: int = field(default=0)
+    episode_length_stagger: bool = field(default=True)
 
 
 @dataclass
@@ -302,6 +310,8 @@ def make_config(yaml_dict: dict | None = None, overrides: Sequence[str] = ()) ->
     if env.push_force > 0.0 and not (env.push_interval >= 1 and 1 <= env.push_duration <= env.push_interval):
         raise ValueError(f"environment.push_interval = {env.push_interval!r} / push_duration = {env.push_duration!r}: the interval is at least one env step and "
                          "the duration lies in 1 .. push_interval")
+    if not env.episode_length >= 0:
+        raise ValueError(f"environment.episode_length = {env.episode_length!r}: the time limit is a number of env steps (0: no limit) and cannot be negative")
     for key in ("obs_norm_clip", "obs_norm_eps", "reward_norm_clip", "reward_norm_eps"):
         if not getattr(cfg.training, key) >= 0.0:
             raise ValueError(f"training.{key} = {getattr(cfg.training, key)!r} cannot be negative")

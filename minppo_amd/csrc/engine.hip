@@ -22,6 +22,7 @@
 #include "obsnorm.h"
 #include "rewnorm.h"
 #include "push.h"
+#include "limit.h"
 
 #include <cmath>
 #include <cstdlib>
@@ -61,11 +62,14 @@ __global__ void advance_counters_kernel(int* count, int opt_steps, int* zero = n
 //   out[0] sum of rewards            out[1] number of done steps (= returned episodes)
 //   out[2] sum over done steps of returned_episode_returns      out[3] ... of returned_episode_lengths
 //   out[4] = out[2]/out[1], out[5] = out[3]/out[1] (0 when no episode ended)    out[6], out[7] = 0
+//   (under an episode time limit - rollout_stats_limit_kernel, whose `done` includes the truncations: out[6] = number of truncated steps)
 constexpr int kStatsThreads = 1024;
-__global__ void __launch_bounds__(kStatsThreads) rollout_stats_kernel(int T, int N, const float* __restrict__ reward, const unsigned char* __restrict__ done,
-                                                                      const float* __restrict__ ret_in, const int* __restrict__ len_in, float* __restrict__ out) {
-  __shared__ double red[kStatsThreads / 64][4];
-  double sr = 0.0, sd = 0.0, sret = 0.0, slen = 0.0;
+template <bool kLimit>
+__device__ __forceinline__ void rollout_stats_body(int T, int N, const float* __restrict__ reward, const unsigned char* __restrict__ done,
+                                                   const unsigned char* __restrict__ truncated, const float* __restrict__ ret_in, const int* __restrict__ len_in,
+                                                   float* __restrict__ out) {
+  __shared__ double red[kStatsThreads / 64][5];
+  double sr = 0.0, sd = 0.0, sret = 0.0, slen = 0.0, str = 0.0;
   for (int n = threadIdx.x; n < N; n += kStatsThreads) {
     float ret = ret_in[n];
     int len = len_in[n];
@@ -73,12 +77,13 @@ __global__ void __launch_bounds__(kStatsThreads) rollout_stats_kernel(int T, int
     // loads are not: one trip to memory per chunk instead of one per step - 16 -> see DESIGN.md 3.6)
     for (int t0 = 0; t0 < T; t0 += 8) {
       float r8[8];
-      unsigned char d8[8];
+      unsigned char d8[8], u8[8];
 #pragma unroll
       for (int u = 0; u < 8; ++u) {
         const int t = t0 + u < T ? t0 + u : T - 1;
         r8[u] = reward[(size_t)t * N + n];
         d8[u] = done[(size_t)t * N + n];
+        if (kLimit) u8[u] = truncated[(size_t)t * N + n];
       }
 #pragma unroll
       for (int u = 0; u < 8; ++u) {
@@ -88,21 +93,32 @@ __global__ void __launch_bounds__(kStatsThreads) rollout_stats_kernel(int T, int
           ret += r; len += 1;                       // new_episode_return / new_episode_length (env.py:183-184)
           sr += (double)r;
           if (d) { sd += 1.0; sret += (double)ret; slen += (double)len; ret = 0.f; len = 0; }  // env.py:187-190
+          if (kLimit) str += u8[u] != 0 ? 1.0 : 0.0;
         }
       }
     }
   }
   sr = wave_sum_f64(sr); sd = wave_sum_f64(sd); sret = wave_sum_f64(sret); slen = wave_sum_f64(slen);
-  if ((threadIdx.x & 63) == 0) { double* q = red[threadIdx.x >> 6]; q[0] = sr; q[1] = sd; q[2] = sret; q[3] = slen; }
+  if (kLimit) str = wave_sum_f64(str);
+  if ((threadIdx.x & 63) == 0) { double* q = red[threadIdx.x >> 6]; q[0] = sr; q[1] = sd; q[2] = sret; q[3] = slen; q[4] = str; }
   __syncthreads();
   if (threadIdx.x == 0) {
-    double a[4] = {0.0, 0.0, 0.0, 0.0};
-    for (int w = 0; w < kStatsThreads / 64; ++w) for (int k = 0; k < 4; ++k) a[k] += red[w][k];
+    double a[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int w = 0; w < kStatsThreads / 64; ++w) for (int k = 0; k < 5; ++k) a[k] += red[w][k];
     for (int k = 0; k < 4; ++k) out[k] = (float)a[k];
     out[4] = a[1] > 0.0 ? (float)(a[2] / a[1]) : 0.f;
     out[5] = a[1] > 0.0 ? (float)(a[3] / a[1]) : 0.f;
-    out[6] = 0.f; out[7] = 0.f;
+    out[6] = kLimit ? (float)a[4] : 0.f; out[7] = 0.f;
   }
+}
+__global__ void __launch_bounds__(kStatsThreads) rollout_stats_kernel(int T, int N, const float* __restrict__ reward, const unsigned char* __restrict__ done,
+                                                                      const float* __restrict__ ret_in, const int* __restrict__ len_in, float* __restrict__ out) {
+  rollout_stats_body<false>(T, N, reward, done, nullptr, ret_in, len_in, out);
+}
+__global__ void __launch_bounds__(kStatsThreads) rollout_stats_limit_kernel(int T, int N, const float* __restrict__ reward, const unsigned char* __restrict__ done,
+                                                                            const unsigned char* __restrict__ truncated, const float* __restrict__ ret_in,
+                                                                            const int* __restrict__ len_in, float* __restrict__ out) {
+  rollout_stats_body<true>(T, N, reward, done, truncated, ret_in, len_in, out);
 }
 
 struct Region { std::string name; size_t off, bytes; };
@@ -157,6 +173,9 @@ struct mppo_engine {
   float* reward_scaled;          // [T][N] what GAE reads; "reward" stays raw
   // random pushes (mppo_engine_set_push; body 0: off - the rollout's step launches are the unpushed ones)
   mppo::EnvPush push;
+  // episode time limit (mppo_engine_set_time_limit; length 0: off - no launch is added, GAE and the statistics are the plain ones)
+  mppo::LimitCfg limit;
+  unsigned char* truncated;  // [T][N] the samples the limit cut
 };
 
 namespace mppo {
@@ -228,6 +247,8 @@ static size_t layout(mppo_engine* e, bool assign) {
   e->reward_norm_carry = (float*)take("reward_norm_carry", N * 4);
   e->reward_norm_partials = (double*)take("reward_norm_partials", (size_t)reward_norm_partials((int)N) * 2 * 8);
   e->reward_scaled = (float*)take("reward_scaled", B * 4);
+  // the episode time limit's flags: behind those again, present whether or not a limit is set
+  e->truncated = (unsigned char*)take("truncated", B);
   return align_up(off, 256);
 }
 
@@ -316,6 +337,11 @@ static int32_t do_rollout(mppo_engine* e, hipStream_t s) {
     push.add = t;
     MPPO_TRY(env_step_push_ws(e->model, e->N, c.n_frames, &c.reward, e->state, e->reset_rec, e->action + t * N * A, e->A, e->obs + (size_t)(t + 1) * N * OP,
                               e->OP, e->reward + t * N, e->done + t * N, &e->met, push, e->env_ws, e->env_ws_bytes, static_cast<hipStream_t>(s)));                       // :165
+    // episode time limit: the environments that have reached it are truncated - flags, metrics, the reset record - as the step's epilogue ends an episode;
+    // done[t] then includes them, so the masked reinit below restarts them too and the reward scaling's carry restarts behind them
+    if (e->limit.length > 0)
+      MPPO_TRY(time_limit_launch(e->limit, e->N, e->mv.rec_dim, e->OP, e->state, e->reset_rec, e->obs + (size_t)(t + 1) * N * OP, e->OP, e->done + t * N,
+                                 e->truncated + t * N, e->met, s));
     // reset noise: the environments whose episode ended at this step restart from a randomised state instead of the constant record the step kernel
     // gave them (env.py:166,179-180) - one masked launch of the reset kernel over done[t]; a workgroup without an ended episode leaves at once
     if (e->reset_noise > 0.f)
@@ -336,8 +362,13 @@ static int32_t do_rollout(mppo_engine* e, hipStream_t s) {
   if (e->reward_norm)
     MPPO_TRY(reward_norm_apply_launch(e->T, e->N, c.gamma, e->reward, e->done, e->reward_norm_carry, e->reward_norm_table, e->reward_norm_clip, e->reward_scaled,
                                       e->reward_norm_partials, s));
-  MPPO_TRY(gae_launch(e->T, e->N, c.gamma, c.gae_lambda, e->reward_norm ? e->reward_scaled : e->reward, e->value, e->done, e->last_val, e->adv, e->target, s));
-  hipLaunchKernelGGL(rollout_stats_kernel, dim3(1), dim3(kStatsThreads), 0, s, e->T, e->N, e->reward, e->done, e->stat_ret_in, e->stat_len_in, e->stats);
+  // (under a time limit the scan is cut at the truncated samples and the statistics count them; without one: the plain launches)
+  MPPO_TRY(gae_truncated_launch(e->T, e->N, c.gamma, c.gae_lambda, e->reward_norm ? e->reward_scaled : e->reward, e->value, e->done,
+                                e->limit.length > 0 ? e->truncated : nullptr, e->last_val, e->adv, e->target, s));
+  if (e->limit.length > 0)
+    hipLaunchKernelGGL(rollout_stats_limit_kernel, dim3(1), dim3(kStatsThreads), 0, s, e->T, e->N, e->reward, e->done, e->truncated, e->stat_ret_in, e->stat_len_in, e->stats);
+  else
+    hipLaunchKernelGGL(rollout_stats_kernel, dim3(1), dim3(kStatsThreads), 0, s, e->T, e->N, e->reward, e->done, e->stat_ret_in, e->stat_len_in, e->stats);
   MPPO_CHECK_LAUNCH("rollout_stats_kernel");
   if (e->obs_norm)  // the T steps' rows join the running statistics; the table is rewritten for the next update (nothing of this one applies it any more)
     MPPO_TRY(obs_norm_update_launch(e->O, e->T * obs_norm_partials(e->N), (long long)e->T * e->N, e->obs_norm_partials, e->obs_norm_stats, e->obs_norm_eps, e->obs_norm_table,
@@ -466,6 +497,7 @@ extern "C" int32_t mppo_engine_create(const mppo_model_t* m, const mppo_engine_c
   e->obs_norm = false; e->obs_norm_clip = 0.f; e->obs_norm_eps = 0.f;
   e->reward_norm = false; e->reward_norm_clip = 0.f; e->reward_norm_eps = 0.f;
   e->push = EnvPush{};
+  e->limit = LimitCfg{};
   *out = e;
   return MPPO_OK;
 }
@@ -595,6 +627,22 @@ extern "C" int32_t mppo_engine_set_push(mppo_engine_t* e, const mppo_push_cfg_t*
     MPPO_TRY(check_push_cfg("mppo_engine_set_push", &pc));  // (the rank that is used - the engine configuration's - fits the stream id's eight bits)
     e->push.body = pc.body; e->push.draw = push_draw_of(pc); e->push.ctr = e->count + 1; e->push.mul = e->T;
   }
+  return MPPO_OK;
+}
+
+extern "C" int32_t mppo_engine_set_time_limit(mppo_engine_t* e, int32_t length, int32_t stagger) {
+  MPPO_REQUIRE(e, "mppo_engine_set_time_limit: null engine");
+  mppo_time_limit_cfg_t lc{};
+  lc.length = length; lc.stagger = stagger != 0 ? 1 : 0; lc.seed = e->cfg.seed;
+  lc.rank = length > 0 ? e->cfg.rank : 0;  // (the engine's own: one stream per rank, as the pushes have; it fits the stream id's eight bits or the limit is refused)
+  MPPO_TRY(check_limit_cfg("mppo_engine_set_time_limit", &lc));
+  if (e->graph || e->prepared)
+    return fail(MPPO_ESTATE, "mppo_engine_set_time_limit: the update has been prepared already (its launch sequence is fixed, a captured graph holds it): "
+                             "set the limit before mppo_engine_prepare and the first mppo_engine_update");
+  if (e->was_reset)
+    return fail(MPPO_ESTATE, "mppo_engine_set_time_limit: mppo_engine_reset has run already: set the limit before it");
+  e->limit = LimitCfg{};
+  if (length > 0) e->limit = limit_cfg_of(lc);
   return MPPO_OK;
 }
 

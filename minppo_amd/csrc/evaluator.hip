@@ -4,13 +4,14 @@
 //
 // The sequence is a composition of the library's own entry points, so that a caller could write it themselves and get the same bits
 // (tests/test_evaluate.py does): mppo_env_reset, [mppo_env_reinit], then per step [mppo_normal_fill], mppo_policy_forward, mppo_env_step,
-// [mppo_env_reinit over done], and the two stages of k_eval.hip.  Launches only: no allocation, no synchronisation, no blocking copy - every
+// [mppo_env_time_limit], [mppo_env_reinit over done], and the two stages of k_eval.hip (under an episode time limit also the two of k_limit.hip).  Launches only: no allocation, no synchronisation, no blocking copy - every
 // buffer is a region of the caller's workspace (a large robot's out-of-LDS matrices included), so the call can be captured into a hipGraph.
 #include "eval.h"
 #include "model_view.h"
 #include "obsnorm.h"
 #include "ppo_layout.h"
 #include "push.h"
+#include "limit.h"
 
 namespace mppo {
 const ModelView& model_view(const mppo_model* m);
@@ -28,10 +29,13 @@ struct EvalWs {
   mppo_env_metrics_t met;
   void* acc;
   size_t env_ws_bytes, total;
+  // behind mppo_eval_ws_bytes' regions (carve_eval's `limit`): the time limit's flags and the two counters per environment
+  unsigned char* truncated;
+  void* limit_acc;
 };
 
 // the regions of the workspace, each on a 256-byte boundary (base = null: sizes only)
-static EvalWs carve_eval(const mppo_model* m, const mppo_net_t& net, int N, unsigned char* base) {
+static EvalWs carve_eval(const mppo_model* m, const mppo_net_t& net, int N, unsigned char* base, bool limit = false) {
   const ModelView& mv = model_view(m);
   EvalWs w{};
   size_t off = 0;
@@ -61,6 +65,7 @@ static EvalWs carve_eval(const mppo_model* m, const mppo_net_t& net, int N, unsi
   w.fwd_ws = (float*)take(fwd_bufs_floats(net, N) * 4);
   w.env_ws_bytes = model_scratch_bytes(m, N);
   w.env_ws = w.env_ws_bytes ? (float*)take(w.env_ws_bytes) : nullptr;
+  if (limit) { w.truncated = take(n); w.limit_acc = take(eval_limit_acc_bytes(N)); }
   w.total = align_up(off, 256);
   return w;
 }
@@ -94,8 +99,18 @@ extern "C" size_t mppo_eval_ws_bytes(const mppo_model_t* m, const mppo_net_t* ne
 
 // obs_table (may be null: the plain evaluation, not one launch more): [2][O] mean32 | inv_std32 of a policy trained on normalised observations
 static int32_t evaluate_impl(const char* who, const mppo_model_t* m, const mppo_net_t* net, const float* params, const mppo_eval_cfg_t* cfg, void* ws, size_t ws_bytes,
-                             const float* obs_table, float clip, const mppo_push_cfg_t* push, mppo_eval_result_t* result, float* traj, void* stream) {
+                             const float* obs_table, float clip, const mppo_push_cfg_t* push, mppo_eval_result_t* result, float* traj, void* stream,
+                             bool limit_ws = false, int32_t episode_length = 0, mppo_eval_limit_result_t* extra = nullptr) {
   MPPO_TRY(check_eval(who, m, net, cfg));
+  // episode time limit (0: none - launch for launch the evaluation without one): no stagger, rank 0, the evaluation's seed (which the unstaggered test does not read)
+  MPPO_REQUIRE(episode_length >= 0, "%s: episode length %d is negative", who, episode_length);
+  MPPO_REQUIRE(episode_length == 0 || (extra && (reinterpret_cast<uintptr_t>(extra) & 7) == 0), "%s: the time limit's result must be given, 8-byte aligned", who);
+  LimitCfg lim{};
+  if (episode_length > 0) {
+    mppo_time_limit_cfg_t lc{};
+    lc.length = episode_length; lc.seed = cfg->seed;
+    lim = limit_cfg_of(lc);
+  }
   // random pushes (may be null, or of force 0: the unpushed evaluation, launch for launch): drawn inside the step's kernel at step t of rank 0 under the evaluation's seed
   EnvPush ep{};
   if (push) {
@@ -114,8 +129,8 @@ static int32_t evaluate_impl(const char* who, const mppo_model_t* m, const mppo_
   MPPO_REQUIRE(clip >= 0.f, "%s: clip %g is negative (or not a number)", who, (double)clip);
   const mppo_eval_cfg_t& c = *cfg;
   const int N = c.N, K = c.K, R = c.record_envs, A = net->A;
-  const EvalWs w = carve_eval(m, *net, N, static_cast<unsigned char*>(ws));
-  MPPO_REQUIRE(ws_bytes >= w.total, "%s: workspace %zu < %zu bytes (mppo_eval_ws_bytes)", who, ws_bytes, w.total);
+  const EvalWs w = carve_eval(m, *net, N, static_cast<unsigned char*>(ws), limit_ws);
+  MPPO_REQUIRE(ws_bytes >= w.total, "%s: workspace %zu < %zu bytes (%s)", who, ws_bytes, w.total, limit_ws ? "mppo_eval_limit_ws_bytes" : "mppo_eval_ws_bytes");
   hipStream_t s = static_cast<hipStream_t>(stream);
   const ModelView& mv = model_view(m);
   const int OP = mv.obs_pad, row_w = mv.nq + mv.nv;
@@ -135,13 +150,17 @@ static int32_t evaluate_impl(const char* who, const mppo_model_t* m, const mppo_
     MPPO_TRY(policy_forward(*net, params, N, w.obs, OP, fb, w.noise, w.action, w.log_prob, w.value, nullptr, s));
     ep.add = t;
     MPPO_TRY(env_step_push_ws(m, N, c.n_frames, &c.reward, w.state, w.reset_rec, w.action, A, w.obs, OP, w.reward, w.done, &w.met, ep, w.env_ws, w.env_ws_bytes, s));
+    if (lim.length > 0)  // the environments that have reached the limit are truncated: done, the metrics and the reset record as the step ends an episode
+      MPPO_TRY(time_limit_launch(lim, N, mv.rec_dim, OP, w.state, w.reset_rec, w.obs, OP, w.done, w.truncated, w.met, s));
     if (noisy_reset)  // the environments whose episode ended restart from a randomised state (event t + 1), as in the engine's rollout
       MPPO_TRY(env_reinit_ws(m, N, w.state, w.obs, OP, w.done, c.reset_noise_scale, 0, c.seed, 0, nullptr, nullptr, 1, t + 1, w.env_ws, w.env_ws_bytes, s));
     if (obs_table)  // the next forward reads what the policy was trained on; the observation after the reset stays raw, as in the engine (the state rows are raw throughout)
       MPPO_TRY(obs_norm_apply_launch(N, net->O, w.obs, OP, obs_table, net->O, clip, nullptr, s));
     MPPO_TRY(eval_accumulate_launch(N, N, t == 0, w.reward, w.done, &w.met, w.acc, w.state, mv.rec_dim, row_w, w.action, A, A, R,
                                     R > 0 ? traj + (size_t)(t + 1) * frame : nullptr, s));
+    if (lim.length > 0) MPPO_TRY(eval_limit_count_launch(N, t == 0, w.done, w.truncated, w.limit_acc, s));
   }
+  if (lim.length > 0) MPPO_TRY(eval_limit_reduce_launch(N, w.limit_acc, extra, s));
   return eval_reduce_launch(N, K, w.acc, result, s);
 }
 
@@ -158,4 +177,15 @@ extern "C" int32_t mppo_evaluate_obs_norm(const mppo_model_t* m, const mppo_net_
 extern "C" int32_t mppo_evaluate_push(const mppo_model_t* m, const mppo_net_t* net, const float* params, const mppo_eval_cfg_t* cfg, void* ws, size_t ws_bytes,
                                       const float* obs_table, float clip, const mppo_push_cfg_t* push, mppo_eval_result_t* result, float* traj, void* stream) {
   return evaluate_impl("mppo_evaluate_push", m, net, params, cfg, ws, ws_bytes, obs_table, clip, push, result, traj, stream);
+}
+
+extern "C" size_t mppo_eval_limit_ws_bytes(const mppo_model_t* m, const mppo_net_t* net, const mppo_eval_cfg_t* cfg) {
+  if (check_eval("mppo_eval_limit_ws_bytes", m, net, cfg) != MPPO_OK) return 0;
+  return carve_eval(m, *net, cfg->N, nullptr, true).total;
+}
+
+extern "C" int32_t mppo_evaluate_limit(const mppo_model_t* m, const mppo_net_t* net, const float* params, const mppo_eval_cfg_t* cfg, void* ws, size_t ws_bytes,
+                                       const float* obs_table, float clip, const mppo_push_cfg_t* push, int32_t episode_length, mppo_eval_result_t* result,
+                                       mppo_eval_limit_result_t* extra, float* traj, void* stream) {
+  return evaluate_impl("mppo_evaluate_limit", m, net, params, cfg, ws, ws_bytes, obs_table, clip, push, result, traj, stream, true, episode_length, extra);
 }

@@ -12,6 +12,7 @@
 #include "ppo_layout.h"
 #include "wgrad.h"
 #include "peer.h"
+#include "limit.h"
 
 namespace mppo {
 
@@ -36,6 +37,34 @@ __global__ void __launch_bounds__(256) gae_kernel(int T, int N, float gamma, flo
     gae = delta + gl * nd * gae;
     adv[o] = gae;
     target[o] = gae + v;
+    next_value = v;
+  }
+}
+
+// The same scan under an episode time limit (limit.h; Brax's compute_gae with its `truncation` mask): `truncated` marks the samples whose episode was cut
+// by the limit (a subset of `done`).  Such a sample has no successor the critic could speak for - the state behind it is the reset - so nothing is learnt
+// from it: adv = 0, target = value (the same bits), and the scan restarts there (the carried gae is 0, next_value this sample's value as always).  Every
+// other sample's arithmetic is gae_kernel's, expression for expression: with no truncated sample the output bits are its bits.  One more coalesced byte
+// per sample.
+__global__ void __launch_bounds__(256) gae_truncated_kernel(int T, int N, float gamma, float lam, const float* __restrict__ reward,
+                                                            const float* __restrict__ value, const unsigned char* __restrict__ done,
+                                                            const unsigned char* __restrict__ truncated, const float* __restrict__ last_val,
+                                                            float* __restrict__ adv, float* __restrict__ target) {
+  const int n = blockIdx.x * blockDim.x + threadIdx.x;
+  if (n >= N) return;
+  float gae = 0.f, next_value = last_val[n];
+  const float gl = gamma * lam;
+  for (int t = T - 1; t >= 0; --t) {
+    const size_t o = (size_t)t * N + n;
+    const float nd = done[o] ? 0.f : 1.f;
+    const bool cut = truncated[o] != 0;
+    const float v = value[o];
+    const float delta = reward[o] + gamma * next_value * nd - v;
+    gae = delta + gl * nd * gae;
+    float tg = gae + v;
+    if (cut) { gae = 0.f; tg = v; }
+    adv[o] = gae;
+    target[o] = tg;
     next_value = v;
   }
 }
@@ -819,6 +848,14 @@ int32_t gae_launch(int T, int N, float gamma, float lam, const float* reward, co
   return MPPO_OK;
 }
 
+int32_t gae_truncated_launch(int T, int N, float gamma, float lam, const float* reward, const float* value, const unsigned char* done, const unsigned char* truncated,
+                             const float* last_val, float* adv, float* target, hipStream_t stream) {
+  if (!truncated) return gae_launch(T, N, gamma, lam, reward, value, done, last_val, adv, target, stream);  // (no limit: the plain scan, launch and bits)
+  hipLaunchKernelGGL(gae_truncated_kernel, dim3(cdiv(N, 256)), dim3(256), 0, stream, T, N, gamma, lam, reward, value, done, truncated, last_val, adv, target);
+  MPPO_CHECK_LAUNCH("gae_truncated_kernel");
+  return MPPO_OK;
+}
+
 }  // namespace mppo
 
 // =================================================================================================
@@ -859,6 +896,12 @@ extern "C" int32_t mppo_gae(int32_t T, int32_t N, float gamma, float lam, const 
                             const float* last_val, float* adv, float* target, void* stream) {
   MPPO_REQUIRE(T >= 1 && N >= 1 && reward && value && done && last_val && adv && target, "mppo_gae: bad argument");
   return gae_launch(T, N, gamma, lam, reward, value, done, last_val, adv, target, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int32_t mppo_gae_truncated(int32_t T, int32_t N, float gamma, float lam, const float* reward, const float* value, const uint8_t* done,
+                                      const uint8_t* truncated, const float* last_val, float* adv, float* target, void* stream) {
+  MPPO_REQUIRE(T >= 1 && N >= 1 && reward && value && done && last_val && adv && target, "mppo_gae_truncated: bad argument");
+  return gae_truncated_launch(T, N, gamma, lam, reward, value, done, truncated, last_val, adv, target, static_cast<hipStream_t>(stream));
 }
 
 extern "C" int32_t mppo_minibatch_rows_per_workgroup(const mppo_net_t* net, int32_t mb, int32_t pre_gathered, int32_t* rows) {

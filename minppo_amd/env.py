@@ -53,6 +53,7 @@ class EnvState(NamedTuple):
     reward: Any
     done: Any
     metrics: EnvMetrics
+    truncation: Any = None  # extension (Brax: `state.info["truncation"]`): bool [N], the environments `environment.episode_length` cut at this step (a subset of `done`); None without a limit
 
 
 class HumanoidEnv:
@@ -97,6 +98,8 @@ class HumanoidEnv:
             self.reset_noise_scale = float(config.environment.reset_noise_scale)
         # random pushes (`environment.push_*`): what `push_wrench` draws (None: push_force = 0)
         self._push = push_cfg(config, self.cm, config.training.seed)
+        # the episode time limit (`environment.episode_length`; 0: none): applied behind every step, every episode cut at the same length (no stagger)
+        self._limit = nat.TimeLimitCfg(length=int(config.environment.episode_length), stagger=0, rank=0, reserved=0, seed=int(config.training.seed) & 0xFFFFFFFFFFFFFFFF)
         self._have_reset = False
         self._camera_name = config.visualization.camera_name
         self._renderer = None
@@ -172,7 +175,9 @@ class HumanoidEnv:
     def step(self, env_state: EnvState, action: Any, rng: Any = None, *, xfrc: Any = None) -> EnvState:
         """`xfrc` (extension; Brax: `pipeline_state.xfrc_applied`): [N, 6] external wrench per environment - force, then torque, world axes, at the
         centre of mass of the body `environment.push_body` (default: body 1, the first root; read whatever `environment.push_force` is) - held for the
-        whole step (`mppo_env_step_xfrc`)."""
+        whole step (`mppo_env_step_xfrc`).  With `environment.episode_length` > 0 an environment whose episode reaches that many steps is truncated
+        (`mppo_env_time_limit`): `done` and the metrics as for an ended episode, its state and observation those of the reset (or, under reset noise,
+        of a fresh noisy one), and `truncation` says which environments those were."""
         t = self.torch
         if not self._have_reset:
             self.reset(num_envs=1)
@@ -197,12 +202,17 @@ class HumanoidEnv:
         else:
             self.lib.env_step(self._model, N, self._n_frames, C.byref(self._rc), state.data_ptr(), self._reset_rec.data_ptr(), action.data_ptr(),
                               self._action_size, obs.data_ptr(), self.dims.obs_pad, reward.data_ptr(), done.data_ptr(), C.byref(ms), self._stream())
+        truncated = None
+        if self._limit.length > 0:  # in front of the masked reinit: its mask `done` then includes the truncated environments
+            truncated = t.empty(N, dtype=t.uint8, device=self.device)
+            self.lib.env_time_limit(self._model, N, C.byref(self._limit), state.data_ptr(), self._reset_rec.data_ptr(), obs.data_ptr(), self.dims.obs_pad,
+                                    done.data_ptr(), truncated.data_ptr(), C.byref(ms), self._stream())
         if noise is not None:  # env.py:166,179-180: the environments that ended restart from `_get_reset_state(rng)`, not from the constant record
             impl, keys = noise
             self.lib.env_reinit(self._model, N, state.data_ptr(), obs.data_ptr(), self.dims.obs_pad, done.data_ptr(), float(self.reset_noise_scale), impl, 0, 0,
                                 keys.data_ptr(), 0, 0, self._stream())
             self._noise_keep = keys
-        return EnvState(state, obs[:, :self.observation_size], reward, done.bool(), m)
+        return EnvState(state, obs[:, :self.observation_size], reward, done.bool(), m, None if truncated is None else truncated.bool())
 
     def push_wrench(self, step: int, num_envs: int, seed: Optional[int] = None) -> Any:
         """The wrench [num_envs, 6] the random pushes of `environment.push_force / push_interval / push_duration` put on the environments at env step

@@ -18,6 +18,13 @@ Under random pushes (`environment.push_force` > 0 with `push_interval`, `push_du
 environments that never fell - is the robustness figure two standing policies are compared by.  The wrench of any (environment, step) is
 `minppo_amd.jaxrng.push_wrench_philox(seed, 0, step, num_envs, push_force, push_interval, push_duration)[environment]`.  The result, its JSON line
 and the trajectory file are what they are without pushes.
+
+Under an episode time limit (`environment.episode_length` = L > 0) the call goes through `mppo_evaluate_limit`: an environment whose episode
+reaches L steps is truncated and restarts, as in training (without the stagger).  The episode statistics then include the truncated episodes, and the
+result - and its JSON line - gain `truncated_episodes` (the episodes the limit cut) and `falls` (the episodes that ended in a fall: `episodes` minus those);
+`survivors` is the number of environments that never FELL (without a limit that is the same thing as "none of its episodes ended") and
+`survivor_mean_return` is null (a survivor's return is spread over its truncated episodes, which `mean_return` already covers).  The trajectory's
+`done` column includes the truncations.
 """
 
 from __future__ import annotations
@@ -59,6 +66,8 @@ class EvalResult:
     survivor_mean_return: float
     mean_reward: float
     steps: int
+    truncated_episodes: Optional[int] = None  # under an episode time limit only (None without one: the statistics' key set is then what it always was)
+    falls: Optional[int] = None
     trajectory: Optional[Dict[str, np.ndarray]] = None
     dt: float = _NAN      # seconds per environment step (the model's timestep x n_frames): what a viewer needs beside the trajectory
     n_frames: int = 1
@@ -68,6 +77,9 @@ class EvalResult:
         d = asdict(self)
         for k in ("trajectory", "dt", "n_frames"):
             d.pop(k)
+        for k in ("truncated_episodes", "falls"):
+            if d[k] is None:
+                d.pop(k)
         return d
 
 
@@ -137,14 +149,22 @@ def eval_cfg(config: Config, **overrides: Any) -> nat.EvalCfg:
 
 
 def run(lib: nat.Lib, xp: str, device: Any, stream: Any, model: C.c_void_p, dims: nat.ModelDims, net: nat.Net, params_dev: Any,
-        ecfg: nat.EvalCfg, obs_norm: Optional[Dict[str, Any]] = None, push: Optional[nat.PushCfg] = None) -> EvalResult:
+        ecfg: nat.EvalCfg, obs_norm: Optional[Dict[str, Any]] = None, push: Optional[nat.PushCfg] = None, episode_length: int = 0) -> EvalResult:
     """One `mppo_evaluate` on an open model and parameters already in device memory (`Trainer.evaluate` comes in here); with `obs_norm`
     ({"mean", "inv_std", "clip"}) one `mppo_evaluate_obs_norm`: the policy reads observations normalised with that table; with `push`
-    (`train.push_cfg`: random pushes, with or without a table) one `mppo_evaluate_push`."""
+    (`train.push_cfg`: random pushes, with or without a table) one `mppo_evaluate_push`; with `episode_length` > 0 (an episode time limit, with or
+    without either) one `mppo_evaluate_limit`."""
     table, clip = obs_norm_table(obs_norm, dims.obs_dim)
+    limited = int(episode_length) > 0
+    if int(episode_length) < 0:
+        raise ValueError(f"evaluate: episode_length = {episode_length!r} cannot be negative")
+    res_bytes = C.sizeof(nat.EvalResultRaw)  # (under a limit the second result lies behind the first in the same allocation)
 
     def call(ws, res, traj, s):
-        if push is not None:
+        if limited:
+            lib.evaluate_limit(model, C.byref(net), nat.ptr(params_dev), C.byref(ecfg), nat.ptr(ws), need, nat.ptr(table_dev), clip,
+                               C.byref(push) if push is not None else None, int(episode_length), nat.ptr(res), nat.ptr(res) + res_bytes, nat.ptr(traj), s)
+        elif push is not None:
             lib.evaluate_push(model, C.byref(net), nat.ptr(params_dev), C.byref(ecfg), nat.ptr(ws), need, nat.ptr(table_dev), clip, C.byref(push), nat.ptr(res),
                               nat.ptr(traj), s)
         elif table is None:
@@ -152,7 +172,7 @@ def run(lib: nat.Lib, xp: str, device: Any, stream: Any, model: C.c_void_p, dims
         else:
             lib.evaluate_obs_norm(model, C.byref(net), nat.ptr(params_dev), C.byref(ecfg), nat.ptr(ws), need, nat.ptr(table_dev), clip, nat.ptr(res), nat.ptr(traj), s)
 
-    need = int(lib.eval_ws_bytes(model, C.byref(net), C.byref(ecfg)))
+    need = int((lib.eval_limit_ws_bytes if limited else lib.eval_ws_bytes)(model, C.byref(net), C.byref(ecfg)))
     if need == 0:  # the arguments are ones mppo_evaluate refuses: let it say why
         lib.evaluate(model, C.byref(net), nat.ptr(params_dev), C.byref(ecfg), None, 0, None, None, None)
     K, R, nq, nv, A = ecfg.K, ecfg.record_envs, dims.nq, dims.nv, net.A
@@ -165,7 +185,7 @@ def run(lib: nat.Lib, xp: str, device: Any, stream: Any, model: C.c_void_p, dims
             o = (-raw.data_ptr()) % 256
             return raw[o:o + nbytes]
 
-        ws, res = alloc(need), alloc(C.sizeof(nat.EvalResultRaw))
+        ws, res = alloc(need), alloc(res_bytes + C.sizeof(nat.EvalLimitResultRaw))
         table_dev = torch.from_numpy(table).to(device) if table is not None else None
         traj = alloc((K + 1) * R * W * 4).view(torch.float32).reshape(K + 1, R, W) if R > 0 else None
         with torch.cuda.device(device):
@@ -181,11 +201,17 @@ def run(lib: nat.Lib, xp: str, device: Any, stream: Any, model: C.c_void_p, dims
             o = (-raw.ctypes.data) % 256
             return raw[o:o + nbytes]
 
-        ws, res_host = alloc(need), alloc(C.sizeof(nat.EvalResultRaw))
+        ws, res_host = alloc(need), alloc(res_bytes + C.sizeof(nat.EvalLimitResultRaw))
         traj_host = alloc((K + 1) * R * W * 4).view(np.float32).reshape(K + 1, R, W) if R > 0 else None
         table_dev = table
         call(ws, res_host, traj_host, None)
-    out = result_from_struct(nat.EvalResultRaw.from_buffer_copy(res_host.tobytes()), split_trajectory(traj_host, nq, nv, A) if traj_host is not None else None)
+    out = result_from_struct(nat.EvalResultRaw.from_buffer_copy(res_host.tobytes()[:res_bytes]), split_trajectory(traj_host, nq, nv, A) if traj_host is not None else None)
+    if limited:
+        extra = nat.EvalLimitResultRaw.from_buffer_copy(res_host.tobytes()[res_bytes:])
+        out.truncated_episodes = int(extra.truncated_episodes)
+        out.falls = out.episodes - out.truncated_episodes
+        out.survivors = int(ecfg.N) - int(extra.fallen_envs)  # the environments that never fell
+        out.survivor_mean_return = _NAN
     out.dt, out.n_frames = float(dims.timestep) * ecfg.n_frames, int(ecfg.n_frames)
     return out
 
@@ -225,7 +251,8 @@ def evaluate(config: Config, params: Any, *, lib: Optional[nat.Lib] = None, xp: 
             obs_norm = params.get("obs_norm")
         flat = _flat_params(params, dims.obs_dim, dims.nu, config.model.hidden_size, L)
         params_dev = torch.from_numpy(flat).to(device) if torch is not None else np.ascontiguousarray(flat)
-        result = run(lib, xp, device, stream, model, dims, net, params_dev, ecfg, obs_norm=obs_norm, push=push_cfg(config, cm, ecfg.seed))
+        result = run(lib, xp, device, stream, model, dims, net, params_dev, ecfg, obs_norm=obs_norm, push=push_cfg(config, cm, ecfg.seed),
+                     episode_length=int(config.environment.episode_length))
     finally:
         if torch is not None:
             torch.cuda.synchronize(device)

@@ -213,3 +213,19 @@ def push_wrench_philox(seed: int, rank: int, step: int, num_envs: int, force: fl
     out = np.zeros((num_envs, 6), np.float32)
     out[:, :2] = np.where(on[:, None], np.maximum(lo, f * (hi - lo) + lo).astype(np.float32), np.float32(0.0))
     return out
+
+
+_LIMIT_STREAM = 0x4C494D4954 << 24  # "LIMIT": the Philox stream of the episode time limit's stagger (csrc/limit.h kStreamLimit)
+
+
+def time_limit_first_philox(seed: int, rank: int, n: int, L: int) -> np.ndarray:
+    """The length at which the staggered episode time limit (`environment.episode_length` = L with `episode_length_stagger`) cuts the FIRST episode of each
+    of a rank's `n` local environments (csrc/limit.h limit_first, bit for bit what `mppo_env_time_limit` tests): with S = "LIMIT" << 24 + (rank << 16),
+    first_k = 1 + word0(philox((k, 0xFFFFFFFE, lo(S), hi(S)), seed)) mod L - every one in 1 .. L; every later episode is cut at L -> int64 [n]."""
+    if not L >= 1:
+        raise ValueError(f"time limit: episode length {L}")
+    k = np.arange(n, dtype=np.uint64)
+    st = _LIMIT_STREAM + (int(rank) << 16)
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    w = _philox4x32(k, np.full_like(k, 0xFFFFFFFE), np.full_like(k, st & 0xFFFFFFFF), np.full_like(k, st >> 32), seed & 0xFFFFFFFF, seed >> 32)[0]
+    return (1 + (w.astype(np.uint64) & np.uint64(0xFFFFFFFF)) % np.uint64(L)).astype(np.int64)

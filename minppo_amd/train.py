@@ -177,7 +177,7 @@ def tree_to_flat(tree: dict, O: int, A: int, H: int, L: int = 2) -> np.ndarray:
 
 _REGION_DTYPES = {
     "count": "int32", "done": "uint8", "perm": "int32", "adv_sums": "float64", "episode_lengths": "int32",
-    "returned_episode_lengths": "int32", "timestep": "int32", "returned_episode": "uint8", "jax_rng": "int32", "reset_rng": "int32",
+    "returned_episode_lengths": "int32", "timestep": "int32", "returned_episode": "uint8", "truncated": "uint8", "jax_rng": "int32", "reset_rng": "int32",
     "obs_norm_stats": "float64", "obs_norm_partials": "float64", "reward_norm_stats": "float64", "reward_norm_partials": "float64",
 }
 
@@ -338,6 +338,11 @@ class Trainer:
         self.push = push_cfg(config, self.cm, self.seed, rank)  # (seed and rank are the engine configuration's: the engine reads its own)
         if self.push is not None:
             self.lib.engine_set_push(self._engine, C.byref(self.push))
+        # environment.episode_length (the episode time limit): 0 leaves every launch as it is.  The staggered first limit is a function of
+        # (seed, rank, environment) and what it is compared with - "timestep", "episode_lengths" - is in checkpoints already: checkpoint / resume needs nothing new
+        self.episode_length = int(config.environment.episode_length)  # (make_config refuses a negative one; so does the engine)
+        if self.episode_length > 0:
+            self.lib.engine_set_time_limit(self._engine, self.episode_length, 1 if config.environment.episode_length_stagger else 0)
         # training.normalize_observations: off leaves the engine's launch sequence as it is
         self.obs_norm_clip, self.obs_norm_eps = float(tr.obs_norm_clip), float(tr.obs_norm_eps)
         if self.obs_norm_on:
@@ -908,22 +913,28 @@ class Trainer:
         ecfg = ev.eval_cfg(self.config, **overrides)
         return ev.run(self.lib, self.xp, self.device, self.stream, self._model, self.dims, self.net, self.region("params"), ecfg,
                       obs_norm=None if on is None else {"mean": on["table"][0], "inv_std": on["table"][1], "clip": on["clip"]},
-                      push=push_cfg(self.config, self.cm, ecfg.seed))  # (environment.push_force > 0: the evaluation is pushed as the training was)
+                      push=push_cfg(self.config, self.cm, ecfg.seed),  # (environment.push_force > 0: the evaluation is pushed as the training was)
+                      episode_length=self.episode_length)  # (environment.episode_length > 0: ... and truncated as the training was)
 
     def rollout_stats(self, reduce: bool = False) -> Dict[str, float]:
         """Device-side reduction of the last rollout's `EnvMetrics` history (`env.py:183-194`, `train.py:170,283`):
         mean reward per env-step, fraction of done steps, number of episodes that ended, and the mean return / length
         of those episodes (`returned_episode_returns / _lengths` at the steps where `returned_episode` is set).
+        Under an episode time limit (`environment.episode_length` > 0) the episodes include the truncated ones and the key "truncated" counts them.
         `reduce=True` sums over the ranks first (a collective)."""
         self._sync()
-        s = self._to_host(self.region("rollout_stats")).astype(np.float64)[:4]
+        full = self._to_host(self.region("rollout_stats")).astype(np.float64)
+        s = np.concatenate([full[:4], full[6:7]]) if self.episode_length > 0 else full[:4]
         n = float(self.T * self.N)
         if reduce and self.world_size > 1:
             s = self._allreduce_host(s)
             n *= self.world_size
         ep = float(s[1])
-        return {"mean_reward": float(s[0]) / n, "done_fraction": ep / n, "episodes": ep,
-                "mean_episode_return": float(s[2]) / ep if ep > 0 else 0.0, "mean_episode_length": float(s[3]) / ep if ep > 0 else 0.0}
+        out = {"mean_reward": float(s[0]) / n, "done_fraction": ep / n, "episodes": ep,
+               "mean_episode_return": float(s[2]) / ep if ep > 0 else 0.0, "mean_episode_length": float(s[3]) / ep if ep > 0 else 0.0}
+        if self.episode_length > 0:
+            out["truncated"] = float(s[4])
+        return out
 
     def losses(self, reduce: bool = False) -> np.ndarray:
         """[E, M, 4] = (total, value, actor, entropy) of every minibatch of the last update.  With more than one rank
@@ -1026,7 +1037,7 @@ def make_train(config: Config, **trainer_kwargs: Any) -> Callable[[Any], TrainOu
                     tr.check_peers()  # (the statistics below synchronise anyway) a dead peer ends the job here, not as silent garbage
                 st, lo = tr.rollout_stats(reduce=True), tr.losses(reduce=True).reshape(-1, 4).mean(0)
                 for k, v in st.items():
-                    metrics[k].append(v)
+                    metrics.setdefault(k, []).append(v)  # ("truncated" is there only under an episode time limit)
                 for k, v in zip(("total_loss", "value_loss", "actor_loss", "entropy"), lo):
                     metrics[k].append(float(v))
                 sps = (u + 1 - first) * tr.T * tr.N * tr.world_size / (time.time() - t0)

@@ -56,6 +56,7 @@ constexpr unsigned kEnvKernelTag = (unsigned)sizeof(ModelView) * 2654435761u ^ (
 // k_physics.hip: the instantiation compiled for these dims (its index in spec_dims.inc; -1: none), whether a build added it (MPPO_SPECIALIZE), its launch (-1: run-time-sized)
 int find_spec(const BlobDims& d);
 bool spec_is_extra(int spec);
-int32_t launch_env_spec(int spec, const ModelView& mv, const EnvArgs& a, const PhysLds& lds, int lds_bytes, int blocks, int waves, hipStream_t stream);
+bool spec_has_split(int spec);  // the instantiation has a split step (KMODE 5), which launch_env_spec picks for small launches unless `may_split` is false
+int32_t launch_env_spec(int spec, const ModelView& mv, const EnvArgs& a, const PhysLds& lds, int lds_bytes, int blocks, int waves, bool may_split, hipStream_t stream);
 
 }  // namespace mppo

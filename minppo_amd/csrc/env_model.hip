@@ -12,6 +12,7 @@ struct mppo_model {
   int lds_bytes;
   int waves;  // wavefronts per workgroup (mv.epw environments each: 4, fewer for a very large robot; one copy of the model tables per workgroup)
   int spec;  // index into the table of model-specialised kernels (spec_dims.inc), -1: the run-time-sized kernel
+  bool no_split = false;  // keep the specialised step unsplit whatever the launch's size (spec_self_check compares both forms; a form that failed it is not used)
   // the records of the matrices a large robot keeps out of LDS (PhysLds::gwords floats per environment group of the grid), for launches
   // through mppo_env_reset / _step / mppo_physics_forward: owned by the handle, grown on demand (the engine passes a region of its arena
   // instead).  One stream at a time may launch through a handle that needs them.
@@ -63,7 +64,7 @@ static int32_t launch_env(const mppo_model_t* m, EnvArgs a, hipStream_t stream, 
     MPPO_CHECK_HIP(hipModuleLaunchKernel(m->jit_fn[env_kernel_index(a)], blocks, 1, 1, 64 * m->waves, 1, 1, m->lds_bytes, stream, params, nullptr));
     return MPPO_OK;
   }
-  return launch_env_spec(m->spec, m->mv, a, m->lds, m->lds_bytes, blocks, m->waves, stream);
+  return launch_env_spec(m->spec, m->mv, a, m->lds, m->lds_bytes, blocks, m->waves, !m->no_split, stream);
 }
 // the engine's entry: mppo_env_step with the out-of-LDS matrices in a region of the engine's arena (hipGraph capture: nothing is allocated)
 int32_t env_step_ws(const mppo_model_t* m, int32_t N, int32_t n_frames, const mppo_reward_cfg_t* rc, float* state, const float* reset_rec, const float* action,
@@ -207,7 +208,7 @@ static int32_t spec_self_check(mppo_model* m) {
   const size_t words = nstate + v.rec_dim + nobs + (size_t)steps * nact + N + N;  // state, reset record, observation, controls, reward, done
   float* dev = nullptr;
   MPPO_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&dev), words * sizeof(float)));
-  std::vector<float> act((size_t)steps * nact), got[2];
+  std::vector<float> act((size_t)steps * nact), got[3];
   unsigned lcg = 12345u;
   for (float& x : act) { lcg = lcg * 1664525u + 1013904223u; x = ((lcg >> 8) & 0xffff) / 32768.f - 1.f; }
   float *state = dev, *reset_rec = state + nstate, *obs = reset_rec + v.rec_dim, *actd = obs + nobs, *rew = actd + (size_t)steps * nact;
@@ -217,8 +218,13 @@ static int32_t spec_self_check(mppo_model* m) {
   mppo_model generic = *m;
   generic.spec = -1; generic.jit = false; generic.scratch = nullptr; generic.scratch_bytes = 0;
   int32_t st = finalize_layout(&generic);
-  for (int which = 0; which < 2 && st == MPPO_OK; ++which) {
-    const mppo_model* mm = which == 0 ? m : &generic;
+  // (an instantiation with a split step runs these 24 environments split - one wave per SIMD at the most: launch_env_spec - so it is run once more unsplit;
+  // BOTH forms are held to the run-time-sized kernel)
+  const bool has_split = m->spec >= 0 && !m->jit && !m->no_split && spec_has_split(m->spec);
+  mppo_model unsplit = *m;
+  unsplit.no_split = true; unsplit.scratch = nullptr; unsplit.scratch_bytes = 0;
+  for (int which = 0; which < (has_split ? 3 : 2) && st == MPPO_OK; ++which) {
+    const mppo_model* mm = which == 0 ? m : which == 1 ? &generic : &unsplit;
     hipError_t he = hipMemset(dev, 0, words * sizeof(float));
     if (he == hipSuccess) he = hipMemcpy(actd, act.data(), act.size() * sizeof(float), hipMemcpyHostToDevice);
     if (he != hipSuccess) { st = fail(MPPO_EHIP, "specialised-kernel self-check: %s", hipGetErrorString(he)); break; }
@@ -233,7 +239,16 @@ static int32_t spec_self_check(mppo_model* m) {
   }
   (void)hipFree(dev);
   if (generic.scratch) (void)hipFree(generic.scratch);
+  if (unsplit.scratch) (void)hipFree(unsplit.scratch);
   if (st != MPPO_OK) return st;
+  if (has_split && memcmp(got[0].data(), got[1].data(), words * sizeof(float)) != 0 && memcmp(got[2].data(), got[1].data(), words * sizeof(float)) == 0) {
+    // the split step alone differs: the model keeps its specialised kernel, unsplit at every size
+    fprintf(stderr, "minppo_amd: the split form of the environment step specialised for this robot (nv %d, %d bodies, %d contact slots) differs from the run-time-sized kernel "
+                    "after a reset and %d steps of %d environments on this device: NOT used - the unsplit form, which agrees, runs at every size.\n", v.nv, v.nbody, v.ncon, steps, N);
+    m->no_split = true;
+    return MPPO_OK;
+  }
+  if (has_split && memcmp(got[2].data(), got[1].data(), words * sizeof(float)) != 0) got[0] = got[2];  // (the unsplit form differs: reported and handled below)
   // (the controls are the same bytes in both; everything else is the kernels' output)
   if (memcmp(got[0].data(), got[1].data(), words * sizeof(float)) != 0) {
     size_t bad = 0;

@@ -63,6 +63,20 @@ __device__ __forceinline__ float reset_noise(const EnvArgs& a, int env, unsigned
 #else
 #define GSYNC() do { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup"); __builtin_amdgcn_wave_barrier(); } while (0)
 #endif
+// ... and the split step's (KMODE 5) rendezvous of the two waves that share an environment group: a workgroup barrier, at the top level of the frame - both
+// waves meet the same ones on every path.  (The emulator's __syncthreads() only yields to the next fiber, which serves workgroup-uniform code; the two roles
+// run different code between their meetings, so there the arrivals are counted: workgroups run one after another in one thread.)
+#ifdef MPPO_EMU
+inline void emu_wg_sync() {
+  static int arrived = 0, round = 0;
+  const int mine = round;
+  if (++arrived == (int)blockDim.x) { arrived = 0; ++round; }
+  do { __syncthreads(); } while (round == mine);  // (the last to arrive yields too: the fibers of a wave leave in one round of the scheduler, as they came)
+}
+#define WGSYNC() emu_wg_sync()
+#else
+#define WGSYNC() __syncthreads()
+#endif
 #define FOR_G(i, n) for (int i = g; i < (n); i += kGroupLanes)
 #ifndef MPPO_DOT_UNROLL_RT
 #define MPPO_DOT_UNROLL_RT 8
@@ -670,10 +684,18 @@ struct StaticModel {
 // MODE (EnvArgs::mode) is a template parameter too: the step kernel carries neither the probe's 17 output pointers nor its stores.
 // KMODE: 0 reset, 1 step, 2 probe; 3 / 4: the step / the probe under an external wrench (EnvArgs::push_body > 0) - instantiations of their own, so that the kernels
 // 0 .. 2 hold no instruction of the wrench's and are, but for the offsets behind the grown EnvArgs, the kernels they were before it existed
+// KMODE 5: the SPLIT step - the step (KMODE 1) of one environment group run by a workgroup of two waves, which share the group's LDS record (the layout
+// make_phys_lds gives with `split`) and meet at WGSYNC(), four times a frame:
+//   wave 0: state, kinematics, contact geometry, cinert / cdof | crb, factor M                   | qacc_smooth, row parameters, solver      |       | integrator .. epilogue
+//   wave 1:                                                    | com_vel .. qfrc_smooth, J rows  | factor M + h D (the loop's trip 1)       | Euler |
+// Trip t of the factorisation loop is run by wave t: ONE copy of that code, as in every other form, and the arithmetic of every phase is the unsplit step's,
+// term by term - only WHICH wave issues it changes (tests/test_env_split.py: bit-equal to the run-time-sized and to the unsplit kernel).  `role` is wave-uniform;
+// within a role SYNC() stays the wave barrier it is.  In every other instantiation SPLIT is a compile-time false and each `r0` / `r1` below a compile-time true.
 template <class SD, int KMODE>
 __global__ void __launch_bounds__(64 * kMaxWavesPerBlock) env_kernel(ModelView mv, EnvArgs a, PhysLds Prt) {
-  constexpr int MODE = KMODE >= 3 ? KMODE - 2 : KMODE;
-  constexpr bool pushed = KMODE >= 3;
+  constexpr bool SPLIT = KMODE == 5;
+  constexpr int MODE = SPLIT ? 1 : KMODE >= 3 ? KMODE - 2 : KMODE;
+  constexpr bool pushed = !SPLIT && KMODE >= 3;
   constexpr BlobDims kSD = SD::dims();
   constexpr BlobOffsets kSO = blob_offsets(kSD);
   constexpr bool kDims = SD::kStatic;
@@ -681,7 +703,8 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerBlock) env_kernel(ModelView m
   constexpr bool kRegChol = kDims && kSD.nv <= kRegCholMaxNv;
   constexpr int kNefc = nefc_of(kSD);
   constexpr int kSpill = kDims ? spill_for(kSD, kRegChol, kSO.words) : 0;
-  constexpr PhysLds kSP = make_phys_lds(kSD, kRegChol, kSpill);
+  static_assert(!SPLIT || split_compiled(kSD, kDims, kSO.words), "the split step: a model-specialised kernel with its factors in registers, every matrix in LDS, one wave per workgroup");
+  constexpr PhysLds kSP = make_phys_lds(kSD, kRegChol, kSpill, SPLIT);
   const PhysLds P = SD::kStatic ? kSP : Prt;
   constexpr int NV = kDims ? kSD.nv : 0;
   constexpr int kDotU = dot_unroll(NV);
@@ -691,8 +714,11 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerBlock) env_kernel(ModelView m
   const int row = (tid & 63) / kGroupLanes;                 // DPP row inside the wave
   // environments per wave: four; a run-time-sized kernel carries two or one when the robot's working set is too large for four (mppo_model_open)
   const int epw = kDims ? kEnvsPerWave : mv.epw;
-  const int el = (tid >> 6) * epw + row;          // environment inside the workgroup
-  int env = blockIdx.x * ((int)(blockDim.x >> 6) * epw) + el;  // the launch chooses the waves per workgroup (launch_env)
+  // (split step: the two waves of the workgroup carry the SAME four environments)
+  const int role = SPLIT ? wave_uniform(tid >> 6) : 0;
+  const bool r0 = !SPLIT || role == 0, r1 = !SPLIT || role == 1;
+  const int el = SPLIT ? row : (tid >> 6) * epw + row;          // environment inside the workgroup
+  int env = SPLIT ? blockIdx.x * epw + el : blockIdx.x * ((int)(blockDim.x >> 6) * epw) + el;  // the launch chooses the waves per workgroup (launch_env)
   // (the rule of kFlagAsBallot below for a per-lane flag that crosses divergent code, applied to the reset's mask: the instantiations that spill vector registers
   // carry it as the wave's ballot)
   constexpr bool kMaskAsBallot = MODE == 0 && kRegChol && kDims && kSD.nv > 2 * kGroupLanes;
@@ -782,8 +808,10 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerBlock) env_kernel(ModelView m
   PT(0);
   // ---- P0: load the state ------------------------------------------------------------------
   if (MODE == 1) {
+    if (r0) {
     FOR_G(i, nq) qpos[i] = rec[i];
     FOR_G(i, nv) { qvel[i] = rec[nq + i]; warm[i] = rec[OP + i]; }
+    }
   } else if (MODE == 0) {
     if (a.noise_scale > 0.f) {  // (uniform: a launch is noisy or it is not)
       const unsigned event = (a.noise_ctr ? (unsigned)a.noise_ctr[0] : 0u) * (unsigned)a.noise_ctr_mul + (unsigned)a.noise_ctr_add;  // (modulo 2^32: no signed overflow)
@@ -804,7 +832,7 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerBlock) env_kernel(ModelView m
   }
   // pre-step quantities the reward needs (env.py:212-217, 222)
   float pre_p0 = 0.f, pre_z = 0.f, pre_comx = 0.f, time_in = 0.f;
-  if (MODE == 1) {
+  if (MODE == 1 && r0) {
     float s = 0.f;
     FOR_G(i, nq) { const float d = TF(qpos0)[i] - rec[i]; s += d * d; }
     pre_p0 = sqrtf(group16_sum(s));
@@ -814,7 +842,7 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerBlock) env_kernel(ModelView m
   }
   // observation = the PRE-step record (env.py:163, quirk C-5): copied out before anything of the new record is written (cinert and
   // cvel of the new state go to the record in the middle of the step); the reset observation replaces it at the end when done
-  if (MODE == 1) {
+  if (MODE == 1 && r0) {
     constexpr int kChunk = 32;  // (one memory round trip for observations of up to 512 words)
     for (int i0 = g; i0 < OP; i0 += kGroupLanes * kChunk) {
       float old[kChunk];
@@ -840,6 +868,7 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerBlock) env_kernel(ModelView m
   const int frames = MODE == 1 ? a.n_frames : 1;
   for (int frame = 0; frame < frames; ++frame) {
     PT(1);
+    if (r0) {  // (split step: wave 0 alone, up to the fork)
     if (g == 0) { st3(xpos, {0.f, 0.f, 0.f}); st4(xquat, {1.f, 0.f, 0.f, 0.f}); }  // the world body (region A1 is rewritten by every frame)
     // the controls: they share the storage of a solver vector (t1, first written in the CG loop), so every frame reads them again
     if (MODE == 1) { FOR_G(i, nu) ctrl[i] = a.action[(size_t)env * a.act_ld + i]; }
@@ -1179,6 +1208,8 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerBlock) env_kernel(ModelView m
     if (spM) { for (int w = g; w < nvq * nv; w += kGroupLanes) Mq[w] = make_float4(0.f, 0.f, 0.f, 0.f); }
     else FOR_G(i, nv) for (int k = 0; k < nv; ++k) M[i * ldm + k] = 0.f;
     if (spM) GSYNC(); else SYNC();
+    }
+    if (SPLIT) WGSYNC();  // the fork: qpos, qvel, ctrl, the contact geometry, cinert and cdof are there for wave 1 (whose last frame's reads are behind it)
     if (pushed) {
       // ---- the external wrench (MJX support.xfrc_accumulate in fwd_acceleration): its generalised force per dof -----------------
       // qfrc[d] = cdof[d] . (torque + (xipos[b] - subtree_com[root(b)]) x force, force) for the dofs of body b and of its ancestors, 0 for every other.
@@ -1216,7 +1247,7 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerBlock) env_kernel(ModelView m
     }
     PT(4);
     // ---- crb: composite inertia over the subtree mask, dense M ------------------------------------
-    FOR_G(i, nv) {
+    if (r0) FOR_G(i, nv) {
       const int bi = TI(dof_bodyid)[i];
       float crb[10];
       for (int k = 0; k < 10; ++k) crb[k] = 0.f;
@@ -1281,10 +1312,11 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerBlock) env_kernel(ModelView m
       else { (void)eul_c; solve_tri<NV>(LL, nv, bvec, tmp, x, g); }
     };
     _Pragma("unroll 1") for (int pass = 0; pass < 2; ++pass) {
+    if (!SPLIT || role == pass) {  // (split step: trip t is wave t's - wave 0 factors M beside the dynamics, wave 1 factors M + h D beside the solver)
     if (kRegChol) {
       const int ldc = P.ldc;
       const bool eul = pass == 1;
-      float* col = t0;  // the column being eliminated, all rows (t0 is free here)
+      float* col = SPLIT ? S + P.ccol : t0;  // the column being eliminated, all rows (t0 is free here; split step: the solver has t0 in trip 1)
       float c[RC][NVc];
       _Pragma("unroll") for (int q = 0; q < RC; ++q) {
         const int i = ir[q];
@@ -1431,8 +1463,12 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerBlock) env_kernel(ModelView m
       }
     }
     SYNC();
-    if (pass == 1) break;  // M + h D is factored: on to the integrator
+    }
+    if (!SPLIT && pass == 1) break;  // M + h D is factored: on to the integrator
     PT(7);
+    // (split step: the dynamics and the constraint rows are wave 1's, beside wave 0's trip 0; what follows the join is wave 0's, beside wave 1's trip 1)
+    const bool dyn = !SPLIT || (pass == 0 && role == 1), sol = !SPLIT || (pass == 1 && role == 0);
+    if (dyn) {
     // ================= fwd_velocity: com_vel, passive, rne (closed forms over ancestor masks) =======
     FOR_G(b, nb) {
       float v[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
@@ -1572,22 +1608,26 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerBlock) env_kernel(ModelView m
       if (a.probe.cvel) FOR_G(i, nb * 6) a.probe.cvel[(size_t)env * nb * 6 + i] = cvel[i];
     }
     SYNC();  // cfrc / cdofdot / cvel (region A3) and cinert are dead from here: the Jacobian (A4) may overwrite them
+    }
     PT(9);
-    solveL(std::false_type{}, qfs, t0, qas);  // fwd_acceleration: qacc_smooth = M^-1 qfrc_smooth
+    if (!SPLIT) solveL(std::false_type{}, qfs, t0, qas);  // fwd_acceleration: qacc_smooth = M^-1 qfrc_smooth  (split step: after the join, below - wave 0 holds the factor)
     PT(10);
     // ================= make_constraint ===================================================================
     // Rows: nlim joint limits, then four pyramid rows per contact slot.  A limit row has ONE non-zero entry (+-1 at the joint's
     // dof): it is kept as that sign (dsgn, per dof; 0 = no active limit) and its row index (drow), and only the contact rows are
     // a dense [4 ncon][nv] matrix in LDS.  Products with the limit rows are written out where they occur; they equal what the
     // dense row gave bit for bit (the other terms of that row's sum were exact zeros).
+    if (dyn) {
     if (!spJ) FOR_G(r, 4 * ncon) for (int k = 0; k < nv; ++k) J[r * ldj + k] = 0.f;
     FOR_G(i, nv) dlim[i] = 0;
     if (has_ball) FOR_G(i, nv) lcoef[i] = 0.f;
+    }
     // Jacobian in global memory (large robots): per contact slot the set of dofs its rows touch - the ancestors of its one or two bodies -
     // if the contact is active, else none; the rows are written and read through these sets only (every other entry is an exact zero)
     u64* jmask = reinterpret_cast<u64*>(S + P.jmask);
     float4* Jc = reinterpret_cast<float4*>(G + (spJ ? P.gJc : 0));  // [ncon][nv]: (rows 4 c .. 4 c + 3) of dof d
     float4* Jq = reinterpret_cast<float4*>(G + (spJ ? P.gJq : 0));  // [nvq][4 ncon]: (dofs 4 q .. 4 q + 3) of row r
+    if (dyn) {
     if (spJ) {
       FOR_G(c, ncon) {
         u64 m = TU(body_ancdof_mask)[TI(con_bodyid)[c]];
@@ -1626,6 +1666,7 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerBlock) env_kernel(ModelView m
       jv[r] = act ? pos : 0.f;               // pos, parked in jv until the row parameters are built
       jaref[r] = act ? TF(dof_invweight0)[da] : 0.f;  // invweight, parked in jaref
     }
+    }
     // the four pyramid rows of contact c at dof d (false: the dof moves neither body - the entries are zeros)
     auto contact_rows = [&](int c, int d, float* r4) -> bool {
       // translational Jacobian of the contact point: body 2 minus body 1 (body 1 = world for a ground contact)
@@ -1652,6 +1693,7 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerBlock) env_kernel(ModelView m
       }
       return any;
     };
+    if (dyn) {
     if (spJ) {
       const int nv4 = 4 * nvq, R = 4 * ncon;
       for (int item = g; item < ncon * nv4; item += kGroupLanes) {  // (contact, dof) per item, the last quad's padding included
@@ -1720,10 +1762,12 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerBlock) env_kernel(ModelView m
         jaref[nlim + 4 * c + k] = act ? iw : 0.f;
       }
     }
+    }
     // equality rows: a dense row each (Je: LDS after the contact rows, or the record in global memory with the contact Jacobian).
     // connect: jacp(p1, body1) - jacp(p2, body2), component k of the world frame; joint: +1 at dof1, -dpoly/dq2 at dof2
     float* Je = has_eq ? (spJ ? G + P.gJe : S + P.Je) : nullptr;
     const int ldje = spJ ? nv : ldj;
+    if (dyn) {
     if (has_eq) {
       for (int item = g; item < neq * nv; item += kGroupLanes) {
         const int r = item / nv, d = item - r * nv;
@@ -1775,6 +1819,18 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerBlock) env_kernel(ModelView m
       }
     }
     if (spJ) GSYNC(); else SYNC();
+    }
+    if (SPLIT) {
+      // the first join: qfrc_smooth, the Jacobian and the rows' parked values are wave 1's, M's factor is in wave 0's registers.  The NaN flag of the dynamics
+      // (a per-lane register of wave 1, read by the epilogue on wave 0) crosses through one word of the group's record
+      int* xflag = reinterpret_cast<int*>(S + P.xflag);
+      if (pass == 0) {
+        if (role == 1) { const bool any = group16_any(bad_lane != 0); if (g == 0) *xflag = any ? 1 : 0; }
+        WGSYNC();
+        if (role == 0) bad_lane |= *xflag;
+        continue;
+      }
+    }
     float k_lim, b_lim, k_con, b_con;
     kb_params(TF(limit_solref), TF(limit_solimp), h, k_lim, b_lim);
     kb_params(TF(contact_solref), TF(contact_solimp), h, k_con, b_con);
@@ -1909,6 +1965,8 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerBlock) env_kernel(ModelView m
       eD[r] = act ? 1.f / R : 0.f;
       earef[r] = act ? -b * s - k * imp * pos : 0.f;
     };
+    if (sol) {
+    if (SPLIT) solveL(std::false_type{}, qfs, t0, qas);  // (the unsplit step's qacc_smooth, in front of make_constraint above: the two are independent)
     FOR_G(r, nefc) row_params(r, jrow_dot(r, qvel));
     SYNC();
     PT(11);
@@ -2149,13 +2207,17 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerBlock) env_kernel(ModelView m
     // ================= euler: implicit damping, semi-implicit integration ====================================
     FOR_G(i, nv) t1[i] = qfs[i] + qfc[i];
     SYNC();
+    }
+    if (SPLIT) WGSYNC();  // the second join: the solver's right-hand side is there, and so is the factor of M + h D - in wave 1's registers
     }  // (factorisation trips)
     if (MODE == 0) break;
-    solveL(std::true_type{}, t1, t0, mvv);  // mvv = (M + h D)^-1 (qfrc_smooth + qfrc_constraint)
+    if (r1) solveL(std::true_type{}, t1, t0, mvv);  // mvv = (M + h D)^-1 (qfrc_smooth + qfrc_constraint)
+    if (SPLIT) WGSYNC();  // the third: wave 0 integrates
     if (MODE == 2) {
       if (valid && a.probe.qacc_euler) FOR_G(i, nv) a.probe.qacc_euler[(size_t)env * nv + i] = mvv[i];
       break;
     }
+    if (!r0) continue;  // (split step: wave 1 goes to the next frame's fork)
     FOR_G(i, nv) { qvel[i] += h * mvv[i]; warm[i] = qacc[i]; }  // qacc_warmstart <- solver qacc
     SYNC();
     FOR_G(j, njnt) {
@@ -2179,6 +2241,7 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerBlock) env_kernel(ModelView m
   }
 
   if (MODE == 2) return;
+  if (!r0) return;  // (split step: the epilogue is wave 0's)
 
   PT(22);
   // ================= epilogue: observation, reward, done, auto-reset, metrics, new record ====================
@@ -2284,8 +2347,46 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerBlock) env_kernel(ModelView m
 
 // host side: the instantiations and their launch (the model handle and the C ABI: env_model.hip)
 namespace mppo {
+// compute units of the current device (the split step's selection rule, model_view.h split_launch); the emulator stands for a device of kEmuCus
+constexpr int kEmuCus = 4;
+static int device_cus() {
+#ifdef MPPO_EMU
+  return kEmuCus;
+#else
+  static int cached[64] = {};  // (0: not asked yet; a race writes the same value twice)
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 0;
+  if (cached[dev] == 0) {
+    int n = 0;
+    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) return 0;
+    cached[dev] = n;
+  }
+  return cached[dev];
+#endif
+}
+
 template <class SD>
-static int32_t launch_env_t(const ModelView& mv, const EnvArgs& a, const PhysLds& lds, int lds_bytes, int blocks, int waves, hipStream_t stream) {
+static int32_t launch_env_t(const ModelView& mv, const EnvArgs& a, const PhysLds& lds, int lds_bytes, int blocks, int waves, bool may_split, hipStream_t stream) {
+#ifndef MPPO_JIT_ONLY  // (an attached code object runs unsplit: mppo_model_attach_kernel knows the five unsplit kernels)
+  if constexpr (split_compiled(SD::dims(), SD::kStatic, blob_offsets(SD::dims()).words)) {
+    // the split step: an unpushed step whose launch would put at most one wave on a SIMD - one two-wave workgroup per environment group, the split layout
+    if (may_split && a.mode == 1 && !(a.push_body > 0) && waves == 1 && mv.epw == kEnvsPerWave && split_launch(a.N, device_cus())) {
+      constexpr PhysLds kSplit = make_phys_lds(SD::dims(), true, 0, true);
+      const int bytes = (mv.blob_words + kSplit.total * kEnvsPerWave) * 4;
+      if (bytes * kSplitWgPerCu <= kLdsPerCu) {
+        void (*kern)(ModelView, EnvArgs, PhysLds) = &env_kernel<SD, 5>;
+        static thread_local int attr = 64 * 1024;
+        if (bytes > attr) {
+          MPPO_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+          attr = bytes;
+        }
+        hipLaunchKernelGGL(kern, dim3((a.N + kEnvsPerWave - 1) / kEnvsPerWave), dim3(128), bytes, stream, mv, a, kSplit);
+        MPPO_CHECK_LAUNCH("env_kernel (split)");
+        return MPPO_OK;
+      }
+    }
+  }
+#endif
   const int k = env_kernel_index(a);  // (a pushed step / probe is a kernel of its own: env_kernel's KMODE)
   void (*kern)(ModelView, EnvArgs, PhysLds) = k == 0 ? &env_kernel<SD, 0> : k == 1 ? &env_kernel<SD, 1> : k == 2 ? &env_kernel<SD, 2> : k == 3 ? &env_kernel<SD, 3> : &env_kernel<SD, 4>;
   // (the run-time-sized instantiation serves robots of different sizes: the limit follows the largest one seen)
@@ -2301,12 +2402,14 @@ static int32_t launch_env_t(const ModelView& mv, const EnvArgs& a, const PhysLds
 
 struct SpecEntry {
   BlobDims d;
-  int32_t (*launch)(const ModelView&, const EnvArgs&, const PhysLds&, int, int, int, hipStream_t);
+  int32_t (*launch)(const ModelView&, const EnvArgs&, const PhysLds&, int, int, int, bool, hipStream_t);
+  bool split;  // the split step is compiled for these dims (model_view.h split_compiled)
   bool extra;  // added by MPPO_SPECIALIZE for this build: not one of the instantiations the test suite holds bit-equal to the run-time-sized
                // kernel on both backends - mppo_model_open checks it against that kernel on the device before trusting it (spec_self_check)
 };
-#define MPPO_SPEC(...) {BlobDims{__VA_ARGS__}, &launch_env_t<StaticModel<__VA_ARGS__>>, false},
-#define MPPO_SPEC_EXTRA(...) {BlobDims{__VA_ARGS__}, &launch_env_t<StaticModel<__VA_ARGS__>>, true},
+#define MPPO_SPEC_SPLIT(...) split_compiled(BlobDims{__VA_ARGS__}, true, blob_offsets(BlobDims{__VA_ARGS__}).words)
+#define MPPO_SPEC(...) {BlobDims{__VA_ARGS__}, &launch_env_t<StaticModel<__VA_ARGS__>>, MPPO_SPEC_SPLIT(__VA_ARGS__), false},
+#define MPPO_SPEC_EXTRA(...) {BlobDims{__VA_ARGS__}, &launch_env_t<StaticModel<__VA_ARGS__>>, MPPO_SPEC_SPLIT(__VA_ARGS__), true},
 // (MPPO_SPEC_INC: minppo_amd/jit.py compiles this file once more, device side only, with a list of ONE robot - the code object
 // mppo_model_attach_kernel takes)
 #ifndef MPPO_SPEC_INC
@@ -2314,7 +2417,7 @@ struct SpecEntry {
 #endif
 static const SpecEntry kSpecs[] = {
 #include MPPO_SPEC_INC
-    {BlobDims{}, nullptr, false}};
+    {BlobDims{}, nullptr, false, false}};
 #undef MPPO_SPEC
 #undef MPPO_SPEC_EXTRA
 
@@ -2323,11 +2426,12 @@ int find_spec(const BlobDims& d) {
   return -1;
 }
 bool spec_is_extra(int spec) { return kSpecs[spec].extra; }
-int32_t launch_env_spec(int spec, const ModelView& mv, const EnvArgs& a, const PhysLds& lds, int lds_bytes, int blocks, int waves, hipStream_t stream) {
+bool spec_has_split(int spec) { return kSpecs[spec].split; }
+int32_t launch_env_spec(int spec, const ModelView& mv, const EnvArgs& a, const PhysLds& lds, int lds_bytes, int blocks, int waves, bool may_split, hipStream_t stream) {
 #ifdef MPPO_JIT_ONLY  // (the device-side compile of minppo_amd/jit.py: one robot's instantiation and nothing else)
-  return kSpecs[0].launch(mv, a, lds, lds_bytes, blocks, waves, stream);
+  return kSpecs[0].launch(mv, a, lds, lds_bytes, blocks, waves, may_split, stream);
 #else
-  return (spec >= 0 ? kSpecs[spec].launch : mv.nball > 0 ? &launch_env_t<RuntimeBallModel> : &launch_env_t<RuntimeModel>)(mv, a, lds, lds_bytes, blocks, waves, stream);
+  return (spec >= 0 ? kSpecs[spec].launch : mv.nball > 0 ? &launch_env_t<RuntimeBallModel> : &launch_env_t<RuntimeModel>)(mv, a, lds, lds_bytes, blocks, waves, may_split, stream);
 #endif
 }
 }  // namespace mppo

@@ -224,12 +224,15 @@ struct PhysLds {
   // memory (gJe) when the contact Jacobian is there too; eqpos: per row, the world points p1, p2 of its connect (written while the poses of
   // region A1 are alive, read by make_constraint; region B's first lifetime)
   int Je, gJe, eqpos;
+  // the split step (k_physics.hip: an environment group run by TWO waves): the factorisation's column buffer (the solver's t0 serves the unsplit forms) and
+  // the word through which the NaN flag of the wave that runs the dynamics reaches the wave that ends the step; 0 in every other layout
+  int ccol, xflag;
 };
 constexpr int kSpillJ = 1, kSpillM = 2;
 
 __host__ __device__ constexpr inline int imax_(int a, int b) { return a > b ? a : b; }
 
-__host__ __device__ constexpr inline PhysLds make_phys_lds(const BlobDims& d, bool li_regs, int spill) {
+__host__ __device__ constexpr inline PhysLds make_phys_lds(const BlobDims& d, bool li_regs, int spill, bool split = false) {
   const int nq = d.nq, nv = d.nv, nbody = d.nbody, njnt = d.njnt, ncon = d.ncon, nefc = nefc_of(d), nroot = d.nroot, ncvx = d.ncvx, neq = d.neq, nball = d.nball;
   PhysLds p{};
   int o = 0;
@@ -249,7 +252,8 @@ __host__ __device__ constexpr inline PhysLds make_phys_lds(const BlobDims& d, bo
   const int rows0 = o;
   p.D = take(ne); p.aref = take(ne); p.jaref = take(ne); p.jv = take(ne); p.force = p.jv;
   const int rows1 = o;
-  o = rows0; p.cinert = take(10 * nbody); o = imax_(o, rows1);
+  if (split) { p.cinert = take(10 * nbody); }  // (split step: crb reads cinert on one wave while make_constraint writes the rows' vectors on the other)
+  else { o = rows0; p.cinert = take(10 * nbody); o = imax_(o, rows1); }
   p.cvxsel = take(12 * ncvx); p.cvxok = take(4 * ncvx);
   p.jmask = (p.spill & kSpillJ) ? take((nv > 64 ? 4 : 2) * ncon) : 0;  // (a 64-bit word per slot; beyond 64 dofs a second block: dofs 64..127)
   // region B, two lifetimes: the dynamics' cdof and the contact geometry, dead once the Jacobian is built | the solver's nv-vectors,
@@ -264,11 +268,16 @@ __host__ __device__ constexpr inline PhysLds make_phys_lds(const BlobDims& d, bo
   p.xpos = take(3 * nbody); p.xquat = take(4 * nbody); p.xipos = take(3 * nbody); p.xanchor = take(3 * njnt); p.xaxis = take(3 * njnt);
   int end = o;
   p.ldc = (nv + 3) & ~3;
-  o = p.A; p.C = take(li_regs ? imax_(nv * imax_(p.ldm, p.ldc), 2 * ntri) : ntri); end = imax_(end, o);
+  if (!split) { o = p.A; p.C = take(li_regs ? imax_(nv * imax_(p.ldm, p.ldc), 2 * ntri) : ntri); end = imax_(end, o); }
   o = p.A; p.cdofdot = take(6 * nv); p.cfrc = take(6 * nbody); p.cvel = take(6 * nbody); end = imax_(end, o);
   p.ldj = nv + 1;
   o = p.A; p.J = (p.spill & kSpillJ) ? o : take((ncon > 0 ? 4 * ncon : 1) * p.ldj);
   p.Je = (p.spill & kSpillJ) ? o : take(neq * p.ldj); end = imax_(end, o);
+  if (split) {
+    // the work copy is alive beside A3 / A4 (trip 0: one wave factors M while the other runs the dynamics and builds the Jacobian; trip 1: it factors
+    // M + h D while the solver runs on J and its vectors): a region of its own behind region A, with its column buffer and the flag word
+    o = end; p.C = take(li_regs ? imax_(nv * imax_(p.ldm, p.ldc), 2 * ntri) : ntri); p.ccol = take(nv); p.xflag = take(1); end = o;
+  }
   {
     const int nvq = (nv + 3) / 4;
     int go = 0;
@@ -338,5 +347,30 @@ constexpr int kRegCholMaxNv = MPPO_REGCHOL_MAX_NV;   // model-specialised kernel
 constexpr int kEnvsPerWave = MPPO_ENVS_PER_WAVE;     // 1, 2 or 4
 constexpr int kMaxWavesPerBlock = 4;                 // the number of waves per workgroup is chosen per model (mppo_model_open): the most
                                                      // waves per CU that 160 KB of LDS hold, one copy of the model tables per workgroup
+// ... that choice (the smaller workgroup on a tie), as a function of the table part's and an environment's words in LDS
+__host__ __device__ constexpr inline int waves_per_block_for(long long blob_words, long long env_words, int epw) {
+  int best = 1, best_per_cu = 0;
+  for (int w = 1; w <= kMaxWavesPerBlock; ++w) {
+    const long long bytes = (blob_words + env_words * epw * w) * 4;
+    const int per_cu = bytes <= kLdsPerCu ? (int)(kLdsPerCu / bytes) * w : 0;
+    if (per_cu > best_per_cu) { best = w; best_per_cu = per_cu; }
+  }
+  return best;
+}
+
+// The split step (k_physics.hip, env_kernel's KMODE 5): an environment group - four environments, 16 lanes each - is run by a workgroup of TWO waves that
+// share the group's LDS record and divide the step's phases between them.  Compiled for the model-specialised kernels that keep the Cholesky factors in
+// registers, hold every matrix in LDS and run one wave per workgroup (the 16-dof stand-in); launched where the unsplit form would put at most one wave on a
+// SIMD (split_launch).  kSplitWgPerCu workgroups stay resident on a CU, as with the unsplit form.
+constexpr int kSplitWgPerCu = 4;
+__host__ __device__ constexpr inline bool split_compiled(const BlobDims& d, bool is_static, int blob_words) {
+  // (beyond 32 dofs a kernel spills vector registers and carries its per-lane flags as ballots: k_physics.hip kFlagAsBallot - not a candidate)
+  if (!is_static || d.nv > kRegCholMaxNv || d.nv > 2 * kGroupLanes || kEnvsPerWave != 4) return false;
+  if (spill_for(d, true, blob_words) != 0) return false;
+  if (waves_per_block_for(blob_words, make_phys_lds(d, true, 0).total, kEnvsPerWave) != 1) return false;
+  return ((long long)blob_words + (long long)make_phys_lds(d, true, 0, true).total * kEnvsPerWave) * 4 * kSplitWgPerCu <= kLdsPerCu;
+}
+// at most one wave per SIMD (four SIMDs per CU) without the split: the second wave fills the gaps of the first; beyond that two full waves per SIMD already do
+__host__ __device__ constexpr inline bool split_launch(int N, int cus) { return (N + kEnvsPerWave - 1) / kEnvsPerWave <= 4 * cus; }
 
 }  // namespace mppo

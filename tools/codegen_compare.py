@@ -105,7 +105,8 @@ flags = "-ffp-contract=off" if env else "-ffp-contract=fast"
 print(f"# {KERNELS.replace('|', ', ')} instantiations of {SOURCE}.hip, parent commit against this tree: hipcc --offload-arch=gfx950 -O3 -std=c++17 {flags}")
 print("# --cuda-device-only -S -Rpass-analysis=kernel-resource-usage; instruction streams compared line by line after dropping comments and")
 print("# renumbering local labels.")
-same = {0: [0, 0], 1: [0, 0], 2: [0, 0]}
+MODES = ("reset", "step", "probe", "pushed step", "pushed probe", "split step")  # env_kernel's KMODE
+same = {m: [0, 0] for m in range(len(MODES))}
 matched = set()
 for n in sorted(old, key=label):
     d = dims(n)
@@ -126,7 +127,8 @@ for n in sorted(set(new) - matched, key=label):
     print(f"{label(n)} (new)\n   new   : {len(new[n])} instructions/directives  {short(rn.get(n, {}))}")
 if env:
     for mode, (s, t) in same.items():
-        print(f"# mode {mode} ({('reset', 'step', 'probe')[mode]}): {s} of {t} instantiations identical to the parent's (kernel-argument offsets aside)")
+        if t:
+            print(f"# mode {mode} ({MODES[mode]}): {s} of {t} instantiations identical to the parent's (kernel-argument offsets aside)")
     print("# scratch bytes per lane, every env_kernel of the new tree:", sorted({rn[n].get("ScratchSize [bytes/lane]") for n in rn if "env_kernel" in n}))
 else:
     print(f"# {same[0][0]} of {same[0][1]} instantiations identical to the parent's (kernel-argument offsets aside)")

@@ -225,6 +225,57 @@ typedef struct mppo_time_limit_cfg {
 int32_t mppo_env_time_limit(const mppo_model_t* m, int32_t N, const mppo_time_limit_cfg_t* cfg, float* state, const float* reset_rec, float* obs, int32_t obs_ld,
                             uint8_t* done, uint8_t* truncated, const mppo_env_metrics_t* metrics, void* stream);
 
+/* ---- domain randomisation: per-environment friction, actuator gain, payload ------------------------------------------------------
+ * The reference has none (every environment is the one robot of the MJCF file).  legged_gym (`randomize_friction`, `randomize_base_mass`, motor strength),
+ * MuJoCo Playground and Brax (`domain_randomize`: `geom_friction`, `actuator_gainprm` / `biasprm`, `body_mass` written into a vmapped model) randomise the
+ * physical parameters of each environment; so does this (csrc/domrand.h, k_domrand.hip).  Environment n owns the row
+ *     p_n = (friction_scale, actuator_scale, added_mass, 0)
+ * of a table `domain` [N][4] floats in DEVICE memory, fixed for the whole run, and behaves IN EVERY BIT as the unrandomised entry points behave on the
+ * model whose tables are replaced, in float32:
+ *     con_friction[3c]   <- con_friction[3c] * friction_scale    for every contact slot c (mixing is a max: every geom's sliding friction scaled)
+ *     act_gain[u]        <- act_gain[u] * actuator_scale         for every actuator
+ *     act_bias[3u + k]   <- act_bias[3u + k] * actuator_scale    k = 0 .. 2, for every actuator NOT on a ball joint (a ball joint's motor keeps its gear there)
+ *     body_mass[b]       <- body_mass[b] + added_mass            for the one body b = mass_body (body_inertia stays: a point payload at the centre of mass)
+ * Force and control ranges and the joints' actuatorfrcrange are not scaled (a stronger motor saturates where it did); nothing derived at compile time
+ * (dof_invweight0, body_invweight0, meaninertia) is recomputed - what `domain_randomize` does when it writes body_mass and geom_friction into an mjx.Model.
+ * The row (1, 1, 0, .) changes no bit.  A randomised launch runs kernel instantiations of its own (csrc/env_kernel.h); every other launch runs the kernels
+ * it always ran.
+ *
+ * The draw is stateless - a function of (seed, rank, environment) alone; nothing is added to the state record or to a checkpoint, a resumed run has the
+ * same robots.  With S = ("DRAND" << 24) + (rank << 16), for local environment n:
+ *     r = philox(counter = {n, 0xFFFFFFFD, lo(S), hi(S)}, key = seed)
+ *     friction_scale = uniform(r.x, friction_min, friction_max); actuator_scale = uniform(r.y, actuator_min, actuator_max); added_mass = uniform(r.z, mass_min, mass_max)
+ * bits -> float as in mppo_env_reinit; min == max gives exactly that value (host statement: minppo_amd/jaxrng.py domain_params_philox).  Philox under both
+ * rng_impl values (the reference has no such stream).  Refused (MPPO_EINVAL, the message names the value): min > max, a negative friction or actuator
+ * scale, a range that is not finite, rank outside 0 .. 255, and - wherever a model is at hand - mass_body outside 1 .. nbody - 1 and
+ * body_mass[mass_body] + mass_min <= 0; a null table where one is required.
+ *
+ * mppo_domain_fill         : writes domain [N][4] (device).  One launch, no workspace; mass_body is not read (there is no model to check it against).
+ * mppo_env_reset_domain    : mppo_env_reset and mppo_env_reinit in one, under a table: the reset kernel with the environment's own row.  mask = NULL: every
+ *                        environment (state, and - each may be NULL - reset_rec = environment 0's record, obs, reward, done, metrics as mppo_env_reset writes
+ *                        them); mask given: the environments it names, state and observation rows only, as mppo_env_reinit.  scale > 0: reset noise, drawn as
+ *                        mppo_env_reinit draws it (rng_impl, seed, rank, key2, counter, counter_offset as there); scale = 0: the plain reset of each robot.
+ *                        Under randomisation the one shared reset record is wrong for every environment but the one it came from: every restart goes through
+ *                        this entry point over the step's `done` (the engine and the evaluator do so), which overwrites what the step copied.
+ * mppo_env_step_domain     : mppo_env_step_xfrc's arguments plus the table.  xfrc may be NULL (push_body is then not read).
+ * mppo_physics_forward_domain : mppo_physics_forward_xfrc's arguments plus the table; cinert, qM, qfrc_actuator, the rows and everything behind them are those
+ *                        of the environment's own robot. */
+typedef struct mppo_domain_cfg {
+  float friction_min, friction_max, actuator_min, actuator_max, mass_min, mass_max;
+  int32_t mass_body;
+  uint64_t seed;
+  int32_t rank;
+} mppo_domain_cfg_t;
+int32_t mppo_domain_fill(const mppo_domain_cfg_t* cfg, int32_t N, float* domain, void* stream);
+int32_t mppo_env_reset_domain(const mppo_model_t* m, int32_t N, float* state, float* reset_rec, float* obs, int32_t obs_ld, float* reward, uint8_t* done,
+                              const mppo_env_metrics_t* metrics, const uint8_t* mask, const float* domain, int32_t mass_body, float scale, int32_t rng_impl,
+                              uint64_t seed, int32_t rank, const uint32_t* key2, const int32_t* counter, int32_t counter_offset, void* stream);
+int32_t mppo_env_step_domain(const mppo_model_t* m, int32_t N, int32_t n_frames, const mppo_reward_cfg_t* rc, float* state, const float* reset_rec,
+                             const float* action, int32_t act_ld, float* obs, int32_t obs_ld, float* reward, uint8_t* done, const mppo_env_metrics_t* metrics,
+                             int32_t push_body, const float* xfrc, const float* domain, int32_t mass_body, void* stream);
+int32_t mppo_physics_forward_domain(const mppo_model_t* m, int32_t N, const float* qpos, const float* qvel, const float* ctrl, const float* qacc_warmstart,
+                                    const mppo_forward_probe_t* out, int32_t push_body, const float* xfrc, const float* domain, int32_t mass_body, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * PPO stages
  * ---------------------------------------------------------------------------------------- */
@@ -558,6 +609,17 @@ int32_t mppo_engine_set_push(mppo_engine_t* e, const mppo_push_cfg_t* push);
  * the number of truncations of the rollout (0 without a limit).  Reward scaling needs nothing: its carry restarts behind every `done`.  Call before
  * mppo_engine_reset, mppo_engine_prepare and the first mppo_engine_update: afterwards it returns MPPO_ESTATE.  MPPO_EINVAL: a negative length. */
 int32_t mppo_engine_set_time_limit(mppo_engine_t* e, int32_t length, int32_t stagger);
+/* Domain randomisation during training (mppo_domain_cfg_t above; NULL or every range at its identity - friction and actuator 1 .. 1, mass 0 .. 0, the default:
+ * no table is allocated and the engine enqueues exactly the launches, with exactly the arguments, it enqueues without this call).  Otherwise the engine
+ * allocates the table [N][4] (its own device allocation, not a region of the arena: the arena's layout and a checkpoint are what they were - the table is a
+ * function of seed and rank, so a resumed run that makes this call again has the same robots), fills it once here, and passes it to every reset, step and
+ * re-initialisation launch, in the captured graph too: mppo_engine_reset is mppo_env_reset_domain (then, under reset noise, the same masked over everyone),
+ * every rollout step mppo_env_step_domain - with the pushes drawn inside it as before - followed by mppo_env_reset_domain over done[t] (truncations included;
+ * at scale 0 when reset noise is off: one launch per rollout step that an unrandomised run without reset noise does not have).  The split step is not used.
+ * `seed` and `rank` of the configuration are NOT read: the engine configuration's are used - every rank randomises its own environments from its own stream,
+ * nothing crosses ranks, any world_size is allowed.  Call before mppo_engine_reset, mppo_engine_prepare and the first mppo_engine_update: afterwards it
+ * returns MPPO_ESTATE.  MPPO_EINVAL: the refusals listed at mppo_domain_cfg_t. */
+int32_t mppo_engine_set_domain(mppo_engine_t* e, const mppo_domain_cfg_t* domain);
 /* one full update: T rollout steps, bootstrap value, GAE, E epochs x M minibatches */
 int32_t mppo_engine_update(mppo_engine_t* e, void* stream);
 /* what mppo_engine_update does before it enqueues anything: the one-time capture of the update into a hipGraph (no device work).
@@ -665,6 +727,17 @@ size_t mppo_eval_limit_ws_bytes(const mppo_model_t* m, const mppo_net_t* net, co
 int32_t mppo_evaluate_limit(const mppo_model_t* m, const mppo_net_t* net, const float* params, const mppo_eval_cfg_t* cfg, void* ws, size_t ws_bytes,
                             const float* obs_table, float clip, const mppo_push_cfg_t* push, int32_t episode_length, mppo_eval_result_t* result,
                             mppo_eval_limit_result_t* extra, float* traj, void* stream);
+/* mppo_evaluate_limit under domain randomisation - the robustness sweep: "does this policy still stand at friction 0.3, or with 5 kg on its back?" is one
+ * call with min = max.  domain = NULL or every range at its identity: exactly mppo_evaluate_limit, bytes and launches.  Otherwise the documented sequence with
+ *        mppo_domain_fill(domain with rank 0 and seed = cfg->seed, N, table) in front, mppo_env_reset_domain for the reset (and, under reset noise, for the
+ *        initial states), mppo_env_step_domain for step t, and mppo_env_reset_domain(mask = done, counter_offset = t + 1) behind every step (and behind the time
+ *        limit's launch) whether or not reset noise is on
+ * - the same bits when the caller writes it out.  `seed` and `rank` of the configuration are not read.  `ws`: >= mppo_eval_domain_ws_bytes
+ * (mppo_eval_limit_ws_bytes' regions, then the table), whatever the ranges are.  MPPO_EINVAL: the refusals listed at mppo_domain_cfg_t. */
+size_t mppo_eval_domain_ws_bytes(const mppo_model_t* m, const mppo_net_t* net, const mppo_eval_cfg_t* cfg);
+int32_t mppo_evaluate_domain(const mppo_model_t* m, const mppo_net_t* net, const float* params, const mppo_eval_cfg_t* cfg, void* ws, size_t ws_bytes,
+                             const float* obs_table, float clip, const mppo_push_cfg_t* push, int32_t episode_length, const mppo_domain_cfg_t* domain,
+                             mppo_eval_result_t* result, mppo_eval_limit_result_t* extra, float* traj, void* stream);
 int32_t mppo_eval_limit_count(int32_t N, int32_t first, const uint8_t* done, const uint8_t* truncated, void* acc, void* stream);
 int32_t mppo_eval_limit_reduce(int32_t N, const void* acc, mppo_eval_limit_result_t* result, void* stream);
 

@@ -104,6 +104,11 @@ class EvalLimitResultRaw(C.Structure):  # mppo_eval_limit_result_t
     _fields_ = [("truncated_episodes", C.c_int64), ("fallen_envs", C.c_int64)]
 
 
+class DomainCfg(C.Structure):  # mppo_domain_cfg_t: domain randomisation (every range at its identity - 1 .. 1, 1 .. 1, 0 .. 0: off)
+    _fields_ = [(n, c_f) for n in ("friction_min", "friction_max", "actuator_min", "actuator_max", "mass_min", "mass_max")] + [
+        ("mass_body", c_i32), ("seed", c_u64), ("rank", c_i32)]
+
+
 class SceneDims(C.Structure):
     _fields_ = [(n, c_i32) for n in ("nq", "nbody", "ngeom", "ncam", "has_plane")]
 
@@ -138,6 +143,12 @@ SIGNATURES = {
     "mppo_push_fill": (c_i32, [P(PushCfg), c_i32, c_vp, c_i32, c_i32, c_vp, c_vp]),
     "mppo_env_time_limit": (c_i32, [c_vp, c_i32, P(TimeLimitCfg), c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, P(EnvMetrics), c_vp]),
     "mppo_gae_truncated": (c_i32, [c_i32, c_i32, c_f, c_f, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "mppo_domain_fill": (c_i32, [P(DomainCfg), c_i32, c_vp, c_vp]),
+    "mppo_env_reset_domain": (c_i32, [c_vp, c_i32, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, P(EnvMetrics), c_vp, c_vp, c_i32, c_f, c_i32, c_u64, c_i32, c_vp, c_vp,
+                                      c_i32, c_vp]),
+    "mppo_env_step_domain": (c_i32, [c_vp, c_i32, c_i32, P(RewardCfg), c_vp, c_vp, c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, P(EnvMetrics), c_i32, c_vp, c_vp,
+                                     c_i32, c_vp]),
+    "mppo_physics_forward_domain": (c_i32, [c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, P(ForwardProbe), c_i32, c_vp, c_vp, c_i32, c_vp]),
     "mppo_param_count": (c_sz, [P(Net)]),
     "mppo_policy_ws_bytes": (c_sz, [P(Net), c_i32]),
     "mppo_policy_forward": (c_i32, [P(Net), c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
@@ -192,6 +203,7 @@ SIGNATURES = {
     "mppo_engine_set_reward_norm": (c_i32, [c_vp, c_i32, c_f, c_f]),
     "mppo_engine_set_push": (c_i32, [c_vp, P(PushCfg)]),
     "mppo_engine_set_time_limit": (c_i32, [c_vp, c_i32, c_i32]),
+    "mppo_engine_set_domain": (c_i32, [c_vp, P(DomainCfg)]),
     "mppo_engine_update": (c_i32, [c_vp, c_vp]),
     "mppo_engine_prepare": (c_i32, [c_vp, c_vp]),
     "mppo_engine_graph_active": (c_i32, [c_vp, P(c_i32)]),
@@ -207,6 +219,8 @@ SIGNATURES = {
     "mppo_evaluate_limit": (c_i32, [c_vp, P(Net), c_vp, P(EvalCfg), c_vp, c_sz, c_vp, c_f, P(PushCfg), c_i32, c_vp, c_vp, c_vp, c_vp]),
     "mppo_eval_limit_count": (c_i32, [c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
     "mppo_eval_limit_reduce": (c_i32, [c_i32, c_vp, c_vp, c_vp]),
+    "mppo_eval_domain_ws_bytes": (c_sz, [c_vp, P(Net), P(EvalCfg)]),
+    "mppo_evaluate_domain": (c_i32, [c_vp, P(Net), c_vp, P(EvalCfg), c_vp, c_sz, c_vp, c_f, P(PushCfg), c_i32, P(DomainCfg), c_vp, c_vp, c_vp, c_vp]),
     "mppo_scene_open": (c_i32, [c_vp, c_sz, c_vp, P(c_vp)]),
     "mppo_scene_close": (c_i32, [c_vp]),
     "mppo_scene_get_dims": (c_i32, [c_vp, P(SceneDims)]),
@@ -214,7 +228,7 @@ SIGNATURES = {
 }
 
 UNCHECKED = {"mppo_last_error", "mppo_abi_version", "mppo_param_count", "mppo_policy_ws_bytes", "mppo_grad_ws_bytes",
-             "mppo_adam_ws_bytes", "mppo_permutation_ws_bytes", "mppo_eval_ws_bytes", "mppo_eval_limit_ws_bytes", "mppo_obs_norm_partials",
+             "mppo_adam_ws_bytes", "mppo_permutation_ws_bytes", "mppo_eval_ws_bytes", "mppo_eval_limit_ws_bytes", "mppo_eval_domain_ws_bytes", "mppo_obs_norm_partials",
              "mppo_reward_norm_partials"}
 
 

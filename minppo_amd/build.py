@@ -38,6 +38,8 @@ FILE_FLAGS["k_rewnorm.hip"] = ["-ffp-contract=off"]
 # (k_push.hip: the pushes' draw `f * (hi - lo) + lo` is a float32 multiply and a float32 add, as the host restatement and the environment kernel - compiled without
 # contraction, above - compute it; fused into one multiply-add the fill kernel's last bit would differ from both)
 FILE_FLAGS["k_push.hip"] = ["-ffp-contract=off"]
+# (k_domrand.hip: the domain randomisation's draw, the same multiply and add - held bit-equal to its host restatement)
+FILE_FLAGS["k_domrand.hip"] = ["-ffp-contract=off"]
 # MPPO_REGCHOL_MAX_NV=32: specialised kernels beyond 32 dofs keep their Cholesky factors in LDS instead of registers (the default, 48, is three
 # matrix rows per lane: fastest, at 400 - 500 registers; the library checks every instantiation MPPO_SPECIALIZE adds against the run-time-sized
 # kernel on the device and falls back if they differ)

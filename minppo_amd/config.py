@@ -80,6 +80,20 @@ class EnvironmentConfig:
     # 1 .. episode_length, so that the batch does not reach the limit in the same step for ever.  0: no limit, nothing changes.  Negative: ValueError.
     episode_length: int = field(default=0)
     episode_length_stagger: bool = field(default=True)
+    # Extension (absent upstream; legged_gym `randomize_friction` / `randomize_base_mass` / motor strength, MuJoCo Playground and Brax `domain_randomize`):
+    # domain randomisation.  Every environment is a robot of its own for the whole run: its sliding friction (every contact) is the model's times a scale
+    # uniform in [friction_scale_min, friction_scale_max], its actuators' gain and bias are the model's times a scale uniform in [actuator_scale_min,
+    # actuator_scale_max] (force and control ranges stay), and `added_mass_body` (a body name of the model; "": body 1, the first root) carries a point
+    # payload uniform in [added_mass_min, added_mass_max] kg at its centre of mass.  Drawn once per environment from (training.seed, rank,
+    # environment); in training, in `evaluate` - min = max asks "does this policy still stand at friction 0.3?" - and in `HumanoidEnv` / the `env` rollout.
+    # All six at their defaults: off, nothing changes.  min > max or a negative scale: ValueError.
+    friction_scale_min: float = field(default=1.0)
+    friction_scale_max: float = field(default=1.0)
+    actuator_scale_min: float = field(default=1.0)
+    actuator_scale_max: float = field(default=1.0)
+    added_mass_min: float = field(default=0.0)
+    added_mass_max: float = field(default=0.0)
+    added_mass_body: str = field(default="")
 
 
 @dataclass
@@ -312,6 +326,12 @@ def make_config(yaml_dict: dict | None = None, overrides: Sequence[str] = ()) ->
                          "the duration lies in 1 .. push_interval")
     if not env.episode_length >= 0:
         raise ValueError(f"environment.episode_length = {env.episode_length!r}: the time limit is a number of env steps (0: no limit) and cannot be negative")
+    for what in ("friction_scale", "actuator_scale", "added_mass"):
+        lo, hi = getattr(env, what + "_min"), getattr(env, what + "_max")
+        if not lo <= hi:
+            raise ValueError(f"environment.{what}_min = {lo!r} > environment.{what}_max = {hi!r}: the range of the domain randomisation is empty")
+        if what != "added_mass" and not lo >= 0.0:
+            raise ValueError(f"environment.{what}_min = {lo!r}: a scale of the domain randomisation cannot be negative")
     for key in ("obs_norm_clip", "obs_norm_eps", "reward_norm_clip", "reward_norm_eps"):
         if not getattr(cfg.training, key) >= 0.0:
             raise ValueError(f"training.{key} = {getattr(cfg.training, key)!r} cannot be negative")

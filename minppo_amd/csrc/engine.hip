@@ -22,6 +22,7 @@
 #include "obsnorm.h"
 #include "rewnorm.h"
 #include "push.h"
+#include "domrand.h"
 #include "limit.h"
 
 #include <cmath>
@@ -36,9 +37,10 @@ size_t model_scratch_bytes(const mppo_model* m, int N);
 int32_t env_step_ws(const mppo_model_t* m, int32_t N, int32_t n_frames, const mppo_reward_cfg_t* rc, float* state, const float* reset_rec, const float* action,
                     int32_t act_ld, float* obs, int32_t obs_ld, float* reward, uint8_t* done, const mppo_env_metrics_t* metrics, float* ws, size_t ws_bytes, hipStream_t stream);
 int32_t env_reset_ws(const mppo_model_t* m, int32_t N, float* state, float* reset_rec, float* obs, int32_t obs_ld, float* reward, uint8_t* done, const mppo_env_metrics_t* metrics,
-                     float* ws, size_t ws_bytes, hipStream_t stream);
+                     float* ws, size_t ws_bytes, hipStream_t stream, const EnvDomain& dom);
 int32_t env_reinit_ws(const mppo_model_t* m, int32_t N, float* state, float* obs, int32_t obs_ld, const uint8_t* mask, float scale, int32_t rng_impl, uint64_t seed,
-                      int32_t rank, const uint32_t* key2, const int32_t* counter, int32_t counter_mul, int32_t counter_add, float* ws, size_t ws_bytes, hipStream_t stream);
+                      int32_t rank, const uint32_t* key2, const int32_t* counter, int32_t counter_mul, int32_t counter_add, float* ws, size_t ws_bytes, hipStream_t stream,
+                      const EnvDomain& dom);
 
 // end of an update: the Adam step index and the update index move on; `zero` (optional): words another kernel of the update wants back
 // at zero before its next use (the bucket counters of the two-launch permutation, k_perm.hip).  The LAST of those words is that form's
@@ -176,6 +178,9 @@ struct mppo_engine {
   // episode time limit (mppo_engine_set_time_limit; length 0: off - no launch is added, GAE and the statistics are the plain ones)
   mppo::LimitCfg limit;
   unsigned char* truncated;  // [T][N] the samples the limit cut
+  // domain randomisation (mppo_engine_set_domain; table null: off - every launch and every argument is what it was).  The table [N][4] is the engine's own
+  // allocation, not a region of the arena: it is a function of (seed, rank) alone, so a checkpoint does not carry it and the arena's layout is what it always was
+  mppo::EnvDomain domain;
 };
 
 namespace mppo {
@@ -336,7 +341,7 @@ static int32_t do_rollout(mppo_engine* e, hipStream_t s) {
     EnvPush push = e->push;
     push.add = t;
     MPPO_TRY(env_step_push_ws(e->model, e->N, c.n_frames, &c.reward, e->state, e->reset_rec, e->action + t * N * A, e->A, e->obs + (size_t)(t + 1) * N * OP,
-                              e->OP, e->reward + t * N, e->done + t * N, &e->met, push, e->env_ws, e->env_ws_bytes, static_cast<hipStream_t>(s)));                       // :165
+                              e->OP, e->reward + t * N, e->done + t * N, &e->met, push, e->env_ws, e->env_ws_bytes, static_cast<hipStream_t>(s), e->domain));            // :165
     // episode time limit: the environments that have reached it are truncated - flags, metrics, the reset record - as the step's epilogue ends an episode;
     // done[t] then includes them, so the masked reinit below restarts them too and the reward scaling's carry restarts behind them
     if (e->limit.length > 0)
@@ -344,9 +349,11 @@ static int32_t do_rollout(mppo_engine* e, hipStream_t s) {
                                  e->truncated + t * N, e->met, s));
     // reset noise: the environments whose episode ended at this step restart from a randomised state instead of the constant record the step kernel
     // gave them (env.py:166,179-180) - one masked launch of the reset kernel over done[t]; a workgroup without an ended episode leaves at once
-    if (e->reset_noise > 0.f)
+    // (domain randomisation: the one shared reset record is another robot's - every restart goes through the reset kernel with the environment's own row,
+    // at scale 0 when reset noise is off)
+    if (e->reset_noise > 0.f || e->domain.table)
       MPPO_TRY(env_reinit_ws(e->model, e->N, e->state, e->obs + (size_t)(t + 1) * N * OP, e->OP, e->done + t * N, e->reset_noise, c.rng_impl, c.seed, c.rank,
-                             e->reset_rng + 2 * t, e->count + 1, e->T, 1 + t, e->env_ws, e->env_ws_bytes, s));
+                             e->reset_rng + 2 * t, e->count + 1, e->T, 1 + t, e->env_ws, e->env_ws_bytes, s, e->domain));
     // observation normalisation: the new rows are stored normalised with this update's table (the next forward and the learn phase read them so);
     // their raw values go into this step's partial sums first
     if (e->obs_norm)
@@ -498,6 +505,7 @@ extern "C" int32_t mppo_engine_create(const mppo_model_t* m, const mppo_engine_c
   e->reward_norm = false; e->reward_norm_clip = 0.f; e->reward_norm_eps = 0.f;
   e->push = EnvPush{};
   e->limit = LimitCfg{};
+  e->domain = EnvDomain{};
   *out = e;
   return MPPO_OK;
 }
@@ -507,6 +515,7 @@ extern "C" int32_t mppo_engine_destroy(mppo_engine_t* e) {
   if (e->graph) graph_destroy(e->graph);
   if (e->comm) comm_destroy(e->comm);
   if (e->peer) peer_destroy(e->peer);
+  if (e->domain.table) (void)hipFree(const_cast<float*>(e->domain.table));
   delete e;
   return MPPO_OK;
 }
@@ -545,12 +554,12 @@ extern "C" int32_t mppo_engine_reset(mppo_engine_t* e, void* stream) {
   MPPO_CHECK_HIP(hipMemsetAsync(e->adam_v, 0, (size_t)e->P * 4, s));
   MPPO_CHECK_HIP(hipMemsetAsync(e->obs, 0, (size_t)(e->T + 1) * e->N * e->OP * 4, s));
   MPPO_TRY(permutation_batch_prepare(e->B, e->E, e->perm_ws, e->perm_ws_bytes, s));
-  MPPO_TRY(env_reset_ws(e->model, e->N, e->state, e->reset_rec, e->obs, e->OP, nullptr, nullptr, &e->met, e->env_ws, e->env_ws_bytes, static_cast<hipStream_t>(s)));  // train.py:142-144
+  MPPO_TRY(env_reset_ws(e->model, e->N, e->state, e->reset_rec, e->obs, e->OP, nullptr, nullptr, &e->met, e->env_ws, e->env_ws_bytes, static_cast<hipStream_t>(s), e->domain));  // train.py:142-144
   // reset noise: the plain reset above made the noise-free reset record and the zeroed metrics; every environment then starts from a state of its own
   // (event 0 of the Philox stream; the reset key behind the step keys of region "reset_rng" for threefry: the caller writes it before this call)
   if (e->reset_noise > 0.f)
     MPPO_TRY(env_reinit_ws(e->model, e->N, e->state, e->obs, e->OP, nullptr, e->reset_noise, e->cfg.rng_impl, e->cfg.seed, e->cfg.rank, e->reset_rng + 2 * e->T, nullptr, 0, 0,
-                           e->env_ws, e->env_ws_bytes, s));
+                           e->env_ws, e->env_ws_bytes, s, e->domain));
   if (e->obs_norm) {  // nothing counted, the identity table (pad columns included); obs[0] above stays raw
     MPPO_CHECK_HIP(hipMemsetAsync(e->obs_norm_stats, 0, (1 + 2 * (size_t)e->O) * 8, s));
     MPPO_TRY(obs_norm_update_launch(e->O, 0, 0, nullptr, e->obs_norm_stats, e->obs_norm_eps, e->obs_norm_table, e->OP, s));
@@ -628,6 +637,54 @@ extern "C" int32_t mppo_engine_set_push(mppo_engine_t* e, const mppo_push_cfg_t*
     e->push.body = pc.body; e->push.draw = push_draw_of(pc); e->push.ctr = e->count + 1; e->push.mul = e->T;
   }
   return MPPO_OK;
+}
+
+extern "C" int32_t mppo_engine_set_domain(mppo_engine_t* e, const mppo_domain_cfg_t* domain) {
+  MPPO_REQUIRE(e, "mppo_engine_set_domain: null engine");
+  mppo_domain_cfg_t dc{};
+  bool on = false;
+  if (domain) {
+    dc = *domain;
+    dc.seed = e->cfg.seed; dc.rank = e->cfg.rank;  // (the engine's own: one stream per rank, as the pushes and the reset noise have; nothing crosses ranks)
+    on = domain_cfg_on(dc);
+    MPPO_TRY(check_domain_cfg("mppo_engine_set_domain", on ? e->model : nullptr, &dc));
+  }
+  if (e->graph || e->prepared)
+    return fail(MPPO_ESTATE, "mppo_engine_set_domain: the update has been prepared already (its launch sequence is fixed, a captured graph holds it): "
+                             "set the randomisation before mppo_engine_prepare and the first mppo_engine_update");
+  if (e->was_reset)
+    return fail(MPPO_ESTATE, "mppo_engine_set_domain: mppo_engine_reset has run already (the environments hold the initial states of the robots they were): set the randomisation before it");
+  // the table lives on the device the arena is on, whatever the calling thread's current device is (restored on the way out)
+  int cur = -1, dev = -1;
+#ifndef MPPO_EMU
+  {
+    hipPointerAttribute_t attr{};
+    MPPO_CHECK_HIP(hipGetDevice(&cur));
+    MPPO_CHECK_HIP(hipPointerGetAttributes(&attr, e->arena));
+    dev = attr.device;
+    if (dev != cur) MPPO_CHECK_HIP(hipSetDevice(dev));
+  }
+#endif
+  auto back = [&](int32_t rc) {
+#ifndef MPPO_EMU
+    if (dev != cur && cur >= 0) (void)hipSetDevice(cur);
+#endif
+    return rc;
+  };
+  if (e->domain.table) {
+    if (hipDeviceSynchronize() != hipSuccess) return back(fail(MPPO_EHIP, "mppo_engine_set_domain: the device does not synchronise"));
+    (void)hipFree(const_cast<float*>(e->domain.table));
+  }
+  e->domain = EnvDomain{};
+  if (on) {
+    float* table = nullptr;
+    if (hipMalloc(reinterpret_cast<void**>(&table), (size_t)e->N * 16) != hipSuccess) return back(fail(MPPO_EHIP, "mppo_engine_set_domain: no device memory for the table of %d environments", e->N));
+    int32_t rc = domain_fill_launch(dc, e->N, table, nullptr);
+    if (rc == MPPO_OK && hipStreamSynchronize(nullptr) != hipSuccess) rc = fail(MPPO_EHIP, "mppo_engine_set_domain: the fill launch failed");
+    if (rc != MPPO_OK) { (void)hipFree(table); return back(rc); }
+    e->domain = EnvDomain{table, dc.mass_body};
+  }
+  return back(MPPO_OK);
 }
 
 extern "C" int32_t mppo_engine_set_time_limit(mppo_engine_t* e, int32_t length, int32_t stagger) {

@@ -4,6 +4,7 @@
 #include "model_view.h"
 #include "mppo_common.h"
 #include "push.h"
+#include "domrand.h"
 
 namespace mppo {
 
@@ -32,6 +33,13 @@ struct EnvArgs {
   unsigned long long noise_seed, noise_stream;  // philox: the key and the stream id (kStreamReset + (rank << 16))
   const int* noise_ctr;         // philox: the event counter's word in device memory (null: 0) ...
   int noise_ctr_mul, noise_ctr_add;  // ... event = word * mul + add: the engine's update index * T + 1 + t, so that a replayed graph draws fresh values
+  // domain randomisation (domrand.h): row n = (friction_scale, actuator_scale, added_mass, 0) replaces, in float32 and before they are used, con_friction[3c] by
+  // con_friction[3c] * friction_scale, act_gain[u] and (not on a ball joint) act_bias[3u + k] by their products with actuator_scale, body_mass[mass_body] by
+  // body_mass[mass_body] + added_mass.  A launch is randomised (domain non-null) or it is not; a randomised launch runs a kernel instantiation of its own
+  // (env_kernel_index below), any other reads nothing of what follows.  In front of the wrench's fields, which stay the LAST of the struct: the run-time-sized pushed kernels load them together with the first words
+  // of PhysLds, the argument behind this one - anything put between the two would change those kernels' scalar loads, not only their offsets.
+  const float* domain;          // [N][4]; null: the launch is not randomised
+  int mass_body;                // 1 .. nbody - 1: the body that carries the payload
   // modes 1 and 2 only - an external wrench on one body (MJX xfrc_applied: world axes, at the body's centre of mass), constant over the frames of the step.
   // A launch is pushed (push_body > 0: the host sets it when xfrc is given or push.force > 0) or it is not; a pushed launch runs a kernel instantiation of its
   // own (env_kernel_index below), an unpushed one reads nothing of what follows.  Behind everything else, by the rule above.
@@ -42,9 +50,12 @@ struct EnvArgs {
   int push_ctr_mul, push_ctr_add;  // ... step = word * mul + add: the engine's update index * T + t
 };
 
-// the kernel a launch runs (env_kernel's KMODE): its mode, and for a pushed step / probe the instantiation that holds the wrench's code
-constexpr int kEnvKernels = 5;
-inline int env_kernel_index(const EnvArgs& a) { return a.mode >= 1 && a.push_body > 0 ? a.mode + 2 : a.mode; }
+// the kernel a launch runs (env_kernel's KMODE): its mode, and for a pushed step / probe the instantiation that holds the wrench's code; a randomised launch
+// (EnvArgs::domain) runs the randomised family's reset, step or probe (6 .. 8), whose step and probe take a wrench behind a run-time test.  5 is the split step,
+// which launch_env_spec picks by itself: no launch asks for it here.
+constexpr int kEnvKernels = 9;
+constexpr int kEnvKernelRand = 6;
+inline int env_kernel_index(const EnvArgs& a) { return a.domain ? kEnvKernelRand + a.mode : a.mode >= 1 && a.push_body > 0 ? a.mode + 2 : a.mode; }
 
 constexpr unsigned long long kStreamReset = 0x5245534554ull << 24;  // "RESET" (engine.hip: beside kStreamNoise / kStreamPerm)
 

@@ -2,6 +2,7 @@
 #include "env_kernel.h"
 
 #include <algorithm>
+#include <cmath>
 #include <memory>
 #include <string>
 #include <vector>
@@ -24,7 +25,8 @@ struct mppo_model {
   bool jit = false;
   int jit_regchol = 0;  // the MPPO_REGCHOL_MAX_NV the code object was compiled with (its LDS layout follows from it)
   hipModule_t jit_module = nullptr;
-  hipFunction_t jit_fn[mppo::kEnvKernels] = {};  // reset, step, probe, pushed step, pushed probe (env_kernel_index)
+  hipFunction_t jit_fn[mppo::kEnvKernels] = {};  // reset, step, probe, pushed step, pushed probe, (none), randomised reset, step, probe (env_kernel_index)
+  std::vector<float> body_mass;  // the blob's body_mass on the host: what a payload's lower end is checked against (check_domain_cfg)
   std::vector<char> jit_image;
 };
 
@@ -75,6 +77,35 @@ int32_t env_step_ws(const mppo_model_t* m, int32_t N, int32_t n_frames, const mp
   if (metrics) a.met = *metrics;
   return launch_env(m, a, stream, ws, ws_bytes);
 }
+// Domain randomisation.  What every entry point that takes a domain configuration refuses (with a model at hand: the payload's body and the mass it leaves)
+int32_t check_domain_body(const char* who, const mppo_model_t* m, int32_t body) {
+  MPPO_REQUIRE(body >= 1 && body < m->mv.nbody, "%s: mass_body %d outside 1 .. nbody - 1 = %d (0 is the world)", who, body, m->mv.nbody - 1);
+  return MPPO_OK;
+}
+int32_t check_domain_cfg(const char* who, const mppo_model_t* m, const mppo_domain_cfg_t* c) {
+  MPPO_REQUIRE(c->friction_min <= c->friction_max, "%s: friction_min %g > friction_max %g (or not a number)", who, (double)c->friction_min, (double)c->friction_max);
+  MPPO_REQUIRE(c->actuator_min <= c->actuator_max, "%s: actuator_min %g > actuator_max %g (or not a number)", who, (double)c->actuator_min, (double)c->actuator_max);
+  MPPO_REQUIRE(c->mass_min <= c->mass_max, "%s: mass_min %g > mass_max %g (or not a number)", who, (double)c->mass_min, (double)c->mass_max);
+  MPPO_REQUIRE(c->friction_min >= 0.f, "%s: friction_min %g is negative", who, (double)c->friction_min);
+  MPPO_REQUIRE(c->actuator_min >= 0.f, "%s: actuator_min %g is negative", who, (double)c->actuator_min);
+  MPPO_REQUIRE(std::isfinite(c->friction_max) && std::isfinite(c->actuator_max) && std::isfinite(c->mass_min) && std::isfinite(c->mass_max),
+               "%s: a range of the domain randomisation is not finite (friction_max %g, actuator_max %g, mass %g .. %g)", who, (double)c->friction_max, (double)c->actuator_max,
+               (double)c->mass_min, (double)c->mass_max);
+  MPPO_REQUIRE(c->rank >= 0 && c->rank < 256, "%s: rank %d (0 .. 255)", who, c->rank);
+  if (m) {
+    MPPO_TRY(check_domain_body(who, m, c->mass_body));
+    const float m0 = m->body_mass[c->mass_body];
+    MPPO_REQUIRE(m0 + c->mass_min > 0.f, "%s: body %d weighs %g kg: mass_min %g leaves it without mass", who, c->mass_body, (double)m0, (double)c->mass_min);
+  }
+  return MPPO_OK;
+}
+// a launch's randomisation: the table and the payload's body into the kernel's arguments (no table: nothing - the launch runs the kernels it always ran)
+static int32_t set_domain(const mppo_model_t* m, const EnvDomain& dom, EnvArgs* a) {
+  if (!dom.table) return MPPO_OK;
+  MPPO_TRY(check_domain_body("environment kernel", m, dom.body));
+  a->domain = dom.table; a->mass_body = dom.body;
+  return MPPO_OK;
+}
 // Random pushes.  What every entry point that takes a push configuration refuses (the body is checked against the model by the callers that have one)
 int32_t check_push_cfg(const char* who, const mppo_push_cfg_t* p) {
   MPPO_REQUIRE(p->force >= 0.f, "%s: push force %g is negative (or not a number)", who, (double)p->force);
@@ -94,11 +125,12 @@ PushDraw push_draw_of(const mppo_push_cfg_t& p) {
 // env_step_ws under an external wrench (push.xfrc given, or drawn in the kernel when push.draw.force > 0; neither: exactly env_step_ws)
 int32_t env_step_push_ws(const mppo_model_t* m, int32_t N, int32_t n_frames, const mppo_reward_cfg_t* rc, float* state, const float* reset_rec, const float* action,
                          int32_t act_ld, float* obs, int32_t obs_ld, float* reward, uint8_t* done, const mppo_env_metrics_t* metrics, const EnvPush& push, float* ws,
-                         size_t ws_bytes, hipStream_t stream) {
+                         size_t ws_bytes, hipStream_t stream, const EnvDomain& dom) {
   EnvArgs a{};
   a.N = N; a.mode = 1; a.n_frames = n_frames; a.state = state; a.reset_in = reset_rec; a.action = action; a.act_ld = act_ld;
   a.obs = obs; a.obs_ld = obs_ld; a.reward = reward; a.done = done; a.rc = *rc;
   if (metrics) a.met = *metrics;
+  MPPO_TRY(set_domain(m, dom, &a));
   if (push.xfrc || push.draw.force > 0.f) {
     MPPO_TRY(check_push_body("environment step", m, push.body));
     a.push_body = push.body; a.xfrc = push.xfrc;
@@ -107,16 +139,18 @@ int32_t env_step_push_ws(const mppo_model_t* m, int32_t N, int32_t n_frames, con
   return launch_env(m, a, stream, ws, ws_bytes);
 }
 int32_t env_reset_ws(const mppo_model_t* m, int32_t N, float* state, float* reset_rec, float* obs, int32_t obs_ld, float* reward, uint8_t* done, const mppo_env_metrics_t* metrics,
-                     float* ws, size_t ws_bytes, hipStream_t stream) {
+                     float* ws, size_t ws_bytes, hipStream_t stream, const EnvDomain& dom) {
   EnvArgs a{};
   a.N = N; a.mode = 0; a.n_frames = 1; a.state = state; a.reset_out = reset_rec; a.obs = obs; a.obs_ld = obs_ld; a.reward = reward; a.done = done;
   if (metrics) a.met = *metrics;
+  MPPO_TRY(set_domain(m, dom, &a));
   return launch_env(m, a, stream, ws, ws_bytes);
 }
 // the reset from randomised states over the environments `mask` names (null: all of them): the reset kernel with its noise fields set and nothing
 // but the state rows and the observation rows to write - reward, done and the metrics are the step's, the reset record stays the noise-free one
 int32_t env_reinit_ws(const mppo_model_t* m, int32_t N, float* state, float* obs, int32_t obs_ld, const uint8_t* mask, float scale, int32_t rng_impl, uint64_t seed,
-                      int32_t rank, const uint32_t* key2, const int32_t* counter, int32_t counter_mul, int32_t counter_add, float* ws, size_t ws_bytes, hipStream_t stream) {
+                      int32_t rank, const uint32_t* key2, const int32_t* counter, int32_t counter_mul, int32_t counter_add, float* ws, size_t ws_bytes, hipStream_t stream,
+                      const EnvDomain& dom) {
   // (the Philox stream numbers an environment's blocks of four elements in the 16 bits of the stream id below the rank)
   MPPO_REQUIRE(m->mv.nq + m->mv.nv <= 4 * 65536, "reset noise: %d noise elements per environment", m->mv.nq + m->mv.nv);
   EnvArgs a{};
@@ -124,6 +158,7 @@ int32_t env_reinit_ws(const mppo_model_t* m, int32_t N, float* state, float* obs
   a.mask = mask; a.noise_scale = scale; a.noise_impl = rng_impl; a.noise_key = key2; a.noise_seed = seed;
   a.noise_stream = kStreamReset + ((unsigned long long)rank << 16);
   a.noise_ctr = counter; a.noise_ctr_mul = counter_mul; a.noise_ctr_add = counter_add;
+  MPPO_TRY(set_domain(m, dom, &a));
   return launch_env(m, a, stream, ws, ws_bytes);
 }
 
@@ -228,7 +263,7 @@ static int32_t spec_self_check(mppo_model* m) {
     hipError_t he = hipMemset(dev, 0, words * sizeof(float));
     if (he == hipSuccess) he = hipMemcpy(actd, act.data(), act.size() * sizeof(float), hipMemcpyHostToDevice);
     if (he != hipSuccess) { st = fail(MPPO_EHIP, "specialised-kernel self-check: %s", hipGetErrorString(he)); break; }
-    st = env_reset_ws(mm, N, state, reset_rec, obs, v.obs_pad, rew, done, nullptr, nullptr, 0, nullptr);
+    st = env_reset_ws(mm, N, state, reset_rec, obs, v.obs_pad, rew, done, nullptr, nullptr, 0, nullptr, EnvDomain{});
     for (int t = 0; t < steps && st == MPPO_OK; ++t)
       st = env_step_ws(mm, N, 1, &rc, state, reset_rec, actd + (size_t)t * nact, nu, obs, v.obs_pad, rew, done, nullptr, nullptr, 0, nullptr);
     if (st != MPPO_OK) break;
@@ -274,6 +309,10 @@ extern "C" int32_t mppo_model_open(const void* host_blob, size_t nbytes, const v
   BlobDims bd{};
   MPPO_TRY(parse_model_blob(host_blob, nbytes, &m->mv, &bd, &m->canon_words));
   m->mv.blob = static_cast<const int32_t*>(dev_blob);
+  {
+    const float* bm = static_cast<const float*>(host_blob) + m->mv.o[BF_body_mass];
+    m->body_mass.assign(bm, bm + m->mv.nbody);
+  }
   m->spec = generic_forced() ? -1 : find_spec(bd);
   MPPO_TRY(finalize_layout(m.get()));
   // every specialised instantiation proves itself on the device it is about to run on (a few milliseconds): the ones a build adds (MPPO_SPECIALIZE) always,
@@ -347,6 +386,18 @@ extern "C" int32_t mppo_model_attach_kernel(mppo_model_t* m, const void* image, 
     he = hipModuleGetFunction(&m->jit_fn[k + 2], mod, name.c_str());
     if (he != hipSuccess) return drop(fail(MPPO_EINVAL, "mppo_model_attach_kernel: no kernel %s in the code object (%s)", name.c_str(), hipGetErrorString(he)));
   }
+  // the randomised reset, step and probe (KMODE 6 .. 8): the three symbols with the mode's digit k replaced by 6 + k
+  for (int k = 0; k <= 2; ++k) {
+    std::string name(names[k]);
+    char from[16], to[16];
+    snprintf(from, sizeof from, "EELi%dEEEv", k);
+    snprintf(to, sizeof to, "EELi%dEEEv", kEnvKernelRand + k);
+    const size_t at = name.rfind(from);
+    if (at == std::string::npos) return drop(fail(MPPO_EINVAL, "mppo_model_attach_kernel: kernel %d is named %s", k, names[k]));
+    name.replace(at, strlen(from), to);
+    he = hipModuleGetFunction(&m->jit_fn[kEnvKernelRand + k], mod, name.c_str());
+    if (he != hipSuccess) return drop(fail(MPPO_EINVAL, "mppo_model_attach_kernel: no kernel %s in the code object (%s)", name.c_str(), hipGetErrorString(he)));
+  }
   // the layout the specialised kernel computed for itself at compile time; then the same proof a build-time instantiation gives
   m->jit_module = mod;
   m->jit = true;
@@ -387,7 +438,7 @@ extern "C" int32_t mppo_env_reset(const mppo_model_t* m, int32_t N, float* state
   MPPO_REQUIRE(N >= 1, "mppo_env_reset: N = %d", N);
   MPPO_REQUIRE(m->mv.nq >= 3, "mppo_env_reset: the environment reads qpos[2] as the height (env.py:239); nq = %d", m->mv.nq);
   MPPO_REQUIRE(!obs || obs_ld >= m->mv.obs_pad, "mppo_env_reset: obs_ld %d < padded observation width %d", obs_ld, m->mv.obs_pad);
-  return env_reset_ws(m, N, state, reset_rec, obs, obs_ld, reward, done, metrics, nullptr, 0, static_cast<hipStream_t>(stream));
+  return env_reset_ws(m, N, state, reset_rec, obs, obs_ld, reward, done, metrics, nullptr, 0, static_cast<hipStream_t>(stream), EnvDomain{});
 }
 
 extern "C" int32_t mppo_env_reinit(const mppo_model_t* m, int32_t N, float* state, float* obs, int32_t obs_ld, const uint8_t* mask, float scale, int32_t rng_impl,
@@ -401,7 +452,7 @@ extern "C" int32_t mppo_env_reinit(const mppo_model_t* m, int32_t N, float* stat
   MPPO_REQUIRE(rng_impl >= 0 && rng_impl <= 2, "mppo_env_reinit: rng_impl %d (0 philox, 1 threefry, 2 threefry from per-environment keys)", rng_impl);
   MPPO_REQUIRE(rng_impl == 0 || scale == 0.f || key2, "mppo_env_reinit: the threefry stream needs a key (two words in device memory)");
   MPPO_REQUIRE(rank >= 0 && rank < 256, "mppo_env_reinit: rank %d (0 .. 255)", rank);
-  return env_reinit_ws(m, N, state, obs, obs_ld, mask, scale, rng_impl, seed, rank, key2, counter, 1, counter_offset, nullptr, 0, static_cast<hipStream_t>(stream));
+  return env_reinit_ws(m, N, state, obs, obs_ld, mask, scale, rng_impl, seed, rank, key2, counter, 1, counter_offset, nullptr, 0, static_cast<hipStream_t>(stream), EnvDomain{});
 }
 
 extern "C" int32_t mppo_env_step(const mppo_model_t* m, int32_t N, int32_t n_frames, const mppo_reward_cfg_t* rc, float* state,
@@ -439,7 +490,7 @@ extern "C" int32_t mppo_env_step_xfrc(const mppo_model_t* m, int32_t N, int32_t 
   if (xfrc) MPPO_TRY(check_push_body("mppo_env_step_xfrc", m, body));
   EnvPush push{};
   push.body = body; push.xfrc = xfrc;
-  return env_step_push_ws(m, N, n_frames, rc, state, reset_rec, action, act_ld, obs, obs_ld, reward, done, metrics, push, nullptr, 0, static_cast<hipStream_t>(stream));
+  return env_step_push_ws(m, N, n_frames, rc, state, reset_rec, action, act_ld, obs, obs_ld, reward, done, metrics, push, nullptr, 0, static_cast<hipStream_t>(stream), EnvDomain{});
 }
 
 extern "C" int32_t mppo_physics_forward_xfrc(const mppo_model_t* m, int32_t N, const float* qpos, const float* qvel, const float* ctrl,
@@ -452,5 +503,68 @@ extern "C" int32_t mppo_physics_forward_xfrc(const mppo_model_t* m, int32_t N, c
   EnvArgs a{};
   a.N = N; a.mode = 2; a.n_frames = 1; a.p_qpos = qpos; a.p_qvel = qvel; a.p_ctrl = ctrl; a.p_warm = qacc_warmstart; a.probe = *out;
   if (xfrc) { a.push_body = body; a.xfrc = xfrc; }
+  return launch_env(m, a, static_cast<hipStream_t>(stream));
+}
+
+/* ---- domain randomisation: the entry points with a table (include/minppo_hip.h) ---- */
+extern "C" int32_t mppo_env_reset_domain(const mppo_model_t* m, int32_t N, float* state, float* reset_rec, float* obs, int32_t obs_ld, float* reward, uint8_t* done,
+                                         const mppo_env_metrics_t* metrics, const uint8_t* mask, const float* domain, int32_t mass_body, float scale, int32_t rng_impl,
+                                         uint64_t seed, int32_t rank, const uint32_t* key2, const int32_t* counter, int32_t counter_offset, void* stream) {
+  using namespace mppo;
+  MPPO_REQUIRE(m && state, "mppo_env_reset_domain: null model / state");
+  MPPO_REQUIRE(domain, "mppo_env_reset_domain: null table (domain, [N][4] floats in device memory)");
+  MPPO_REQUIRE(N >= 1, "mppo_env_reset_domain: N = %d", N);
+  MPPO_REQUIRE(m->mv.nq >= 3, "mppo_env_reset_domain: the environment reads qpos[2] as the height (env.py:239); nq = %d", m->mv.nq);
+  MPPO_REQUIRE(!obs || obs_ld >= m->mv.obs_pad, "mppo_env_reset_domain: obs_ld %d < padded observation width %d", obs_ld, m->mv.obs_pad);
+  MPPO_REQUIRE(scale >= 0.f, "mppo_env_reset_domain: scale %g is negative (or not a number)", (double)scale);
+  MPPO_REQUIRE(rng_impl >= 0 && rng_impl <= 2, "mppo_env_reset_domain: rng_impl %d (0 philox, 1 threefry, 2 threefry from per-environment keys)", rng_impl);
+  MPPO_REQUIRE(rng_impl == 0 || scale == 0.f || key2, "mppo_env_reset_domain: the threefry stream needs a key (two words in device memory)");
+  MPPO_REQUIRE(rank >= 0 && rank < 256, "mppo_env_reset_domain: rank %d (0 .. 255)", rank);
+  MPPO_TRY(check_domain_body("mppo_env_reset_domain", m, mass_body));
+  MPPO_REQUIRE(m->mv.nq + m->mv.nv <= 4 * 65536, "reset noise: %d noise elements per environment", m->mv.nq + m->mv.nv);
+  // (the reset kernel with everything it can be given: the full reset's outputs - each may be null - and the re-initialisation's mask and noise)
+  EnvArgs a{};
+  a.N = N; a.mode = 0; a.n_frames = 1; a.state = state; a.reset_out = reset_rec; a.obs = obs; a.obs_ld = obs_ld; a.reward = reward; a.done = done;
+  if (metrics) a.met = *metrics;
+  a.mask = mask; a.noise_scale = scale; a.noise_impl = rng_impl; a.noise_key = key2; a.noise_seed = seed;
+  a.noise_stream = kStreamReset + ((unsigned long long)rank << 16);
+  a.noise_ctr = counter; a.noise_ctr_mul = 1; a.noise_ctr_add = counter_offset;
+  a.domain = domain; a.mass_body = mass_body;
+  return launch_env(m, a, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int32_t mppo_env_step_domain(const mppo_model_t* m, int32_t N, int32_t n_frames, const mppo_reward_cfg_t* rc, float* state,
+                                        const float* reset_rec, const float* action, int32_t act_ld, float* obs, int32_t obs_ld, float* reward,
+                                        uint8_t* done, const mppo_env_metrics_t* metrics, int32_t push_body, const float* xfrc, const float* domain,
+                                        int32_t mass_body, void* stream) {
+  using namespace mppo;
+  MPPO_REQUIRE(m && rc && state && reset_rec && action && obs && reward && done, "mppo_env_step_domain: null argument");
+  MPPO_REQUIRE(domain, "mppo_env_step_domain: null table (domain, [N][4] floats in device memory)");
+  MPPO_REQUIRE(N >= 1 && n_frames >= 1, "mppo_env_step_domain: N = %d, n_frames = %d", N, n_frames);
+  MPPO_REQUIRE(m->mv.nq >= 3, "mppo_env_step_domain: the environment reads qpos[2] as the height (env.py:239); nq = %d", m->mv.nq);
+  MPPO_REQUIRE(act_ld >= m->mv.nu, "mppo_env_step_domain: act_ld %d < nu %d", act_ld, m->mv.nu);
+  MPPO_REQUIRE(obs_ld >= m->mv.obs_pad, "mppo_env_step_domain: obs_ld %d < padded observation width %d", obs_ld, m->mv.obs_pad);
+  if (xfrc) MPPO_TRY(check_push_body("mppo_env_step_domain", m, push_body));
+  MPPO_TRY(check_domain_body("mppo_env_step_domain", m, mass_body));
+  EnvPush push{};
+  push.body = xfrc ? push_body : 0; push.xfrc = xfrc;
+  return env_step_push_ws(m, N, n_frames, rc, state, reset_rec, action, act_ld, obs, obs_ld, reward, done, metrics, push, nullptr, 0, static_cast<hipStream_t>(stream),
+                          EnvDomain{domain, mass_body});
+}
+
+extern "C" int32_t mppo_physics_forward_domain(const mppo_model_t* m, int32_t N, const float* qpos, const float* qvel, const float* ctrl, const float* qacc_warmstart,
+                                               const mppo_forward_probe_t* out, int32_t push_body, const float* xfrc, const float* domain, int32_t mass_body,
+                                               void* stream) {
+  using namespace mppo;
+  MPPO_REQUIRE(m && qpos && qvel && qacc_warmstart && out, "mppo_physics_forward_domain: null argument");
+  MPPO_REQUIRE(domain, "mppo_physics_forward_domain: null table (domain, [N][4] floats in device memory)");
+  MPPO_REQUIRE(ctrl || m->mv.nu == 0, "mppo_physics_forward_domain: ctrl is null but the model has actuators");
+  MPPO_REQUIRE(N >= 1, "mppo_physics_forward_domain: N = %d", N);
+  if (xfrc) MPPO_TRY(check_push_body("mppo_physics_forward_domain", m, push_body));
+  MPPO_TRY(check_domain_body("mppo_physics_forward_domain", m, mass_body));
+  EnvArgs a{};
+  a.N = N; a.mode = 2; a.n_frames = 1; a.p_qpos = qpos; a.p_qvel = qvel; a.p_ctrl = ctrl; a.p_warm = qacc_warmstart; a.probe = *out;
+  if (xfrc) { a.push_body = push_body; a.xfrc = xfrc; }
+  a.domain = domain; a.mass_body = mass_body;
   return launch_env(m, a, static_cast<hipStream_t>(stream));
 }

@@ -12,6 +12,7 @@
 #include "ppo_layout.h"
 #include "push.h"
 #include "limit.h"
+#include "domrand.h"
 
 namespace mppo {
 const ModelView& model_view(const mppo_model* m);
@@ -19,9 +20,10 @@ size_t model_scratch_bytes(const mppo_model* m, int N);
 int32_t env_step_ws(const mppo_model_t* m, int32_t N, int32_t n_frames, const mppo_reward_cfg_t* rc, float* state, const float* reset_rec, const float* action,
                     int32_t act_ld, float* obs, int32_t obs_ld, float* reward, uint8_t* done, const mppo_env_metrics_t* metrics, float* ws, size_t ws_bytes, hipStream_t stream);
 int32_t env_reset_ws(const mppo_model_t* m, int32_t N, float* state, float* reset_rec, float* obs, int32_t obs_ld, float* reward, uint8_t* done, const mppo_env_metrics_t* metrics,
-                     float* ws, size_t ws_bytes, hipStream_t stream);
+                     float* ws, size_t ws_bytes, hipStream_t stream, const EnvDomain& dom);
 int32_t env_reinit_ws(const mppo_model_t* m, int32_t N, float* state, float* obs, int32_t obs_ld, const uint8_t* mask, float scale, int32_t rng_impl, uint64_t seed,
-                      int32_t rank, const uint32_t* key2, const int32_t* counter, int32_t counter_mul, int32_t counter_add, float* ws, size_t ws_bytes, hipStream_t stream);
+                      int32_t rank, const uint32_t* key2, const int32_t* counter, int32_t counter_mul, int32_t counter_add, float* ws, size_t ws_bytes, hipStream_t stream,
+                      const EnvDomain& dom);
 
 struct EvalWs {
   float *state, *reset_rec, *obs, *action, *log_prob, *value, *noise, *reward, *fwd_ws, *env_ws;
@@ -32,10 +34,12 @@ struct EvalWs {
   // behind mppo_eval_ws_bytes' regions (carve_eval's `limit`): the time limit's flags and the two counters per environment
   unsigned char* truncated;
   void* limit_acc;
+  // behind those (carve_eval's `domain`): the domain randomisation's table [N][4]
+  float* domain;
 };
 
 // the regions of the workspace, each on a 256-byte boundary (base = null: sizes only)
-static EvalWs carve_eval(const mppo_model* m, const mppo_net_t& net, int N, unsigned char* base, bool limit = false) {
+static EvalWs carve_eval(const mppo_model* m, const mppo_net_t& net, int N, unsigned char* base, bool limit = false, bool domain = false) {
   const ModelView& mv = model_view(m);
   EvalWs w{};
   size_t off = 0;
@@ -66,6 +70,7 @@ static EvalWs carve_eval(const mppo_model* m, const mppo_net_t& net, int N, unsi
   w.env_ws_bytes = model_scratch_bytes(m, N);
   w.env_ws = w.env_ws_bytes ? (float*)take(w.env_ws_bytes) : nullptr;
   if (limit) { w.truncated = take(n); w.limit_acc = take(eval_limit_acc_bytes(N)); }
+  if (domain) w.domain = (float*)take(n * 16);
   w.total = align_up(off, 256);
   return w;
 }
@@ -100,8 +105,19 @@ extern "C" size_t mppo_eval_ws_bytes(const mppo_model_t* m, const mppo_net_t* ne
 // obs_table (may be null: the plain evaluation, not one launch more): [2][O] mean32 | inv_std32 of a policy trained on normalised observations
 static int32_t evaluate_impl(const char* who, const mppo_model_t* m, const mppo_net_t* net, const float* params, const mppo_eval_cfg_t* cfg, void* ws, size_t ws_bytes,
                              const float* obs_table, float clip, const mppo_push_cfg_t* push, mppo_eval_result_t* result, float* traj, void* stream,
-                             bool limit_ws = false, int32_t episode_length = 0, mppo_eval_limit_result_t* extra = nullptr) {
+                             bool limit_ws = false, int32_t episode_length = 0, mppo_eval_limit_result_t* extra = nullptr, bool domain_ws = false,
+                             const mppo_domain_cfg_t* domain = nullptr) {
   MPPO_TRY(check_eval(who, m, net, cfg));
+  // domain randomisation (may be null, or every range at its identity: the evaluation without it, launch for launch): the table is drawn once, from the evaluation's
+  // seed as rank 0, and every reset, step and re-initialisation launch reads it
+  mppo_domain_cfg_t dc{};
+  bool randomised = false;
+  if (domain) {
+    dc = *domain;
+    dc.rank = 0; dc.seed = cfg->seed;
+    randomised = domain_cfg_on(dc);
+    MPPO_TRY(check_domain_cfg(who, randomised ? m : nullptr, &dc));
+  }
   // episode time limit (0: none - launch for launch the evaluation without one): no stagger, rank 0, the evaluation's seed (which the unstaggered test does not read)
   MPPO_REQUIRE(episode_length >= 0, "%s: episode length %d is negative", who, episode_length);
   MPPO_REQUIRE(episode_length == 0 || (extra && (reinterpret_cast<uintptr_t>(extra) & 7) == 0), "%s: the time limit's result must be given, 8-byte aligned", who);
@@ -129,8 +145,10 @@ static int32_t evaluate_impl(const char* who, const mppo_model_t* m, const mppo_
   MPPO_REQUIRE(clip >= 0.f, "%s: clip %g is negative (or not a number)", who, (double)clip);
   const mppo_eval_cfg_t& c = *cfg;
   const int N = c.N, K = c.K, R = c.record_envs, A = net->A;
-  const EvalWs w = carve_eval(m, *net, N, static_cast<unsigned char*>(ws), limit_ws);
-  MPPO_REQUIRE(ws_bytes >= w.total, "%s: workspace %zu < %zu bytes (%s)", who, ws_bytes, w.total, limit_ws ? "mppo_eval_limit_ws_bytes" : "mppo_eval_ws_bytes");
+  const EvalWs w = carve_eval(m, *net, N, static_cast<unsigned char*>(ws), limit_ws, domain_ws);
+  MPPO_REQUIRE(ws_bytes >= w.total, "%s: workspace %zu < %zu bytes (%s)", who, ws_bytes, w.total,
+               domain_ws ? "mppo_eval_domain_ws_bytes" : limit_ws ? "mppo_eval_limit_ws_bytes" : "mppo_eval_ws_bytes");
+  const EnvDomain dom = randomised ? EnvDomain{w.domain, dc.mass_body} : EnvDomain{};
   hipStream_t s = static_cast<hipStream_t>(stream);
   const ModelView& mv = model_view(m);
   const int OP = mv.obs_pad, row_w = mv.nq + mv.nv;
@@ -138,10 +156,11 @@ static int32_t evaluate_impl(const char* who, const mppo_model_t* m, const mppo_
   const bool noisy_reset = c.reset_noise_scale > 0.f;
   const FwdBufs fb = carve_fwd(*net, N, w.fwd_ws);
 
+  if (randomised) MPPO_TRY(domain_fill_launch(dc, N, w.domain, s));
   // the reset zeroes the metrics; reward / done are the step's to write
-  MPPO_TRY(env_reset_ws(m, N, w.state, w.reset_rec, w.obs, OP, w.reward, w.done, &w.met, w.env_ws, w.env_ws_bytes, s));
+  MPPO_TRY(env_reset_ws(m, N, w.state, w.reset_rec, w.obs, OP, w.reward, w.done, &w.met, w.env_ws, w.env_ws_bytes, s, dom));
   if (noisy_reset)  // event 0 of the reset noise's Philox stream: every environment starts from a state of its own
-    MPPO_TRY(env_reinit_ws(m, N, w.state, w.obs, OP, nullptr, c.reset_noise_scale, 0, c.seed, 0, nullptr, nullptr, 1, 0, w.env_ws, w.env_ws_bytes, s));
+    MPPO_TRY(env_reinit_ws(m, N, w.state, w.obs, OP, nullptr, c.reset_noise_scale, 0, c.seed, 0, nullptr, nullptr, 1, 0, w.env_ws, w.env_ws_bytes, s, dom));
   if (c.deterministic) MPPO_TRY(eval_zero_launch(w.noise, (size_t)N * A, s));
   // frame 0: the initial states, the action / reward / done columns zero
   MPPO_TRY(eval_accumulate_launch(0, N, true, nullptr, nullptr, nullptr, nullptr, w.state, mv.rec_dim, row_w, nullptr, A, A, R, traj, s));
@@ -149,11 +168,13 @@ static int32_t evaluate_impl(const char* who, const mppo_model_t* m, const mppo_
     if (!c.deterministic) MPPO_TRY(normal_fill_ctr(c.seed, (unsigned long long)t, nullptr, (size_t)N * A, w.noise, s));
     MPPO_TRY(policy_forward(*net, params, N, w.obs, OP, fb, w.noise, w.action, w.log_prob, w.value, nullptr, s));
     ep.add = t;
-    MPPO_TRY(env_step_push_ws(m, N, c.n_frames, &c.reward, w.state, w.reset_rec, w.action, A, w.obs, OP, w.reward, w.done, &w.met, ep, w.env_ws, w.env_ws_bytes, s));
+    MPPO_TRY(env_step_push_ws(m, N, c.n_frames, &c.reward, w.state, w.reset_rec, w.action, A, w.obs, OP, w.reward, w.done, &w.met, ep, w.env_ws, w.env_ws_bytes, s, dom));
     if (lim.length > 0)  // the environments that have reached the limit are truncated: done, the metrics and the reset record as the step ends an episode
       MPPO_TRY(time_limit_launch(lim, N, mv.rec_dim, OP, w.state, w.reset_rec, w.obs, OP, w.done, w.truncated, w.met, s));
-    if (noisy_reset)  // the environments whose episode ended restart from a randomised state (event t + 1), as in the engine's rollout
-      MPPO_TRY(env_reinit_ws(m, N, w.state, w.obs, OP, w.done, c.reset_noise_scale, 0, c.seed, 0, nullptr, nullptr, 1, t + 1, w.env_ws, w.env_ws_bytes, s));
+    // the environments whose episode ended restart from a randomised state (event t + 1), as in the engine's rollout; under domain randomisation every restart
+    // goes through the reset kernel with the environment's own row (the one shared reset record is another robot's), at scale 0 without reset noise
+    if (noisy_reset || randomised)
+      MPPO_TRY(env_reinit_ws(m, N, w.state, w.obs, OP, w.done, c.reset_noise_scale, 0, c.seed, 0, nullptr, nullptr, 1, t + 1, w.env_ws, w.env_ws_bytes, s, dom));
     if (obs_table)  // the next forward reads what the policy was trained on; the observation after the reset stays raw, as in the engine (the state rows are raw throughout)
       MPPO_TRY(obs_norm_apply_launch(N, net->O, w.obs, OP, obs_table, net->O, clip, nullptr, s));
     MPPO_TRY(eval_accumulate_launch(N, N, t == 0, w.reward, w.done, &w.met, w.acc, w.state, mv.rec_dim, row_w, w.action, A, A, R,
@@ -188,4 +209,15 @@ extern "C" int32_t mppo_evaluate_limit(const mppo_model_t* m, const mppo_net_t* 
                                        const float* obs_table, float clip, const mppo_push_cfg_t* push, int32_t episode_length, mppo_eval_result_t* result,
                                        mppo_eval_limit_result_t* extra, float* traj, void* stream) {
   return evaluate_impl("mppo_evaluate_limit", m, net, params, cfg, ws, ws_bytes, obs_table, clip, push, result, traj, stream, true, episode_length, extra);
+}
+
+extern "C" size_t mppo_eval_domain_ws_bytes(const mppo_model_t* m, const mppo_net_t* net, const mppo_eval_cfg_t* cfg) {
+  if (check_eval("mppo_eval_domain_ws_bytes", m, net, cfg) != MPPO_OK) return 0;
+  return carve_eval(m, *net, cfg->N, nullptr, true, true).total;
+}
+
+extern "C" int32_t mppo_evaluate_domain(const mppo_model_t* m, const mppo_net_t* net, const float* params, const mppo_eval_cfg_t* cfg, void* ws, size_t ws_bytes,
+                                        const float* obs_table, float clip, const mppo_push_cfg_t* push, int32_t episode_length, const mppo_domain_cfg_t* domain,
+                                        mppo_eval_result_t* result, mppo_eval_limit_result_t* extra, float* traj, void* stream) {
+  return evaluate_impl("mppo_evaluate_domain", m, net, params, cfg, ws, ws_bytes, obs_table, clip, push, result, traj, stream, true, episode_length, extra, true, domain);
 }

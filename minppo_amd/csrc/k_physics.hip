@@ -694,8 +694,12 @@ struct StaticModel {
 template <class SD, int KMODE>
 __global__ void __launch_bounds__(64 * kMaxWavesPerBlock) env_kernel(ModelView mv, EnvArgs a, PhysLds Prt) {
   constexpr bool SPLIT = KMODE == 5;
-  constexpr int MODE = SPLIT ? 1 : KMODE >= 3 ? KMODE - 2 : KMODE;
-  constexpr bool pushed = !SPLIT && KMODE >= 3;
+  constexpr bool RAND = KMODE >= 6;
+  constexpr int MODE = SPLIT ? 1 : RAND ? KMODE - 6 : KMODE >= 3 ? KMODE - 2 : KMODE;
+  constexpr bool pushed = !SPLIT && !RAND && KMODE >= 3;
+  // the randomised step and probe hold the wrench's code behind a run-time test, so that pushes and randomisation combine without a fourth family (in the
+  // kernels 0 .. 5 a compile-time false: their tests of `pushed` are what they were)
+  constexpr bool kRandPush = RAND && MODE != 0;
   constexpr BlobDims kSD = SD::dims();
   constexpr BlobOffsets kSO = blob_offsets(kSD);
   constexpr bool kDims = SD::kStatic;
@@ -744,6 +748,12 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerBlock) env_kernel(ModelView m
   }
   __syncthreads();  // the only workgroup-wide barrier: model tables are shared by the waves of the block
   if (row >= epw) return;  // rows without an environment
+  // domain randomisation (KMODE 6 .. 8): this environment's row of EnvArgs::domain.  A table value is REPLACED first - one float32 product or sum - and the
+  // replaced value is used where the table's was: the bits of the kernels 0 .. 2 on a model whose tables hold the replaced values.  In the kernels 0 .. 5
+  // RAND is a compile-time false and each of the four reads below is the table read it was.
+  float dr_fric = 1.f, dr_act = 1.f, dr_mass = 0.f;
+  if (RAND) { const float* dp = a.domain + (size_t)env * 4; dr_fric = dp[0]; dr_act = dp[1]; dr_mass = dp[2]; }
+  const int dr_body = RAND ? a.mass_body : 0;
   float* S = reinterpret_cast<float*>(smem_raw) + mv.blob_words + (size_t)el * P.total;
   // matrices in global memory (large robots; model_view.h PhysLds::spill): this group's record - one per group of the GRID, so that a
   // surplus group (which shadows the last environment) has a record of its own
@@ -965,7 +975,7 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerBlock) env_kernel(ModelView m
       float sx = 0.f, sy = 0.f, sz = 0.f, sm = 0.f;
       FOR_G(b, nb) {
         if (((b < 64 ? mask : mask_hi) >> (b & 63)) & 1ull) {
-          const float m = TF(body_mass)[b];
+          const float m = RAND && b == dr_body ? TF(body_mass)[b] + dr_mass : TF(body_mass)[b];
           sx += m * xipos[3 * b]; sy += m * xipos[3 * b + 1]; sz += m * xipos[3 * b + 2]; sm += m;
         }
       }
@@ -1157,7 +1167,7 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerBlock) env_kernel(ModelView m
         int ri = 0;
         for (int r = 0; r < nroot; ++r) if (TI(root_body)[r] == TI(body_rootid)[b]) ri = r;
         const V3 off = sub3(ld3(xipos + 3 * b), ld3(rootcom + 3 * ri));
-        const float m = TF(body_mass)[b];
+        const float m = RAND && b == dr_body ? TF(body_mass)[b] + dr_mass : TF(body_mass)[b];
         float R[9];  // ximat
         qmat(qmul(ld4(xquat + 4 * b), ld4(TF(body_iquat) + 4 * b)), R);
         const float d0 = TF(body_inertia)[3 * b], d1 = TF(body_inertia)[3 * b + 1], d2 = TF(body_inertia)[3 * b + 2];
@@ -1210,7 +1220,7 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerBlock) env_kernel(ModelView m
     if (spM) GSYNC(); else SYNC();
     }
     if (SPLIT) WGSYNC();  // the fork: qpos, qvel, ctrl, the contact geometry, cinert and cdof are there for wave 1 (whose last frame's reads are behind it)
-    if (pushed) {
+    if (pushed || (kRandPush && a.push_body > 0)) {
       // ---- the external wrench (MJX support.xfrc_accumulate in fwd_acceleration): its generalised force per dof -----------------
       // qfrc[d] = cdof[d] . (torque + (xipos[b] - subtree_com[root(b)]) x force, force) for the dofs of body b and of its ancestors, 0 for every other.
       // Formed HERE, where the poses of region A1 and cdof are both alive (the factorisation's work copy takes A1 next), and parked in qfs, which is
@@ -1549,14 +1559,19 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerBlock) env_kernel(ModelView m
           float c = ctrl[u];
           if (TI(act_ctrllimited)[u]) c = fminf(fmaxf(c, TF(act_ctrlrange)[2 * u]), TF(act_ctrlrange)[2 * u + 1]);
           if (balld) {  // a motor on a ball joint: the scalar force times the gear's three components (kept in the actuator's bias row: no length, no bias there)
-            float fo = TF(act_gain)[u] * c;
+            float fo = (RAND ? TF(act_gain)[u] * dr_act : TF(act_gain)[u]) * c;
             if (TI(act_forcelimited)[u]) fo = fminf(fmaxf(fo, TF(act_forcerange)[2 * u]), TF(act_forcerange)[2 * u + 1]);
             act += fo * TF(act_bias)[3 * u + kb];
             continue;
           }
           const float gear = TF(act_gear)[u];
           const float len = gear * qpos[TI(act_qposadr)[u]], vel = gear * qvel[d];
-          float fo = TF(act_gain)[u] * c + TF(act_bias)[3 * u] + TF(act_bias)[3 * u + 1] * len + TF(act_bias)[3 * u + 2] * vel;
+          float fo;
+          if (RAND) {  // (a ball joint's motor, above, keeps its gear in the bias row: only its gain is scaled)
+            const float ga = TF(act_gain)[u] * dr_act, b0 = TF(act_bias)[3 * u] * dr_act, b1 = TF(act_bias)[3 * u + 1] * dr_act, b2 = TF(act_bias)[3 * u + 2] * dr_act;
+            fo = ga * c + b0 + b1 * len + b2 * vel;
+          } else
+            fo = TF(act_gain)[u] * c + TF(act_bias)[3 * u] + TF(act_bias)[3 * u + 1] * len + TF(act_bias)[3 * u + 2] * vel;
           if (TI(act_forcelimited)[u]) fo = fminf(fmaxf(fo, TF(act_forcerange)[2 * u]), TF(act_forcerange)[2 * u + 1]);
           act += fo * gear;
         }
@@ -1568,7 +1583,7 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerBlock) env_kernel(ModelView m
         act = act < lo ? lo : (act > hi ? hi : act);
       }
       float smooth = passive - bias + act;
-      if (pushed) { const float w = qfs[d]; if (w != 0.f) smooth += w; }  // (this lane left the wrench's share there, above; a zero of either sign changes no bit)
+      if (pushed || (kRandPush && a.push_body > 0)) { const float w = qfs[d]; if (w != 0.f) smooth += w; }  // (this lane left the wrench's share there, above; a zero of either sign changes no bit)
       qfs[d] = smooth;
       // qfrc_actuator is part of the new record / observation (env.py:252) and of the NaN guard, not of the solver: it leaves here
       bad_lane |= (int)isnan(act);
@@ -1687,7 +1702,7 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerBlock) env_kernel(ModelView m
       if (any) {
         const V3 n = ld3(confr + 6 * c), t1 = ld3(confr + 6 * c + 3), t2 = cross3(n, t1);
         const float jn = dot3(n, jp), jt1 = dot3(t1, jp), jt2 = dot3(t2, jp);
-        const float mu = TF(con_friction)[3 * c];
+        const float mu = RAND ? TF(con_friction)[3 * c] * dr_fric : TF(con_friction)[3 * c];
         r4[0] = jn + mu * jt1; r4[1] = jn - mu * jt1; r4[2] = jn + mu * jt2; r4[3] = jn - mu * jt2;
         if (cp && cpi[cpv.con_condim + c] == 1) { r4[0] = jn; r4[1] = 0.f; r4[2] = 0.f; r4[3] = 0.f; }  // frictionless: the normal row, three inert ones
       }
@@ -1729,7 +1744,7 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerBlock) env_kernel(ModelView m
         if (any) {
           const V3 n = ld3(confr + 6 * c), t1 = ld3(confr + 6 * c + 3), t2 = cross3(n, t1);
           const float jn = dot3(n, jp), jt1 = dot3(t1, jp), jt2 = dot3(t2, jp);
-          const float mu = TF(con_friction)[3 * c];
+          const float mu = RAND ? TF(con_friction)[3 * c] * dr_fric : TF(con_friction)[3 * c];
           const int r0 = 4 * c;
           if (cp && cpi[cpv.con_condim + c] == 1) { J[r0 * ldj + d] = jn; continue; }  // frictionless: the normal row (the other three stay zero)
           J[(r0 + 0) * ldj + d] = jn + mu * jt1;
@@ -1740,7 +1755,7 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerBlock) env_kernel(ModelView m
       }
     }
     FOR_G(c, ncon) {
-      const float mu = TF(con_friction)[3 * c];
+      const float mu = RAND ? TF(con_friction)[3 * c] * dr_fric : TF(con_friction)[3 * c];
       float tw = TF(body_invweight0)[2 * TI(con_bodyid)[c]];
       if (c >= nplane) tw += TF(body_invweight0)[2 * TI(pair_body)[2 * (c - nplane)]];
       const float iw = (tw + mu * mu * tw) * 2.f * mu * mu / mv.impratio;
@@ -2369,8 +2384,8 @@ template <class SD>
 static int32_t launch_env_t(const ModelView& mv, const EnvArgs& a, const PhysLds& lds, int lds_bytes, int blocks, int waves, bool may_split, hipStream_t stream) {
 #ifndef MPPO_JIT_ONLY  // (an attached code object runs unsplit: mppo_model_attach_kernel knows the five unsplit kernels)
   if constexpr (split_compiled(SD::dims(), SD::kStatic, blob_offsets(SD::dims()).words)) {
-    // the split step: an unpushed step whose launch would put at most one wave on a SIMD - one two-wave workgroup per environment group, the split layout
-    if (may_split && a.mode == 1 && !(a.push_body > 0) && waves == 1 && mv.epw == kEnvsPerWave && split_launch(a.N, device_cus())) {
+    // the split step: an unpushed, unrandomised step whose launch would put at most one wave on a SIMD - one two-wave workgroup per environment group, the split layout
+    if (may_split && a.mode == 1 && !(a.push_body > 0) && !a.domain && waves == 1 && mv.epw == kEnvsPerWave && split_launch(a.N, device_cus())) {
       constexpr PhysLds kSplit = make_phys_lds(SD::dims(), true, 0, true);
       const int bytes = (mv.blob_words + kSplit.total * kEnvsPerWave) * 4;
       if (bytes * kSplitWgPerCu <= kLdsPerCu) {
@@ -2388,9 +2403,10 @@ static int32_t launch_env_t(const ModelView& mv, const EnvArgs& a, const PhysLds
   }
 #endif
   const int k = env_kernel_index(a);  // (a pushed step / probe is a kernel of its own: env_kernel's KMODE)
-  void (*kern)(ModelView, EnvArgs, PhysLds) = k == 0 ? &env_kernel<SD, 0> : k == 1 ? &env_kernel<SD, 1> : k == 2 ? &env_kernel<SD, 2> : k == 3 ? &env_kernel<SD, 3> : &env_kernel<SD, 4>;
+  void (*kern)(ModelView, EnvArgs, PhysLds) = k == 0 ? &env_kernel<SD, 0> : k == 1 ? &env_kernel<SD, 1> : k == 2 ? &env_kernel<SD, 2> : k == 3 ? &env_kernel<SD, 3> : k == 4 ? &env_kernel<SD, 4> :
+                                              k == 6 ? &env_kernel<SD, 6> : k == 7 ? &env_kernel<SD, 7> : &env_kernel<SD, 8>;  // (6 .. 8: the randomised reset, step, probe; 5, the split step, is launched above)
   // (the run-time-sized instantiation serves robots of different sizes: the limit follows the largest one seen)
-  static thread_local int attr_lds[kEnvKernels] = {64 * 1024, 64 * 1024, 64 * 1024, 64 * 1024, 64 * 1024};
+  static thread_local int attr_lds[kEnvKernels] = {64 * 1024, 64 * 1024, 64 * 1024, 64 * 1024, 64 * 1024, 64 * 1024, 64 * 1024, 64 * 1024, 64 * 1024};
   if (lds_bytes > attr_lds[k]) {
     MPPO_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes));
     attr_lds[k] = lds_bytes;

@@ -46,13 +46,14 @@ struct EnvPush {
   int mul, add;
 };
 
+struct EnvDomain;  // domrand.h: the table of a randomised launch (table null: none)
 // env_model.hip: the refusals every entry point with a push configuration shares, the draw's parameters of a configuration, the pushed step launch
 int32_t check_push_cfg(const char* who, const mppo_push_cfg_t* p);
 int32_t check_push_body(const char* who, const mppo_model_t* m, int32_t body);
 PushDraw push_draw_of(const mppo_push_cfg_t& p);
 int32_t env_step_push_ws(const mppo_model_t* m, int32_t N, int32_t n_frames, const mppo_reward_cfg_t* rc, float* state, const float* reset_rec, const float* action,
                          int32_t act_ld, float* obs, int32_t obs_ld, float* reward, uint8_t* done, const mppo_env_metrics_t* metrics, const EnvPush& push, float* ws,
-                         size_t ws_bytes, hipStream_t stream);
+                         size_t ws_bytes, hipStream_t stream, const EnvDomain& dom);
 // k_push.hip: the draw written out, xfrc [N][6] of step (*ctr) * mul + add
 int32_t push_fill_launch(const PushDraw& p, int N, const int* ctr, int mul, int add, float* xfrc, hipStream_t stream);
 

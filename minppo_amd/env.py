@@ -27,7 +27,7 @@ import numpy as np
 from minppo_amd import _native as nat
 from minppo_amd.config import Config, load_config_from_cli, require
 from minppo_amd.model import CompiledModel, load_model
-from minppo_amd.train import push_body_id, push_cfg, resolve_model, reward_cfg
+from minppo_amd.train import domain_body_id, domain_cfg, push_body_id, push_cfg, resolve_model, reward_cfg
 
 logger = logging.getLogger(__name__)
 
@@ -100,6 +100,11 @@ class HumanoidEnv:
         self._push = push_cfg(config, self.cm, config.training.seed)
         # the episode time limit (`environment.episode_length`; 0: none): applied behind every step, every episode cut at the same length (no stagger)
         self._limit = nat.TimeLimitCfg(length=int(config.environment.episode_length), stagger=0, rank=0, reserved=0, seed=int(config.training.seed) & 0xFFFFFFFFFFFFFFFF)
+        # domain randomisation (`environment.friction_scale_* / actuator_scale_* / added_mass_*`): what `domain_params` draws (None: every range at its default);
+        # the payload's body is resolved whatever the ranges are - `reset(..., domain=)` takes an explicit table.  `_domain`: the table of the last reset
+        self._domain_cfg = domain_cfg(config, self.cm, config.training.seed)
+        self._domain_body = domain_body_id(config, self.cm, always=True)
+        self._domain = None
         self._have_reset = False
         self._camera_name = config.visualization.camera_name
         self._renderer = None
@@ -152,21 +157,41 @@ class HumanoidEnv:
         return impl, t.from_numpy(np.ascontiguousarray(key).view(np.int32)).to(self.device)
 
     # -- env.py:124-145 ---------------------------------------------------------
-    def reset(self, rng: Any = None, num_envs: int = 1) -> EnvState:
+    def reset(self, rng: Any = None, num_envs: int = 1, *, domain: Any = None) -> EnvState:
+        """`domain` (extension; Brax `domain_randomize`'s vmapped model): [N, 4] rows (friction_scale, actuator_scale, added_mass, 0) - environment n is then
+        the robot whose sliding friction, actuator gain / bias and `environment.added_mass_body`'s mass are replaced by its row, in this reset and in every
+        `step` until the next reset.  None: the table `domain_params(num_envs)` draws when the configuration's ranges are on, else no randomisation.
+        The table belongs to this object, not to the returned `EnvState`: `step` uses the table of the LAST reset, so an `EnvState` kept from before a later
+        reset is stepped on the later reset's robots (only a different number of environments is refused) - step the states of one reset at a time."""
         t = self.torch
         N = int(num_envs)
+        if domain is not None:
+            domain = (domain if hasattr(domain, "data_ptr") else t.as_tensor(np.asarray(domain, np.float32))).to(device=self.device, dtype=t.float32).contiguous()
+            if domain.shape != (N, 4):
+                raise ValueError(f"domain must have shape ({N}, 4) - friction_scale, actuator_scale, added_mass, 0 per environment - got {tuple(domain.shape)}")
+        elif self._domain_cfg is not None:
+            domain = self.domain_params(N)
+        self._domain = domain
         noise = self._noise_keys(rng, N, "reset") if self.reset_noise_scale != 0 else None  # (a missing key is refused before anything is launched)
         state = t.empty(N, self.dims.rec_dim, dtype=t.float32, device=self.device)
         obs = t.empty(N, self.dims.obs_pad, dtype=t.float32, device=self.device)
         reward, done = t.empty(N, dtype=t.float32, device=self.device), t.empty(N, dtype=t.uint8, device=self.device)
         m = self._metrics(N)
         ms = self._mstruct(m)
-        self.lib.env_reset(self._model, N, state.data_ptr(), self._reset_rec.data_ptr(), obs.data_ptr(), self.dims.obs_pad, reward.data_ptr(),
-                           done.data_ptr(), C.byref(ms), self._stream())
+        if domain is not None:  # every robot's own reset (mppo_env_reset_domain: the reset kernel with the environment's row)
+            self.lib.env_reset_domain(self._model, N, state.data_ptr(), self._reset_rec.data_ptr(), obs.data_ptr(), self.dims.obs_pad, reward.data_ptr(),
+                                      done.data_ptr(), C.byref(ms), None, domain.data_ptr(), self._domain_body, 0.0, 0, 0, 0, None, None, 0, self._stream())
+        else:
+            self.lib.env_reset(self._model, N, state.data_ptr(), self._reset_rec.data_ptr(), obs.data_ptr(), self.dims.obs_pad, reward.data_ptr(),
+                               done.data_ptr(), C.byref(ms), self._stream())
         if noise is not None:  # env.py:115-121: every environment from a state of its own, keyed by split(rng, num_envs) (train.py:135)
             impl, keys = noise
-            self.lib.env_reinit(self._model, N, state.data_ptr(), obs.data_ptr(), self.dims.obs_pad, 0, float(self.reset_noise_scale), impl, 0, 0, keys.data_ptr(), 0, 0,
-                                self._stream())
+            if domain is not None:
+                self.lib.env_reset_domain(self._model, N, state.data_ptr(), None, obs.data_ptr(), self.dims.obs_pad, None, None, None, None, domain.data_ptr(),
+                                          self._domain_body, float(self.reset_noise_scale), impl, 0, 0, keys.data_ptr(), None, 0, self._stream())
+            else:
+                self.lib.env_reinit(self._model, N, state.data_ptr(), obs.data_ptr(), self.dims.obs_pad, 0, float(self.reset_noise_scale), impl, 0, 0, keys.data_ptr(), 0, 0,
+                                    self._stream())
             self._noise_keep = keys  # (lives until the next call: the launch reads it; same-stream allocations are reused in stream order)
         self._have_reset = True
         return EnvState(state, obs[:, :self.observation_size], reward, done.bool(), m)
@@ -191,14 +216,22 @@ class HumanoidEnv:
         reward, done = t.empty(N, dtype=t.float32, device=self.device), t.empty(N, dtype=t.uint8, device=self.device)
         m = EnvMetrics(*[x.clone() if x.dtype != t.bool else x.to(t.uint8) for x in env_state.metrics])
         ms = self._mstruct(m)
+        dom = self._domain
+        if dom is not None and dom.shape[0] != N:
+            raise ValueError(f"step: {N} environments, but the last reset randomised {dom.shape[0]} - reset(num_envs={N}) first")
         if xfrc is not None:
             xfrc = (xfrc if hasattr(xfrc, "data_ptr") else t.as_tensor(np.asarray(xfrc, np.float32))).to(device=self.device, dtype=t.float32).contiguous()
             if xfrc.shape != (N, 6):
                 raise ValueError(f"xfrc must have shape ({N}, 6) - force, then torque, per environment - got {tuple(xfrc.shape)}")
+            self._xfrc_keep = xfrc  # (lives until the next call: the launch reads it)
+        if dom is not None:  # the randomised step (mppo_env_step_domain), with or without a wrench
+            self.lib.env_step_domain(self._model, N, self._n_frames, C.byref(self._rc), state.data_ptr(), self._reset_rec.data_ptr(), action.data_ptr(),
+                                     self._action_size, obs.data_ptr(), self.dims.obs_pad, reward.data_ptr(), done.data_ptr(), C.byref(ms), self._push_body,
+                                     None if xfrc is None else xfrc.data_ptr(), dom.data_ptr(), self._domain_body, self._stream())
+        elif xfrc is not None:
             self.lib.env_step_xfrc(self._model, N, self._n_frames, C.byref(self._rc), state.data_ptr(), self._reset_rec.data_ptr(), action.data_ptr(),
                                    self._action_size, obs.data_ptr(), self.dims.obs_pad, reward.data_ptr(), done.data_ptr(), C.byref(ms), self._push_body,
                                    xfrc.data_ptr(), self._stream())
-            self._xfrc_keep = xfrc  # (lives until the next call: the launch reads it)
         else:
             self.lib.env_step(self._model, N, self._n_frames, C.byref(self._rc), state.data_ptr(), self._reset_rec.data_ptr(), action.data_ptr(),
                               self._action_size, obs.data_ptr(), self.dims.obs_pad, reward.data_ptr(), done.data_ptr(), C.byref(ms), self._stream())
@@ -207,7 +240,13 @@ class HumanoidEnv:
             truncated = t.empty(N, dtype=t.uint8, device=self.device)
             self.lib.env_time_limit(self._model, N, C.byref(self._limit), state.data_ptr(), self._reset_rec.data_ptr(), obs.data_ptr(), self.dims.obs_pad,
                                     done.data_ptr(), truncated.data_ptr(), C.byref(ms), self._stream())
-        if noise is not None:  # env.py:166,179-180: the environments that ended restart from `_get_reset_state(rng)`, not from the constant record
+        if dom is not None:  # every restart through the reset kernel with the environment's own row: the one shared reset record is another robot's
+            impl, keys = noise if noise is not None else (0, None)
+            self.lib.env_reset_domain(self._model, N, state.data_ptr(), None, obs.data_ptr(), self.dims.obs_pad, None, None, None, done.data_ptr(), dom.data_ptr(),
+                                      self._domain_body, float(self.reset_noise_scale) if noise is not None else 0.0, impl, 0, 0,
+                                      None if keys is None else keys.data_ptr(), None, 0, self._stream())
+            self._noise_keep = keys
+        elif noise is not None:  # env.py:166,179-180: the environments that ended restart from `_get_reset_state(rng)`, not from the constant record
             impl, keys = noise
             self.lib.env_reinit(self._model, N, state.data_ptr(), obs.data_ptr(), self.dims.obs_pad, done.data_ptr(), float(self.reset_noise_scale), impl, 0, 0,
                                 keys.data_ptr(), 0, 0, self._stream())
@@ -225,6 +264,19 @@ class HumanoidEnv:
             p.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
         out = t.empty(int(num_envs), 6, dtype=t.float32, device=self.device)
         self.lib.push_fill(C.byref(p), int(num_envs), None, 0, int(step) & 0x7FFFFFFF, out.data_ptr(), self._stream())
+        return out
+
+    def domain_params(self, num_envs: int, seed: Optional[int] = None) -> Any:
+        """The table [num_envs, 4] of the domain randomisation - rows (friction_scale, actuator_scale, added_mass, 0) - that `reset(num_envs=)` draws and
+        keeps for its steps (`mppo_domain_fill`; rank 0; seed: `training.seed`); `jaxrng.domain_params_philox` is its host statement."""
+        if self._domain_cfg is None:
+            raise ValueError("domain_params: every environment.friction_scale_* / actuator_scale_* / added_mass_* key is at its default - there is nothing to draw")
+        t = self.torch
+        p = nat.DomainCfg.from_buffer_copy(self._domain_cfg)
+        if seed is not None:
+            p.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        out = t.empty(int(num_envs), 4, dtype=t.float32, device=self.device)
+        self.lib.domain_fill(C.byref(p), int(num_envs), out.data_ptr(), self._stream())
         return out
 
     # -- env.py:245-261 / 238-242 / 199-235 on the state record (host-side views, for inspection) ------

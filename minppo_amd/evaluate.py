@@ -66,6 +66,7 @@ class EvalResult:
     survivor_mean_return: float
     mean_reward: float
     steps: int
+    domain: Optional[Dict[str, float]] = None  # under domain randomisation only: the six numbers of its ranges (None without it: the key set is what it was)
     truncated_episodes: Optional[int] = None  # under an episode time limit only (None without one: the statistics' key set is then what it always was)
     falls: Optional[int] = None
     trajectory: Optional[Dict[str, np.ndarray]] = None
@@ -80,6 +81,9 @@ class EvalResult:
         for k in ("truncated_episodes", "falls"):
             if d[k] is None:
                 d.pop(k)
+        dom = d.pop("domain")
+        if dom is not None:  # (the ranges the figures belong to: a robustness sweep's lines say what they measured)
+            d.update(dom)
         return d
 
 
@@ -149,11 +153,13 @@ def eval_cfg(config: Config, **overrides: Any) -> nat.EvalCfg:
 
 
 def run(lib: nat.Lib, xp: str, device: Any, stream: Any, model: C.c_void_p, dims: nat.ModelDims, net: nat.Net, params_dev: Any,
-        ecfg: nat.EvalCfg, obs_norm: Optional[Dict[str, Any]] = None, push: Optional[nat.PushCfg] = None, episode_length: int = 0) -> EvalResult:
+        ecfg: nat.EvalCfg, obs_norm: Optional[Dict[str, Any]] = None, push: Optional[nat.PushCfg] = None, episode_length: int = 0,
+        domain: Optional[nat.DomainCfg] = None) -> EvalResult:
     """One `mppo_evaluate` on an open model and parameters already in device memory (`Trainer.evaluate` comes in here); with `obs_norm`
     ({"mean", "inv_std", "clip"}) one `mppo_evaluate_obs_norm`: the policy reads observations normalised with that table; with `push`
     (`train.push_cfg`: random pushes, with or without a table) one `mppo_evaluate_push`; with `episode_length` > 0 (an episode time limit, with or
-    without either) one `mppo_evaluate_limit`."""
+    without either) one `mppo_evaluate_limit`; with `domain` (`train.domain_cfg`: domain randomisation, with or without any of those) one
+    `mppo_evaluate_domain`."""
     table, clip = obs_norm_table(obs_norm, dims.obs_dim)
     limited = int(episode_length) > 0
     if int(episode_length) < 0:
@@ -161,7 +167,11 @@ def run(lib: nat.Lib, xp: str, device: Any, stream: Any, model: C.c_void_p, dims
     res_bytes = C.sizeof(nat.EvalResultRaw)  # (under a limit the second result lies behind the first in the same allocation)
 
     def call(ws, res, traj, s):
-        if limited:
+        if domain is not None:
+            lib.evaluate_domain(model, C.byref(net), nat.ptr(params_dev), C.byref(ecfg), nat.ptr(ws), need, nat.ptr(table_dev), clip,
+                                C.byref(push) if push is not None else None, int(episode_length), C.byref(domain), nat.ptr(res), nat.ptr(res) + res_bytes,
+                                nat.ptr(traj), s)
+        elif limited:
             lib.evaluate_limit(model, C.byref(net), nat.ptr(params_dev), C.byref(ecfg), nat.ptr(ws), need, nat.ptr(table_dev), clip,
                                C.byref(push) if push is not None else None, int(episode_length), nat.ptr(res), nat.ptr(res) + res_bytes, nat.ptr(traj), s)
         elif push is not None:
@@ -172,7 +182,7 @@ def run(lib: nat.Lib, xp: str, device: Any, stream: Any, model: C.c_void_p, dims
         else:
             lib.evaluate_obs_norm(model, C.byref(net), nat.ptr(params_dev), C.byref(ecfg), nat.ptr(ws), need, nat.ptr(table_dev), clip, nat.ptr(res), nat.ptr(traj), s)
 
-    need = int((lib.eval_limit_ws_bytes if limited else lib.eval_ws_bytes)(model, C.byref(net), C.byref(ecfg)))
+    need = int((lib.eval_domain_ws_bytes if domain is not None else lib.eval_limit_ws_bytes if limited else lib.eval_ws_bytes)(model, C.byref(net), C.byref(ecfg)))
     if need == 0:  # the arguments are ones mppo_evaluate refuses: let it say why
         lib.evaluate(model, C.byref(net), nat.ptr(params_dev), C.byref(ecfg), None, 0, None, None, None)
     K, R, nq, nv, A = ecfg.K, ecfg.record_envs, dims.nq, dims.nv, net.A
@@ -222,7 +232,7 @@ def evaluate(config: Config, params: Any, *, lib: Optional[nat.Lib] = None, xp: 
     the robot, network geometry, reward window and `evaluation` section of `config`.  `lib=` / `xp="numpy"` as in `Trainer`.
     A tree or pickle with an "obs_norm" entry (a policy trained with `training.normalize_observations`) is evaluated on observations normalised
     with it; `obs_norm=` ({"mean", "inv_std", "clip"}) supplies the entry for a flat vector or overrides the tree's.  A flat vector without it: none."""
-    from minppo_amd.train import open_model, push_cfg, resolve_model
+    from minppo_amd.train import domain_cfg, domain_echo, domain_on, open_model, push_cfg, resolve_model
 
     lib = lib if lib is not None else nat.load()
     if not 1 <= config.model.num_layers <= 4:
@@ -252,7 +262,9 @@ def evaluate(config: Config, params: Any, *, lib: Optional[nat.Lib] = None, xp: 
         flat = _flat_params(params, dims.obs_dim, dims.nu, config.model.hidden_size, L)
         params_dev = torch.from_numpy(flat).to(device) if torch is not None else np.ascontiguousarray(flat)
         result = run(lib, xp, device, stream, model, dims, net, params_dev, ecfg, obs_norm=obs_norm, push=push_cfg(config, cm, ecfg.seed),
-                     episode_length=int(config.environment.episode_length))
+                     episode_length=int(config.environment.episode_length), domain=domain_cfg(config, cm, ecfg.seed))
+        if domain_on(config):
+            result.domain = domain_echo(config)
     finally:
         if torch is not None:
             torch.cuda.synchronize(device)

@@ -229,3 +229,27 @@ def time_limit_first_philox(seed: int, rank: int, n: int, L: int) -> np.ndarray:
     seed = int(seed) & 0xFFFFFFFFFFFFFFFF
     w = _philox4x32(k, np.full_like(k, 0xFFFFFFFE), np.full_like(k, st & 0xFFFFFFFF), np.full_like(k, st >> 32), seed & 0xFFFFFFFF, seed >> 32)[0]
     return (1 + (w.astype(np.uint64) & np.uint64(0xFFFFFFFF)) % np.uint64(L)).astype(np.int64)
+
+
+_DOMAIN_STREAM = 0x4452414E44 << 24  # "DRAND": the Philox stream of the domain randomisation (csrc/domrand.h kStreamDomain)
+
+
+def domain_params_philox(seed: int, rank: int, num_envs: int, friction=(1.0, 1.0), actuator=(1.0, 1.0), mass=(0.0, 0.0)) -> np.ndarray:
+    """The table of the domain randomisation (csrc/domrand.h, bit for bit what `mppo_domain_fill` writes): row n = (friction_scale, actuator_scale,
+    added_mass, 0) with S = "DRAND" << 24 + (rank << 16), r = philox((n, 0xFFFFFFFD, lo(S), hi(S)), seed) and the three values
+    uniform(r[0], *friction), uniform(r[1], *actuator), uniform(r[2], *mass); min == max gives exactly that value.  The engine draws with its configuration's
+    seed and rank, the evaluator with the evaluation's seed as rank 0 -> float32 [N, 4]."""
+    for name, (lo, hi) in (("friction", friction), ("actuator", actuator), ("mass", mass)):
+        if not lo <= hi or (name != "mass" and lo < 0):
+            raise ValueError(f"domain randomisation: {name} range {lo} .. {hi}")
+    n = np.arange(num_envs, dtype=np.uint64)
+    st = _DOMAIN_STREAM + (int(rank) << 16)
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    z = _philox4x32(n, np.full_like(n, 0xFFFFFFFD), np.full_like(n, st & 0xFFFFFFFF), np.full_like(n, st >> 32), seed & 0xFFFFFFFF, seed >> 32)
+    out = np.zeros((num_envs, 4), np.float32)
+    for k, (lo, hi) in enumerate((friction, actuator, mass)):
+        bits = z[k].astype(np.uint32)
+        f = ((bits >> np.uint32(9)) | np.uint32(0x3F800000)).view(np.float32) - np.float32(1.0)
+        lo, hi = np.float32(lo), np.float32(hi)
+        out[:, k] = np.maximum(lo, f * (hi - lo) + lo).astype(np.float32)
+    return out

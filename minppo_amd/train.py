@@ -197,6 +197,7 @@ def resolve_model(config: Config) -> CompiledModel:
     name = config.environment.model or require(config.kscale_id, "kscale_id")
     cm = load_model(name)
     push_body_id(config, cm)  # (an unknown environment.push_body is refused here, where the model's names are first at hand)
+    domain_body_id(config, cm)  # (... and an unknown environment.added_mass_body)
     return cm
 
 
@@ -219,6 +220,40 @@ def push_cfg(config: Config, cm: CompiledModel, seed: int = 0, rank: int = 0) ->
         return None
     return nat.PushCfg(body=push_body_id(config, cm), interval=int(env.push_interval), duration=int(env.push_duration), rank=int(rank), force=float(env.push_force),
                        seed=int(seed) & 0xFFFFFFFFFFFFFFFF)
+
+
+def domain_on(config: Config) -> bool:
+    """Domain randomisation is on: some `environment.friction_scale_* / actuator_scale_* / added_mass_*` key differs from its default."""
+    env = config.environment
+    return (env.friction_scale_min, env.friction_scale_max, env.actuator_scale_min, env.actuator_scale_max, env.added_mass_min, env.added_mass_max) != (1.0, 1.0, 1.0, 1.0, 0.0, 0.0)
+
+
+def domain_body_id(config: Config, cm: CompiledModel, always: bool = False) -> int:
+    """The body id of `environment.added_mass_body` in `cm` ("": body 1, the first root), resolved as `push_body` is; read only when the randomisation is on,
+    or `always` (`HumanoidEnv`, whose `reset(..., domain=)` takes an explicit table whether or not the random draw is switched on)."""
+    name = config.environment.added_mass_body
+    if not (always or domain_on(config)) or not name:
+        return 1
+    names = list(cm.body_names)
+    if name not in names[1:]:
+        raise ValueError(f"environment.added_mass_body = {name!r}: no such body in the model; its bodies are {names[1:]}")
+    return names.index(name)
+
+
+def domain_cfg(config: Config, cm: CompiledModel, seed: int = 0, rank: int = 0) -> Optional[nat.DomainCfg]:
+    """`mppo_domain_cfg_t` of a config's domain-randomisation keys; None when every range is at its default (off)."""
+    if not domain_on(config):
+        return None
+    env = config.environment
+    return nat.DomainCfg(float(env.friction_scale_min), float(env.friction_scale_max), float(env.actuator_scale_min), float(env.actuator_scale_max),
+                         float(env.added_mass_min), float(env.added_mass_max), domain_body_id(config, cm), int(seed) & 0xFFFFFFFFFFFFFFFF, int(rank))
+
+
+def domain_echo(config: Config) -> Dict[str, float]:
+    """The six numbers of the randomisation, as `evaluate` echoes them in its JSON line."""
+    env = config.environment
+    return {k: float(getattr(env, k)) for k in ("friction_scale_min", "friction_scale_max", "actuator_scale_min", "actuator_scale_max", "added_mass_min",
+                                                 "added_mass_max")}
 
 
 def open_model(lib: nat.Lib, config: Config, cm: CompiledModel, xp: str, device: Any = None, verbose: bool = False):
@@ -338,6 +373,11 @@ class Trainer:
         self.push = push_cfg(config, self.cm, self.seed, rank)  # (seed and rank are the engine configuration's: the engine reads its own)
         if self.push is not None:
             self.lib.engine_set_push(self._engine, C.byref(self.push))
+        # environment.friction_scale_* / actuator_scale_* / added_mass_* (domain randomisation): all at their defaults leaves every launch as it
+        # is.  The table is a function of (seed, rank, environment) that the engine fills here, outside its arena: checkpoint / resume needs nothing new
+        self.domain = domain_cfg(config, self.cm, self.seed, rank)  # (seed and rank are the engine configuration's: the engine reads its own)
+        if self.domain is not None:
+            self.lib.engine_set_domain(self._engine, C.byref(self.domain))
         # environment.episode_length (the episode time limit): 0 leaves every launch as it is.  The staggered first limit is a function of
         # (seed, rank, environment) and what it is compared with - "timestep", "episode_lengths" - is in checkpoints already: checkpoint / resume needs nothing new
         self.episode_length = int(config.environment.episode_length)  # (make_config refuses a negative one; so does the engine)
@@ -911,10 +951,14 @@ class Trainer:
         on = self.obs_norm() if self.obs_norm_on else None  # (the table the next rollout would apply: what these parameters were last trained towards)
         # (on the trainer's own stream: behind the last enqueued update, whose parameters it reads)
         ecfg = ev.eval_cfg(self.config, **overrides)
-        return ev.run(self.lib, self.xp, self.device, self.stream, self._model, self.dims, self.net, self.region("params"), ecfg,
-                      obs_norm=None if on is None else {"mean": on["table"][0], "inv_std": on["table"][1], "clip": on["clip"]},
-                      push=push_cfg(self.config, self.cm, ecfg.seed),  # (environment.push_force > 0: the evaluation is pushed as the training was)
-                      episode_length=self.episode_length)  # (environment.episode_length > 0: ... and truncated as the training was)
+        result = ev.run(self.lib, self.xp, self.device, self.stream, self._model, self.dims, self.net, self.region("params"), ecfg,
+                        obs_norm=None if on is None else {"mean": on["table"][0], "inv_std": on["table"][1], "clip": on["clip"]},
+                        push=push_cfg(self.config, self.cm, ecfg.seed),  # (environment.push_force > 0: the evaluation is pushed as the training was)
+                        episode_length=self.episode_length,  # (environment.episode_length > 0: ... and truncated as the training was)
+                        domain=domain_cfg(self.config, self.cm, ecfg.seed))  # (... and on robots randomised as the training's were)
+        if domain_on(self.config):
+            result.domain = domain_echo(self.config)  # (the ranges the figures belong to, as `evaluate()` reports them)
+        return result
 
     def rollout_stats(self, reduce: bool = False) -> Dict[str, float]:
         """Device-side reduction of the last rollout's `EnvMetrics` history (`env.py:183-194`, `train.py:170,283`):

@@ -276,6 +276,47 @@ int32_t mppo_env_step_domain(const mppo_model_t* m, int32_t N, int32_t n_frames,
 int32_t mppo_physics_forward_domain(const mppo_model_t* m, int32_t N, const float* qpos, const float* qvel, const float* ctrl, const float* qacc_warmstart,
                                     const mppo_forward_probe_t* out, int32_t push_body, const float* xfrc, const float* domain, int32_t mass_body, void* stream);
 
+/* ---- sensor noise and actuation latency: observation noise, delayed actions ---------------------------------------------------------
+ * The reference has neither: env.py:245-261 returns the simulator's observation to the last bit and env.py:148-196 applies an action in the step it was
+ * computed.  legged_gym (`add_noise`, `noise_scale_vec`), MuJoCo Playground (`noise_config`, action latency) and Isaac Lab (`ActionDelay`) train with both;
+ * so does this (csrc/sensor.h, k_sensor.hip), as launches of their own beside the environment step.  Both draws are stateless Philox under both rng_impl values
+ * (the reference has no such stream); bits -> float as in mppo_env_reinit.
+ *
+ * mppo_obs_noise_apply : one launch, in place on obs[n, 0:O] (row stride obs_ld).  With S = ("ONOIS" << 24) + (rank << 16) and the step
+ *     s = (counter ? *counter : 0) * counter_mul + counter_add modulo 2^32 (`counter` a word in DEVICE memory, NULL: 0, read when the launch runs):
+ *         r = philox(counter = {n, s, lo(S) + (j >> 2), hi(S)}, key = seed);   obs[n][j] <- obs[n][j] + uniform(word j & 3 of r, -sigma[j], sigma[j])
+ *     one float32 add (host statement: minppo_amd/jaxrng.py obs_noise_philox).  `sigma`: DEVICE memory, 4 * ceil(O / 4) floats (the entries behind O are
+ *     read and not used).  A column whose sigma is not above 0 is NOT WRITTEN - every bit stays, a -0 or a NaN included - and neither are the columns
+ *     O .. obs_ld - 1; a negative sigma cannot be refused here (the table is device memory): the entry points that take the vector from the host
+ *     (mppo_engine_set_obs_noise, mppo_evaluate_sensors) refuse it.  The state record is not touched: what is perturbed is what the policy reads.  One lane per
+ *     four columns; 16-byte loads and stores when obs and sigma are 16-byte aligned and obs_ld is a multiple of 4.  One writer per word, no atomics.
+ *     MPPO_EINVAL: a null pointer, N < 1, O outside 1 .. 262144 (the block index j >> 2 has 16 bits of lo(S)), rank outside 0 .. 255, obs_ld below the
+ *     padded observation width.
+ * mppo_action_delay_fill : writes delay [N] (device int32), the latency of every environment for the whole run: with S = ("DELAY" << 24) + (rank << 16),
+ *         d_n = min + (word 0 of philox(counter = {n, 0xFFFFFFFC, lo(S), hi(S)}, key = seed) mod (max - min + 1))
+ *     (host statement: minppo_amd/jaxrng.py action_delays_philox).  MPPO_EINVAL (the message names the value): min < 0, min > max, max > 16, rank outside 0 .. 255.
+ * mppo_action_delay_apply : one launch IN FRONT OF an environment step.  `action` [N] rows of A (row stride act_ld) is the policy's; `applied` [N] rows of A
+ *     (row stride applied_ld) is what the step is to be given; `hist` [D][N][A] floats, D = cfg->max, is the ring of past actions (zeroed by the caller at the
+ *     reset).  With k = episode_lengths[n] and ts = timestep[n] as they stand BEFORE the step (the metrics of mppo_env_step) and d = delay[n]:
+ *         out = d == 0 ? action[n] : (k < d ? 0 : hist[(ts - d) mod D][n]);   hist[ts mod D][n] <- action[n];   applied[n] <- out      (the read first)
+ *     so the environment is given the policy's action of step k - d of the SAME episode, exact zeros on the first d steps of every episode (after a fall or a
+ *     truncation alike: episode_lengths is 0 again, there is no clearing launch), and with d = 0 the very bits of the policy's action.  Delay counts env
+ *     steps, whatever n_frames is.  cfg->min, seed and rank are not read.  MPPO_EINVAL: the refusals of mppo_action_delay_fill, max = 0 (there is nothing
+ *     to launch), a null pointer, act_ld or applied_ld below A. */
+typedef struct mppo_obs_noise_cfg {
+  uint64_t seed;
+  int32_t rank, reserved;
+} mppo_obs_noise_cfg_t;
+typedef struct mppo_action_delay_cfg {
+  int32_t min, max, rank, reserved;
+  uint64_t seed;
+} mppo_action_delay_cfg_t;
+int32_t mppo_obs_noise_apply(const mppo_obs_noise_cfg_t* cfg, int32_t N, int32_t O, float* obs, int32_t obs_ld, const float* sigma, const int32_t* counter,
+                             int32_t counter_mul, int32_t counter_add, void* stream);
+int32_t mppo_action_delay_fill(const mppo_action_delay_cfg_t* cfg, int32_t N, int32_t* delay, void* stream);
+int32_t mppo_action_delay_apply(const mppo_action_delay_cfg_t* cfg, int32_t N, int32_t A, const int32_t* delay, const int32_t* timestep,
+                                const int32_t* episode_lengths, const float* action, int32_t act_ld, float* hist, float* applied, int32_t applied_ld, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * PPO stages
  * ---------------------------------------------------------------------------------------- */
@@ -515,6 +556,7 @@ typedef struct mppo_engine_cfg {
  * "obs_norm_stats" (float64) "obs_norm_table" "obs_norm_partials" (float64)
  * "reward_norm_stats" (float64 [3]) "reward_norm_table" ([2]) "reward_norm_carry" ([N]) "reward_norm_partials" (float64 [G][2]) "reward_scaled" ([T][N])
  * "truncated" (bytes [T][N]: the samples an episode time limit cut, mppo_engine_set_time_limit)
+ * "action_hist" ([16][N][A]: the latency's ring) "action_applied" ([N][A]: what the last step launch was given) "action_delay" (int32 [N]) "obs_noise_scale" ([OP])
  * ("rollout_stats": 8 floats: sum reward, episodes ended, sum of their returns, sum of their lengths, the two means, truncations (0 without a time limit), 0) ... */
 int32_t mppo_engine_arena_bytes(const mppo_model_t* m, const mppo_engine_cfg_t* cfg, size_t* out);
 int32_t mppo_engine_create(const mppo_model_t* m, const mppo_engine_cfg_t* cfg, void* arena, size_t arena_bytes,
@@ -620,6 +662,26 @@ int32_t mppo_engine_set_time_limit(mppo_engine_t* e, int32_t length, int32_t sta
  * nothing crosses ranks, any world_size is allowed.  Call before mppo_engine_reset, mppo_engine_prepare and the first mppo_engine_update: afterwards it
  * returns MPPO_ESTATE.  MPPO_EINVAL: the refusals listed at mppo_domain_cfg_t. */
 int32_t mppo_engine_set_domain(mppo_engine_t* e, const mppo_domain_cfg_t* domain);
+/* Sensor noise during training (mppo_obs_noise_apply above; scale = NULL or every entry 0, the default: the engine enqueues exactly the launches, with exactly
+ * the arguments, it enqueues without this call).  `scale`: HOST memory, [O] floats, the half-width sigma_j of every observation column; it is copied into arena
+ * region "obs_noise_scale" ([OP], pad columns 0) by this call.  Then mppo_engine_reset follows its reset (and the initial reinit) with mppo_obs_noise_apply on
+ * observation slot 0 at step 0, and every rollout step becomes step -> time limit -> masked reinit -> mppo_obs_noise_apply(counter = "count" + 1, counter_mul = T,
+ * counter_add = t + 1) on slot t + 1 -> the observation normalisation's apply, in the captured graph too: one launch more per rollout step.  So the noisy row
+ * is what the trajectory stores, what the next forward, the critic's bootstrap and the learn phase read and what the normalisation's statistics collect; a
+ * replayed graph draws fresh values and a resumed run continues the sequence (checkpoints carry the counter; nothing else is state).  The state records stay
+ * exact.  Seed and rank are the engine configuration's; nothing crosses ranks, any world_size is allowed.  Call before mppo_engine_reset, mppo_engine_prepare
+ * and the first mppo_engine_update: afterwards it returns MPPO_ESTATE.  MPPO_EINVAL: a negative (or NaN) entry - the message names it -, more than 262144
+ * columns, and, with the noise on, an engine rank outside 0 .. 255. */
+int32_t mppo_engine_set_obs_noise(mppo_engine_t* e, const float* scale);
+/* Actuation latency during training (mppo_action_delay_fill / _apply above; 0 / 0, the default: the engine enqueues exactly the launches, with exactly the
+ * arguments, it enqueues without this call).  max > 0: mppo_engine_reset zeroes arena region "action_hist" and fills "action_delay" (seed and rank: the engine
+ * configuration's), and every rollout step's environment launch is preceded by one mppo_action_delay_apply(action[t] -> "action_applied") and given that buffer
+ * (act_ld = A) instead of action[t], in the captured graph too: one launch more per rollout step.  "action" and "log_prob" stay the policy's own - what PPO's
+ * ratio refers to -; the reward's control cost sees the applied action, which is what the robot did.  The ring is indexed by the environments' own "timestep",
+ * so a checkpoint needs "action_hist" beside the regions it always had and a resumed run continues bit for bit.  The four regions lie behind every other one
+ * and exist whether or not the options are on.  Call before mppo_engine_reset, mppo_engine_prepare and the first mppo_engine_update: afterwards it returns
+ * MPPO_ESTATE.  MPPO_EINVAL: the refusals of mppo_action_delay_fill. */
+int32_t mppo_engine_set_action_delay(mppo_engine_t* e, int32_t min, int32_t max);
 /* one full update: T rollout steps, bootstrap value, GAE, E epochs x M minibatches */
 int32_t mppo_engine_update(mppo_engine_t* e, void* stream);
 /* what mppo_engine_update does before it enqueues anything: the one-time capture of the update into a hipGraph (no device work).
@@ -738,6 +800,22 @@ size_t mppo_eval_domain_ws_bytes(const mppo_model_t* m, const mppo_net_t* net, c
 int32_t mppo_evaluate_domain(const mppo_model_t* m, const mppo_net_t* net, const float* params, const mppo_eval_cfg_t* cfg, void* ws, size_t ws_bytes,
                              const float* obs_table, float clip, const mppo_push_cfg_t* push, int32_t episode_length, const mppo_domain_cfg_t* domain,
                              mppo_eval_result_t* result, mppo_eval_limit_result_t* extra, float* traj, void* stream);
+/* mppo_evaluate_domain under sensor noise and actuation latency - "does it still stand with 20 ms of latency and noisy encoders?".  obs_noise_scale = NULL or
+ * all zero and delay = NULL or 0 / 0: exactly mppo_evaluate_domain, bytes and launches.  Otherwise the documented sequence with
+ *        mppo_action_delay_fill(delay with rank 0 and seed = cfg->seed, N, table) behind the reset, the ring zeroed;
+ *        mppo_obs_noise_apply({cfg->seed, 0}, ..., sigma, NULL, 0, 0) on the observation after the reset (and the initial reinit);
+ *        per step t: mppo_action_delay_apply(action -> applied, act_ld = A) in front of the step, which is given `applied`; and
+ *        mppo_obs_noise_apply(..., NULL, 0, t + 1) behind the step, the time limit's launch and the masked reinit, in front of the observation normalisation
+ * - the same bits when the caller writes it out; both apply under `deterministic` too.  obs_noise_scale: HOST memory, [O] floats (copied into the workspace: the
+ * one host-to-device copy of this call, so enqueue it outside a stream capture; a negative entry is MPPO_EINVAL).  The trajectory's action columns stay the
+ * policy's; traj_applied (device, may be NULL; written only under a latency): [K + 1][R][A], frame t + 1 = what step t's environments 0 .. R - 1 were given, frame 0
+ * zero.  `seed` and `rank` of the delay configuration are not read.  `ws`: >= mppo_eval_sensors_ws_bytes (mppo_eval_domain_ws_bytes' regions, then the ring
+ * [16][N][A], the applied actions, the latency table and sigma), whatever the options are. */
+size_t mppo_eval_sensors_ws_bytes(const mppo_model_t* m, const mppo_net_t* net, const mppo_eval_cfg_t* cfg);
+int32_t mppo_evaluate_sensors(const mppo_model_t* m, const mppo_net_t* net, const float* params, const mppo_eval_cfg_t* cfg, void* ws, size_t ws_bytes,
+                              const float* obs_table, float clip, const mppo_push_cfg_t* push, int32_t episode_length, const mppo_domain_cfg_t* domain,
+                              const float* obs_noise_scale, const mppo_action_delay_cfg_t* delay, mppo_eval_result_t* result, mppo_eval_limit_result_t* extra,
+                              float* traj, float* traj_applied, void* stream);
 int32_t mppo_eval_limit_count(int32_t N, int32_t first, const uint8_t* done, const uint8_t* truncated, void* acc, void* stream);
 int32_t mppo_eval_limit_reduce(int32_t N, const void* acc, mppo_eval_limit_result_t* result, void* stream);
 

@@ -109,6 +109,14 @@ class DomainCfg(C.Structure):  # mppo_domain_cfg_t: domain randomisation (every 
         ("mass_body", c_i32), ("seed", c_u64), ("rank", c_i32)]
 
 
+class ObsNoiseCfg(C.Structure):  # mppo_obs_noise_cfg_t: the stream of the sensor noise (the half-widths are a table of their own)
+    _fields_ = [("seed", c_u64), ("rank", c_i32), ("reserved", c_i32)]
+
+
+class ActionDelayCfg(C.Structure):  # mppo_action_delay_cfg_t: actuation latency in env steps (0 / 0: off)
+    _fields_ = [("min", c_i32), ("max", c_i32), ("rank", c_i32), ("reserved", c_i32), ("seed", c_u64)]
+
+
 class SceneDims(C.Structure):
     _fields_ = [(n, c_i32) for n in ("nq", "nbody", "ngeom", "ncam", "has_plane")]
 
@@ -149,6 +157,9 @@ SIGNATURES = {
     "mppo_env_step_domain": (c_i32, [c_vp, c_i32, c_i32, P(RewardCfg), c_vp, c_vp, c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, P(EnvMetrics), c_i32, c_vp, c_vp,
                                      c_i32, c_vp]),
     "mppo_physics_forward_domain": (c_i32, [c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, P(ForwardProbe), c_i32, c_vp, c_vp, c_i32, c_vp]),
+    "mppo_obs_noise_apply": (c_i32, [P(ObsNoiseCfg), c_i32, c_i32, c_vp, c_i32, c_vp, c_vp, c_i32, c_i32, c_vp]),
+    "mppo_action_delay_fill": (c_i32, [P(ActionDelayCfg), c_i32, c_vp, c_vp]),
+    "mppo_action_delay_apply": (c_i32, [P(ActionDelayCfg), c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_i32, c_vp]),
     "mppo_param_count": (c_sz, [P(Net)]),
     "mppo_policy_ws_bytes": (c_sz, [P(Net), c_i32]),
     "mppo_policy_forward": (c_i32, [P(Net), c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
@@ -204,6 +215,8 @@ SIGNATURES = {
     "mppo_engine_set_push": (c_i32, [c_vp, P(PushCfg)]),
     "mppo_engine_set_time_limit": (c_i32, [c_vp, c_i32, c_i32]),
     "mppo_engine_set_domain": (c_i32, [c_vp, P(DomainCfg)]),
+    "mppo_engine_set_obs_noise": (c_i32, [c_vp, c_vp]),
+    "mppo_engine_set_action_delay": (c_i32, [c_vp, c_i32, c_i32]),
     "mppo_engine_update": (c_i32, [c_vp, c_vp]),
     "mppo_engine_prepare": (c_i32, [c_vp, c_vp]),
     "mppo_engine_graph_active": (c_i32, [c_vp, P(c_i32)]),
@@ -221,6 +234,9 @@ SIGNATURES = {
     "mppo_eval_limit_reduce": (c_i32, [c_i32, c_vp, c_vp, c_vp]),
     "mppo_eval_domain_ws_bytes": (c_sz, [c_vp, P(Net), P(EvalCfg)]),
     "mppo_evaluate_domain": (c_i32, [c_vp, P(Net), c_vp, P(EvalCfg), c_vp, c_sz, c_vp, c_f, P(PushCfg), c_i32, P(DomainCfg), c_vp, c_vp, c_vp, c_vp]),
+    "mppo_eval_sensors_ws_bytes": (c_sz, [c_vp, P(Net), P(EvalCfg)]),
+    "mppo_evaluate_sensors": (c_i32, [c_vp, P(Net), c_vp, P(EvalCfg), c_vp, c_sz, c_vp, c_f, P(PushCfg), c_i32, P(DomainCfg), c_vp, P(ActionDelayCfg), c_vp, c_vp, c_vp,
+                                      c_vp, c_vp]),
     "mppo_scene_open": (c_i32, [c_vp, c_sz, c_vp, P(c_vp)]),
     "mppo_scene_close": (c_i32, [c_vp]),
     "mppo_scene_get_dims": (c_i32, [c_vp, P(SceneDims)]),
@@ -228,7 +244,7 @@ SIGNATURES = {
 }
 
 UNCHECKED = {"mppo_last_error", "mppo_abi_version", "mppo_param_count", "mppo_policy_ws_bytes", "mppo_grad_ws_bytes",
-             "mppo_adam_ws_bytes", "mppo_permutation_ws_bytes", "mppo_eval_ws_bytes", "mppo_eval_limit_ws_bytes", "mppo_eval_domain_ws_bytes", "mppo_obs_norm_partials",
+             "mppo_adam_ws_bytes", "mppo_permutation_ws_bytes", "mppo_eval_ws_bytes", "mppo_eval_limit_ws_bytes", "mppo_eval_domain_ws_bytes", "mppo_eval_sensors_ws_bytes", "mppo_obs_norm_partials",
              "mppo_reward_norm_partials"}
 
 

@@ -40,6 +40,8 @@ FILE_FLAGS["k_rewnorm.hip"] = ["-ffp-contract=off"]
 FILE_FLAGS["k_push.hip"] = ["-ffp-contract=off"]
 # (k_domrand.hip: the domain randomisation's draw, the same multiply and add - held bit-equal to its host restatement)
 FILE_FLAGS["k_domrand.hip"] = ["-ffp-contract=off"]
+# (k_sensor.hip: the sensor noise's draw, the same multiply and add, and the one float32 add onto the observation - held bit-equal to its host restatement)
+FILE_FLAGS["k_sensor.hip"] = ["-ffp-contract=off"]
 # MPPO_REGCHOL_MAX_NV=32: specialised kernels beyond 32 dofs keep their Cholesky factors in LDS instead of registers (the default, 48, is three
 # matrix rows per lane: fastest, at 400 - 500 registers; the library checks every instantiation MPPO_SPECIALIZE adds against the run-time-sized
 # kernel on the device and falls back if they differ)

@@ -94,6 +94,26 @@ class EnvironmentConfig:
     added_mass_min: float = field(default=0.0)
     added_mass_max: float = field(default=0.0)
     added_mass_body: str = field(default="")
+    # Extension (absent upstream; legged_gym `add_noise` / `noise_scale_vec`, MuJoCo Playground `noise_config`): sensor noise.  Above 0, every observation the
+    # policy reads - the reset's included - is the simulator's plus U(-s_j, s_j) per column, s_j = obs_noise_level x the scale of the column's group in the
+    # layout `qpos | qvel | cinert[1:] | cvel[1:] | qfrc_actuator` (without c-values: `qpos | qvel | qfrc_actuator`); the state itself stays exact (DESIGN.md
+    # 3.12).  The group defaults are conventions, not measurements: legged_gym's and Playground's joint-position (0.01), angular-velocity (0.2) and
+    # linear-velocity (0.1) scales; computed quantities (cinert, qfrc_actuator) default to 0.  A free joint's quaternion columns of qpos are perturbed like
+    # any other column and not renormalised.  In training, in `evaluate` (under `deterministic` too) and in `HumanoidEnv`.  0: off, nothing changes.
+    # A negative level or scale: ValueError.
+    obs_noise_level: float = field(default=0.0)
+    obs_noise_qpos: float = field(default=0.01)
+    obs_noise_qvel: float = field(default=0.2)
+    obs_noise_cinert: float = field(default=0.0)
+    obs_noise_cvel: float = field(default=0.1)
+    obs_noise_qfrc: float = field(default=0.0)
+    # Extension (absent upstream; MuJoCo Playground's action latency, Isaac Lab `ActionDelay`): actuation latency.  Every environment has, for the whole run,
+    # a latency of its own drawn in action_delay_min .. action_delay_max env steps (whatever n_frames is; at most 16): the actuators get the action the
+    # policy computed that many steps ago in the same episode, zeros on an episode's first steps.  PPO's ratio keeps the policy's own
+    # action; the reward's control cost sees the applied one.  In training, in `evaluate` and in `HumanoidEnv`.  0 / 0: off, nothing changes.
+    # min < 0, min > max or max > 16: ValueError.
+    action_delay_min: int = field(default=0)
+    action_delay_max: int = field(default=0)
 
 
 @dataclass
@@ -332,6 +352,12 @@ def make_config(yaml_dict: dict | None = None, overrides: Sequence[str] = ()) ->
             raise ValueError(f"environment.{what}_min = {lo!r} > environment.{what}_max = {hi!r}: the range of the domain randomisation is empty")
         if what != "added_mass" and not lo >= 0.0:
             raise ValueError(f"environment.{what}_min = {lo!r}: a scale of the domain randomisation cannot be negative")
+    for key in ("obs_noise_level", "obs_noise_qpos", "obs_noise_qvel", "obs_noise_cinert", "obs_noise_cvel", "obs_noise_qfrc"):
+        if not getattr(env, key) >= 0.0:
+            raise ValueError(f"environment.{key} = {getattr(env, key)!r}: a half-width of the sensor noise cannot be negative")
+    if not 0 <= env.action_delay_min <= env.action_delay_max <= 16:
+        raise ValueError(f"environment.action_delay_min = {env.action_delay_min!r} / action_delay_max = {env.action_delay_max!r}: the latency is a number of env "
+                         "steps with 0 <= min <= max <= 16")
     for key in ("obs_norm_clip", "obs_norm_eps", "reward_norm_clip", "reward_norm_eps"):
         if not getattr(cfg.training, key) >= 0.0:
             raise ValueError(f"training.{key} = {getattr(cfg.training, key)!r} cannot be negative")

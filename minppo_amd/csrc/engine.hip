@@ -24,6 +24,7 @@
 #include "push.h"
 #include "domrand.h"
 #include "limit.h"
+#include "sensor.h"
 
 #include <cmath>
 #include <cstdlib>
@@ -181,6 +182,14 @@ struct mppo_engine {
   // domain randomisation (mppo_engine_set_domain; table null: off - every launch and every argument is what it was).  The table [N][4] is the engine's own
   // allocation, not a region of the arena: it is a function of (seed, rank) alone, so a checkpoint does not carry it and the arena's layout is what it always was
   mppo::EnvDomain domain;
+  // sensor noise and actuation latency (mppo_engine_set_obs_noise / _set_action_delay; off: nothing below is used, no launch is added and the step reads action[t])
+  bool obs_noise;
+  mppo::ObsNoiseDraw noise_draw;
+  float* obs_noise_scale;  // [OP] the per-column half-widths, pad columns 0
+  mppo::DelayDraw delay;   // dmax 0: off
+  float* action_hist;      // [kMaxActionDelay][N][A] the ring of the policy's past actions (the first dmax slots are used)
+  float* action_applied;   // [N][A] what the step launch is given
+  int* action_delay;       // [N] the latency table
 };
 
 namespace mppo {
@@ -254,6 +263,11 @@ static size_t layout(mppo_engine* e, bool assign) {
   e->reward_scaled = (float*)take("reward_scaled", B * 4);
   // the episode time limit's flags: behind those again, present whether or not a limit is set
   e->truncated = (unsigned char*)take("truncated", B);
+  // actuation latency and sensor noise: behind those again, present whether or not the options are on
+  e->action_hist = (float*)take("action_hist", (size_t)kMaxActionDelay * N * A * 4);
+  e->action_applied = (float*)take("action_applied", N * A * 4);
+  e->action_delay = (int*)take("action_delay", N * 4);
+  e->obs_noise_scale = (float*)take("obs_noise_scale", OP * 4);
   return align_up(off, 256);
 }
 
@@ -340,7 +354,15 @@ static int32_t do_rollout(mppo_engine* e, hipStream_t s) {
     // (random pushes: the wrench of step u * T + t, u the device's update index, is drawn inside this launch - a replayed graph draws fresh ones; off: the plain step)
     EnvPush push = e->push;
     push.add = t;
-    MPPO_TRY(env_step_push_ws(e->model, e->N, c.n_frames, &c.reward, e->state, e->reset_rec, e->action + t * N * A, e->A, e->obs + (size_t)(t + 1) * N * OP,
+    // actuation latency: the policy's action goes into the ring, the step is given the one its environment's latency ago (zeros at an episode's start); the
+    // trajectory keeps the policy's own action and log_prob - what PPO's ratio refers to.  Off: the step reads action[t] as it always did
+    const float* act_t = e->action + t * N * A;
+    if (e->delay.dmax > 0) {
+      MPPO_TRY(action_delay_launch(e->N, e->A, e->delay.dmax, e->action_delay, e->met.timestep, e->met.episode_lengths, act_t, e->A, e->action_hist, e->action_applied,
+                                   e->A, s));
+      act_t = e->action_applied;
+    }
+    MPPO_TRY(env_step_push_ws(e->model, e->N, c.n_frames, &c.reward, e->state, e->reset_rec, act_t, e->A, e->obs + (size_t)(t + 1) * N * OP,
                               e->OP, e->reward + t * N, e->done + t * N, &e->met, push, e->env_ws, e->env_ws_bytes, static_cast<hipStream_t>(s), e->domain));            // :165
     // episode time limit: the environments that have reached it are truncated - flags, metrics, the reset record - as the step's epilogue ends an episode;
     // done[t] then includes them, so the masked reinit below restarts them too and the reward scaling's carry restarts behind them
@@ -354,6 +376,10 @@ static int32_t do_rollout(mppo_engine* e, hipStream_t s) {
     if (e->reset_noise > 0.f || e->domain.table)
       MPPO_TRY(env_reinit_ws(e->model, e->N, e->state, e->obs + (size_t)(t + 1) * N * OP, e->OP, e->done + t * N, e->reset_noise, c.rng_impl, c.seed, c.rank,
                              e->reset_rng + 2 * t, e->count + 1, e->T, 1 + t, e->env_ws, e->env_ws_bytes, s, e->domain));
+    // sensor noise: the new rows - restarted environments' included - get the noise of step u * T + t + 1, u the device's update index; what is stored is what
+    // the next forward, the critic's bootstrap, the learn phase and the normalisation's statistics read
+    if (e->obs_noise)
+      MPPO_TRY(obs_noise_launch(e->noise_draw, e->N, e->O, e->obs + (size_t)(t + 1) * N * OP, e->OP, e->obs_noise_scale, e->count + 1, e->T, t + 1, s));
     // observation normalisation: the new rows are stored normalised with this update's table (the next forward and the learn phase read them so);
     // their raw values go into this step's partial sums first
     if (e->obs_norm)
@@ -506,6 +532,7 @@ extern "C" int32_t mppo_engine_create(const mppo_model_t* m, const mppo_engine_c
   e->push = EnvPush{};
   e->limit = LimitCfg{};
   e->domain = EnvDomain{};
+  e->obs_noise = false; e->noise_draw = ObsNoiseDraw{}; e->delay = DelayDraw{};
   *out = e;
   return MPPO_OK;
 }
@@ -560,6 +587,13 @@ extern "C" int32_t mppo_engine_reset(mppo_engine_t* e, void* stream) {
   if (e->reset_noise > 0.f)
     MPPO_TRY(env_reinit_ws(e->model, e->N, e->state, e->obs, e->OP, nullptr, e->reset_noise, e->cfg.rng_impl, e->cfg.seed, e->cfg.rank, e->reset_rng + 2 * e->T, nullptr, 0, 0,
                            e->env_ws, e->env_ws_bytes, s, e->domain));
+  // sensor noise: the row the reset wrote is step 0 of the noise's stream (the state records stay exact)
+  if (e->obs_noise) MPPO_TRY(obs_noise_launch(e->noise_draw, e->N, e->O, e->obs, e->OP, e->obs_noise_scale, nullptr, 0, 0, s));
+  // actuation latency: an empty ring, and the table of every environment's latency (a function of seed and rank: a resumed run has the same robots)
+  if (e->delay.dmax > 0) {
+    MPPO_CHECK_HIP(hipMemsetAsync(e->action_hist, 0, (size_t)kMaxActionDelay * e->N * e->A * 4, s));
+    MPPO_TRY(action_delay_fill_launch(e->delay, e->N, e->action_delay, s));
+  }
   if (e->obs_norm) {  // nothing counted, the identity table (pad columns included); obs[0] above stays raw
     MPPO_CHECK_HIP(hipMemsetAsync(e->obs_norm_stats, 0, (1 + 2 * (size_t)e->O) * 8, s));
     MPPO_TRY(obs_norm_update_launch(e->O, 0, 0, nullptr, e->obs_norm_stats, e->obs_norm_eps, e->obs_norm_table, e->OP, s));
@@ -700,6 +734,46 @@ extern "C" int32_t mppo_engine_set_time_limit(mppo_engine_t* e, int32_t length, 
     return fail(MPPO_ESTATE, "mppo_engine_set_time_limit: mppo_engine_reset has run already: set the limit before it");
   e->limit = LimitCfg{};
   if (length > 0) e->limit = limit_cfg_of(lc);
+  return MPPO_OK;
+}
+
+extern "C" int32_t mppo_engine_set_obs_noise(mppo_engine_t* e, const float* scale) {
+  MPPO_REQUIRE(e, "mppo_engine_set_obs_noise: null engine");
+  MPPO_TRY(check_obs_noise_scale("mppo_engine_set_obs_noise", scale, e->O));
+  bool on = false;
+  if (scale) for (int j = 0; j < e->O; ++j) on = on || scale[j] > 0.f;
+  mppo_obs_noise_cfg_t nc{};
+  nc.seed = e->cfg.seed; nc.rank = on ? e->cfg.rank : 0;  // (the engine's own: one stream per rank, as the pushes have; it fits the stream id's eight bits or the noise is refused)
+  MPPO_TRY(check_obs_noise_cfg("mppo_engine_set_obs_noise", &nc));
+  if (e->graph || e->prepared)
+    return fail(MPPO_ESTATE, "mppo_engine_set_obs_noise: the update has been prepared already (its launch sequence is fixed, a captured graph holds it): "
+                             "set the noise before mppo_engine_prepare and the first mppo_engine_update");
+  if (e->was_reset)
+    return fail(MPPO_ESTATE, "mppo_engine_set_obs_noise: mppo_engine_reset has run already (the observation it wrote has its noise or has none): set the noise before it");
+  e->obs_noise = false;
+  if (on) {  // the table into its region (pad columns 0), before anything is enqueued
+    std::vector<float> table((size_t)e->OP, 0.f);
+    for (int j = 0; j < e->O; ++j) table[j] = scale[j];
+    MPPO_CHECK_HIP(hipMemcpy(e->obs_noise_scale, table.data(), (size_t)e->OP * 4, hipMemcpyHostToDevice));
+    e->obs_noise = true;
+    e->noise_draw = obs_noise_draw_of(nc);
+  }
+  return MPPO_OK;
+}
+
+extern "C" int32_t mppo_engine_set_action_delay(mppo_engine_t* e, int32_t dmin, int32_t dmax) {
+  MPPO_REQUIRE(e, "mppo_engine_set_action_delay: null engine");
+  mppo_action_delay_cfg_t dc{};
+  dc.min = dmin; dc.max = dmax; dc.seed = e->cfg.seed;
+  dc.rank = dmax > 0 ? e->cfg.rank : 0;  // (the engine's own, as above)
+  MPPO_TRY(check_action_delay_cfg("mppo_engine_set_action_delay", &dc));
+  if (e->graph || e->prepared)
+    return fail(MPPO_ESTATE, "mppo_engine_set_action_delay: the update has been prepared already (its launch sequence is fixed, a captured graph holds it): "
+                             "set the latency before mppo_engine_prepare and the first mppo_engine_update");
+  if (e->was_reset)
+    return fail(MPPO_ESTATE, "mppo_engine_set_action_delay: mppo_engine_reset has run already (it empties the ring and writes the latency table): set the latency before it");
+  e->delay = DelayDraw{};
+  if (dmax > 0) e->delay = delay_draw_of(dc);
   return MPPO_OK;
 }
 

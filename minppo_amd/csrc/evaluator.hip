@@ -13,6 +13,7 @@
 #include "push.h"
 #include "limit.h"
 #include "domrand.h"
+#include "sensor.h"
 
 namespace mppo {
 const ModelView& model_view(const mppo_model* m);
@@ -36,10 +37,13 @@ struct EvalWs {
   void* limit_acc;
   // behind those (carve_eval's `domain`): the domain randomisation's table [N][4]
   float* domain;
+  // behind that (carve_eval's `sensors`): the latency's ring [D][N][A], D = kMaxActionDelay, the applied actions [N][A], the latency table [N], the noise's sigma [OP]
+  float *action_hist, *action_applied, *obs_noise_scale;
+  int* action_delay;
 };
 
 // the regions of the workspace, each on a 256-byte boundary (base = null: sizes only)
-static EvalWs carve_eval(const mppo_model* m, const mppo_net_t& net, int N, unsigned char* base, bool limit = false, bool domain = false) {
+static EvalWs carve_eval(const mppo_model* m, const mppo_net_t& net, int N, unsigned char* base, bool limit = false, bool domain = false, bool sensors = false) {
   const ModelView& mv = model_view(m);
   EvalWs w{};
   size_t off = 0;
@@ -71,6 +75,12 @@ static EvalWs carve_eval(const mppo_model* m, const mppo_net_t& net, int N, unsi
   w.env_ws = w.env_ws_bytes ? (float*)take(w.env_ws_bytes) : nullptr;
   if (limit) { w.truncated = take(n); w.limit_acc = take(eval_limit_acc_bytes(N)); }
   if (domain) w.domain = (float*)take(n * 16);
+  if (sensors) {
+    w.action_hist = (float*)take((size_t)kMaxActionDelay * n * net.A * 4);
+    w.action_applied = (float*)take(n * net.A * 4);
+    w.action_delay = (int*)take(n * 4);
+    w.obs_noise_scale = (float*)take((size_t)mv.obs_pad * 4);
+  }
   w.total = align_up(off, 256);
   return w;
 }
@@ -106,8 +116,25 @@ extern "C" size_t mppo_eval_ws_bytes(const mppo_model_t* m, const mppo_net_t* ne
 static int32_t evaluate_impl(const char* who, const mppo_model_t* m, const mppo_net_t* net, const float* params, const mppo_eval_cfg_t* cfg, void* ws, size_t ws_bytes,
                              const float* obs_table, float clip, const mppo_push_cfg_t* push, mppo_eval_result_t* result, float* traj, void* stream,
                              bool limit_ws = false, int32_t episode_length = 0, mppo_eval_limit_result_t* extra = nullptr, bool domain_ws = false,
-                             const mppo_domain_cfg_t* domain = nullptr) {
+                             const mppo_domain_cfg_t* domain = nullptr, bool sensors_ws = false, const float* noise_scale = nullptr,
+                             const mppo_action_delay_cfg_t* delay = nullptr, float* traj_applied = nullptr) {
   MPPO_TRY(check_eval(who, m, net, cfg));
+  // sensor noise (a HOST vector [O]; null or all zero: the evaluation without it, launch for launch) and actuation latency (null or 0 / 0: likewise): rank 0 under
+  // the evaluation's seed, the noise of step k's row at index k + 1 (0: the reset's), under `deterministic` too
+  MPPO_TRY(check_obs_noise_scale(who, noise_scale, net->O));
+  bool noisy_obs = false;
+  if (noise_scale) for (int j = 0; j < net->O; ++j) noisy_obs = noisy_obs || noise_scale[j] > 0.f;
+  mppo_obs_noise_cfg_t nc{};
+  nc.seed = cfg->seed;
+  const ObsNoiseDraw nd = obs_noise_draw_of(nc);
+  DelayDraw dd{};
+  if (delay) {
+    mppo_action_delay_cfg_t dc = *delay;
+    dc.rank = 0; dc.seed = cfg->seed;
+    MPPO_TRY(check_action_delay_cfg(who, &dc));
+    if (dc.max > 0) dd = delay_draw_of(dc);
+  }
+  const bool delayed = dd.dmax > 0;
   // domain randomisation (may be null, or every range at its identity: the evaluation without it, launch for launch): the table is drawn once, from the evaluation's
   // seed as rank 0, and every reset, step and re-initialisation launch reads it
   mppo_domain_cfg_t dc{};
@@ -145,9 +172,9 @@ static int32_t evaluate_impl(const char* who, const mppo_model_t* m, const mppo_
   MPPO_REQUIRE(clip >= 0.f, "%s: clip %g is negative (or not a number)", who, (double)clip);
   const mppo_eval_cfg_t& c = *cfg;
   const int N = c.N, K = c.K, R = c.record_envs, A = net->A;
-  const EvalWs w = carve_eval(m, *net, N, static_cast<unsigned char*>(ws), limit_ws, domain_ws);
+  const EvalWs w = carve_eval(m, *net, N, static_cast<unsigned char*>(ws), limit_ws, domain_ws, sensors_ws);
   MPPO_REQUIRE(ws_bytes >= w.total, "%s: workspace %zu < %zu bytes (%s)", who, ws_bytes, w.total,
-               domain_ws ? "mppo_eval_domain_ws_bytes" : limit_ws ? "mppo_eval_limit_ws_bytes" : "mppo_eval_ws_bytes");
+               sensors_ws ? "mppo_eval_sensors_ws_bytes" : domain_ws ? "mppo_eval_domain_ws_bytes" : limit_ws ? "mppo_eval_limit_ws_bytes" : "mppo_eval_ws_bytes");
   const EnvDomain dom = randomised ? EnvDomain{w.domain, dc.mass_body} : EnvDomain{};
   hipStream_t s = static_cast<hipStream_t>(stream);
   const ModelView& mv = model_view(m);
@@ -161,6 +188,16 @@ static int32_t evaluate_impl(const char* who, const mppo_model_t* m, const mppo_
   MPPO_TRY(env_reset_ws(m, N, w.state, w.reset_rec, w.obs, OP, w.reward, w.done, &w.met, w.env_ws, w.env_ws_bytes, s, dom));
   if (noisy_reset)  // event 0 of the reset noise's Philox stream: every environment starts from a state of its own
     MPPO_TRY(env_reinit_ws(m, N, w.state, w.obs, OP, nullptr, c.reset_noise_scale, 0, c.seed, 0, nullptr, nullptr, 1, 0, w.env_ws, w.env_ws_bytes, s, dom));
+  if (noisy_obs) {  // the sigma table into the workspace (pad columns 0; the one host-to-device copy of this call), then the reset's row: step 0
+    MPPO_CHECK_HIP(hipMemsetAsync(w.obs_noise_scale, 0, (size_t)OP * 4, s));
+    MPPO_CHECK_HIP(hipMemcpyAsync(w.obs_noise_scale, noise_scale, (size_t)net->O * 4, hipMemcpyHostToDevice, s));
+    MPPO_TRY(obs_noise_launch(nd, N, net->O, w.obs, OP, w.obs_noise_scale, nullptr, 0, 0, s));
+  }
+  if (delayed) {  // an empty ring, every environment's latency; frame 0 of the applied actions' trajectory is zero as the action columns of frame 0 are
+    MPPO_CHECK_HIP(hipMemsetAsync(w.action_hist, 0, (size_t)kMaxActionDelay * N * A * 4, s));
+    MPPO_TRY(action_delay_fill_launch(dd, N, w.action_delay, s));
+    if (traj_applied && R > 0) MPPO_CHECK_HIP(hipMemsetAsync(traj_applied, 0, (size_t)R * A * 4, s));
+  }
   if (c.deterministic) MPPO_TRY(eval_zero_launch(w.noise, (size_t)N * A, s));
   // frame 0: the initial states, the action / reward / done columns zero
   MPPO_TRY(eval_accumulate_launch(0, N, true, nullptr, nullptr, nullptr, nullptr, w.state, mv.rec_dim, row_w, nullptr, A, A, R, traj, s));
@@ -168,13 +205,21 @@ static int32_t evaluate_impl(const char* who, const mppo_model_t* m, const mppo_
     if (!c.deterministic) MPPO_TRY(normal_fill_ctr(c.seed, (unsigned long long)t, nullptr, (size_t)N * A, w.noise, s));
     MPPO_TRY(policy_forward(*net, params, N, w.obs, OP, fb, w.noise, w.action, w.log_prob, w.value, nullptr, s));
     ep.add = t;
-    MPPO_TRY(env_step_push_ws(m, N, c.n_frames, &c.reward, w.state, w.reset_rec, w.action, A, w.obs, OP, w.reward, w.done, &w.met, ep, w.env_ws, w.env_ws_bytes, s, dom));
+    const float* act = w.action;
+    if (delayed) {  // the step is given the action of its environment's latency ago; the trajectory's action columns stay the policy's
+      MPPO_TRY(action_delay_launch(N, A, dd.dmax, w.action_delay, w.met.timestep, w.met.episode_lengths, w.action, A, w.action_hist, w.action_applied, A, s));
+      act = w.action_applied;
+      if (traj_applied && R > 0)  // (the first R rows of the dense [N][A] buffer: one contiguous block)
+        MPPO_CHECK_HIP(hipMemcpyAsync(traj_applied + (size_t)(t + 1) * R * A, w.action_applied, (size_t)R * A * 4, hipMemcpyDeviceToDevice, s));
+    }
+    MPPO_TRY(env_step_push_ws(m, N, c.n_frames, &c.reward, w.state, w.reset_rec, act, A, w.obs, OP, w.reward, w.done, &w.met, ep, w.env_ws, w.env_ws_bytes, s, dom));
     if (lim.length > 0)  // the environments that have reached the limit are truncated: done, the metrics and the reset record as the step ends an episode
       MPPO_TRY(time_limit_launch(lim, N, mv.rec_dim, OP, w.state, w.reset_rec, w.obs, OP, w.done, w.truncated, w.met, s));
     // the environments whose episode ended restart from a randomised state (event t + 1), as in the engine's rollout; under domain randomisation every restart
     // goes through the reset kernel with the environment's own row (the one shared reset record is another robot's), at scale 0 without reset noise
     if (noisy_reset || randomised)
       MPPO_TRY(env_reinit_ws(m, N, w.state, w.obs, OP, w.done, c.reset_noise_scale, 0, c.seed, 0, nullptr, nullptr, 1, t + 1, w.env_ws, w.env_ws_bytes, s, dom));
+    if (noisy_obs) MPPO_TRY(obs_noise_launch(nd, N, net->O, w.obs, OP, w.obs_noise_scale, nullptr, 0, t + 1, s));  // (restarted environments' rows included)
     if (obs_table)  // the next forward reads what the policy was trained on; the observation after the reset stays raw, as in the engine (the state rows are raw throughout)
       MPPO_TRY(obs_norm_apply_launch(N, net->O, w.obs, OP, obs_table, net->O, clip, nullptr, s));
     MPPO_TRY(eval_accumulate_launch(N, N, t == 0, w.reward, w.done, &w.met, w.acc, w.state, mv.rec_dim, row_w, w.action, A, A, R,
@@ -220,4 +265,17 @@ extern "C" int32_t mppo_evaluate_domain(const mppo_model_t* m, const mppo_net_t*
                                         const float* obs_table, float clip, const mppo_push_cfg_t* push, int32_t episode_length, const mppo_domain_cfg_t* domain,
                                         mppo_eval_result_t* result, mppo_eval_limit_result_t* extra, float* traj, void* stream) {
   return evaluate_impl("mppo_evaluate_domain", m, net, params, cfg, ws, ws_bytes, obs_table, clip, push, result, traj, stream, true, episode_length, extra, true, domain);
+}
+
+extern "C" size_t mppo_eval_sensors_ws_bytes(const mppo_model_t* m, const mppo_net_t* net, const mppo_eval_cfg_t* cfg) {
+  if (check_eval("mppo_eval_sensors_ws_bytes", m, net, cfg) != MPPO_OK) return 0;
+  return carve_eval(m, *net, cfg->N, nullptr, true, true, true).total;
+}
+
+extern "C" int32_t mppo_evaluate_sensors(const mppo_model_t* m, const mppo_net_t* net, const float* params, const mppo_eval_cfg_t* cfg, void* ws, size_t ws_bytes,
+                                         const float* obs_table, float clip, const mppo_push_cfg_t* push, int32_t episode_length, const mppo_domain_cfg_t* domain,
+                                         const float* obs_noise_scale, const mppo_action_delay_cfg_t* delay, mppo_eval_result_t* result,
+                                         mppo_eval_limit_result_t* extra, float* traj, float* traj_applied, void* stream) {
+  return evaluate_impl("mppo_evaluate_sensors", m, net, params, cfg, ws, ws_bytes, obs_table, clip, push, result, traj, stream, true, episode_length, extra, true, domain,
+                       true, obs_noise_scale, delay, traj_applied);
 }

@@ -27,7 +27,7 @@ import numpy as np
 from minppo_amd import _native as nat
 from minppo_amd.config import Config, load_config_from_cli, require
 from minppo_amd.model import CompiledModel, load_model
-from minppo_amd.train import domain_body_id, domain_cfg, push_body_id, push_cfg, resolve_model, reward_cfg
+from minppo_amd.train import action_delay_cfg, domain_body_id, domain_cfg, obs_noise_scales, push_body_id, push_cfg, resolve_model, reward_cfg
 
 logger = logging.getLogger(__name__)
 
@@ -47,13 +47,26 @@ class EnvMetrics(NamedTuple):
     returned_episode: Any
 
 
-class EnvState(NamedTuple):
+class _EnvStateFields(NamedTuple):
     pipeline_state: Any  # [N, rec_dim] float32 record (layout: include/minppo_hip.h)
     obs: Any
     reward: Any
     done: Any
     metrics: EnvMetrics
     truncation: Any = None  # extension (Brax: `state.info["truncation"]`): bool [N], the environments `environment.episode_length` cut at this step (a subset of `done`); None without a limit
+
+
+class EnvState(_EnvStateFields):
+    """The six fields above - as a tuple it is what it always was - plus the optional trailing `action_history` (extension): float32 [D, N, A], the ring of the
+    policy's past actions under `environment.action_delay_max` = D > 0 (slot metrics.timestep mod D holds that step's action); None without a latency.  It is an
+    attribute beside the tuple's fields, not a seventh element: `len`, unpacking and `_replace` see six (`_replace` returns a state without it)."""
+
+    action_history: Any = None
+
+    def __new__(cls, pipeline_state, obs, reward, done, metrics, truncation=None, action_history=None):
+        self = super().__new__(cls, pipeline_state, obs, reward, done, metrics, truncation)
+        self.action_history = action_history
+        return self
 
 
 class HumanoidEnv:
@@ -105,6 +118,17 @@ class HumanoidEnv:
         self._domain_cfg = domain_cfg(config, self.cm, config.training.seed)
         self._domain_body = domain_body_id(config, self.cm, always=True)
         self._domain = None
+        # sensor noise (`environment.obs_noise_*`): the per-column half-widths as the [OP] device table the kernel reads (None: off); rank 0, seed `training.seed`,
+        # the step index metrics.timestep[0] (0 for `reset`).  Actuation latency (`environment.action_delay_min / _max`): `_delays` is the table of the last reset
+        sig = obs_noise_scales(config, self.cm)
+        self._obs_noise = None
+        if sig is not None:
+            table = np.zeros(self.dims.obs_pad, np.float32)
+            table[:sig.size] = sig
+            self._obs_noise = torch.from_numpy(table).to(self.device)
+        self._noise_cfg = nat.ObsNoiseCfg(seed=int(config.training.seed) & 0xFFFFFFFFFFFFFFFF, rank=0, reserved=0)
+        self._delay_cfg = action_delay_cfg(config, config.training.seed)
+        self._delays = None
         self._have_reset = False
         self._camera_name = config.visualization.camera_name
         self._renderer = None
@@ -193,8 +217,15 @@ class HumanoidEnv:
                 self.lib.env_reinit(self._model, N, state.data_ptr(), obs.data_ptr(), self.dims.obs_pad, 0, float(self.reset_noise_scale), impl, 0, 0, keys.data_ptr(), 0, 0,
                                     self._stream())
             self._noise_keep = keys  # (lives until the next call: the launch reads it; same-stream allocations are reused in stream order)
+        if self._obs_noise is not None:  # the policy's first observation is a noisy one too (step 0 of the noise's stream); the state stays exact
+            self.lib.obs_noise_apply(C.byref(self._noise_cfg), N, self.observation_size, obs.data_ptr(), self.dims.obs_pad, self._obs_noise.data_ptr(), None, 0, 0,
+                                     self._stream())
+        hist = None
+        if self._delay_cfg is not None:  # every environment's latency for its steps until the next reset, and an empty ring
+            self._delays = self.action_delays(N)
+            hist = t.zeros(self._delay_cfg.max, N, self._action_size, dtype=t.float32, device=self.device)
         self._have_reset = True
-        return EnvState(state, obs[:, :self.observation_size], reward, done.bool(), m)
+        return EnvState(state, obs[:, :self.observation_size], reward, done.bool(), m, None, hist)
 
     # -- env.py:148-196 -----------------------------------------------------------
     def step(self, env_state: EnvState, action: Any, rng: Any = None, *, xfrc: Any = None) -> EnvState:
@@ -219,6 +250,15 @@ class HumanoidEnv:
         dom = self._domain
         if dom is not None and dom.shape[0] != N:
             raise ValueError(f"step: {N} environments, but the last reset randomised {dom.shape[0]} - reset(num_envs={N}) first")
+        hist = None
+        if self._delay_cfg is not None:  # actuation latency: the step is given the action of the environment's latency ago (mppo_action_delay_apply, on the metrics as they stand before the step)
+            if env_state.action_history is None or self._delays is None or self._delays.shape[0] != N:
+                raise ValueError("step: environment.action_delay_max > 0 needs the EnvState of a reset() of this environment (its action_history and latency table)")
+            hist = env_state.action_history.clone()
+            applied = t.empty(N, self._action_size, dtype=t.float32, device=self.device)
+            self.lib.action_delay_apply(C.byref(self._delay_cfg), N, self._action_size, self._delays.data_ptr(), m.timestep.data_ptr(), m.episode_lengths.data_ptr(),
+                                        action.data_ptr(), self._action_size, hist.data_ptr(), applied.data_ptr(), self._action_size, self._stream())
+            action = applied
         if xfrc is not None:
             xfrc = (xfrc if hasattr(xfrc, "data_ptr") else t.as_tensor(np.asarray(xfrc, np.float32))).to(device=self.device, dtype=t.float32).contiguous()
             if xfrc.shape != (N, 6):
@@ -251,7 +291,10 @@ class HumanoidEnv:
             self.lib.env_reinit(self._model, N, state.data_ptr(), obs.data_ptr(), self.dims.obs_pad, done.data_ptr(), float(self.reset_noise_scale), impl, 0, 0,
                                 keys.data_ptr(), 0, 0, self._stream())
             self._noise_keep = keys
-        return EnvState(state, obs[:, :self.observation_size], reward, done.bool(), m, None if truncated is None else truncated.bool())
+        if self._obs_noise is not None:  # behind the restarts, so their rows are noisy too; the step index is environment 0's timestep after the step, read on the device
+            self.lib.obs_noise_apply(C.byref(self._noise_cfg), N, self.observation_size, obs.data_ptr(), self.dims.obs_pad, self._obs_noise.data_ptr(),
+                                     m.timestep.data_ptr(), 1, 0, self._stream())
+        return EnvState(state, obs[:, :self.observation_size], reward, done.bool(), m, None if truncated is None else truncated.bool(), hist)
 
     def push_wrench(self, step: int, num_envs: int, seed: Optional[int] = None) -> Any:
         """The wrench [num_envs, 6] the random pushes of `environment.push_force / push_interval / push_duration` put on the environments at env step
@@ -277,6 +320,26 @@ class HumanoidEnv:
             p.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
         out = t.empty(int(num_envs), 4, dtype=t.float32, device=self.device)
         self.lib.domain_fill(C.byref(p), int(num_envs), out.data_ptr(), self._stream())
+        return out
+
+    def obs_noise_scales(self) -> np.ndarray:
+        """The half-width of the sensor noise per observation column, float32 [O] (`environment.obs_noise_level` x the scale of the column's group; all zero
+        when the noise is off); `jaxrng.obs_noise_philox(seed, 0, step, num_envs, scales)` is the noise of step `step` (0: `reset`, else metrics.timestep[0])."""
+        if self._obs_noise is None:
+            return np.zeros(self.observation_size, np.float32)
+        return self._obs_noise[:self.observation_size].cpu().numpy()
+
+    def action_delays(self, num_envs: int, seed: Optional[int] = None) -> Any:
+        """The latency, in env steps, of each of `num_envs` environments - int32 [num_envs] - that `reset(num_envs=)` draws and keeps for its steps
+        (`mppo_action_delay_fill`; rank 0; seed: `training.seed`); `jaxrng.action_delays_philox` is its host statement."""
+        if self._delay_cfg is None:
+            raise ValueError("action_delays: environment.action_delay_max is 0 - there is no latency to draw")
+        t = self.torch
+        p = nat.ActionDelayCfg.from_buffer_copy(self._delay_cfg)
+        if seed is not None:
+            p.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        out = t.empty(int(num_envs), dtype=t.int32, device=self.device)
+        self.lib.action_delay_fill(C.byref(p), int(num_envs), out.data_ptr(), self._stream())
         return out
 
     # -- env.py:245-261 / 238-242 / 199-235 on the state record (host-side views, for inspection) ------

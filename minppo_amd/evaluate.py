@@ -25,6 +25,10 @@ result - and its JSON line - gain `truncated_episodes` (the episodes the limit c
 `survivors` is the number of environments that never FELL (without a limit that is the same thing as "none of its episodes ended") and
 `survivor_mean_return` is null (a survivor's return is spread over its truncated episodes, which `mean_return` already covers).  The trajectory's
 `done` column includes the truncations.
+
+Under sensor noise (`environment.obs_noise_level` > 0) and actuation latency (`environment.action_delay_max` > 0) the call goes through
+`mppo_evaluate_sensors` - "does it still stand with 20 ms of latency and noisy encoders?" - under `deterministic` too; the JSON line echoes the keys that are
+on, and under a latency the trajectory gains `applied_action` (what the actuators were given; `action` stays the policy's own).
 """
 
 from __future__ import annotations
@@ -67,6 +71,7 @@ class EvalResult:
     mean_reward: float
     steps: int
     domain: Optional[Dict[str, float]] = None  # under domain randomisation only: the six numbers of its ranges (None without it: the key set is what it was)
+    sensors: Optional[Dict[str, float]] = None  # under sensor noise / actuation latency only: the keys that are on (None without either)
     truncated_episodes: Optional[int] = None  # under an episode time limit only (None without one: the statistics' key set is then what it always was)
     falls: Optional[int] = None
     trajectory: Optional[Dict[str, np.ndarray]] = None
@@ -84,6 +89,9 @@ class EvalResult:
         dom = d.pop("domain")
         if dom is not None:  # (the ranges the figures belong to: a robustness sweep's lines say what they measured)
             d.update(dom)
+        sens = d.pop("sensors")
+        if sens is not None:  # (likewise: the noise and the latency the figures were measured under)
+            d.update(sens)
         return d
 
 
@@ -154,20 +162,31 @@ def eval_cfg(config: Config, **overrides: Any) -> nat.EvalCfg:
 
 def run(lib: nat.Lib, xp: str, device: Any, stream: Any, model: C.c_void_p, dims: nat.ModelDims, net: nat.Net, params_dev: Any,
         ecfg: nat.EvalCfg, obs_norm: Optional[Dict[str, Any]] = None, push: Optional[nat.PushCfg] = None, episode_length: int = 0,
-        domain: Optional[nat.DomainCfg] = None) -> EvalResult:
+        domain: Optional[nat.DomainCfg] = None, obs_noise: Optional[np.ndarray] = None, action_delay: Optional[nat.ActionDelayCfg] = None) -> EvalResult:
     """One `mppo_evaluate` on an open model and parameters already in device memory (`Trainer.evaluate` comes in here); with `obs_norm`
     ({"mean", "inv_std", "clip"}) one `mppo_evaluate_obs_norm`: the policy reads observations normalised with that table; with `push`
     (`train.push_cfg`: random pushes, with or without a table) one `mppo_evaluate_push`; with `episode_length` > 0 (an episode time limit, with or
     without either) one `mppo_evaluate_limit`; with `domain` (`train.domain_cfg`: domain randomisation, with or without any of those) one
-    `mppo_evaluate_domain`."""
+    `mppo_evaluate_domain`; with `obs_noise` (`train.obs_noise_scales`: float32 [O]) or `action_delay` (`train.action_delay_cfg`), with or without any of
+    those, one `mppo_evaluate_sensors` - under a latency the trajectory then carries "applied_action"."""
+    sensors = obs_noise is not None or action_delay is not None
+    if obs_noise is not None:
+        obs_noise = np.ascontiguousarray(obs_noise, np.float32).reshape(-1)
+        if obs_noise.size != dims.obs_dim:
+            raise ValueError(f"evaluate: obs_noise of {obs_noise.size} columns, the robot's observation has {dims.obs_dim}")
     table, clip = obs_norm_table(obs_norm, dims.obs_dim)
     limited = int(episode_length) > 0
     if int(episode_length) < 0:
         raise ValueError(f"evaluate: episode_length = {episode_length!r} cannot be negative")
     res_bytes = C.sizeof(nat.EvalResultRaw)  # (under a limit the second result lies behind the first in the same allocation)
 
-    def call(ws, res, traj, s):
-        if domain is not None:
+    def call(ws, res, traj, s, traj_applied=None):
+        if sensors:
+            lib.evaluate_sensors(model, C.byref(net), nat.ptr(params_dev), C.byref(ecfg), nat.ptr(ws), need, nat.ptr(table_dev), clip,
+                                 C.byref(push) if push is not None else None, int(episode_length), C.byref(domain) if domain is not None else None,
+                                 nat.ptr(obs_noise), C.byref(action_delay) if action_delay is not None else None, nat.ptr(res), nat.ptr(res) + res_bytes,
+                                 nat.ptr(traj), nat.ptr(traj_applied), s)
+        elif domain is not None:
             lib.evaluate_domain(model, C.byref(net), nat.ptr(params_dev), C.byref(ecfg), nat.ptr(ws), need, nat.ptr(table_dev), clip,
                                 C.byref(push) if push is not None else None, int(episode_length), C.byref(domain), nat.ptr(res), nat.ptr(res) + res_bytes,
                                 nat.ptr(traj), s)
@@ -182,7 +201,7 @@ def run(lib: nat.Lib, xp: str, device: Any, stream: Any, model: C.c_void_p, dims
         else:
             lib.evaluate_obs_norm(model, C.byref(net), nat.ptr(params_dev), C.byref(ecfg), nat.ptr(ws), need, nat.ptr(table_dev), clip, nat.ptr(res), nat.ptr(traj), s)
 
-    need = int((lib.eval_domain_ws_bytes if domain is not None else lib.eval_limit_ws_bytes if limited else lib.eval_ws_bytes)(model, C.byref(net), C.byref(ecfg)))
+    need = int((lib.eval_sensors_ws_bytes if sensors else lib.eval_domain_ws_bytes if domain is not None else lib.eval_limit_ws_bytes if limited else lib.eval_ws_bytes)(model, C.byref(net), C.byref(ecfg)))
     if need == 0:  # the arguments are ones mppo_evaluate refuses: let it say why
         lib.evaluate(model, C.byref(net), nat.ptr(params_dev), C.byref(ecfg), None, 0, None, None, None)
     K, R, nq, nv, A = ecfg.K, ecfg.record_envs, dims.nq, dims.nv, net.A
@@ -198,12 +217,14 @@ def run(lib: nat.Lib, xp: str, device: Any, stream: Any, model: C.c_void_p, dims
         ws, res = alloc(need), alloc(res_bytes + C.sizeof(nat.EvalLimitResultRaw))
         table_dev = torch.from_numpy(table).to(device) if table is not None else None
         traj = alloc((K + 1) * R * W * 4).view(torch.float32).reshape(K + 1, R, W) if R > 0 else None
+        applied = alloc((K + 1) * R * A * 4).view(torch.float32).reshape(K + 1, R, A) if R > 0 and action_delay is not None else None
         with torch.cuda.device(device):
             torch.cuda.synchronize(device)  # (the allocations were zeroed on torch's current stream)
-            call(ws, res, traj, stream.cuda_stream)
+            call(ws, res, traj, stream.cuda_stream, applied)
             stream.synchronize()
         res_host = res.cpu().numpy()
         traj_host = traj.cpu().numpy() if traj is not None else None
+        applied_host = applied.cpu().numpy() if applied is not None else None
     else:  # NumPy "device" memory: the CPU emulator build of the test-suite
 
         def alloc(nbytes):
@@ -213,9 +234,12 @@ def run(lib: nat.Lib, xp: str, device: Any, stream: Any, model: C.c_void_p, dims
 
         ws, res_host = alloc(need), alloc(res_bytes + C.sizeof(nat.EvalLimitResultRaw))
         traj_host = alloc((K + 1) * R * W * 4).view(np.float32).reshape(K + 1, R, W) if R > 0 else None
+        applied_host = alloc((K + 1) * R * A * 4).view(np.float32).reshape(K + 1, R, A) if R > 0 and action_delay is not None else None
         table_dev = table
-        call(ws, res_host, traj_host, None)
+        call(ws, res_host, traj_host, None, applied_host)
     out = result_from_struct(nat.EvalResultRaw.from_buffer_copy(res_host.tobytes()[:res_bytes]), split_trajectory(traj_host, nq, nv, A) if traj_host is not None else None)
+    if applied_host is not None:  # (what the actuators were given; "action" stays the policy's own)
+        out.trajectory["applied_action"] = np.array(applied_host)
     if limited:
         extra = nat.EvalLimitResultRaw.from_buffer_copy(res_host.tobytes()[res_bytes:])
         out.truncated_episodes = int(extra.truncated_episodes)
@@ -232,7 +256,7 @@ def evaluate(config: Config, params: Any, *, lib: Optional[nat.Lib] = None, xp: 
     the robot, network geometry, reward window and `evaluation` section of `config`.  `lib=` / `xp="numpy"` as in `Trainer`.
     A tree or pickle with an "obs_norm" entry (a policy trained with `training.normalize_observations`) is evaluated on observations normalised
     with it; `obs_norm=` ({"mean", "inv_std", "clip"}) supplies the entry for a flat vector or overrides the tree's.  A flat vector without it: none."""
-    from minppo_amd.train import domain_cfg, domain_echo, domain_on, open_model, push_cfg, resolve_model
+    from minppo_amd.train import action_delay_cfg, domain_cfg, domain_echo, domain_on, obs_noise_scales, open_model, push_cfg, resolve_model, sensors_echo
 
     lib = lib if lib is not None else nat.load()
     if not 1 <= config.model.num_layers <= 4:
@@ -262,7 +286,9 @@ def evaluate(config: Config, params: Any, *, lib: Optional[nat.Lib] = None, xp: 
         flat = _flat_params(params, dims.obs_dim, dims.nu, config.model.hidden_size, L)
         params_dev = torch.from_numpy(flat).to(device) if torch is not None else np.ascontiguousarray(flat)
         result = run(lib, xp, device, stream, model, dims, net, params_dev, ecfg, obs_norm=obs_norm, push=push_cfg(config, cm, ecfg.seed),
-                     episode_length=int(config.environment.episode_length), domain=domain_cfg(config, cm, ecfg.seed))
+                     episode_length=int(config.environment.episode_length), domain=domain_cfg(config, cm, ecfg.seed),
+                     obs_noise=obs_noise_scales(config, cm), action_delay=action_delay_cfg(config, ecfg.seed))
+        result.sensors = sensors_echo(config) or None
         if domain_on(config):
             result.domain = domain_echo(config)
     finally:

@@ -253,3 +253,47 @@ def domain_params_philox(seed: int, rank: int, num_envs: int, friction=(1.0, 1.0
         lo, hi = np.float32(lo), np.float32(hi)
         out[:, k] = np.maximum(lo, f * (hi - lo) + lo).astype(np.float32)
     return out
+
+
+_OBS_NOISE_STREAM = 0x4F4E4F4953 << 24  # "ONOIS": the Philox stream of the sensor noise (csrc/sensor.h kStreamObsNoise)
+
+
+def obs_noise_philox(seed: int, rank: int, step: int, num_envs: int, sigma) -> np.ndarray:
+    """The noise the sensor-noise stage adds to the observation rows of env step `step` (csrc/sensor.h, bit for bit what `mppo_obs_noise_apply` adds): with
+    S = "ONOIS" << 24 + (rank << 16), column j of local environment n gets uniform(word j & 3 of philox((n, step, lo(S) + (j >> 2), hi(S)), seed), -sigma[j],
+    sigma[j]); a column whose sigma is 0 gets an exact 0 here and is NOT WRITTEN by the kernel (so `obs + noise` in float32 is the kernel's row up to the sign
+    of a zero in such a column).  Steps: 0 is the row a reset writes, the engine's step t of update u is u * T + t + 1, the evaluator's step k is k + 1 (seed:
+    the evaluation's, rank 0) -> float32 [N, O]."""
+    sigma = np.asarray(sigma, np.float32).reshape(-1)
+    if not np.all(sigma >= 0):
+        raise ValueError("observation noise: a scale is negative (or not a number)")
+    O = sigma.size
+    nblk = (O + 3) // 4
+    if nblk > 65536:
+        raise ValueError(f"observation noise: {O} columns (the block index has 16 bits)")
+    n = np.repeat(np.arange(num_envs, dtype=np.uint64), nblk)
+    st = _OBS_NOISE_STREAM + (int(rank) << 16)
+    s0 = (np.uint64(st & 0xFFFFFFFF) + np.tile(np.arange(nblk, dtype=np.uint64), num_envs)) & np.uint64(0xFFFFFFFF)
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    z = np.stack(_philox4x32(n, np.full_like(n, int(step) & 0xFFFFFFFF), s0, np.full_like(n, st >> 32), seed & 0xFFFFFFFF, seed >> 32), 1)
+    bits = z.reshape(num_envs, nblk * 4)[:, :O].astype(np.uint32)
+    f = ((bits >> np.uint32(9)) | np.uint32(0x3F800000)).view(np.float32) - np.float32(1.0)
+    lo, hi = -sigma, sigma
+    u = np.maximum(lo, (f * (hi - lo)).astype(np.float32) + lo).astype(np.float32)
+    return np.where(sigma > 0, u, np.float32(0.0)).astype(np.float32)
+
+
+_DELAY_STREAM = 0x44454C4159 << 24  # "DELAY": the Philox stream of the actuation latency (csrc/sensor.h kStreamDelay)
+
+
+def action_delays_philox(seed: int, rank: int, num_envs: int, dmin: int, dmax: int) -> np.ndarray:
+    """The actuation latency, in env steps, of each of a rank's `num_envs` local environments for the whole run (csrc/sensor.h delay_draw, bit for bit what
+    `mppo_action_delay_fill` writes): with S = "DELAY" << 24 + (rank << 16), d_n = dmin + word0(philox((n, 0xFFFFFFFC, lo(S), hi(S)), seed)) mod (dmax - dmin + 1).
+    The engine draws with its configuration's seed and rank, the evaluator with the evaluation's seed as rank 0 -> int32 [N]."""
+    if not 0 <= dmin <= dmax <= 16:
+        raise ValueError(f"action delay: {dmin} .. {dmax} (0 <= min <= max <= 16)")
+    n = np.arange(num_envs, dtype=np.uint64)
+    st = _DELAY_STREAM + (int(rank) << 16)
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    w = _philox4x32(n, np.full_like(n, 0xFFFFFFFC), np.full_like(n, st & 0xFFFFFFFF), np.full_like(n, st >> 32), seed & 0xFFFFFFFF, seed >> 32)[0]
+    return (dmin + (w & np.uint64(0xFFFFFFFF)) % np.uint64(dmax - dmin + 1)).astype(np.int32)

@@ -177,7 +177,7 @@ def tree_to_flat(tree: dict, O: int, A: int, H: int, L: int = 2) -> np.ndarray:
 
 _REGION_DTYPES = {
     "count": "int32", "done": "uint8", "perm": "int32", "adv_sums": "float64", "episode_lengths": "int32",
-    "returned_episode_lengths": "int32", "timestep": "int32", "returned_episode": "uint8", "truncated": "uint8", "jax_rng": "int32", "reset_rng": "int32",
+    "returned_episode_lengths": "int32", "timestep": "int32", "returned_episode": "uint8", "truncated": "uint8", "action_delay": "int32", "jax_rng": "int32", "reset_rng": "int32",
     "obs_norm_stats": "float64", "obs_norm_partials": "float64", "reward_norm_stats": "float64", "reward_norm_partials": "float64",
 }
 
@@ -254,6 +254,47 @@ def domain_echo(config: Config) -> Dict[str, float]:
     env = config.environment
     return {k: float(getattr(env, k)) for k in ("friction_scale_min", "friction_scale_max", "actuator_scale_min", "actuator_scale_max", "added_mass_min",
                                                  "added_mass_max")}
+
+
+_OBS_NOISE_KEYS = ("obs_noise_level", "obs_noise_qpos", "obs_noise_qvel", "obs_noise_cinert", "obs_noise_cvel", "obs_noise_qfrc")
+_ACTION_DELAY_KEYS = ("action_delay_min", "action_delay_max")
+
+
+def obs_noise_scales(config: Config, cm: CompiledModel) -> Optional[np.ndarray]:
+    """The half-width of the sensor noise per observation column, float32 [O]: `environment.obs_noise_level` x the scale of the column's group in the layout
+    `CompiledModel.obs_size` / `to_blob` define - qpos | qvel | cinert[1:] | cvel[1:] | qfrc_actuator, without c-values qpos | qvel | qfrc_actuator.  None when
+    the level is 0 or every column comes out 0 (off)."""
+    env = config.environment
+    level = float(env.obs_noise_level)
+    if not level > 0:
+        return None
+    nb = cm.nbody - 1
+    groups = [(cm.nq, env.obs_noise_qpos), (cm.nv, env.obs_noise_qvel)]
+    if env.include_c_vals:
+        groups += [(10 * nb, env.obs_noise_cinert), (6 * nb, env.obs_noise_cvel)]
+    groups += [(cm.nv, env.obs_noise_qfrc)]
+    out = np.concatenate([np.full(n, np.float32(level) * np.float32(s), np.float32) for n, s in groups])
+    assert out.size == cm.obs_size(env.include_c_vals)
+    return out if np.any(out > 0) else None
+
+
+def action_delay_cfg(config: Config, seed: int = 0, rank: int = 0) -> Optional[nat.ActionDelayCfg]:
+    """`mppo_action_delay_cfg_t` of `environment.action_delay_min / _max`; None when the maximum is 0 (off)."""
+    env = config.environment
+    if not env.action_delay_max > 0:
+        return None
+    return nat.ActionDelayCfg(min=int(env.action_delay_min), max=int(env.action_delay_max), rank=int(rank), reserved=0, seed=int(seed) & 0xFFFFFFFFFFFFFFFF)
+
+
+def sensors_echo(config: Config) -> Dict[str, float]:
+    """The sensor-noise and latency keys that are on, as `evaluate` echoes them in its JSON line."""
+    env = config.environment
+    out: Dict[str, float] = {}
+    if env.obs_noise_level > 0:
+        out.update({k: float(getattr(env, k)) for k in _OBS_NOISE_KEYS})
+    if env.action_delay_max > 0:
+        out.update({k: int(getattr(env, k)) for k in _ACTION_DELAY_KEYS})
+    return out
 
 
 def open_model(lib: nat.Lib, config: Config, cm: CompiledModel, xp: str, device: Any = None, verbose: bool = False):
@@ -383,6 +424,15 @@ class Trainer:
         self.episode_length = int(config.environment.episode_length)  # (make_config refuses a negative one; so does the engine)
         if self.episode_length > 0:
             self.lib.engine_set_time_limit(self._engine, self.episode_length, 1 if config.environment.episode_length_stagger else 0)
+        # environment.obs_noise_* (sensor noise) and action_delay_min / _max (actuation latency), DESIGN.md 3.12: off leaves every launch as it is.  The noise is
+        # a function of (seed, rank, environment, update index * T + t + 1, column) and the latency table one of (seed, rank, environment); the ring of past
+        # actions is the arena region "action_hist", which checkpoints carry
+        self.obs_noise = obs_noise_scales(config, self.cm)
+        if self.obs_noise is not None:
+            self.lib.engine_set_obs_noise(self._engine, self.obs_noise.ctypes.data)
+        self.action_delay = action_delay_cfg(config, self.seed, rank)  # (seed and rank are the engine configuration's: the engine reads its own)
+        if self.action_delay is not None:
+            self.lib.engine_set_action_delay(self._engine, self.action_delay.min, self.action_delay.max)
         # training.normalize_observations: off leaves the engine's launch sequence as it is
         self.obs_norm_clip, self.obs_norm_eps = float(tr.obs_norm_clip), float(tr.obs_norm_eps)
         if self.obs_norm_on:
@@ -479,14 +529,15 @@ class Trainer:
     # uninterrupted run bit for bit (tests/test_train_surface.py).
     _CKPT_REGIONS = ("params", "adam_m", "adam_v", "count", "state", "episode_returns", "episode_lengths", "returned_episode_returns",
                      "returned_episode_lengths", "timestep", "returned_episode", "jax_rng")
-    _CKPT_OPTIONAL = ("reset_rng", "obs_norm_stats", "obs_norm_table", "reward_norm_stats", "reward_norm_table", "reward_norm_carry")  # (regions younger than checkpoint version 2: written always, read when the file has them)
+    _CKPT_OPTIONAL = ("reset_rng", "obs_norm_stats", "obs_norm_table", "reward_norm_stats", "reward_norm_table", "reward_norm_carry", "action_hist")  # (regions younger than checkpoint version 2: written always, read when the file has them)
     _CKPT_VERSION = 2  # 2: 16-byte-aligned flat parameter layout
 
     def _ckpt_meta(self) -> Dict[str, Any]:
         return dict(version=self._CKPT_VERSION, model=self.cm.name, num_envs=self.N, num_steps=self.T, obs_dim=self.O, act_dim=self.A, hidden=self.H,
                     params=self.P, rec_dim=int(self.dims.rec_dim), seed=int(self.seed), rank=self.rank, world_size=self.world_size,
                     rng_impl="threefry" if self.ecfg.rng_impl == 1 else "philox", normalize_observations=self.obs_norm_on,
-                    normalize_rewards=self.reward_norm_on)
+                    normalize_rewards=self.reward_norm_on,
+                    **{k: getattr(self.config.environment, k) for k in _OBS_NOISE_KEYS + _ACTION_DELAY_KEYS})
 
     def save_checkpoint(self, path: str) -> None:
         self._sync()
@@ -521,6 +572,13 @@ class Trainer:
                 # the critic's targets are in units of the scale: a value head trained on scaled returns is off by that factor on raw ones, and back
                 raise ValueError(f"checkpoint {path}: written with training.normalize_rewards={str(meta['normalize_rewards']).lower()}, this run has "
                                  f"training.normalize_rewards={str(want['normalize_rewards']).lower()}")
+            env_defaults = type(self.config.environment)()
+            for k in _OBS_NOISE_KEYS + _ACTION_DELAY_KEYS:  # (files written before the keys existed: off, whatever the group scales say)
+                meta.setdefault(k, getattr(env_defaults, k))
+            sens = lambda m: ([float(m[k]) for k in _OBS_NOISE_KEYS] if m["obs_noise_level"] > 0 else None, [int(m[k]) for k in _ACTION_DELAY_KEYS])
+            if sens(meta) != sens(want):
+                # the policy was trained on that noise and that latency, and the ring of past actions belongs to them: the resumed run applies the same ones
+                raise ValueError(f"checkpoint {path}: written with environment.obs_noise_* / action_delay_* = {sens(meta)}, this run has {sens(want)}")
             for k in ("version", "model", "num_envs", "num_steps", "obs_dim", "act_dim", "hidden", "params", "rec_dim", "world_size", "rank", "seed", "rng_impl"):
                 if meta.get(k) != want[k]:
                     raise ValueError(f"checkpoint {path}: {k} = {meta.get(k)!r} does not match this run ({want[k]!r})")
@@ -955,7 +1013,9 @@ class Trainer:
                         obs_norm=None if on is None else {"mean": on["table"][0], "inv_std": on["table"][1], "clip": on["clip"]},
                         push=push_cfg(self.config, self.cm, ecfg.seed),  # (environment.push_force > 0: the evaluation is pushed as the training was)
                         episode_length=self.episode_length,  # (environment.episode_length > 0: ... and truncated as the training was)
-                        domain=domain_cfg(self.config, self.cm, ecfg.seed))  # (... and on robots randomised as the training's were)
+                        domain=domain_cfg(self.config, self.cm, ecfg.seed),  # (... and on robots randomised as the training's were)
+                        obs_noise=self.obs_noise, action_delay=action_delay_cfg(self.config, ecfg.seed))  # (... under the training's sensor noise and latency)
+        result.sensors = sensors_echo(self.config) or None
         if domain_on(self.config):
             result.domain = domain_echo(self.config)  # (the ranges the figures belong to, as `evaluate()` reports them)
         return result

@@ -497,8 +497,17 @@ int32_t mppo_threefry_permutation(const uint32_t* sort_keys, int32_t rounds, int
  *                           rows they hold (Chan): b = mean32 + S1/k, M2b = max(S2 - S1^2/k, 0), delta = b - mean, n' = n + k, mean' = mean + delta k/n',
  *                           M2' = M2 + M2b + delta^2 n k/n' (mean32: the table as it stands, which the partials were taken against); then rewrites
  *                           the table, columns O .. table_ld - 1 as 0 / 1.  rows = 0 (then n_partials = 0, partial may be NULL): the table from the
- *                           statistics alone.  The same inputs give the same bytes on every run. */
+ *                           statistics alone.  The same inputs give the same bytes on every run.
+ *   mppo_obs_norm_rank_sums several ranks: one small launch, one thread per column, in front of the ranks' gather.  Adds this rank's n_partials x [2][O] partials
+ *                           in index order (from +0.0, as mppo_obs_norm_update adds them) into slot `rank` of `slots` [world][2][O] float64 - a sum of -0.0 is
+ *                           written as +0.0 - and writes +0.0 into every other slot; nothing outside `slots` is written.  Once every rank holds all slots
+ *                           (a gather; or a sum all-reduce of `slots`, in which every foreign term is +0.0 and x + 0 is exact, so the order of the library's
+ *                           additions does not matter), mppo_obs_norm_update(O, world, rows of all ranks, slots, ...) adds them in rank order and merges:
+ *                           every rank that starts from the same statistics and table ends with the same bytes.  world = 1: update(n_partials = 1) on
+ *                           the one slot gives the bytes of update on the partials themselves.  The reward scaling's partials are the case O = 1.
+ *                           MPPO_EINVAL: O or n_partials below 1, rank outside 0 .. world - 1, a null or misaligned pointer. */
 int32_t mppo_obs_norm_partials(int32_t N);
+int32_t mppo_obs_norm_rank_sums(int32_t O, int32_t n_partials, const double* partial, int32_t rank, int32_t world, double* slots, void* stream);
 int32_t mppo_obs_norm_apply(int32_t N, int32_t O, float* obs, int32_t obs_ld, const float* table, int32_t table_ld, float clip, double* partial, void* stream);
 int32_t mppo_obs_norm_update(int32_t O, int32_t n_partials, int64_t rows, const double* partial, double* stats, float eps, float* table, int32_t table_ld,
                              void* stream);
@@ -557,6 +566,7 @@ typedef struct mppo_engine_cfg {
  * "reward_norm_stats" (float64 [3]) "reward_norm_table" ([2]) "reward_norm_carry" ([N]) "reward_norm_partials" (float64 [G][2]) "reward_scaled" ([T][N])
  * "truncated" (bytes [T][N]: the samples an episode time limit cut, mppo_engine_set_time_limit)
  * "action_hist" ([16][N][A]: the latency's ring) "action_applied" ([N][A]: what the last step launch was given) "action_delay" (int32 [N]) "obs_noise_scale" ([OP])
+ * "norm_slots" (float64 [G][2][O] then [G][2]: the ranks' gathered sums of the two normalisations, G = world_size; untouched on one rank)
  * ("rollout_stats": 8 floats: sum reward, episodes ended, sum of their returns, sum of their lengths, the two means, truncations (0 without a time limit), 0) ... */
 int32_t mppo_engine_arena_bytes(const mppo_model_t* m, const mppo_engine_cfg_t* cfg, size_t* out);
 int32_t mppo_engine_create(const mppo_model_t* m, const mppo_engine_cfg_t* cfg, void* arena, size_t arena_bytes,
@@ -582,7 +592,7 @@ int32_t mppo_engine_comm_init(mppo_engine_t* e, const void* id128);
  *                            shared-GPU form
  *   mppo_engine_peer_status  synchronises the device; *timed_out != 0: a rank waited longer than MPPO_PEER_TIMEOUT_MS (default
  *                            60000) for a peer - the kernels ran to their end, the results are invalid.  info8 (optional, 8 words):
- *                            the first such wait {kind: 1 a peer's local gradient, 2 a reduced piece, 3 a peer's advantage sums;
+ *                            the first such wait {kind: 1 a peer's local gradient, 2 a reduced piece, 3 a peer's advantage sums, 5 a peer's normalisation sums;
  *                            index; epoch waited for; value seen}, then {optimizer steps, updates, workgroups counted into an unfinished gradient slice (0 between
  *                            launches), pieces per slice}
  *   mppo_engine_peer_selftest  collective (every rank, after the barrier that follows connect), on `stream`: one all-reduce of a
@@ -621,7 +631,13 @@ int32_t mppo_engine_set_reset_noise(mppo_engine_t* e, float scale);
  * normalised with the table of the moment it was collected (the learn phase reads what the rollout's forward read), and the count is updates * T * N.
  * mppo_engine_reset zeroes the statistics and writes the identity table; the observation it makes (slot 0) stays raw.  The three regions lie behind
  * every other one and exist whether or not the option is on.  Call before mppo_engine_reset, mppo_engine_prepare and the first mppo_engine_update:
- * afterwards it returns MPPO_ESTATE.  MPPO_EINVAL: a negative (or NaN) clip / eps; enabled with world_size > 1 (the statistics are not summed over ranks). */
+ * afterwards it returns MPPO_ESTATE.  MPPO_EINVAL: a negative (or NaN) clip / eps.
+ * world_size > 1 (every rank makes the same call, AFTER mppo_engine_peer_connect or mppo_engine_comm_init: without a connected transport enabling is
+ * MPPO_EINVAL - the statistics would silently be one rank's): the rollout ends with mppo_obs_norm_rank_sums into arena region "norm_slots" ([G][2][O] float64, behind them
+ * [G][2] for the reward scaling), ONE gather of the slots per update for both options on the transport the learn phase uses (the peer exchange's own small
+ * kernel, inside the captured graph; or one float64 all-reduce of the slots on the communicator), and mppo_obs_norm_update(O, G, T * N * G, slots, ...): two or
+ * three launches more.  Statistics and table are bit-identical on every rank, the count is updates * T * N * G.  mppo_engine_rollout then needs a connected
+ * transport like mppo_engine_learn (MPPO_ESTATE without one).  One rank: exactly the launches and arguments described above. */
 int32_t mppo_engine_set_obs_norm(mppo_engine_t* e, int32_t enabled, float clip, float eps);
 /* Reward scaling (mppo_reward_norm_* above; enabled = 0, the default: the engine enqueues exactly the launches it enqueues without this call).
  * enabled != 0: behind the rollout's bootstrap critic forward, one mppo_reward_norm_apply over the T steps reads arena region "reward" and writes
@@ -631,8 +647,9 @@ int32_t mppo_engine_set_obs_norm(mppo_engine_t* e, int32_t enabled, float clip, 
  * an update - update u divides by the deviation collected through update u - 1, the first by 1 - and the count is updates * T * N.  "reward",
  * "rollout_stats" and the environment's metrics stay raw: users see real returns.  mppo_engine_reset zeroes the statistics and the carry and writes the
  * identity table 0 | 1.  The five regions lie behind every other one and exist whether or not the option is on.  Call before mppo_engine_reset,
- * mppo_engine_prepare and the first mppo_engine_update: afterwards it returns MPPO_ESTATE.  MPPO_EINVAL: a negative (or NaN) clip / eps; enabled with
- * world_size > 1 (the sums are not exchanged between ranks; switching it off is never refused for the rank count). */
+ * mppo_engine_prepare and the first mppo_engine_update: afterwards it returns MPPO_ESTATE.  MPPO_EINVAL: a negative (or NaN) clip / eps.
+ * world_size > 1: as for mppo_engine_set_obs_norm (a connected transport first) - the ranks' (S1, S2) travel in the same gather, the statistics and the scale are bit-identical on every
+ * rank and count updates * T * N * G returns; "reward_norm_carry" stays this rank's own (one return per environment). */
 int32_t mppo_engine_set_reward_norm(mppo_engine_t* e, int32_t enabled, float clip, float eps);
 /* Random pushes during training (mppo_push_cfg_t above; NULL or force = 0, the default: the engine enqueues exactly the launches, with exactly the
  * arguments, it enqueues without this call).  force > 0: every rollout step's environment launch draws its wrench inside the kernel - no launch more,

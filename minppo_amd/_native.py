@@ -193,6 +193,7 @@ SIGNATURES = {
     "mppo_obs_norm_partials": (c_i32, [c_i32]),
     "mppo_obs_norm_apply": (c_i32, [c_i32, c_i32, c_vp, c_i32, c_vp, c_i32, c_f, c_vp, c_vp]),
     "mppo_obs_norm_update": (c_i32, [c_i32, c_i32, C.c_int64, c_vp, c_vp, c_f, c_vp, c_i32, c_vp]),
+    "mppo_obs_norm_rank_sums": (c_i32, [c_i32, c_i32, c_vp, c_i32, c_i32, c_vp, c_vp]),
     "mppo_reward_norm_partials": (c_i32, [c_i32]),
     "mppo_reward_norm_apply": (c_i32, [c_i32, c_i32, c_f, c_vp, c_vp, c_vp, c_vp, c_f, c_vp, c_vp, c_vp]),
     "mppo_engine_arena_bytes": (c_i32, [c_vp, P(EngineCfg), P(c_sz)]),

@@ -191,14 +191,15 @@ class TrainingConfig:
     keep_metrics_history: bool = field(default=False)
     # Extension (absent upstream; Brax `normalize_observations`, gym `NormalizeObservation`): running mean / standard deviation per observation
     # column, collected from the rollout's own rows, applied in place before the network sees them.  `obs_norm_clip` clamps the
-    # normalised value to [-clip, clip] (0 = no clamp); `obs_norm_eps` is added to the variance.  Off: nothing changes.  Single rank only.
+    # normalised value to [-clip, clip] (0 = no clamp); `obs_norm_eps` is added to the variance.  Off: nothing changes.  Any number of ranks:
+    # the statistics are those of all ranks' rows, bit-identical on every rank.
     normalize_observations: bool = field(default=False)
     obs_norm_clip: float = field(default=10.0)
     obs_norm_eps: float = field(default=1e-8)
     # Extension (absent upstream; gym `NormalizeReward`, SB3 `VecNormalize(norm_reward=True)`, Brax `reward_scaling`): the rewards GAE reads are divided
     # by the running standard deviation of the discounted return, collected on the device from the rollout's own rewards.  Scaled, never
     # centred; the scale is frozen within an update.  `reward_norm_clip` clamps the scaled reward to [-clip, clip] (0 = no clamp); `reward_norm_eps` is
-    # added to the variance.  Metrics and `evaluate` report raw returns.  Off: nothing changes.  Single rank only.
+    # added to the variance.  Metrics and `evaluate` report raw returns.  Off: nothing changes.  Any number of ranks, as above.
     normalize_rewards: bool = field(default=False)
     reward_norm_clip: float = field(default=10.0)
     reward_norm_eps: float = field(default=1e-8)

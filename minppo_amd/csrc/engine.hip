@@ -174,6 +174,8 @@ struct mppo_engine {
   float* reward_norm_carry;      // [N] the discounted return carried from one update to the next
   double* reward_norm_partials;  // [G][2] the apply launch's sums of this update
   float* reward_scaled;          // [T][N] what GAE reads; "reward" stays raw
+  // both of them on several ranks: the ranks' sums of this update, gathered - [world][2][O] for the observations, behind them [world][2] for the returns
+  double* norm_slots;
   // random pushes (mppo_engine_set_push; body 0: off - the rollout's step launches are the unpushed ones)
   mppo::EnvPush push;
   // episode time limit (mppo_engine_set_time_limit; length 0: off - no launch is added, GAE and the statistics are the plain ones)
@@ -268,6 +270,8 @@ static size_t layout(mppo_engine* e, bool assign) {
   e->action_applied = (float*)take("action_applied", N * A * 4);
   e->action_delay = (int*)take("action_delay", N * 4);
   e->obs_noise_scale = (float*)take("obs_noise_scale", OP * 4);
+  // the normalisations across ranks: behind those again, present whatever the options and the rank count are (one rank never touches it)
+  e->norm_slots = (double*)take("norm_slots", (size_t)e->cfg.world_size * 2 * ((size_t)e->O + 1) * 8);
   return align_up(off, 256);
 }
 
@@ -318,6 +322,16 @@ static bool shadow_enabled() {  // MPPO_NO_SHADOW=1: A/B switch for measurements
 static bool pregather_enabled() {  // MPPO_NO_PREGATHER=1: A/B switch for measurements
   static const bool off = [] { const char* v = MPPO_EXPERIMENT_ENV("MPPO_NO_PREGATHER"); return v && v[0] == '1'; }();
   return !off;
+}
+
+// What carries this engine's collectives: the ranks' hipIpc-mapped exchange buffers (peer.h) once connected, else the RCCL communicator.
+// MPPO_FORCE_COMM=1 runs the collectives also at world size 1 (identity all-reduce): hardware check of the RCCL path
+struct Transport { bool peer, comm; };
+static Transport transport_of(const mppo_engine* e) {
+  const char* fc = getenv("MPPO_FORCE_COMM");
+  const bool force_comm = fc && fc[0] == '1';
+  const bool peer = peer_connected(e->peer);
+  return Transport{peer, !peer && (e->cfg.world_size > 1 || (force_comm && e->comm))};
 }
 
 static int32_t do_rollout(mppo_engine* e, hipStream_t s) {
@@ -403,6 +417,28 @@ static int32_t do_rollout(mppo_engine* e, hipStream_t s) {
   else
     hipLaunchKernelGGL(rollout_stats_kernel, dim3(1), dim3(kStatsThreads), 0, s, e->T, e->N, e->reward, e->done, e->stat_ret_in, e->stat_len_in, e->stats);
   MPPO_CHECK_LAUNCH("rollout_stats_kernel");
+  const Transport tp = transport_of(e);
+  if ((e->obs_norm || e->reward_norm) && (tp.peer || tp.comm)) {
+    // Several ranks (or MPPO_FORCE_COMM=1 at one: the gather as the identity): every rank adds its own partials in index order into its slot, the slots are
+    // gathered - ONE exchange per update for both options, on the transport the learn phase uses - and the update kernel adds them in rank order and merges
+    // k = T N G rows.  Every rank started from the same statistics and table and merges the same bytes: statistics and tables stay replicas.
+    const int G = c.world_size;
+    double* const obs_slots = e->norm_slots;
+    double* const rew_slots = e->norm_slots + (size_t)G * 2 * e->O;
+    if (e->obs_norm) MPPO_TRY(obs_norm_rank_sums_launch(e->O, e->T * obs_norm_partials(e->N), e->obs_norm_partials, c.rank, G, obs_slots, s));
+    if (e->reward_norm) MPPO_TRY(obs_norm_rank_sums_launch(1, reward_norm_partials(e->N), e->reward_norm_partials, c.rank, G, rew_slots, s));
+    if (tp.peer) {
+      if (e->obs_norm) MPPO_TRY(peer_gather_f64(e->peer, obs_slots, 2 * e->O, (size_t)G * 2 * e->O, e->reward_norm ? 2 : 0, s));
+      else MPPO_TRY(peer_gather_f64(e->peer, rew_slots, 2, 0, 0, s));
+    } else {  // a sum in which every foreign term is +0.0: a gather, whatever order the library adds in
+      double* const first = e->obs_norm ? obs_slots : rew_slots;
+      MPPO_TRY(comm_allreduce_f64(e->comm, first, (size_t)G * 2 * ((e->obs_norm ? (size_t)e->O : 0) + (e->reward_norm ? 1 : 0)), s));
+    }
+    const long long rows = (long long)e->T * e->N * G;
+    if (e->obs_norm) MPPO_TRY(obs_norm_update_launch(e->O, G, rows, obs_slots, e->obs_norm_stats, e->obs_norm_eps, e->obs_norm_table, e->OP, s));
+    if (e->reward_norm) MPPO_TRY(obs_norm_update_launch(1, G, rows, rew_slots, e->reward_norm_stats, e->reward_norm_eps, e->reward_norm_table, 1, s));
+    return MPPO_OK;
+  }
   if (e->obs_norm)  // the T steps' rows join the running statistics; the table is rewritten for the next update (nothing of this one applies it any more)
     MPPO_TRY(obs_norm_update_launch(e->O, e->T * obs_norm_partials(e->N), (long long)e->T * e->N, e->obs_norm_partials, e->obs_norm_stats, e->obs_norm_eps, e->obs_norm_table,
                                     e->OP, s));
@@ -426,11 +462,9 @@ static int32_t do_learn(mppo_engine* e, hipStream_t s) {
     }
   }
   MPPO_TRY(mppo_adv_sums(e->adv, e->perm, EM, e->mb, e->adv_sums, s));
-  // MPPO_FORCE_COMM=1 runs the collectives also at world size 1 (identity all-reduce): hardware check of the RCCL path
-  const char* fc = getenv("MPPO_FORCE_COMM");
-  const bool force_comm = fc && fc[0] == '1';
-  const bool use_peer = peer_connected(e->peer);  // gradients travel through the ranks' hipIpc-mapped exchange buffers (peer.h)
-  const bool use_comm = !use_peer && (c.world_size > 1 || (force_comm && e->comm));
+  const Transport tp = transport_of(e);
+  const bool use_peer = tp.peer;  // gradients travel through the ranks' hipIpc-mapped exchange buffers (peer.h)
+  const bool use_comm = tp.comm;
   if (use_peer) MPPO_TRY(peer_allreduce_f64(e->peer, e->adv_sums, (size_t)EM * 2, s));
   if (use_comm) MPPO_TRY(comm_allreduce_f64(e->comm, e->adv_sums, (size_t)EM * 2, s));
   MPPO_TRY(mppo_adv_stats_finalize(e->adv_sums, EM, (double)e->mb * c.world_size, e->adv_stats, s));
@@ -610,8 +644,8 @@ extern "C" int32_t mppo_engine_reset(mppo_engine_t* e, void* stream) {
 extern "C" int32_t mppo_engine_set_obs_norm(mppo_engine_t* e, int32_t enabled, float clip, float eps) {
   MPPO_REQUIRE(e, "mppo_engine_set_obs_norm: null engine");
   MPPO_REQUIRE(clip >= 0.f && eps >= 0.f, "mppo_engine_set_obs_norm: clip %g / eps %g is negative (or not a number)", (double)clip, (double)eps);
-  MPPO_REQUIRE(!enabled || e->cfg.world_size == 1, "mppo_engine_set_obs_norm: world_size = %d ranks - the running statistics are not summed over ranks, observation "
-               "normalisation runs on a single rank only", e->cfg.world_size);
+  MPPO_REQUIRE(!enabled || e->cfg.world_size == 1 || e->comm || peer_connected(e->peer), "mppo_engine_set_obs_norm: world_size = %d ranks - the running statistics are "
+               "gathered over the ranks' transport once per update: connect it first (mppo_engine_peer_connect or mppo_engine_comm_init), then enable the option", e->cfg.world_size);
   if (e->graph || e->prepared)
     return fail(MPPO_ESTATE, "mppo_engine_set_obs_norm: the update has been prepared already (its launch sequence is fixed, a captured graph holds it): "
                              "call it before mppo_engine_reset, mppo_engine_prepare and the first mppo_engine_update");
@@ -626,8 +660,8 @@ extern "C" int32_t mppo_engine_set_obs_norm(mppo_engine_t* e, int32_t enabled, f
 extern "C" int32_t mppo_engine_set_reward_norm(mppo_engine_t* e, int32_t enabled, float clip, float eps) {
   MPPO_REQUIRE(e, "mppo_engine_set_reward_norm: null engine");
   MPPO_REQUIRE(clip >= 0.f && eps >= 0.f, "mppo_engine_set_reward_norm: clip %g / eps %g is negative (or not a number)", (double)clip, (double)eps);
-  MPPO_REQUIRE(!enabled || e->cfg.world_size == 1, "mppo_engine_set_reward_norm: world_size = %d ranks - the running statistics are not summed over ranks, reward "
-               "scaling runs on a single rank only", e->cfg.world_size);
+  MPPO_REQUIRE(!enabled || e->cfg.world_size == 1 || e->comm || peer_connected(e->peer), "mppo_engine_set_reward_norm: world_size = %d ranks - the running statistics are "
+               "gathered over the ranks' transport once per update: connect it first (mppo_engine_peer_connect or mppo_engine_comm_init), then enable the option", e->cfg.world_size);
   if (e->graph || e->prepared)
     return fail(MPPO_ESTATE, "mppo_engine_set_reward_norm: the update has been prepared already (its launch sequence is fixed, a captured graph holds it): "
                              "call it before mppo_engine_reset, mppo_engine_prepare and the first mppo_engine_update");
@@ -786,7 +820,8 @@ static int32_t require_ready(mppo_engine_t* e, bool needs_comm) {
 }
 
 extern "C" int32_t mppo_engine_rollout(mppo_engine_t* e, void* stream) {
-  MPPO_TRY(require_ready(e, false));  // the rollout needs no communication: environments are independent
+  // environments are independent: the rollout needs no communication - except for the normalisations' running statistics, which are those of all ranks
+  MPPO_TRY(require_ready(e, e && (e->obs_norm || e->reward_norm)));
   return do_rollout(e, static_cast<hipStream_t>(stream));
 }
 
@@ -872,7 +907,9 @@ extern "C" int32_t mppo_engine_peer_export(mppo_engine_t* e, void* handle64) {
   MPPO_REQUIRE(!e->peer, "mppo_engine_peer_export: already exported");
   MPPO_REQUIRE(e->cfg.world_size >= 2, "mppo_engine_peer_export: one rank has nobody to exchange with");
   const size_t adv = (size_t)e->E * e->M * 2;
-  return peer_create(e->cfg.rank, e->cfg.world_size, (size_t)e->P, adv < 4 ? 4 : adv, &e->peer, handle64);  // (the self-test sums four values)
+  // (the self-test sums four values; the gather's region holds one rank's sums of both normalisations, whether or not they are on: the order of this call and
+  // mppo_engine_set_*_norm does not matter)
+  return peer_create(e->cfg.rank, e->cfg.world_size, (size_t)e->P, adv < 4 ? 4 : adv, 2 * ((size_t)e->O + 1), &e->peer, handle64);
 }
 
 extern "C" int32_t mppo_engine_peer_connect(mppo_engine_t* e, const void* handles, int32_t shared_device) {
@@ -884,6 +921,8 @@ extern "C" int32_t mppo_engine_peer_connect(mppo_engine_t* e, const void* handle
 // Everything the gradient path depends on, once, on known inputs, before anything depends on it:
 //  1. the once-per-update all-reduce of the advantage sums: every rank publishes (rank + 1) four times, waits for the peers' values and
 //     adds them in rank order (scalar system-scope stores / loads, the adv_done flags);
+//  1b. the once-per-update gather of the normalisations' sums, in the engine's shape: slot r = (r + 1) c(i); every rank checks every slot EXACTLY (the gat_done
+//     flags, the gather's own epoch and region);
 //  2. ONE full optimizer step's exchange in the form the engine will launch it (fused / split / shared): a known local gradient
 //     g_r[i] = (r + 1) c(i), c(i) a multiple of 1/256, goes into `pub` through the publish kernel (16-byte system-scope stores, the
 //     arrival counter, the wg_done flags), then clip_adam<PEER> on SCRATCH parameters and moments: phase A pulls this rank's slice of
@@ -937,7 +976,18 @@ extern "C" int32_t mppo_engine_peer_selftest(mppo_engine_t* e, void* stream, int
   int soak = 2000;
 #endif
   if (const char* sv = getenv("MPPO_PEER_SOAK")) soak = atoi(sv) < 0 ? 0 : atoi(sv);
-  he = hipMemcpy(dev, host, sizeof(host), hipMemcpyHostToDevice);
+  // the gather of the normalisations' sums in the shape the engine launches it ([G][2 O] and [G][2] slots): slot r = (r + 1) c(i), every other slot a
+  // value no rank publishes until its owner's bits arrive
+  const int gn0 = 2 * e->O, gn1 = 2;
+  const size_t goff1 = (size_t)G * gn0;
+  auto gslot = [&](int q, int i) -> size_t { return i < gn0 ? (size_t)q * gn0 + i : goff1 + (size_t)q * gn1 + (i - gn0); };
+  std::vector<double> gat((size_t)G * (gn0 + gn1), -7.0);
+  for (int i = 0; i < gn0 + gn1; ++i) gat[gslot(e->cfg.rank, i)] = (double)(e->cfg.rank + 1) * (double)selftest_pattern((size_t)i);
+  double* gdev = nullptr;
+  he = hipMalloc(reinterpret_cast<void**>(&gdev), gat.size() * sizeof(double));
+  if (he != hipSuccess) { (void)hipFree(dev); (void)hipFree(scratch); return fail(MPPO_EHIP, "mppo_engine_peer_selftest: %s", hipGetErrorString(he)); }
+  he = hipMemcpy(gdev, gat.data(), gat.size() * sizeof(double), hipMemcpyHostToDevice);
+  if (he == hipSuccess) he = hipMemcpy(dev, host, sizeof(host), hipMemcpyHostToDevice);
   if (he == hipSuccess) he = hipMemcpy(scratch, g.data(), P * sizeof(float), hipMemcpyHostToDevice);
   if (he == hipSuccess) he = hipMemset(scratch + P, 0, 3 * P * sizeof(float));
   mppo_adam_cfg_t ac = e->cfg.adam;
@@ -955,6 +1005,7 @@ extern "C" int32_t mppo_engine_peer_selftest(mppo_engine_t* e, void* stream, int
 #endif
   if (he == hipSuccess) {
     rc = peer_allreduce_f64(e->peer, dev, 4, st);
+    if (rc == MPPO_OK) rc = peer_gather_f64(e->peer, gdev, gn0, goff1, gn1, st);
     const PeerStep ps = peer_step(e->peer, 0);
     if (rc == MPPO_OK) rc = peer_publish(e->peer, scratch, P, 0, st);
     if (rc == MPPO_OK)
@@ -962,7 +1013,8 @@ extern "C" int32_t mppo_engine_peer_selftest(mppo_engine_t* e, void* stream, int
     if (rc == MPPO_OK) rc = peer_advance(e->peer, 1, st);
     if (rc == MPPO_OK) rc = peer_status(e->peer, &timed_out, nullptr);  // synchronises
     if (rc == MPPO_OK) he = hipMemcpy(host, dev, sizeof(host), hipMemcpyDeviceToHost);
-    if (rc == MPPO_OK && he == hipSuccess) he = hipMemcpy(red.data(), peer_red(e->peer), 2 * (P + kSqSlots) * sizeof(float), hipMemcpyDeviceToHost);
+    if (rc == MPPO_OK && he == hipSuccess) he = hipMemcpy(gat.data(), gdev, gat.size() * sizeof(double), hipMemcpyDeviceToHost);
+    if (rc == MPPO_OK && he == hipSuccess) he = hipMemcpy(red.data(),peer_red(e->peer), 2 * (P + kSqSlots) * sizeof(float), hipMemcpyDeviceToHost);
     if (rc == MPPO_OK && he == hipSuccess) he = hipMemcpy(m1.data(), scratch + 2 * P, P * sizeof(float), hipMemcpyDeviceToHost);
     // ---- the soak (round 6): ONE exchange on known values finds a transport that carries no stores; it does not find a pair torn or a store
     // reordered once in 10^5.  `soak` more exchanges follow back to back at the rate of training (no host in between), every element checked
@@ -988,10 +1040,13 @@ extern "C" int32_t mppo_engine_peer_selftest(mppo_engine_t* e, void* stream, int
   }
   peer_set_limit_ms(e->peer, (double)limit_ms);
   (void)hipFree(dev);
+  (void)hipFree(gdev);
   (void)hipFree(scratch);
   if (he != hipSuccess) return fail(MPPO_EHIP, "mppo_engine_peer_selftest: %s", hipGetErrorString(he));
   if (rc != MPPO_OK) return rc;
   bool good = !timed_out;
+  for (int q = 0; q < G && good; ++q)  // the gather: every rank's slot, bit for bit what its owner published
+    for (int i = 0; i < gn0 + gn1 && good; ++i) good = gat[gslot(q, i)] == (double)(q + 1) * (double)selftest_pattern((size_t)i);
   if (timed_out)  // say WHY the job is about to continue on RCCL: a wait ran into the self-test's limit, as opposed to a wrong value
     fprintf(stderr, "[minppo_amd] warning: rank %d: the peer exchange's connect-time self-test timed out (%d wait(s) gave up after %llu ms) - a peer did not "
                     "answer in time (a rank that started late, ranks serialised on a shared stream, or a mapping that carries no stores); the caller falls back to RCCL\n",

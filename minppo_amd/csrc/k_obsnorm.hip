@@ -13,6 +13,8 @@
 //                           per workgroup 4096 x 225 made 9.2 MB of them per update, and the one workgroup that sums them in index order took 150 us.
 //   obs_norm_update_kernel  once per update, ONE workgroup, one thread per column: the partials in index order, then Chan's merge of (k rows, their mean
 //                           b and sum of squared deviations M2b) into the running (n, mean, M2), then the float32 table the next update applies.
+//   obs_norm_rank_sums_kernel  several ranks only, once per update in front of the gather: this rank's partials in index order into its slot of [G][2][O];
+//                           the update kernel then runs on the gathered slots (n_partials = G, rows = T N G).
 //
 // This file is compiled without floating-point contraction (minppo_amd/build.py): the merge is a dozen float64 operations whose roundings the tests restate.
 #include "obsnorm.h"
@@ -137,6 +139,34 @@ __global__ void __launch_bounds__(kObsNormUpdateThreads) obs_norm_update_kernel(
   if (threadIdx.x == 0 && rows > 0) stats[0] = n + k;
 }
 
+// Several ranks (DESIGN.md 3.7 "Across ranks"): ONE workgroup, one thread per column, adds this rank's partials in index order - the update kernel's own
+// loop, from the same +0.0 - into slot `rank` of slots [world][2][O] and writes +0.0 into every other slot.  The slots are then GATHERED (peer.h
+// peer_gather_f64, or a sum all-reduce in which every foreign term is +0.0: x + 0 is exact, so the transport's order does not matter) and the update kernel
+// adds them in rank order.  A sum of -0.0 is published as +0.0: under the all-reduce -0.0 + 0.0 is +0.0 anyway, and both transports carry the same bits.
+// world = 1: slot 0 alone, and update(n_partials = 1) on it computes 0.0 + S = S - the bytes of the update kernel on the partials themselves.
+__global__ void __launch_bounds__(kObsNormUpdateThreads) obs_norm_rank_sums_kernel(int O, int n_partials, const double* __restrict__ partial, int rank, int world,
+                                                                                   double* __restrict__ slots) {
+  for (int c = threadIdx.x; c < O; c += kObsNormUpdateThreads) {
+    double S1 = 0.0, S2 = 0.0;
+#pragma unroll 16
+    for (int p = 0; p < n_partials; ++p) {  // index order: launch-major, workgroup-minor
+      S1 += partial[(size_t)p * 2 * O + c];
+      S2 += partial[(size_t)p * 2 * O + O + c];
+    }
+    for (int q = 0; q < world; ++q) {
+      const bool mine = q == rank;
+      slots[((size_t)q * 2) * O + c] = mine && S1 != 0.0 ? S1 : 0.0;  // (a NaN stays a NaN: NaN != 0)
+      slots[((size_t)q * 2 + 1) * O + c] = mine && S2 != 0.0 ? S2 : 0.0;
+    }
+  }
+}
+
+int32_t obs_norm_rank_sums_launch(int O, int n_partials, const double* partial, int rank, int world, double* slots, hipStream_t stream) {
+  hipLaunchKernelGGL(obs_norm_rank_sums_kernel, dim3(1), dim3(kObsNormUpdateThreads), 0, stream, O, n_partials, partial, rank, world, slots);
+  MPPO_CHECK_LAUNCH("obs_norm_rank_sums_kernel");
+  return MPPO_OK;
+}
+
 int32_t obs_norm_apply_launch(int N, int O, float* obs, int obs_ld, const float* table, int table_ld, float clip, double* partial, hipStream_t stream) {
   const dim3 grid(obs_norm_partials(N)), block(kObsNormWaves * 64);
   const bool vec = (reinterpret_cast<uintptr_t>(obs) & 15) == 0 && obs_ld % 4 == 0;
@@ -168,6 +198,14 @@ extern "C" int32_t mppo_obs_norm_apply(int32_t N, int32_t O, float* obs, int32_t
   MPPO_REQUIRE((reinterpret_cast<uintptr_t>(obs) & 3) == 0 && (reinterpret_cast<uintptr_t>(table) & 3) == 0 && (reinterpret_cast<uintptr_t>(partial) & 7) == 0,
                "mppo_obs_norm_apply: observations / table must be 4-byte aligned, the partials 8-byte aligned");
   return obs_norm_apply_launch(N, O, obs, obs_ld, table, table_ld, clip, partial, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int32_t mppo_obs_norm_rank_sums(int32_t O, int32_t n_partials, const double* partial, int32_t rank, int32_t world, double* slots, void* stream) {
+  MPPO_REQUIRE(O >= 1 && n_partials >= 1, "mppo_obs_norm_rank_sums: O = %d, %d partials", O, n_partials);
+  MPPO_REQUIRE(world >= 1 && rank >= 0 && rank < world, "mppo_obs_norm_rank_sums: rank %d of %d", rank, world);
+  MPPO_REQUIRE(partial && slots, "mppo_obs_norm_rank_sums: null partials / slots");
+  MPPO_REQUIRE((reinterpret_cast<uintptr_t>(partial) & 7) == 0 && (reinterpret_cast<uintptr_t>(slots) & 7) == 0, "mppo_obs_norm_rank_sums: partials and slots must be 8-byte aligned");
+  return obs_norm_rank_sums_launch(O, n_partials, partial, rank, world, slots, static_cast<hipStream_t>(stream));
 }
 
 extern "C" int32_t mppo_obs_norm_update(int32_t O, int32_t n_partials, int64_t rows, const double* partial, double* stats, float eps, float* table, int32_t table_ld,

@@ -15,7 +15,7 @@ namespace mppo {
 
 struct PeerComm {
   int rank, world;
-  size_t P, adv_doubles, bytes;
+  size_t P, adv_doubles, gather_doubles, bytes;
   unsigned char* mine;
   void* mapped[kPeerMaxRanks];
   bool local[kPeerMaxRanks];  // a peer engine of THIS process: its buffer is used through its own pointer, nothing to unmap
@@ -68,6 +68,36 @@ __global__ void __launch_bounds__(256) peer_allreduce_f64_kernel(PeerView v, dou
   }
 }
 
+// The normalisations' per-rank sums (k_obsnorm.hip obs_norm_rank_sums_kernel): an all-GATHER, so that the order in which the ranks' sums are added is the
+// update kernel's (rank order) and not a transport's.  The all-reduce above with the sum replaced by a copy: one workgroup publishes this rank's slot
+// (system-scope stores, drain, barrier, one flag store per peer), waits for the peers' flags - bounded like every wait, kind 5 - and copies their slots into
+// `buf`; this rank's own slot in `buf` is not touched: its own bits.  Flags, epoch and region are the gather's own: a rollout may run without a learn phase
+// (mppo_engine_rollout), and the advantage exchange's epoch moves only with peer_advance.  The region has two halves, gather g uses half g & 1: a rank
+// rewrites a half two gathers later, and it gets through the gather in between only on every peer's flag for THAT one - which a peer raises in a launch that
+// follows, in its stream, the launch that read the half.  (With one half a rank could overwrite its slot of gather g + 1 while a slow peer still copies g.)
+__global__ void __launch_bounds__(256) peer_gather_f64_kernel(PeerView v, double* buf, int n0, size_t off1, int n1) {
+  PeerHdr* me = peer_hdr(v, v.rank);
+  const int t = threadIdx.x, epoch = me->gat_epoch + 1, n = n0 + n1;
+  const size_t half = (size_t)v.gat_off + (size_t)(epoch & 1) * (size_t)v.gat_cap * 8;
+  auto slot = [&](int q, int i) -> double* { return i < n0 ? buf + (size_t)q * n0 + i : buf + off1 + (size_t)q * n1 + (i - n0); };
+  double* mine = reinterpret_cast<double*>(v.base[v.rank] + half);
+  for (int i = t; i < n; i += blockDim.x) sys_store_f64(mine + i, *slot(v.rank, i));
+  drain_stores();
+  __syncthreads();  // (every thread has read gat_epoch, every wave's stores have been acknowledged)
+  if (t == 0) {
+    me->gat_epoch = epoch;
+#pragma unroll
+    for (int q = 0; q < kPeerMaxRanks; ++q)
+      if (q < v.world && q != v.rank) sys_store_i32(&peer_hdr(v, q)->gat_done[v.rank][0], epoch);
+  }
+  if (t < v.world && t != v.rank) peer_wait(&me->gat_done[t][0], epoch, me, v.limit_ticks, 5, t);
+  __syncthreads();
+  for (int j = t; j < v.world * n; j += blockDim.x) {
+    const int q = j / n, i = j - q * n;
+    if (q != v.rank) *slot(q, i) = sys_load_f64(reinterpret_cast<const double*>(v.base[q] + half) + i);
+  }
+}
+
 // a gradient computed by kernels that do not know about the exchange (the layer-wise path) -> pub, then the completion signal
 __global__ void __launch_bounds__(256) peer_publish_kernel(PeerView v, const float* __restrict__ grad, const int* epoch_base, int step) {
   const int epoch = epoch_base[0] + step + 1;
@@ -91,12 +121,12 @@ static unsigned long long limit_ticks() {
   return (unsigned long long)(ms * 1e5);
 }
 
-int32_t peer_create(int rank, int world, size_t P, size_t adv_doubles, PeerComm** out, void* handle64) {
+int32_t peer_create(int rank, int world, size_t P, size_t adv_doubles, size_t gather_doubles, PeerComm** out, void* handle64) {
   MPPO_REQUIRE(world >= 2 && world <= kPeerMaxRanks && rank >= 0 && rank < world, "peer exchange: %d ranks (2 .. %d on one node)", world, kPeerMaxRanks);
   MPPO_REQUIRE(P % 4 == 0 && P >= 4, "peer exchange: the flat gradient must be a whole number of float4 (P = %zu)", P);
   static_assert(sizeof(hipIpcMemHandle_t) == 64, "the ABI passes hipIpc handles as 64 bytes");
   PeerComm* c = new PeerComm();
-  c->rank = rank; c->world = world; c->P = P; c->adv_doubles = adv_doubles; c->connected = false;
+  c->rank = rank; c->world = world; c->P = P; c->adv_doubles = adv_doubles; c->gather_doubles = gather_doubles; c->connected = false;
   for (int q = 0; q < kPeerMaxRanks; ++q) c->mapped[q] = nullptr;
   PeerView& v = c->view;
   memset(&v, 0, sizeof(v));
@@ -108,7 +138,9 @@ int32_t peer_create(int rank, int world, size_t P, size_t adv_doubles, PeerComm*
   v.pub_off = (unsigned)sizeof(PeerHdr);
   v.red_off = (unsigned)align_up(v.pub_off + P * 4, 256);
   v.adv_off = (unsigned)align_up(v.red_off + (P + kSqSlots) * 8, 256);  // (tagged: 8 bytes per float)
-  c->bytes = align_up(v.adv_off + adv_doubles * 8, 256);
+  v.gat_off = (unsigned)align_up(v.adv_off + adv_doubles * 8, 256);  // behind every older region; sized whether or not a normalisation is on
+  v.gat_cap = (int)gather_doubles;
+  c->bytes = align_up(v.gat_off + 2 * gather_doubles * 8, 256);
   v.limit_ticks = limit_ticks();
   { const char* e = MPPO_EXPERIMENT_ENV("MPPO_PEER_POLL_RMW"); v.poll_rmw = e && e[0] == '1'; }
   // fine-grained device memory: coherent for accesses from other agents (what RCCL allocates for its own peer buffers);
@@ -215,6 +247,14 @@ int32_t peer_allreduce_f64(const PeerComm* c, double* buf, size_t n, hipStream_t
   return MPPO_OK;
 }
 
+int32_t peer_gather_f64(const PeerComm* c, double* buf, int n0, size_t off1, int n1, hipStream_t s) {
+  MPPO_REQUIRE(c && c->connected && buf && n0 >= 1 && n1 >= 0 && (size_t)n0 + (size_t)n1 <= c->gather_doubles, "peer_gather_f64: %d + %d values per rank exceed the exchange buffer's %zu",
+               n0, n1, c ? c->gather_doubles : (size_t)0);
+  hipLaunchKernelGGL(peer_gather_f64_kernel, dim3(1), dim3(256), 0, s, c->view, buf, n0, off1, n1);
+  MPPO_CHECK_LAUNCH("peer_gather_f64_kernel");
+  return MPPO_OK;
+}
+
 int32_t peer_advance(const PeerComm* c, int steps, hipStream_t s) {
   hipLaunchKernelGGL(peer_advance_kernel, dim3(1), dim3(64), 0, s, c->view, steps);
   MPPO_CHECK_LAUNCH("peer_advance_kernel");
@@ -273,6 +313,8 @@ int32_t peer_status(const PeerComm* c, int32_t* timed_out, int32_t* info8) {
     for (int q = 0; q < c->world; ++q) fprintf(stderr, " %d", h.wg_done[q][0]);
     fprintf(stderr, "\n  adv_done:");
     for (int q = 0; q < c->world; ++q) fprintf(stderr, " %d", h.adv_done[q][0]);
+    fprintf(stderr, "\n  gat_done (gathers done: %d):", h.gat_epoch);
+    for (int q = 0; q < c->world; ++q) fprintf(stderr, " %d", h.gat_done[q][0]);
     fprintf(stderr, "\n  red_done:");
     for (int k = 0; k < c->world * c->view.nA; ++k) fprintf(stderr, " %d", h.red_done[k]);
     fprintf(stderr, "\n");

@@ -20,5 +20,8 @@ inline size_t obs_norm_partial_doubles(int N, int O) { return (size_t)obs_norm_p
 int32_t obs_norm_apply_launch(int N, int O, float* obs, int obs_ld, const float* table, int table_ld, float clip, double* partial, hipStream_t stream);
 // the partials in index order, Chan's merge into stats [1 + 2 O] = n | mean | M2, then the table (columns O .. table_ld - 1: 0 / 1)
 int32_t obs_norm_update_launch(int O, int n_partials, long long rows, const double* partial, double* stats, float eps, float* table, int table_ld, hipStream_t stream);
+// several ranks: this rank's partials in index order -> slots[rank] of slots [world][2][O] (a -0.0 sum as +0.0), every other slot +0.0; the gathered slots are
+// obs_norm_update_launch's partials (n_partials = world, rows summed over the ranks)
+int32_t obs_norm_rank_sums_launch(int O, int n_partials, const double* partial, int rank, int world, double* slots, hipStream_t stream);
 
 }  // namespace mppo

@@ -50,9 +50,12 @@ struct PeerHdr {
   int arrive[kPeerMaxRanks + 1][16];
   int error;                        // != 0: a wait ran into its time limit (the run is invalid)
   int epoch[2];                     // optimizer steps / updates completed since creation (peer_advance_kernel)
-  int error_info[4];                // the first wait that timed out: kind (1 wg_done, 2 red_done, 3 adv_done), index, epoch waited for, value seen
+  int error_info[4];                // the first wait that timed out: kind (1 wg_done, 2 red_done, 3 adv_done, 5 gat_done), index, epoch waited for, value seen
   int probe[kPeerMaxRanks];         // [q]: the count of the latency probe's flags rank q has stored here (peer_latency: a ping-pong of one word between two ranks)
-  int pad[33];
+  int gat_epoch;                    // gathers completed since creation: advanced by peer_gather_f64_kernel itself (a rollout may run without a learn phase, so
+                                    // the gather shares neither epoch[1] nor adv_done with the advantage sums)
+  int pad[32];
+  int gat_done[kPeerMaxRanks][16];  // [q][0]: gather epoch of rank q's published normalisation sums (one 64-byte line per writer)
 };
 static_assert(sizeof(PeerHdr) % 256 == 0, "the regions behind the header stay 256-byte aligned");
 
@@ -62,6 +65,8 @@ struct PeerView {  // kernel argument: the G exchange buffers as mapped in THIS 
   int nA, K;    // pieces per slice; float4 per thread and piece (piece = 256 K float4)
   int P4, S4;   // float4 in the gradient / in a slice
   unsigned pub_off, red_off, adv_off;  // byte offsets of pub [4 P4] floats, red [4 P4 + kSqSlots] (value, epoch) PAIRS, adv [n] doubles
+  unsigned gat_off;                    // byte offset of the gather's region: [2][gat_cap] doubles, this rank's slot of gather g in half g & 1
+  int gat_cap;                         // doubles of one half
   unsigned long long limit_ticks;      // time limit of one wait, 100 MHz ticks
   int poll_rmw;                        // experiment (MPPO_PEER_POLL_RMW=1): poll with a system-scope atomic OR of 0 instead of a load
 };
@@ -243,7 +248,7 @@ __device__ __forceinline__ void peer_reduce_piece(const PeerView& v, int epoch, 
 // ---- host side (k_peer.hip) ----
 struct PeerComm;
 int32_t peer_wait_launch(const PeerStep& ps, int kind, hipStream_t s);  // one wave waits for every peer's gradient (1) / every reduced piece (2)
-int32_t peer_create(int rank, int world, size_t P, size_t adv_doubles, PeerComm** out, void* handle64);
+int32_t peer_create(int rank, int world, size_t P, size_t adv_doubles, size_t gather_doubles, PeerComm** out, void* handle64);  // gather_doubles: the largest slot of one rank
 int32_t peer_connect(PeerComm* c, const void* handles, int shared_device);  // world x 64 bytes, rank order; shared_device: several ranks on one GPU
 bool peer_connected(const PeerComm* c);
 bool peer_has_local(const PeerComm* c);  // some peer's buffer belongs to an engine of THIS process (found in the registry, not opened through hipIpc)
@@ -254,6 +259,10 @@ float* peer_pub(const PeerComm* c);                 // this rank's local gradien
 const float* peer_red(const PeerComm* c);           // the reduced gradient [P] + kSqSlots sums of squares as (value, epoch) pairs: float k at [2 k] (what Adam reads)
 int32_t peer_publish(const PeerComm* c, const float* grad, size_t P, int step, hipStream_t s);  // a gradient computed elsewhere -> pub + signal
 int32_t peer_allreduce_f64(const PeerComm* c, double* buf, size_t n, hipStream_t s);            // in-place sum over the ranks, once per update
+// all-gather of the ranks' slots, once per update (the normalisations' sums: every rank then adds the slots in rank order itself).  `buf` (this rank's own
+// memory) holds two arrays of per-rank slots: [world][n0] doubles at buf and [world][n1] at buf + off1 (n1 may be 0); slot `rank` of each is published, every
+// other slot is overwritten with its owner's bits.  n0 + n1 <= gather_doubles of peer_create
+int32_t peer_gather_f64(const PeerComm* c, double* buf, int n0, size_t off1, int n1, hipStream_t s);
 int32_t peer_advance(const PeerComm* c, int steps, hipStream_t s);                              // end of an update
 int32_t peer_status(const PeerComm* c, int32_t* timed_out, int32_t* info8);
 // one-way latency of a system-scope flag between this rank and `other` (both ranks call it at the same time, one as initiator): `iters` round

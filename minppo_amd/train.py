@@ -178,7 +178,7 @@ def tree_to_flat(tree: dict, O: int, A: int, H: int, L: int = 2) -> np.ndarray:
 _REGION_DTYPES = {
     "count": "int32", "done": "uint8", "perm": "int32", "adv_sums": "float64", "episode_lengths": "int32",
     "returned_episode_lengths": "int32", "timestep": "int32", "returned_episode": "uint8", "truncated": "uint8", "action_delay": "int32", "jax_rng": "int32", "reset_rng": "int32",
-    "obs_norm_stats": "float64", "obs_norm_partials": "float64", "reward_norm_stats": "float64", "reward_norm_partials": "float64",
+    "obs_norm_stats": "float64", "obs_norm_partials": "float64", "reward_norm_stats": "float64", "reward_norm_partials": "float64", "norm_slots": "float64",
 }
 
 
@@ -334,7 +334,7 @@ class Trainer:
 
     def __init__(self, config: Config, *, lib: Optional[nat.Lib] = None, device: Any = None, rank: int = 0, world_size: int = 1,
                  seed: Optional[int] = None, use_graph: bool = True, external_random: bool = False, stream: Any = None,
-                 num_envs_local: Optional[int] = None, xp: str = "torch"):
+                 num_envs_local: Optional[int] = None, xp: str = "torch", norm_after_connect: bool = False):
         self.config = config
         self.lib = lib if lib is not None else nat.load()
         self.xp = xp
@@ -346,12 +346,19 @@ class Trainer:
         if not 1 <= config.model.num_layers <= 4:
             raise ValueError(f"model.num_layers = {config.model.num_layers}: the MI355X engine lays out 1 to 4 hidden layers (reference default 2, config.py:53)")
         self.L = int(config.model.num_layers)
+        # Several ranks: the ranks' sums are gathered once per update over the engine's transport and merged in rank order, so statistics and tables are replicas
+        # (DESIGN.md 3.7 "Across ranks").  The engine enables the options only once a transport is connected, i.e. in `init_comm`, not here: a caller that
+        # builds a Trainer for several ranks says so with `norm_after_connect=True` (`make_train` does) and calls `init_comm()` before `reset()`; without it
+        # the options stay refused, before anything is created - a rank that never connects would collect its own rows' statistics only
         self.obs_norm_on = bool(tr.normalize_observations)
-        if self.obs_norm_on and world_size > 1:  # (the engine refuses it too; here before anything is created)
-            raise ValueError(f"training.normalize_observations with {world_size} ranks: the running statistics are not summed over ranks (single rank only)")
+        if self.obs_norm_on and world_size > 1 and not norm_after_connect:
+            raise ValueError(f"training.normalize_observations with {world_size} ranks: the running statistics are gathered over the ranks' transport - construct the "
+                             "Trainer with norm_after_connect=True and call init_comm() before reset()")
         self.reward_norm_on = bool(tr.normalize_rewards)
-        if self.reward_norm_on and world_size > 1:  # (the engine refuses it too; here before anything is created)
-            raise ValueError(f"training.normalize_rewards with {world_size} ranks: the running return statistics are not summed over ranks (single rank only)")
+        if self.reward_norm_on and world_size > 1 and not norm_after_connect:
+            raise ValueError(f"training.normalize_rewards with {world_size} ranks: the running return statistics are gathered over the ranks' transport - construct the "
+                             "Trainer with norm_after_connect=True and call init_comm() before reset()")
+        self._norm_pending = world_size > 1 and (self.obs_norm_on or self.reward_norm_on)
         if tr.num_envs % world_size != 0:
             raise ValueError(f"training.num_envs ({tr.num_envs}) must be divisible by the number of ranks ({world_size})")
         self.num_envs_global = tr.num_envs
@@ -435,13 +442,11 @@ class Trainer:
             self.lib.engine_set_action_delay(self._engine, self.action_delay.min, self.action_delay.max)
         # training.normalize_observations: off leaves the engine's launch sequence as it is
         self.obs_norm_clip, self.obs_norm_eps = float(tr.obs_norm_clip), float(tr.obs_norm_eps)
-        if self.obs_norm_on:
-            self.lib.engine_set_obs_norm(self._engine, 1, self.obs_norm_clip, self.obs_norm_eps)
         # training.normalize_rewards: likewise
         self.reward_norm_clip, self.reward_norm_eps = float(tr.reward_norm_clip), float(tr.reward_norm_eps)
-        if self.reward_norm_on:
-            self.lib.engine_set_reward_norm(self._engine, 1, self.reward_norm_clip, self.reward_norm_eps)
-        self.P = int(self.lib.param_count(C.byref(self.net)))
+        if not self._norm_pending:
+            self._enable_norm()
+        self.P =int(self.lib.param_count(C.byref(self.net)))
         self.updates_done = 0
         self._prepared = False
         self._keep_hist, self._hist_carry, self._hist_last = False, None, None
@@ -613,7 +618,8 @@ class Trainer:
         return tree
 
     def obs_norm(self) -> Dict[str, Any]:
-        """The running observation statistics on the host: "count" (rows seen = updates x T x N), "mean" / "var" (float64 [O], var = M2 / count),
+        """The running observation statistics on the host: "count" (rows seen on ALL ranks = updates x T x N x world_size - every rank holds the same
+        statistics), "mean" / "var" (float64 [O], var = M2 / count),
         "table" (float32 [2, O]: mean32 | inv_std32, what the next rollout applies), "clip", "eps".  Identity table and zero count when the option is off."""
         self._sync()
         st = self._to_host(self.region("obs_norm_stats")).astype(np.float64)
@@ -624,7 +630,8 @@ class Trainer:
         return dict(count=n, mean=st[1:1 + O].copy(), var=st[1 + O:1 + 2 * O] / n if n > 0 else np.zeros(O), table=table, clip=self.obs_norm_clip, eps=self.obs_norm_eps)
 
     def reward_norm(self) -> Dict[str, Any]:
-        """The running statistics of the discounted return on the host: "count" (steps seen = updates x T x N), "mean" / "var" (float64, var = M2 / count),
+        """The running statistics of the discounted return on the host: "count" (steps seen on ALL ranks = updates x T x N x world_size), "mean" / "var"
+        (float64, var = M2 / count),
         "scale" (the float32 inv_std the next rollout multiplies the rewards with; rewards are never centred), "clip", "eps".  Zero count and scale 1
         when the option is off."""
         self._sync()
@@ -633,6 +640,15 @@ class Trainer:
         if not self.reward_norm_on:
             n, st, scale = 0.0, np.zeros_like(st), 1.0
         return dict(count=n, mean=float(st[1]), var=float(st[2] / n) if n > 0 else 0.0, scale=scale, clip=self.reward_norm_clip, eps=self.reward_norm_eps)
+
+    def _enable_norm(self) -> None:
+        """Switches the configured normalisations on in the engine: at construction on one rank, at the end of `init_comm` on several (the engine wants the
+        ranks' transport connected first)."""
+        if self.obs_norm_on:
+            self.lib.engine_set_obs_norm(self._engine, 1, self.obs_norm_clip, self.obs_norm_eps)
+        if self.reward_norm_on:
+            self.lib.engine_set_reward_norm(self._engine, 1, self.reward_norm_clip, self.reward_norm_eps)
+        self._norm_pending = False
 
     # -- multi-GPU ---------------------------------------------------------------
     def init_comm(self, mode: Optional[str] = None) -> str:
@@ -710,6 +726,8 @@ class Trainer:
                     if all_ok(err is None and ok.value == 1):
                         self.comm_note = ("hipIpc buffers mapped on every rank, connect-time self-test exact on every rank (one fully checked exchange + "
                                           f"{os.environ.get('MPPO_PEER_SOAK', '2000')} more, every element compared on the device)")
+                        if self._norm_pending:
+                            self._enable_norm()
                         return "peer"
                     err = err or "the self-test all-reduce timed out or returned a wrong sum"
                 with device_ctx():
@@ -727,6 +745,8 @@ class Trainer:
         host = idbuf.cpu().numpy().copy()
         with device_ctx():  # (emulator build: the "communicator" is a shared-memory segment between the rank processes, tests/emu)
             self.lib.engine_comm_init(self._engine, host.ctypes.data)
+        if self._norm_pending:
+            self._enable_norm()
         return "rccl"
 
     def _device_guard(self):
@@ -779,7 +799,8 @@ class Trainer:
 
     def check_replicas(self) -> None:
         """COLLECTIVE (every rank): the replicas of a data-parallel run must hold bit-identical parameters after the same updates - a slice of
-        the gradient is reduced once, by its owner, and broadcast.  Compares a checksum of the parameter bits over the ranks and raises on
+        the gradient is reduced once, by its owner, and broadcast - and, with `training.normalize_observations` / `normalize_rewards`, bit-identical
+        statistics and tables (the ranks' sums are gathered and merged in rank order).  Compares checksums of those bits over the ranks and raises on
         every rank if they differ (a torn or reordered store in the exchange that the tags did not catch would show here, within
         `checkpoint_every` updates, and not only at the end of the run)."""
         if self.world_size < 2 or not self._dist_ready():
@@ -787,15 +808,27 @@ class Trainer:
         import torch
         import torch.distributed as dist
 
-        bits = self.params_flat().view(np.uint32).astype(np.uint64)
-        chk = torch.tensor([int(bits.sum() % (1 << 62)), int((bits * (np.arange(bits.size, dtype=np.uint64) % 65521 + 1)).sum() % (1 << 62))], dtype=torch.int64)
+        def checksums(words: np.ndarray) -> List[int]:
+            bits = np.ascontiguousarray(words).view(np.uint32).astype(np.uint64).reshape(-1)
+            return [int(bits.sum() % (1 << 62)), int((bits * (np.arange(bits.size, dtype=np.uint64) % 65521 + 1)).sum() % (1 << 62))]
+
+        # the parameters, and - where the options are on - the normalisations' statistics and tables: replicas too (every rank merges the same gathered slots)
+        parts = [("parameter", self.params_flat())]
+        self._sync()
+        if self.obs_norm_on:
+            parts += [("observation statistics", self._to_host(self.region("obs_norm_stats"))), ("observation table", self._to_host(self.region("obs_norm_table")))]
+        if self.reward_norm_on:
+            parts += [("return statistics", self._to_host(self.region("reward_norm_stats"))), ("reward table", self._to_host(self.region("reward_norm_table")))]
+        chk = torch.tensor([c for _, words in parts for c in checksums(words)], dtype=torch.int64)
         if dist.get_backend() == "nccl":
             chk = chk.to(self.device)
         lo, hi = chk.clone(), chk.clone()
         dist.all_reduce(lo, op=dist.ReduceOp.MIN)
         dist.all_reduce(hi, op=dist.ReduceOp.MAX)
         if not bool((lo == hi).all().item()):
-            raise RuntimeError(f"rank {self.rank}: the ranks' parameter replicas differ (checksums {lo.tolist()} .. {hi.tolist()}): the gradient exchange delivered "
+            same = (lo == hi).cpu().numpy().reshape(-1, 2).all(1)
+            what = ", ".join(name for (name, _), ok in zip(parts, same) if not ok)
+            raise RuntimeError(f"rank {self.rank}: the ranks' {what} replicas differ (checksums {lo.tolist()} .. {hi.tolist()}): the exchange delivered "
                                "different bytes to different ranks - this run's results are invalid")
 
     def check_peers(self, collective: bool = True) -> None:
@@ -822,7 +855,7 @@ class Trainer:
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             worst, where = int(t[0].item()) >> 16, int(t[0].item()) & 0xFFFF
         if out.value:
-            kind = {1: "the local gradient of rank", 2: "the reduced piece", 3: "the advantage sums of rank"}.get(info[0], "?")
+            kind = {1: "the local gradient of rank", 2: "the reduced piece", 3: "the advantage sums of rank", 5: "the normalisation sums of rank"}.get(info[0], "?")
             raise RuntimeError(f"rank {self.rank}: a wait for {kind} {info[1]} timed out (epoch {info[2]}, flag read {info[3]}; this rank: {info[4]} optimizer steps, "
                                f"{info[5]} updates, {info[6]} open arrivals, {info[7]} pieces per slice, {out.value} waits gave up); this run's results are invalid")
         if worst:
@@ -857,6 +890,9 @@ class Trainer:
     # -- stepping ----------------------------------------------------------------
     def reset(self) -> None:
         self._hist_carry = None  # (the metric words change under the history's feet: re-read before the next update)
+        if self._norm_pending:
+            raise RuntimeError(f"rank {self.rank}: training.normalize_observations / normalize_rewards with {self.world_size} ranks are enabled by init_comm() "
+                               "(the engine gathers the ranks' sums over its transport): call init_comm() before reset()")
         if self.ecfg.rng_impl == 1 and self.reset_noise_scale > 0:
             self._sync()
             self._seed_reset_key()  # (read by the engine's noisy reset)
@@ -966,6 +1002,9 @@ class Trainer:
         exercised with torch.distributed/gloo where RCCL is not available, and as a reference for integrators
         who drive the stages themselves.  Requires external_random-style permutations already in "perm"."""
         E, M, mb, B, W = self.E, self.M, (self.T * self.N) // self.M, self.T * self.N, self.world_size
+        if W > 1 and (self.obs_norm_on or self.reward_norm_on):
+            raise RuntimeError("learn_host_driven: training.normalize_observations / normalize_rewards with several ranks need the engine's own transport (the rollout "
+                               "gathers the ranks' sums through it: init_comm, then rollout() / learn() or update()); the host-driven learn phase does not cover them")
         lib, s = self.lib, self._stream_ptr
         reg = {k: self.region(k) for k in ("adv", "perm", "adv_sums", "adv_stats", "params", "adam_m", "adam_v", "grad", "count", "losses", "obs",
                                            "action", "value", "log_prob", "target", "grad_ws", "adam_ws")}
@@ -1107,7 +1146,7 @@ def make_train(config: Config, **trainer_kwargs: Any) -> Callable[[Any], TrainOu
                          "metrics are for small runs; the default returns per-update reductions")
 
     def train(rng: Any, max_updates: Optional[int] = None, log_every: int = 0) -> TrainOutput:
-        tr = Trainer(config, seed=_seed_from_rng(rng), **trainer_kwargs)
+        tr = Trainer(config, seed=_seed_from_rng(rng), **{"norm_after_connect": True, **trainer_kwargs})  # (init_comm follows at once)
         tr.init_comm()
         tr.keep_metrics_history(keep_hist)
         hist: list = []

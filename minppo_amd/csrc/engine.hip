@@ -986,17 +986,20 @@ extern "C" int32_t mppo_engine_peer_selftest(mppo_engine_t* e, void* stream, int
   double* gdev = nullptr;
   he = hipMalloc(reinterpret_cast<void**>(&gdev), gat.size() * sizeof(double));
   if (he != hipSuccess) { (void)hipFree(dev); (void)hipFree(scratch); return fail(MPPO_EHIP, "mppo_engine_peer_selftest: %s", hipGetErrorString(he)); }
-  he = hipMemcpy(gdev, gat.data(), gat.size() * sizeof(double), hipMemcpyHostToDevice);
-  if (he == hipSuccess) he = hipMemcpy(dev, host, sizeof(host), hipMemcpyHostToDevice);
-  if (he == hipSuccess) he = hipMemcpy(scratch, g.data(), P * sizeof(float), hipMemcpyHostToDevice);
-  if (he == hipSuccess) he = hipMemset(scratch + P, 0, 3 * P * sizeof(float));
-  mppo_adam_cfg_t ac = e->cfg.adam;
-  ac.anneal = 0; ac.sched_div = 1; ac.num_updates = 1;
   // on the CALLER's stream (the one its updates will run on): several engines of one process (one per GPU, or ranks sharing a GPU in the
   // tests) run their self-tests at the same time and each one's kernels wait for the others' - streams they shared would block them all.
   // (A stream created here costs more than it looks: measured on a GPU shared by two rank processes, one extra stream per process
   // - even destroyed again - slowed every later update from 11.7 to 27.8 ms.)
+  // EVERYTHING between here and the end of the soak - copies, fills, waits of the host - goes through that stream and waits for that stream alone: a copy
+  // on the default stream or a device-wide wait in the middle would also wait for what a sibling engine's thread has enqueued by then, i.e. for kernels
+  // that wait for launches this thread has yet to make (peer_status_on, k_peer.hip).
   hipStream_t st = static_cast<hipStream_t>(stream);
+  he = hipMemcpyAsync(gdev, gat.data(), gat.size() * sizeof(double), hipMemcpyHostToDevice, st);
+  if (he == hipSuccess) he = hipMemcpyAsync(dev, host, sizeof(host), hipMemcpyHostToDevice, st);
+  if (he == hipSuccess) he = hipMemcpyAsync(scratch, g.data(), P * sizeof(float), hipMemcpyHostToDevice, st);
+  if (he == hipSuccess) he = hipMemsetAsync(scratch + P, 0, 3 * P * sizeof(float), st);
+  mppo_adam_cfg_t ac = e->cfg.adam;
+  ac.anneal = 0; ac.sched_div = 1; ac.num_updates = 1;
   // the self-test answers in milliseconds when the transport works; when it does not, ten seconds are enough to say so (the run-time limit
   // of a wait, MPPO_PEER_TIMEOUT_MS, is sized for host-side skew between ranks in the middle of a job: a minute by default)
   const unsigned long long limit_ms = peer_set_limit_ms(e->peer, 0.0);
@@ -1011,11 +1014,12 @@ extern "C" int32_t mppo_engine_peer_selftest(mppo_engine_t* e, void* stream, int
     if (rc == MPPO_OK)
       rc = clip_adam(P, scratch + P, scratch + 2 * P, scratch + 3 * P, peer_red(e->peer), e->count, 0, ac, const_cast<float*>(peer_red(e->peer)) + P, true, st, nullptr, &ps);
     if (rc == MPPO_OK) rc = peer_advance(e->peer, 1, st);
-    if (rc == MPPO_OK) rc = peer_status(e->peer, &timed_out, nullptr);  // synchronises
-    if (rc == MPPO_OK) he = hipMemcpy(host, dev, sizeof(host), hipMemcpyDeviceToHost);
-    if (rc == MPPO_OK && he == hipSuccess) he = hipMemcpy(gat.data(), gdev, gat.size() * sizeof(double), hipMemcpyDeviceToHost);
-    if (rc == MPPO_OK && he == hipSuccess) he = hipMemcpy(red.data(),peer_red(e->peer), 2 * (P + kSqSlots) * sizeof(float), hipMemcpyDeviceToHost);
-    if (rc == MPPO_OK && he == hipSuccess) he = hipMemcpy(m1.data(), scratch + 2 * P, P * sizeof(float), hipMemcpyDeviceToHost);
+    if (rc == MPPO_OK) rc = peer_status_on(e->peer, st, &timed_out, nullptr);  // waits for the stream
+    if (rc == MPPO_OK) he = hipMemcpyAsync(host, dev, sizeof(host), hipMemcpyDeviceToHost, st);
+    if (rc == MPPO_OK && he == hipSuccess) he = hipMemcpyAsync(gat.data(), gdev, gat.size() * sizeof(double), hipMemcpyDeviceToHost, st);
+    if (rc == MPPO_OK && he == hipSuccess) he = hipMemcpyAsync(red.data(), peer_red(e->peer), 2 * (P + kSqSlots) * sizeof(float), hipMemcpyDeviceToHost, st);
+    if (rc == MPPO_OK && he == hipSuccess) he = hipMemcpyAsync(m1.data(), scratch + 2 * P, P * sizeof(float), hipMemcpyDeviceToHost, st);
+    if (rc == MPPO_OK && he == hipSuccess) he = hipStreamSynchronize(st);
     // ---- the soak (round 6): ONE exchange on known values finds a transport that carries no stores; it does not find a pair torn or a store
     // reordered once in 10^5.  `soak` more exchanges follow back to back at the rate of training (no host in between), every element checked
     // on the device; every rank runs the same number (the ranks wait for each other inside every step).
@@ -1034,8 +1038,9 @@ extern "C" int32_t mppo_engine_peer_selftest(mppo_engine_t* e, void* stream, int
         }
         if (rc == MPPO_OK) rc = peer_advance(e->peer, 1, st);
       }
-      if (rc == MPPO_OK && he == hipSuccess) rc = peer_status(e->peer, &timed_out, nullptr);  // synchronises
-      if (rc == MPPO_OK && he == hipSuccess) he = hipMemcpy(&soak_bad, dev, sizeof(int), hipMemcpyDeviceToHost);
+      if (rc == MPPO_OK && he == hipSuccess) rc = peer_status_on(e->peer, st, &timed_out, nullptr);  // waits for the stream
+      if (rc == MPPO_OK && he == hipSuccess) he = hipMemcpyAsync(&soak_bad, dev, sizeof(int), hipMemcpyDeviceToHost, st);
+      if (rc == MPPO_OK && he == hipSuccess) he = hipStreamSynchronize(st);
     }
   }
   peer_set_limit_ms(e->peer, (double)limit_ms);

@@ -299,11 +299,7 @@ unsigned long long peer_set_limit_ms(PeerComm* c, double ms) {
   return old_ms;
 }
 
-int32_t peer_status(const PeerComm* c, int32_t* timed_out, int32_t* info8) {
-  MPPO_REQUIRE(c && timed_out, "peer_status: null argument");
-  MPPO_CHECK_HIP(hipDeviceSynchronize());
-  PeerHdr h;
-  MPPO_CHECK_HIP(hipMemcpy(&h, c->mine, sizeof(h), hipMemcpyDeviceToHost));
+static void report_status(const PeerComm* c, const PeerHdr& h, int32_t* timed_out, int32_t* info8) {
   *timed_out = h.error;
   if (const char* dbg = getenv("MPPO_PEER_DEBUG"); dbg && dbg[0] == '1') {  // the whole header, for post-mortems of a wait that gave up
     fprintf(stderr, "[peer rank %d] error %d info %d %d %d %d epoch %d %d nA %d K %d\n  arrive:", c->rank, h.error, h.error_info[0], h.error_info[1], h.error_info[2],
@@ -324,6 +320,28 @@ int32_t peer_status(const PeerComm* c, int32_t* timed_out, int32_t* info8) {
     info8[4] = h.epoch[0]; info8[5] = h.epoch[1]; info8[6] = 0; info8[7] = c->view.nA;
     for (int q = 0; q <= kPeerMaxRanks; ++q) info8[6] += h.arrive[q][0];  // workgroups counted into an unfinished slice (0 between launches)
   }
+}
+
+int32_t peer_status(const PeerComm* c, int32_t* timed_out, int32_t* info8) {
+  MPPO_REQUIRE(c && timed_out, "peer_status: null argument");
+  MPPO_CHECK_HIP(hipDeviceSynchronize());
+  PeerHdr h;
+  MPPO_CHECK_HIP(hipMemcpy(&h, c->mine, sizeof(h), hipMemcpyDeviceToHost));
+  report_status(c, h, timed_out, info8);
+  return MPPO_OK;
+}
+
+// The same behind everything enqueued on `s` so far, waiting for `s` ALONE.  hipDeviceSynchronize waits for every stream of the process: with several
+// engines in one process it also waits for what a sibling engine has enqueued already, and those kernels may wait for launches that THIS caller makes
+// only after the call returns - the sibling's waits then run into their limit while the caller sits in the runtime (seen as an intermittent time-out
+// between the self-test's first exchange and its soak with two ranks per process: whichever thread came back first had the soak enqueued by the time the
+// other one's device-wide wait looked at its stream).
+int32_t peer_status_on(const PeerComm* c, hipStream_t s, int32_t* timed_out, int32_t* info8) {
+  MPPO_REQUIRE(c && timed_out, "peer_status_on: null argument");
+  PeerHdr h;
+  MPPO_CHECK_HIP(hipMemcpyAsync(&h, c->mine, sizeof(h), hipMemcpyDeviceToHost, s));
+  MPPO_CHECK_HIP(hipStreamSynchronize(s));
+  report_status(c, h, timed_out, info8);
   return MPPO_OK;
 }
 

@@ -264,7 +264,9 @@ int32_t peer_allreduce_f64(const PeerComm* c, double* buf, size_t n, hipStream_t
 // other slot is overwritten with its owner's bits.  n0 + n1 <= gather_doubles of peer_create
 int32_t peer_gather_f64(const PeerComm* c, double* buf, int n0, size_t off1, int n1, hipStream_t s);
 int32_t peer_advance(const PeerComm* c, int steps, hipStream_t s);                              // end of an update
-int32_t peer_status(const PeerComm* c, int32_t* timed_out, int32_t* info8);
+int32_t peer_status(const PeerComm* c, int32_t* timed_out, int32_t* info8);                      // synchronises the DEVICE (every stream of the process)
+// the same behind the work enqueued on `s`, waiting for `s` alone: for a caller whose process holds further engines whose kernels wait for launches it has yet to make
+int32_t peer_status_on(const PeerComm* c, hipStream_t s, int32_t* timed_out, int32_t* info8);
 // one-way latency of a system-scope flag between this rank and `other` (both ranks call it at the same time, one as initiator): `iters` round
 // trips of one word through the two exchange buffers' headers, timed by the initiator's kernel on the 100 MHz clock; synchronises
 int32_t peer_latency(PeerComm* c, int other, int iters, int initiator, hipStream_t s, double* one_way_us);

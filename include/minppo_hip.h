@@ -848,7 +848,7 @@ int32_t mppo_eval_limit_reduce(int32_t N, const void* acc, mppo_eval_limit_resul
  * frame f at qpos + f * q_ld: q_ld = nq for packed joint positions, q_ld = rec_dim to draw straight from state records or an
  * evaluation's trajectory rows (qpos is at offset 0 of both).  Outputs are device memory; any may be NULL.
  * The image: MuJoCo's camera convention (looks along -z, +x right, +y up, vertical fovy), row 0 at the top, one ray through every
- * pixel centre, no anti-aliasing; Lambert shading from one fixed directional light plus ambient, hard shadows, a two-tone 1 m
+ * pixel centre (anti-aliasing: mppo_render_grid's `samples`); Lambert shading from one fixed directional light plus ambient, hard shadows, a two-tone 1 m
  * checker on the ground plane, a constant sky; meshes are drawn as their convex hulls. */
 typedef struct mppo_scene mppo_scene_t;
 typedef struct mppo_scene_dims { int32_t nq, nbody, ngeom, ncam, has_plane; } mppo_scene_dims_t;
@@ -863,6 +863,20 @@ typedef struct mppo_render_out {   /* any pointer may be NULL */
 } mppo_render_out_t;
 int32_t mppo_render(const mppo_scene_t* s, int32_t F, const float* qpos, int32_t q_ld, int32_t camera, int32_t width, int32_t height,
                     const mppo_render_out_t* out, void* stream);
+/* Many environments per frame, with supersampling: frame f shows E environments as a grid of `cols` columns and rows = ceil(E / cols)
+ * rows of cell_width x cell_height pixel cells, environment e in cell (e / cols, e % cols), row 0 of the image at the top:
+ * rgb [F, rows * cell_height, cols * cell_width, 3].  Every cell is that environment's own view through `camera` (a track camera
+ * follows its own robot); a cell past the last environment is the sky colour.  Environment e of frame f is read at
+ * qpos + f * q_ld_frame + e * q_ld_env: packed [F, E, nq] is (E * nq, nq); the first E of N state records per frame is
+ * (N * rec_dim, rec_dim); an evaluation's trajectory block [K + 1, R, row] is (R * row, row).  `samples` = S in 1 .. 4 casts
+ * S x S rays per pixel, through the pixel centres of an image S times as large, and stores the mean of their linear colours (summed
+ * row-major, times 1 / S^2, then quantised as mppo_render quantises); S = 1 is mppo_render's image of every cell, bit for bit.
+ * Two launches on `stream` (F * E pose records, then the rays: one workgroup per 16 x 16 tile of one cell stages that environment's
+ * scene once for its S^2 * 256 rays), no synchronisation; the pose scratch is the handle's, as in mppo_render.  Refused with a message
+ * (MPPO_EINVAL): samples outside 1 .. 4, cols < 1, E < 1, F < 1, a cell size < 1, a stride below nq, a camera whose mode is not drawn,
+ * a scene over the LDS budget, an image of more than 2^31 - 1 bytes (its index would overflow int32). */
+int32_t mppo_render_grid(const mppo_scene_t* s, int32_t F, int32_t E, const float* qpos, int32_t q_ld_frame, int32_t q_ld_env,
+                         int32_t camera, int32_t cols, int32_t cell_width, int32_t cell_height, int32_t samples, uint8_t* rgb, void* stream);
 
 #ifdef __cplusplus
 }

@@ -242,6 +242,7 @@ SIGNATURES = {
     "mppo_scene_close": (c_i32, [c_vp]),
     "mppo_scene_get_dims": (c_i32, [c_vp, P(SceneDims)]),
     "mppo_render": (c_i32, [c_vp, c_i32, c_vp, c_i32, c_i32, c_i32, c_i32, P(RenderOut), c_vp]),
+    "mppo_render_grid": (c_i32, [c_vp, c_i32, c_i32, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp]),
 }
 
 UNCHECKED = {"mppo_last_error", "mppo_abi_version", "mppo_param_count", "mppo_policy_ws_bytes", "mppo_grad_ws_bytes",

@@ -126,6 +126,11 @@ class VisualizationConfig:
     video_length: float = field(default=5.0)
     num_episodes: int = field(default=20)
     video_save_path: str = field(default="episode.mp4")
+    # Extensions (absent upstream; minppo_amd/render.py, `mppo_render_grid`).  `samples` = S: S x S rays per pixel, averaged (anti-aliasing; 1 .. 4;
+    # 1 = one ray through the pixel centre).  `grid_envs` = G > 0: `minppo env` runs G environments side by side and draws them as a grid whose cells
+    # are width x height (0 = one environment, the image is width x height).  `samples` also applies to `evaluation.video_path`.
+    samples: int = field(default=1)
+    grid_envs: int = field(default=0)
 
 
 @dataclass
@@ -228,6 +233,8 @@ class EvaluationConfig:
     # `video_path` renders recorded environment 0's trajectory (camera and image size: `visualization`) and writes it as a video
     # (.npz / .avi / .mp4: minppo_amd.render.write_video) - train, then watch it.  Needs record_envs >= 1.
     video_path: str = field(default="")
+    # `video_grid`: every recorded environment (`record_envs`) is drawn, as a grid of visualization.width x height cells, instead of environment 0 alone.
+    video_grid: bool = field(default=False)
 
 
 @dataclass

@@ -1,8 +1,10 @@
-// k_render.hip - the two kernels of mppo_render (render.hip): what the reference leaves to MuJoCo's renderer (`env.render`, minppo/env.py:264-333).
+// k_render.hip - the kernels of mppo_render and mppo_render_grid (render.hip): what the reference leaves to MuJoCo's renderer (`env.render`,
+// minppo/env.py:264-333).
 //
-//   render_poses  one thread per frame: forward kinematics of the scene's tree from that frame's qpos - bodies in index order, parents first; free, ball,
+//   render_poses  one thread per pose record (frame f, environment e; frame-major, E = 1 for mppo_render): forward kinematics of the scene's tree from
+//                 qpos + f * q_ld_frame + e * q_ld_env - bodies in index order, parents first; free, ball,
 //                 hinge and slide joints; quaternions normalised as the environment kernel's kinematics normalises them - then the world pose of every
-//                 visual (position + row-major rotation) and the frame's camera (position, basis, tan(fovy / 2)).
+//                 visual (position + row-major rotation) and the record's camera (position, basis, tan(fovy / 2)).
 //   render_rays   256 threads per workgroup, one 16 x 16 pixel tile of one frame: wave w owns the 8 x 8 block (w & 1, w >> 1) of the tile, a lane one pixel.
 //                 The workgroup stages its frame's visuals (24 words each) and camera into LDS once; every lane then casts one primary ray through its
 //                 pixel centre and loops over ALL visuals, so the trip count, the LDS addresses and the shape-type switch are the same in every lane of a
@@ -11,6 +13,8 @@
 //                 hit is the ray ENTERING a shape at t > 0.  Shading: Lambert from one directional light plus a constant ambient term, a hard shadow ray
 //                 toward the light through the same routines, a two-tone 1 m checker on the ground, a constant sky.  One sample per pixel: the image is
 //                 a pure function of the inputs.  Partial tiles: every lane computes (a clamped pixel), only lanes inside the image store.
+//   render_grid_rays<S>  the same per-ray path (shared device functions, not a copy) for a frame tiled with E environments' cells, S x S rays per pixel:
+//                 described at the kernel.
 //
 // The quadratic is solved in its cancellation-free form: the discriminant comes from the squared distance of the centre to the ray (the point of
 // closest approach), not from b * b - c.
@@ -66,13 +70,14 @@ constexpr int kPoseThreads = 64;
 
 }  // namespace
 
-__global__ void __launch_bounds__(kPoseThreads) render_poses_kernel(SceneView v, const void* __restrict__ blob, int F, const float* __restrict__ qpos_all, int q_ld, int camera,
-                                                                    float* __restrict__ body_ws, float* __restrict__ pose_all, float* __restrict__ cam_all) {
+// (`f` below is the pose record: frame f / E, environment f % E)
+__global__ void __launch_bounds__(kPoseThreads) render_poses_kernel(SceneView v, const void* __restrict__ blob, int F, int E, const float* __restrict__ qpos_all, int q_ld_frame,
+                                                                    int q_ld_env, int camera, float* __restrict__ body_ws, float* __restrict__ pose_all, float* __restrict__ cam_all) {
   const int f = blockIdx.x * kPoseThreads + threadIdx.x;
-  if (f >= F) return;
+  if (f >= F * E) return;
   const int32_t* bi = static_cast<const int32_t*>(blob);
   const float* bf = static_cast<const float*>(blob);
-  const float* qpos = qpos_all + (size_t)f * q_ld;
+  const float* qpos = qpos_all + (size_t)(f / E) * q_ld_frame + (size_t)(f % E) * q_ld_env;
   float* xb = body_ws + (size_t)f * v.nbody * 7;  // per body: position 3, quaternion 4
   xb[0] = 0.f; xb[1] = 0.f; xb[2] = 0.f; xb[3] = 1.f; xb[4] = 0.f; xb[5] = 0.f; xb[6] = 0.f;
   const int32_t *parent = bi + v.o[SI_body_parent], *jntadr = bi + v.o[SI_body_jntadr], *jntnum = bi + v.o[SI_body_jntnum], *jtype = bi + v.o[SI_jnt_type],
@@ -277,50 +282,46 @@ __device__ __forceinline__ float to_level(float x) {  // [0, 1] -> 0 .. 255, rou
 
 // light, shading and colours: fixed (the image is a function of the scene blob, qpos, the camera and the size alone)
 #define RENDER_LIGHT R3{2.f / 7.f, -3.f / 7.f, 6.f / 7.f}  /* a unit vector toward the light */
+#define RENDER_SKY R3{0.55f, 0.70f, 0.90f}
 constexpr float kAmbient = 0.35f, kDiffuse = 0.65f, kShadowBias = 1e-3f;
 
-__global__ void __launch_bounds__(kRenderThreads) render_rays_kernel(SceneView v, const void* __restrict__ blob, int W, int H, int tiles_x, int tiles_per_frame,
-                                                                     const float* __restrict__ pose_all, const float* __restrict__ cam_all, unsigned char* __restrict__ rgb,
-                                                                     float* __restrict__ depth, int32_t* __restrict__ geom_id) {
-  MPPO_DYN_SMEM(smem);
-  float* sg = reinterpret_cast<float*>(smem);  // [ngeom][kGeomWords], then the camera
-  const int ng = v.ngeom;
-  float* scam = sg + (size_t)ng * kGeomWords;
-  const int32_t* bi = static_cast<const int32_t*>(blob);
-  const float* bf = static_cast<const float*>(blob);
-  const int f = blockIdx.x / tiles_per_frame, tile = blockIdx.x % tiles_per_frame;
-  const int tid = threadIdx.x;
-  {
-    const float* pose = pose_all + (size_t)f * ng * 12;
-    const int32_t *gtype = bi + v.o[SI_geom_type], *ghull = bi + v.o[SI_geom_hull];
-    const float *gsize = bf + v.o[SF_geom_size], *grgb = bf + v.o[SF_geom_rgb], *grb = bf + v.o[SF_geom_rbound];
-    for (int g = tid; g < ng; g += kRenderThreads) {
-      float* d = sg + kGeomWords * g;
-      for (int k = 0; k < 12; ++k) d[k] = pose[12 * g + k];
-      d[12] = __uint_as_float((unsigned)(gtype[g]));
-      for (int k = 0; k < 3; ++k) { d[13 + k] = gsize[3 * g + k]; d[16 + k] = grgb[3 * g + k]; }
-      d[19] = grb[g];
-      d[20] = __uint_as_float((unsigned)(ghull[2 * g]));
-      d[21] = __uint_as_float((unsigned)(ghull[2 * g + 1]));
-      d[22] = 0.f; d[23] = 0.f;
-    }
-    if (tid < kCamWords) scam[tid] = cam_all[(size_t)f * kCamWords + tid];
-  }
-  __syncthreads();
-  const int wave = tid >> 6, lane = tid & 63;
-  const int px = (tile % tiles_x) * 16 + (wave & 1) * 8 + (lane & 7), py = (tile / tiles_x) * 16 + (wave >> 1) * 8 + (lane >> 3);
-  const bool inside = px < W && py < H;
-  const int cx = px < W ? px : W - 1, cy = py < H ? py : H - 1;  // (a masked lane casts its neighbour's ray: every lane runs the same loops)
-  // MuJoCo's camera: looks along -z, +x right, +y up, vertical field of view
-  const float th = scam[12];
-  const R3 dc = {(2.f * ((float)cx + 0.5f) / (float)W - 1.f) * th * ((float)W / (float)H), (1.f - 2.f * ((float)cy + 0.5f) / (float)H) * th, -1.f};
-  const R3 org = rld3(scam);
-  R3 dir = rmatv(scam + 3, dc);
-  dir = rmul(dir, 1.f / sqrtf(rdot(dir, dir)));
-  const float* planes = bf + v.o[SF_hull_plane];
+namespace {
 
-  float best = INFINITY;
-  int id = -1;
+// The workgroup's (frame, environment) into LDS: pose record `rec`'s visuals, 24 words each, then its camera.  The caller barriers.
+__device__ __forceinline__ void stage_scene(const SceneView& v, const int32_t* bi, const float* bf, size_t rec, const float* __restrict__ pose_all, const float* __restrict__ cam_all,
+                                            float* sg, float* scam, int tid) {
+  const int ng = v.ngeom;
+  const float* pose = pose_all + rec * ng * 12;
+  const int32_t *gtype = bi + v.o[SI_geom_type], *ghull = bi + v.o[SI_geom_hull];
+  const float *gsize = bf + v.o[SF_geom_size], *grgb = bf + v.o[SF_geom_rgb], *grb = bf + v.o[SF_geom_rbound];
+  for (int g = tid; g < ng; g += kRenderThreads) {
+    float* d = sg + kGeomWords * g;
+    for (int k = 0; k < 12; ++k) d[k] = pose[12 * g + k];
+    d[12] = __uint_as_float((unsigned)(gtype[g]));
+    for (int k = 0; k < 3; ++k) { d[13 + k] = gsize[3 * g + k]; d[16 + k] = grgb[3 * g + k]; }
+    d[19] = grb[g];
+    d[20] = __uint_as_float((unsigned)(ghull[2 * g]));
+    d[21] = __uint_as_float((unsigned)(ghull[2 * g + 1]));
+    d[22] = 0.f; d[23] = 0.f;
+  }
+  if (tid < kCamWords) scam[tid] = cam_all[rec * kCamWords + tid];
+}
+
+// The unit ray through the image position (x, y) in pixels (a pixel's centre is at its index + 0.5) of a W x H view.  MuJoCo's camera: looks along -z, +x
+// right, +y up, vertical field of view.
+__device__ __forceinline__ R3 camera_ray(const float* scam, float x, float y, int W, int H) {
+  const float th = scam[12];
+  const R3 dc = {(2.f * x / (float)W - 1.f) * th * ((float)W / (float)H), (1.f - 2.f * y / (float)H) * th, -1.f};
+  const R3 dir = rmatv(scam + 3, dc);
+  return rmul(dir, 1.f / sqrtf(rdot(dir, dir)));
+}
+
+// One ray against the staged scene: the primary ray over all visuals and the ground, the shadow ray toward the light, shading.  -> the linear colour;
+// `best` = the distance along the ray (inf on a miss), `id` = the visual (ngeom = the ground, -1 = a miss).
+__device__ __forceinline__ R3 shade_ray(const SceneView& v, const float* sg, const float* __restrict__ planes, R3 org, R3 dir, float& best, int& id) {
+  const int ng = v.ngeom;
+  best = INFINITY;
+  id = -1;
   R3 bn = {0.f, 0.f, 1.f};
   for (int g = 0; g < ng; ++g) {
     const float* s = sg + kGeomWords * g;
@@ -338,7 +339,7 @@ __global__ void __launch_bounds__(kRenderThreads) render_rays_kernel(SceneView v
     const float t = (v.plane_z - org.z) / dir.z;
     if (t > 0.f && t < best) { best = t; id = ng; bn = R3{0.f, 0.f, 1.f}; }
   }
-  R3 col = {0.55f, 0.70f, 0.90f};  // the sky
+  R3 col = RENDER_SKY;
   if (id >= 0) {
     const R3 light = RENDER_LIGHT;
     const R3 hit = radd(org, rmul(dir, best));
@@ -367,6 +368,29 @@ __global__ void __launch_bounds__(kRenderThreads) render_rays_kernel(SceneView v
     const float k = kAmbient + kDiffuse * lit;
     col = rmul(base, k);
   }
+  return col;
+}
+
+}  // namespace
+
+__global__ void __launch_bounds__(kRenderThreads) render_rays_kernel(SceneView v, const void* __restrict__ blob, int W, int H, int tiles_x, int tiles_per_frame,
+                                                                     const float* __restrict__ pose_all, const float* __restrict__ cam_all, unsigned char* __restrict__ rgb,
+                                                                     float* __restrict__ depth, int32_t* __restrict__ geom_id) {
+  MPPO_DYN_SMEM(smem);
+  float* sg = reinterpret_cast<float*>(smem);  // [ngeom][kGeomWords], then the camera
+  float* scam = sg + (size_t)v.ngeom * kGeomWords;
+  const float* bf = static_cast<const float*>(blob);
+  const int f = blockIdx.x / tiles_per_frame, tile = blockIdx.x % tiles_per_frame;
+  const int tid = threadIdx.x;
+  stage_scene(v, static_cast<const int32_t*>(blob), bf, (size_t)f, pose_all, cam_all, sg, scam, tid);
+  __syncthreads();
+  const int wave = tid >> 6, lane = tid & 63;
+  const int px = (tile % tiles_x) * 16 + (wave & 1) * 8 + (lane & 7), py = (tile / tiles_x) * 16 + (wave >> 1) * 8 + (lane >> 3);
+  const bool inside = px < W && py < H;
+  const int cx = px < W ? px : W - 1, cy = py < H ? py : H - 1;  // (a masked lane casts its neighbour's ray: every lane runs the same loops)
+  float best;
+  int id;
+  const R3 col = shade_ray(v, sg, bf + v.o[SF_hull_plane], rld3(scam), camera_ray(scam, (float)cx + 0.5f, (float)cy + 0.5f, W, H), best, id);
   if (inside) {
     const size_t pix = ((size_t)f * H + py) * W + px;
     if (rgb) {
@@ -379,10 +403,86 @@ __global__ void __launch_bounds__(kRenderThreads) render_rays_kernel(SceneView v
   }
 }
 
-int32_t render_poses_launch(const SceneView& v, const void* dev_blob, int F, const float* qpos, int q_ld, int camera, float* body_ws, float* pose, float* camw,
-                            hipStream_t stream) {
-  hipLaunchKernelGGL(render_poses_kernel, dim3(cdiv(F, kPoseThreads)), dim3(kPoseThreads), 0, stream, v, dev_blob, F, qpos, q_ld, camera, body_ws, pose, camw);
+// The tiled many-environment view with supersampling: 256 threads = one 16 x 16 pixel tile inside ONE environment's cell of one frame (wave w owns the
+// 8 x 8 block (w & 1, w >> 1), as above); grid = tiles per cell x (rows * cols cells) x F.  The workgroup stages the visuals and the camera of its
+// (frame, environment) once - pose record f * E + e - and every lane then casts S x S rays through its pixel, row-major, at the pixel centres of an image S
+// times as large: sub-sample (a, b) of pixel (i, j) goes through (j + (b + 0.5) / S, i + (a + 0.5) / S).  The staged scene is so read S * S times for one
+// staging, and the sub-sample loop's trip count is a constant: LDS addresses and the shape switch stay wave-uniform (lanes are pixels, never sub-samples -
+// no cross-lane reduction, no fewer pixels per staging).  The S * S linear colours are summed in that order, scaled by 1 / (S * S) and quantised as above;
+// at S = 1 that is render_rays_kernel's image of the cell, bit for bit.  Partial tiles at a cell's right and bottom edge are masked at the store (a masked
+// lane casts its clamped neighbour's rays); a cell past the last environment is the sky, stored before any barrier.
+template <int S>
+__global__ void __launch_bounds__(kRenderThreads) render_grid_rays_kernel(SceneView v, const void* __restrict__ blob, int E, int cols, int cw, int ch, int tiles_x, int tiles_per_cell,
+                                                                          int cells, const float* __restrict__ pose_all, const float* __restrict__ cam_all,
+                                                                          unsigned char* __restrict__ rgb) {
+  MPPO_DYN_SMEM(smem);
+  float* sg = reinterpret_cast<float*>(smem);  // [ngeom][kGeomWords], then the camera
+  float* scam = sg + (size_t)v.ngeom * kGeomWords;
+  const float* bf = static_cast<const float*>(blob);
+  const int tile = blockIdx.x % tiles_per_cell, fc = blockIdx.x / tiles_per_cell;
+  const int f = fc / cells, e = fc % cells;  // (environment e is at cell (e / cols, e % cols): the cell's index IS the environment)
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int px = (tile % tiles_x) * 16 + (wave & 1) * 8 + (lane & 7), py = (tile / tiles_x) * 16 + (wave >> 1) * 8 + (lane >> 3);
+  const bool inside = px < cw && py < ch;
+  const size_t pix = ((size_t)f * (cells / cols) * ch + (size_t)(e / cols) * ch + py) * ((size_t)cols * cw) + (size_t)(e % cols) * cw + px;
+  if (e >= E) {  // a blank cell (workgroup-uniform)
+    const R3 sky = RENDER_SKY;
+    if (inside) {
+      rgb[3 * pix] = (unsigned char)to_level(sky.x);
+      rgb[3 * pix + 1] = (unsigned char)to_level(sky.y);
+      rgb[3 * pix + 2] = (unsigned char)to_level(sky.z);
+    }
+    return;
+  }
+  stage_scene(v, static_cast<const int32_t*>(blob), bf, (size_t)f * E + e, pose_all, cam_all, sg, scam, tid);
+  __syncthreads();
+  const int cx = px < cw ? px : cw - 1, cy = py < ch ? py : ch - 1;
+  const float* planes = bf + v.o[SF_hull_plane];
+  const R3 org = rld3(scam);
+  R3 sum = {0.f, 0.f, 0.f};
+#pragma unroll 1
+  for (int k = 0; k < S * S; ++k) {  // (a = k / S down, b = k % S across: wave-uniform)
+    float best;
+    int id;
+    const float x = (float)cx + ((float)(k % S) + 0.5f) / (float)S, y = (float)cy + ((float)(k / S) + 0.5f) / (float)S;
+    sum = radd(sum, shade_ray(v, sg, planes, org, camera_ray(scam, x, y, cw, ch), best, id));
+  }
+  if (inside) {
+    const R3 col = rmul(sum, 1.f / (float)(S * S));
+    rgb[3 * pix] = (unsigned char)to_level(col.x);
+    rgb[3 * pix + 1] = (unsigned char)to_level(col.y);
+    rgb[3 * pix + 2] = (unsigned char)to_level(col.z);
+  }
+}
+
+int32_t render_poses_launch(const SceneView& v, const void* dev_blob, int F, int E, const float* qpos, int q_ld_frame, int q_ld_env, int camera, float* body_ws, float* pose,
+                            float* camw, hipStream_t stream) {
+  hipLaunchKernelGGL(render_poses_kernel, dim3(cdiv(F * E, kPoseThreads)), dim3(kPoseThreads), 0, stream, v, dev_blob, F, E, qpos, q_ld_frame, q_ld_env, camera, body_ws, pose,
+                     camw);
   MPPO_CHECK_LAUNCH("render_poses_kernel");
+  return MPPO_OK;
+}
+
+template <int S>
+static void grid_rays_launch(const SceneView& v, const void* dev_blob, unsigned blocks, size_t lds, int E, int cols, int cw, int ch, int tiles_x, int tiles_per_cell, int cells,
+                             const float* pose, const float* camw, uint8_t* rgb, hipStream_t stream) {
+  hipLaunchKernelGGL(render_grid_rays_kernel<S>, dim3(blocks), dim3(kRenderThreads), lds, stream, v, dev_blob, E, cols, cw, ch, tiles_x, tiles_per_cell, cells, pose, camw, rgb);
+}
+
+int32_t render_grid_rays_launch(const SceneView& v, const void* dev_blob, int F, int E, int cols, int cw, int ch, int samples, const float* pose, const float* camw, uint8_t* rgb,
+                                hipStream_t stream) {
+  const int tiles_x = cdiv(cw, 16), tiles_per_cell = tiles_x * cdiv(ch, 16), cells = cdiv(E, cols) * cols;
+  const long blocks = (long)tiles_per_cell * cells * F;
+  MPPO_REQUIRE(blocks <= 0x7fffffffL, "mppo_render_grid: %ld tiles exceed one launch", blocks);
+  const size_t lds = ((size_t)v.ngeom * kGeomWords + kCamWords) * sizeof(float);
+  switch (samples) {
+    case 1: grid_rays_launch<1>(v, dev_blob, (unsigned)blocks, lds, E, cols, cw, ch, tiles_x, tiles_per_cell, cells, pose, camw, rgb, stream); break;
+    case 2: grid_rays_launch<2>(v, dev_blob, (unsigned)blocks, lds, E, cols, cw, ch, tiles_x, tiles_per_cell, cells, pose, camw, rgb, stream); break;
+    case 3: grid_rays_launch<3>(v, dev_blob, (unsigned)blocks, lds, E, cols, cw, ch, tiles_x, tiles_per_cell, cells, pose, camw, rgb, stream); break;
+    case 4: grid_rays_launch<4>(v, dev_blob, (unsigned)blocks, lds, E, cols, cw, ch, tiles_x, tiles_per_cell, cells, pose, camw, rgb, stream); break;
+    default: return fail(MPPO_EINVAL, "mppo_render_grid: samples = %d (1 .. 4 per pixel axis)", samples);
+  }
+  MPPO_CHECK_LAUNCH("render_grid_rays_kernel");
   return MPPO_OK;
 }
 

@@ -36,8 +36,12 @@ struct SceneView {
 
 int32_t parse_scene_blob(const void* host_blob, size_t nbytes, SceneView* view);
 
-int32_t render_poses_launch(const SceneView& v, const void* dev_blob, int F, const float* qpos, int q_ld, int camera, float* body_ws, float* pose, float* camw,
-                            hipStream_t stream);
+// F * E pose records, frame-major: record f * E + e from qpos + f * q_ld_frame + e * q_ld_env
+int32_t render_poses_launch(const SceneView& v, const void* dev_blob, int F, int E, const float* qpos, int q_ld_frame, int q_ld_env, int camera, float* body_ws, float* pose,
+                            float* camw, hipStream_t stream);
+// rgb [F, ceil(E / cols) * ch, cols * cw, 3]: environment e in cell (e / cols, e % cols), samples x samples rays per pixel
+int32_t render_grid_rays_launch(const SceneView& v, const void* dev_blob, int F, int E, int cols, int cw, int ch, int samples, const float* pose, const float* camw, uint8_t* rgb,
+                                hipStream_t stream);
 int32_t render_rays_launch(const SceneView& v, const void* dev_blob, int F, int W, int H, const float* pose, const float* camw, uint8_t* rgb, float* depth, int32_t* geom_id,
                            hipStream_t stream);
 

@@ -6,7 +6,7 @@
 // the same for the model blob): sizes and addresses in range, parents before children, body ids / types / hull ranges valid, every number finite,
 // at most kSceneMaxGeoms visuals (their staged form must fit in LDS: more is an error, not a truncation).
 //
-// mppo_render makes two launches on the caller's stream.  The poses' scratch lives inside the handle and grows on demand.
+// mppo_render and mppo_render_grid make two launches each on the caller's stream.  The poses' scratch lives inside the handle and grows on demand.
 #include "render.h"
 
 #include <cmath>
@@ -152,6 +152,20 @@ extern "C" int32_t mppo_scene_get_dims(const mppo_scene_t* s, mppo_scene_dims_t*
   return MPPO_OK;
 }
 
+// The handle's own scratch, grown on demand (one render at a time per handle).
+static int32_t scene_scratch(const mppo_scene_t* s, size_t need) {
+  mppo_scene* ms = const_cast<mppo_scene*>(s);
+  if (need <= ms->scratch_bytes) return MPPO_OK;
+  if (ms->scratch) MPPO_CHECK_HIP(hipFree(ms->scratch));  // (synchronises with whatever still reads it)
+  ms->scratch = nullptr;
+  ms->scratch_bytes = 0;
+  void* p = nullptr;
+  MPPO_CHECK_HIP(hipMalloc(&p, need));
+  ms->scratch = static_cast<float*>(p);
+  ms->scratch_bytes = need;
+  return MPPO_OK;
+}
+
 extern "C" int32_t mppo_render(const mppo_scene_t* s, int32_t F, const float* qpos, int32_t q_ld, int32_t camera, int32_t width, int32_t height, const mppo_render_out_t* out,
                                void* stream) {
   MPPO_REQUIRE(s && qpos && out, "mppo_render: null scene / qpos / out");
@@ -164,21 +178,39 @@ extern "C" int32_t mppo_render(const mppo_scene_t* s, int32_t F, const float* qp
   hipStream_t st = static_cast<hipStream_t>(stream);
   // scratch: body poses [F][nbody][7], camera [F][16], and the visuals' poses [F][ngeom][12] unless the caller wants them
   const size_t n_body = (size_t)F * v.nbody * 7, n_cam = (size_t)F * kCamWords, n_pose = out->geom_pose ? 0 : (size_t)F * v.ngeom * 12;
-  const size_t need = (n_body + n_cam + n_pose) * sizeof(float);
-  mppo_scene* ms = const_cast<mppo_scene*>(s);  // (the scratch is the handle's own: one render at a time per handle)
-  if (need > ms->scratch_bytes) {
-    if (ms->scratch) MPPO_CHECK_HIP(hipFree(ms->scratch));  // (synchronises with whatever still reads it)
-    ms->scratch = nullptr;
-    ms->scratch_bytes = 0;
-    void* p = nullptr;
-    MPPO_CHECK_HIP(hipMalloc(&p, need));
-    ms->scratch = static_cast<float*>(p);
-    ms->scratch_bytes = need;
-  }
-  float* body_ws = ms->scratch;
+  MPPO_TRY(scene_scratch(s, (n_body + n_cam + n_pose) * sizeof(float)));
+  float* body_ws = s->scratch;
   float* camw = body_ws + n_body;
   float* pose = out->geom_pose ? out->geom_pose : camw + n_cam;
-  MPPO_TRY(render_poses_launch(v, s->dev_blob, F, qpos, q_ld, camera, body_ws, pose, camw, st));
+  MPPO_TRY(render_poses_launch(v, s->dev_blob, F, 1, qpos, q_ld, 0, camera, body_ws, pose, camw, st));
   if (!out->rgb && !out->depth && !out->geom_id) return MPPO_OK;
   return render_rays_launch(v, s->dev_blob, F, width, height, pose, camw, out->rgb, out->depth, out->geom_id, st);
+}
+
+extern "C" int32_t mppo_render_grid(const mppo_scene_t* s, int32_t F, int32_t E, const float* qpos, int32_t q_ld_frame, int32_t q_ld_env, int32_t camera, int32_t cols,
+                                    int32_t cell_width, int32_t cell_height, int32_t samples, uint8_t* rgb, void* stream) {
+  MPPO_REQUIRE(s && qpos && rgb, "mppo_render_grid: null scene / qpos / rgb");
+  const SceneView& v = s->view;
+  MPPO_REQUIRE(F >= 1 && F <= (1 << 20), "mppo_render_grid: F = %d frames", F);
+  MPPO_REQUIRE(E >= 1 && E <= (1 << 20) && (long)F * E <= (1 << 20), "mppo_render_grid: E = %d environments (at least 1, F * E <= %d pose records)", E, 1 << 20);
+  MPPO_REQUIRE(q_ld_frame >= v.nq && q_ld_env >= v.nq, "mppo_render_grid: q_ld_frame = %d / q_ld_env = %d is less than nq = %d", q_ld_frame, q_ld_env, v.nq);
+  MPPO_REQUIRE(camera >= 0 && camera < v.ncam, "mppo_render_grid: camera %d of %d", camera, v.ncam);
+  MPPO_REQUIRE(s->cam_mode[camera] != CAM_UNSUPPORTED, "mppo_render_grid: camera %d has a mode other than fixed / track", camera);
+  MPPO_REQUIRE(cols >= 1 && cols <= 8192, "mppo_render_grid: cols = %d columns (1 .. 8192)", cols);
+  MPPO_REQUIRE(cell_width >= 1 && cell_width <= 8192 && cell_height >= 1 && cell_height <= 8192, "mppo_render_grid: cell_width x cell_height = %d x %d (1 .. 8192 each way)",
+               cell_width, cell_height);
+  MPPO_REQUIRE(samples >= 1 && samples <= 4, "mppo_render_grid: samples = %d (1 .. 4 per pixel axis)", samples);
+  MPPO_REQUIRE(v.ngeom <= kSceneMaxGeoms, "mppo_render_grid: %d visuals, at most %d are staged in LDS", v.ngeom, kSceneMaxGeoms);
+  const long rows = (E + cols - 1) / cols;
+  const double bytes = 3.0 * F * (double)(rows * cell_height) * (double)((long)cols * cell_width);
+  MPPO_REQUIRE(bytes <= 2147483647.0, "mppo_render_grid: an image of %d x %ld x %ld x 3 bytes is indexed past int32", F, rows * cell_height, (long)cols * cell_width);
+  // scratch: body poses [F * E][nbody][7], cameras [F * E][16], the visuals' poses [F * E][ngeom][12]
+  const size_t R = (size_t)F * E, n_body = R * v.nbody * 7, n_cam = R * kCamWords, n_pose = R * v.ngeom * 12;
+  MPPO_TRY(scene_scratch(s, (n_body + n_cam + n_pose) * sizeof(float)));
+  float* body_ws = s->scratch;
+  float* camw = body_ws + n_body;
+  float* pose = camw + n_cam;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  MPPO_TRY(render_poses_launch(v, s->dev_blob, F, E, qpos, q_ld_frame, q_ld_env, camera, body_ws, pose, camw, st));
+  return render_grid_rays_launch(v, s->dev_blob, F, E, cols, cell_width, cell_height, samples, pose, camw, rgb, st);
 }

@@ -364,16 +364,37 @@ class HumanoidEnv:
         return r.weights_ctrl_cost * ctrl + r.weights_original_pos_reward * pos_r + r.weights_velocity * vel + r.weights_is_healthy * healthy
 
     # -- Brax's env.render(trajectory, camera, width, height) (what env.py:322-329 calls) ------------------------------------
-    def render(self, states: Any, camera: Optional[str] = None, width: int = 640, height: int = 480, env_index: int = 0) -> np.ndarray:
+    def render(self, states: Any, camera: Optional[str] = None, width: int = 640, height: int = 480, env_index: int = 0, envs: Optional[Sequence[int]] = None,
+               samples: int = 1, cols: Optional[int] = None) -> np.ndarray:
         """Frames of a rollout, uint8 [F, H, W, 3], ray-cast on the device (minppo_amd/render.py).  `states`: a [F, nq] or [F, rec_dim]
         tensor / array (joint positions, or state records - qpos leads a record), a sequence of `EnvState`s, or a sequence of
         `pipeline_state` tensors [N, rec_dim]; of a batched state the environment `env_index` is drawn.  `camera=None`: the config's
-        `visualization.camera_name`."""
+        `visualization.camera_name`.  `samples` = S: S x S rays per pixel (anti-aliasing; 1 .. 4).
+        `envs` = a sequence of environment indices: those environments of batched states (a sequence as above, or a [F, N, nq | rec_dim]
+        tensor) are drawn side by side as a grid of `cols` columns (None: ceil(sqrt(len(envs)))) whose CELLS are width x height, each
+        environment through its own camera -> [F, rows * height, cols * width, 3]."""
         from minppo_amd.render import Renderer
 
         t = self.torch
         if camera is None:
             camera = require(self._camera_name, "visualization.camera_name")
+        if self._renderer is None:  # (opened on the first render)
+            self._renderer = Renderer(self.cm, lib=self.lib, device=self.device)
+        if envs is not None:
+            if isinstance(states, (list, tuple)):
+                if not states:
+                    raise ValueError("render: no states")
+                ps = [s.pipeline_state if isinstance(s, EnvState) else s for s in states]
+                states = t.stack([p if hasattr(p, "data_ptr") else t.as_tensor(np.asarray(p, np.float32)) for p in ps])
+            q = states if hasattr(states, "data_ptr") else t.as_tensor(np.asarray(states, np.float32))
+            if q.ndim != 3 or q.shape[2] not in (self.cm.nq, self.dims.rec_dim):
+                raise ValueError(f"render: with envs=, states must be [F, N, {self.cm.nq}] joint positions or [F, N, {self.dims.rec_dim}] state records, got {tuple(q.shape)}")
+            idx = [int(e) for e in envs]
+            if not idx or min(idx) < 0 or max(idx) >= q.shape[1]:
+                raise ValueError(f"render: envs {idx} of {q.shape[1]} environments")
+            q = q.to(device=self.device, dtype=t.float32)
+            q = q[:, :len(idx)] if idx == list(range(len(idx))) else q[:, idx]  # (the first E environments are drawn in place)
+            return self._renderer.render_grid(q, camera, width, height, cols=cols, samples=samples)
         if isinstance(states, (list, tuple)):
             if not states:
                 raise ValueError("render: no states")
@@ -392,9 +413,7 @@ class HumanoidEnv:
             q = q.to(device=self.device, dtype=t.float32)
         if q.ndim != 2 or q.shape[1] not in (self.cm.nq, self.dims.rec_dim):
             raise ValueError(f"render: states must be [F, {self.cm.nq}] joint positions or [F, {self.dims.rec_dim}] state records, got {tuple(q.shape)}")
-        if self._renderer is None:  # (opened on the first render)
-            self._renderer = Renderer(self.cm, lib=self.lib, device=self.device)
-        return self._renderer.render(q, camera, width, height)
+        return self._renderer.render(q, camera, width, height, samples)
 
     def close(self) -> None:
         if getattr(self, "_renderer", None) is not None:
@@ -427,17 +446,23 @@ def main(args: Sequence[str] | None = None) -> None:
         max_frames = int(vis.video_length * fps)
         rollout = []
         n_steps = 0  # (env steps so far, over all episodes: the pushes' step index - a push keeps running across a restart)
+        # visualization.grid_envs = G > 0 (extension): G environments run side by side and are drawn as a grid of width x height cells; an episode
+        # still ends with environment 0's, the others restart on their own as training environments do
+        G = int(vis.grid_envs)
+        if G < 0:
+            raise ValueError(f"visualization.grid_envs = {G}")
+        n = max(G, 1)
         for episode in range(int(vis.num_episodes)):
             seed = int(torch.randint(0, 2**31 - 1, (1,), generator=gen))
-            es = env.reset(seed if env.reset_noise_scale != 0 else None, num_envs=1)
+            es = env.reset(seed if env.reset_noise_scale != 0 else None, num_envs=n)
             total = 0.0
             pushed = config.environment.push_force > 0  # (random pushes: the rollout is shoved as a training environment is, so a push can be watched)
             for _ in range(int(vis.max_steps)):
                 if len(rollout) < vis.video_length * fps:
-                    rollout.append(es.pipeline_state[0].clone())
-                action = torch.rand(1, env.action_size, generator=gen).to(env.device)
+                    rollout.append(es.pipeline_state.clone() if G else es.pipeline_state[0].clone())
+                action = torch.rand(n, env.action_size, generator=gen).to(env.device)
                 step_seed = int(torch.randint(0, 2**31 - 1, (1,), generator=gen))
-                es = env.step(es, action, step_seed if env.reset_noise_scale != 0 else None, xfrc=env.push_wrench(n_steps, 1) if pushed else None)
+                es = env.step(es, action, step_seed if env.reset_noise_scale != 0 else None, xfrc=env.push_wrench(n_steps, n) if pushed else None)
                 n_steps += 1
                 total += float(es.reward[0])
                 if bool(es.done[0]):
@@ -448,7 +473,8 @@ def main(args: Sequence[str] | None = None) -> None:
         if not rollout:
             raise ValueError(f"visualization.video_length = {vis.video_length} and max_steps = {vis.max_steps} leave no frame to render")
         logger.info("Rendering video with %d frames at %d fps", len(rollout), fps)
-        images = env.render(torch.stack(rollout[::max(1, int(vis.render_every))]), camera=vis.camera_name, width=vis.width, height=vis.height)
+        images = env.render(torch.stack(rollout[::max(1, int(vis.render_every))]), camera=vis.camera_name, width=vis.width, height=vis.height,
+                            envs=range(G) if G else None, samples=int(vis.samples))
         write_video(vis.video_save_path, images, fps=fps)
         logger.info("Video saved to %s", vis.video_save_path)
     finally:

@@ -10,7 +10,8 @@ episodes that ended and the environments that never fell.
 
 prints one JSON line with the statistics; `evaluation.trajectory_path=run.npz evaluation.record_envs=4` also writes the joint
 trajectory of the first four environments (`qpos`, `qvel`, `action`, `reward`, `done`, and `dt`, `n_frames`); `evaluation.video_path=policy.avi`
-(with `record_envs >= 1`) renders recorded environment 0 - one frame per step, camera and size from `visualization` - and writes the video
+(with `record_envs >= 1`) renders recorded environment 0 - with `evaluation.video_grid=true` every recorded environment, each in its own cell of a
+tiled frame - one frame per step, camera, size and `samples` (anti-aliasing) from `visualization` - and writes the video
 (minppo_amd/render.py: train, then watch it).
 
 Under random pushes (`environment.push_force` > 0 with `push_interval`, `push_duration`, `push_body`) the same call goes through
@@ -311,17 +312,23 @@ def save_trajectory(path: str, result: EvalResult) -> None:
 
 
 def save_video(path: str, config: Config, result: EvalResult, *, lib: Optional[nat.Lib] = None, xp: str = "torch", device: Any = "cuda:0") -> None:
-    """Renders recorded environment 0's trajectory with `visualization.camera_name / width / height` and writes it to `path`
-    (minppo_amd.render.write_video), at the frame rate of the environment step."""
-    from minppo_amd.render import render, write_video
+    """Renders recorded environment 0's trajectory - with `evaluation.video_grid`, every recorded environment's, as a grid of cells - with
+    `visualization.camera_name / width / height / samples` and writes it to `path` (minppo_amd.render.write_video), at the frame rate of the
+    environment step."""
+    from minppo_amd.render import Renderer, write_video
     from minppo_amd.train import resolve_model
 
     if result.trajectory is None:
         raise ValueError("save_video: the evaluation recorded no environment (evaluation.record_envs = 0)")
     vis = config.visualization
+    camera = require(vis.camera_name, "visualization.camera_name")
     # one frame per step: the state every step STARTED from (trajectory rows 0 .. K - 1; as env.py:302-303 collects a state before it steps)
-    frames = render(resolve_model(config), result.trajectory["qpos"][:-1, 0], require(vis.camera_name, "visualization.camera_name"), vis.width, vis.height, lib=lib, xp=xp,
-                    device=device)
+    qpos = result.trajectory["qpos"][:-1]
+    with Renderer(resolve_model(config), lib=lib, xp=xp, device=device) as r:
+        if config.evaluation.video_grid:
+            frames = r.render_grid(qpos, camera, vis.width, vis.height, samples=int(vis.samples))
+        else:
+            frames = r.render(qpos[:, 0], camera, vis.width, vis.height, int(vis.samples))
     write_video(path, frames, fps=1.0 / result.dt)
 
 

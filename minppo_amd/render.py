@@ -7,11 +7,14 @@ ellipsoid, convex hull, the ground plane - has a closed-form ray intersection, s
   scene_blob(cm)            the little-endian blob `mppo_scene_open` reads (layout: csrc/render.h): dimensions, the kinematic tree taken from
                             `cm.t`, the visuals (`cm.visuals`: every geom of the MJCF, colliding or not, in document order; a built-in robot's
                             colliders in MuJoCo's default colour), hull faces as planes in the geom frame, the ground plane, the cameras
-  Renderer(cm, lib=, xp=)   an open scene; `.render(qpos, camera, width, height)` -> uint8 [F, H, W, 3]
-  render(cm, qpos, ...)     the same in one call
+  Renderer(cm, lib=, xp=)   an open scene; `.render(qpos, camera, width, height, samples=1)` -> uint8 [F, H, W, 3];
+                            `.render_grid(qpos [F, E, nq], camera, cell_width, cell_height, cols=None, samples=1)` -> E environments per frame,
+                            each in its own cell of a tiled image (`mppo_render_grid`)
+  render(cm, qpos, ...)     `.render` in one call
   write_video(path, frames, fps)   .npz, .avi (uncompressed, written here) or .mp4 (through an installed ffmpeg)
 
-What is approximated: a mesh is drawn as its CONVEX HULL (what the engine collides it as); one sample per pixel (no anti-aliasing); no
+What is approximated: a mesh is drawn as its CONVEX HULL (what the engine collides it as); one sample per pixel unless `samples` = S > 1 asks
+for S x S (box-filtered supersampling, S <= 4); no
 textures; alpha is ignored except that a geom with alpha 0 is not drawn.  Cameras: `fixed` (rigid in its body's frame) and `track` (offset from
 the body's position, orientation fixed in the world, both as they are at qpos0); every model has the camera `track` (model.compile_model).
 """
@@ -246,8 +249,59 @@ class Renderer:
         self.lib.render(self._scene, F, q.ctypes.data, q_ld, cam, W, H, C.byref(out), None)
         return bufs
 
-    def render(self, qpos: Any, camera: str = "track", width: int = 640, height: int = 480) -> np.ndarray:
-        return self.render_raw(qpos, camera, width, height)["rgb"]
+    def render(self, qpos: Any, camera: str = "track", width: int = 640, height: int = 480, samples: int = 1) -> np.ndarray:
+        """`samples` = S > 1: S x S rays per pixel, averaged (the grid kernel with one environment); S = 1: one ray per pixel centre."""
+        if samples == 1:
+            return self.render_raw(qpos, camera, width, height)["rgb"]
+        q = self._as_f32(qpos)
+        if q.ndim != 2:
+            raise ValueError(f"qpos must be [F, >= {self.cm.nq}], got {tuple(q.shape)}")
+        return self.render_grid(q[:, None, :], camera, width, height, cols=1, samples=samples)
+
+    def _as_f32(self, qpos: Any) -> Any:
+        """-> float32 on the scene's device (torch) or a float32 NumPy array; a strided float32 view stays a view."""
+        if self.torch is not None:
+            q = qpos if hasattr(qpos, "data_ptr") else self.torch.from_numpy(np.asarray(qpos, np.float32))
+            return q.to(device=self.device, dtype=self.torch.float32)
+        return np.asarray(qpos.detach().cpu().numpy() if hasattr(qpos, "detach") else qpos, np.float32)
+
+    def render_grid(self, qpos: Any, camera: str = "track", cell_width: int = 320, cell_height: int = 240, cols: Optional[int] = None, samples: int = 1) -> np.ndarray:
+        """Many environments per frame (`mppo_render_grid`): `qpos` [F, E, >= nq] - packed joint positions, or a strided view such as the
+        first E of N state records `recs[:, :E]` or a recorded trajectory's [F, R, row] block, drawn in place - -> uint8
+        [F, rows * cell_height, cols * cell_width, 3] with environment e in cell (e // cols, e % cols), every cell that environment's own
+        view through `camera`; `cols=None`: ceil(sqrt(E)); a cell past the last environment is sky.  `samples` = S in 1 .. 4: S x S rays
+        per pixel, averaged in linear colour before quantisation."""
+        if not self._scene:
+            raise RuntimeError("the renderer is closed")
+        cam = camera_index(self.cm, camera)
+        q = self._as_f32(qpos)
+        nq = self.cm.nq
+        if q.ndim != 3 or q.shape[2] < nq:
+            raise ValueError(f"qpos must be [F, E, >= {nq}], got {tuple(q.shape)}")
+        F, E = int(q.shape[0]), int(q.shape[1])
+        if F == 0 or E == 0:
+            raise ValueError("no frames / environments to render")
+        torch = self.torch
+        strides = tuple(q.stride()) if torch is not None else tuple(s // 4 for s in q.strides)
+        if strides[2] != 1 or (F > 1 and strides[0] < nq) or (E > 1 and strides[1] < nq) or max(strides) >= 2**31:  # (not drawable in place)
+            q = q.contiguous() if torch is not None else np.ascontiguousarray(q)
+            strides = (E * int(q.shape[2]), int(q.shape[2]), 1)
+        ld_frame, ld_env = (int(strides[0]) if F > 1 else int(q.shape[2])), (int(strides[1]) if E > 1 else int(q.shape[2]))
+        cols = int(cols) if cols is not None else math.isqrt(E - 1) + 1
+        w, h = int(cell_width), int(cell_height)
+        if cols < 1 or w < 1 or h < 1:
+            raise ValueError(f"grid of {cols} columns of {w} x {h} cells")
+        shape = (F, -(-E // cols) * h, cols * w, 3)
+        if torch is not None:
+            rgb = torch.zeros(shape, dtype=torch.uint8, device=self.device)
+            with torch.cuda.device(self.device):
+                stream = torch.cuda.current_stream(self.device)
+                self.lib.render_grid(self._scene, F, E, q.data_ptr(), ld_frame, ld_env, cam, cols, w, h, int(samples), rgb.data_ptr(), stream.cuda_stream)
+                stream.synchronize()
+            return rgb.cpu().numpy()
+        rgb = np.zeros(shape, np.uint8)
+        self.lib.render_grid(self._scene, F, E, q.ctypes.data, ld_frame, ld_env, cam, cols, w, h, int(samples), rgb.ctypes.data, None)
+        return rgb
 
     def close(self) -> None:
         if getattr(self, "_scene", None):
@@ -263,11 +317,12 @@ class Renderer:
         self.close()
 
 
-def render(cm: CompiledModel, qpos: Any, camera: str = "track", width: int = 640, height: int = 480, *, lib: Optional[nat.Lib] = None, xp: str = "torch",
+def render(cm: CompiledModel, qpos: Any, camera: str = "track", width: int = 640, height: int = 480, *, samples: int = 1, lib: Optional[nat.Lib] = None, xp: str = "torch",
            device: Any = "cuda:0") -> np.ndarray:
-    """Frames [F, H, W, 3] uint8 of the joint positions `qpos` [F, >= nq] of the model `cm`, seen by its camera `camera`."""
+    """Frames [F, H, W, 3] uint8 of the joint positions `qpos` [F, >= nq] of the model `cm`, seen by its camera `camera`; `samples` x `samples`
+    rays per pixel."""
     with Renderer(cm, lib=lib, xp=xp, device=device) as r:
-        return r.render(qpos, camera, width, height)
+        return r.render(qpos, camera, width, height, samples)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------------

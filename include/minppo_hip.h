@@ -327,7 +327,8 @@ typedef struct mppo_net {
   int32_t use_tanh;  /* actor activation; the critic is always ReLU (train.py:82) */
   int32_t bf16;      /* 0: exact f32 MFMA; 1: bf16-in/f32-accumulate MFMA for the hidden GEMMs */
   int32_t num_layers; /* hidden layers of each MLP (`model.num_layers`, config.py:53, train.py:79,82): 1 .. 4; 0 means 2, the
-                         reference's default.  Two hidden layers take the fused kernels, other depths the layer-wise path. */
+                         reference's default.  Two hidden layers take the fused kernels; 1, 3 and 4 hidden layers of a float network take the
+                         depth-generic row pass where the geometry fits it, the layer-wise path otherwise (mppo_network_path). */
 } mppo_net_t;
 
 /* Length (floats) of the flat parameter / gradient / Adam-moment vectors: the model's parameters with every tensor starting on
@@ -385,6 +386,9 @@ typedef struct mppo_loss_cfg { float clip_eps, vf_coef, ent_coef; } mppo_loss_cf
 /* *fused = 1 if mppo_minibatch_grad takes the fused row pass + single-launch weight gradients for this geometry
  * (H a multiple of 32 up to 256, A <= 32, 16-byte aligned observation rows), 0 if it runs the layer-wise kernels. */
 int32_t mppo_minibatch_path(const mppo_net_t* net, const mppo_batch_t* batch, int32_t* fused);
+/* 0: layer-wise kernels, 1: the two-layer fused kernels (k_fused.hip), 2: the depth-generic row pass (k_deep.hip).
+ * *rowpass: the row-local half of mppo_minibatch_grad / mppo_minibatch_rowpass; *rollout: mppo_policy_forward. */
+int32_t mppo_network_path(const mppo_net_t* net, const float* obs, int32_t obs_ld, int32_t* rowpass, int32_t* rollout);
 /* *rows = minibatch rows per workgroup of the fused row pass for a minibatch of mb rows: 16, or 32 where the engine's minibatch loop
  * (pre_gathered = 1) runs a float network's row pass on two 16-row tiles per workgroup because the 16-row tiling would need more
  * workgroups than the chip has CUs (BASELINE configs[4]: 2560-row minibatches).  One row of loss partials is written per workgroup. */
@@ -395,7 +399,8 @@ int32_t mppo_minibatch_grad(const mppo_net_t* net, const float* params, const mp
                             float* loss4, void* ws, size_t ws_bytes, void* stream);
 
 /* The row-local half of mppo_minibatch_grad on its own (forward of both networks, loss terms, d loss / d outputs and the
- * activation gradients dZ2, dZ1; one fused launch when H % 32 == 0 and A <= 16).  Same arguments; leaves its results in
+ * activation gradients of every hidden layer; one launch where mppo_network_path reports 1 or 2: H % 32 == 0 up to 256 and
+ * A <= 32 - the fused kernel at two hidden layers, the depth-generic row pass at 1, 3 and 4).  Same arguments; leaves its results in
  * `ws` for the weight-gradient product.  Exposed so that benchmarks can time exactly this kernel. */
 int32_t mppo_minibatch_rowpass(const mppo_net_t* net, const float* params, const mppo_batch_t* batch, const int32_t* idx,
                                int32_t mb, const float* adv_stat, float inv_count, const mppo_loss_cfg_t* lc, void* ws,

@@ -10,6 +10,7 @@
 #include "philox.h"
 #include "mppo_common.h"
 #include "ppo_layout.h"
+#include "deep.h"
 #include "wgrad.h"
 #include "peer.h"
 #include "limit.h"
@@ -633,6 +634,8 @@ int32_t policy_forward(const mppo_net_t& net, const float* params, int n, const 
   static const char* nofuse = MPPO_EXPERIMENT_ENV("MPPO_NO_FUSED");  // A/B switch for measurements
   if (fused_rollout_supported(net, obs, obs_ld) && !(nofuse && nofuse[0] == '1'))
     return fused_policy_forward(net, params, n, obs, obs_ld, noise, action, log_prob, value, noise ? mean_out : nullptr, fb.AP, stream, fb.frag, fb.frag_net_stride);  // one launch
+  if (deep_rollout_supported(net, obs, obs_ld) && !(nofuse && nofuse[0] == '1'))  // 1, 3 or 4 hidden layers: one launch as well (k_deep.hip)
+    return deep_policy_forward(net, params, n, obs, obs_ld, noise, action, log_prob, value, noise ? mean_out : nullptr, fb.AP, stream);
   MPPO_TRY(mlp_hidden_forward(net, params, n, obs, obs_ld, nullptr, fb, nullptr, stream));
   HeadArgs a = head_args(net, params, n, fb);
   a.noise = noise; a.action = action; a.log_prob = log_prob; a.value = value; a.mean_out = mean_out;
@@ -643,7 +646,7 @@ int32_t policy_forward(const mppo_net_t& net, const float* params, int n, const 
 }
 
 // Everything of a minibatch step that is local to a row: forward of both networks, loss terms, d(loss)/d(outputs), dZ2, dZ1
-// (one fused launch where supported, k_fused.hip; otherwise layer-wise GEMMs + the head kernel).  Leaves h1, h2, dZ2, dZ1,
+// (one fused launch where supported - k_fused.hip at two hidden layers, k_deep.hip at 1, 3 and 4; otherwise layer-wise GEMMs + the head kernel).  Leaves h1, h2, dZ2, dZ1,
 // dOut, xmb and the loss partials in the GradBufs; *nblk_out = number of partial rows written.
 int32_t minibatch_rowpass(const mppo_net_t& net, const float* params, const mppo_batch_t& batch, const int* idx, int mb, const float* adv_stat,
                           float inv_count, const mppo_loss_cfg_t& lc, const GradBufs& gbuf, int* nblk_out, bool* fused_out, hipStream_t stream, const XPre* pre = nullptr) {
@@ -657,6 +660,13 @@ int32_t minibatch_rowpass(const mppo_net_t& net, const float* params, const mppo
   if (fused) {
     MPPO_TRY(fused_forward_backward(net, params, batch, idx, mb, adv_stat, inv_count, lc, gbuf, stream, pre));
     *nblk_out = cdiv(mb, fused_rows_per_workgroup(net, mb, pre != nullptr));  // one row of loss partials per row-pass workgroup
+    return MPPO_OK;
+  }
+  // 1, 3 or 4 hidden layers: the depth-generic row pass (k_deep.hip), one launch.  *fused_out stays false: it means "k-quad operands for
+  // wgrad_kernel", and this kernel writes the layer-wise path's plain buffers for the layer-wise weight-gradient GEMMs.
+  if (deep_supported(net, batch) && !(nofuse && nofuse[0] == '1')) {
+    MPPO_TRY(deep_forward_backward(net, params, batch, idx, mb, adv_stat, inv_count, lc, gbuf, stream));
+    *nblk_out = cdiv(mb, kDeepRows);  // one row of loss partials per 16-row tile
     return MPPO_OK;
   }
   MPPO_REQUIRE(!net.bf16, "minibatch_grad: bf16 products need the fused kernels and this geometry (O=%d A=%d H=%d: e.g. an observation too wide for the weight-gradient "
@@ -915,6 +925,18 @@ extern "C" int32_t mppo_minibatch_path(const mppo_net_t* net, const mppo_batch_t
   MPPO_REQUIRE(batch && fused, "mppo_minibatch_path: null argument");
   static const char* nofuse = MPPO_EXPERIMENT_ENV("MPPO_NO_FUSED");
   *fused = (fused_supported(*net, *batch) && !(nofuse && nofuse[0] == '1')) ? 1 : 0;
+  return MPPO_OK;
+}
+
+extern "C" int32_t mppo_network_path(const mppo_net_t* net, const float* obs, int32_t obs_ld, int32_t* rowpass, int32_t* rollout) {
+  MPPO_TRY(check_net(net));
+  MPPO_REQUIRE(rowpass && rollout, "mppo_network_path: null argument");
+  static const char* nofuse = MPPO_EXPERIMENT_ENV("MPPO_NO_FUSED");
+  const bool off = nofuse && nofuse[0] == '1';
+  mppo_batch_t b{};
+  b.obs = obs; b.obs_ld = obs_ld;
+  *rowpass = off ? 0 : fused_supported(*net, b) ? 1 : deep_supported(*net, b) ? 2 : 0;
+  *rollout = off ? 0 : fused_rollout_supported(*net, obs, obs_ld) ? 1 : deep_rollout_supported(*net, obs, obs_ld) ? 2 : 0;
   return MPPO_OK;
 }
 

@@ -19,12 +19,8 @@
 #include "ppo_layout.h"
 #include "platform.h"
 #include "peer.h"
-#include "obsnorm.h"
 #include "rewnorm.h"
-#include "push.h"
-#include "domrand.h"
-#include "limit.h"
-#include "sensor.h"
+#include "env_sequence.h"
 
 #include <cmath>
 #include <cstdlib>
@@ -33,15 +29,6 @@
 #include <vector>
 
 namespace mppo {
-const ModelView& model_view(const mppo_model* m);
-size_t model_scratch_bytes(const mppo_model* m, int N);
-int32_t env_step_ws(const mppo_model_t* m, int32_t N, int32_t n_frames, const mppo_reward_cfg_t* rc, float* state, const float* reset_rec, const float* action,
-                    int32_t act_ld, float* obs, int32_t obs_ld, float* reward, uint8_t* done, const mppo_env_metrics_t* metrics, float* ws, size_t ws_bytes, hipStream_t stream);
-int32_t env_reset_ws(const mppo_model_t* m, int32_t N, float* state, float* reset_rec, float* obs, int32_t obs_ld, float* reward, uint8_t* done, const mppo_env_metrics_t* metrics,
-                     float* ws, size_t ws_bytes, hipStream_t stream, const EnvDomain& dom);
-int32_t env_reinit_ws(const mppo_model_t* m, int32_t N, float* state, float* obs, int32_t obs_ld, const uint8_t* mask, float scale, int32_t rng_impl, uint64_t seed,
-                      int32_t rank, const uint32_t* key2, const int32_t* counter, int32_t counter_mul, int32_t counter_add, float* ws, size_t ws_bytes, hipStream_t stream,
-                      const EnvDomain& dom);
 
 // end of an update: the Adam step index and the update index move on; `zero` (optional): words another kernel of the update wants back
 // at zero before its next use (the bucket counters of the two-launch permutation, k_perm.hip).  The LAST of those words is that form's
@@ -128,70 +115,57 @@ struct Region { std::string name; size_t off, bytes; };
 }  // namespace mppo
 
 struct mppo_engine {
-  const mppo_model* model;
-  mppo_engine_cfg_t cfg;
-  mppo::ModelView mv;
-  unsigned char* arena;
-  size_t arena_bytes;
+  const mppo_model* model = nullptr;
+  mppo_engine_cfg_t cfg{};
+  mppo::ModelView mv{};
+  unsigned char* arena = nullptr;
+  size_t arena_bytes = 0;
   std::vector<mppo::Region> regions;
-  int N, T, B, mb, M, E, O, OP, A, H, P;
-  float *params, *adam_m, *adam_v, *grad;
-  int* count;
-  float *state, *reset_rec, *obs, *action, *value, *reward, *log_prob, *last_val, *adv, *target, *noise, *adv_stats, *losses, *stats;
-  unsigned char* done;
-  int* perm;
-  double* adv_sums;
-  mppo_env_metrics_t met;
-  float *fwd_ws, *grad_ws, *adam_ws;
-  float* stat_ret_in;
-  int* stat_len_in;
-  unsigned* jax_rng;  // [2] carried key | [T][2] action keys | [E][rounds][2] sort keys (rng_impl = 1)
-  int jax_rounds;
-  void* perm_ws;
-  size_t perm_ws_bytes;
-  float* env_ws;
-  size_t env_ws_bytes;
-  mppo::Comm* comm;
-  mppo::PeerComm* peer;  // the ranks' peer-to-peer exchange (peer.h); takes precedence over `comm` once connected
-  mppo::GraphExec* graph;
-  bool graph_failed, was_reset, graph_agreed;
-  float* flag_ws;        // one float of the arena: the ranks' agreement on the graph capture (RCCL path)
-  // reset noise (mppo_engine_set_reset_noise; 0: every environment restarts from the one constant reset record, nothing below is used)
-  float reset_noise;
-  unsigned* reset_rng;   // [T][2] this update's step keys (train.py:163) | [2] the reset key (train.py:142): the threefry stream's keys (rng_impl = 1)
-  bool prepared;         // an update has been prepared (captured or not): the launch sequence is fixed
-  // observation normalisation (mppo_engine_set_obs_norm; off: nothing below is used and no launch is added)
-  bool obs_norm;
-  float obs_norm_clip, obs_norm_eps;
-  double* obs_norm_stats;     // [1 + 2 O] count | mean | M2
-  float* obs_norm_table;      // [2][OP] mean32 | inv_std32: what this update's rollout applies
-  double* obs_norm_partials;  // [T][G][2][O] the apply launches' sums of this update
+  int N = 0, T = 0, B = 0, mb = 0, M = 0, E = 0, O = 0, OP = 0, A = 0, H = 0, P = 0;
+  float *params = nullptr, *adam_m = nullptr, *adam_v = nullptr, *grad = nullptr;
+  int* count = nullptr;
+  float *obs = nullptr, *action = nullptr, *value = nullptr, *reward = nullptr, *log_prob = nullptr, *last_val = nullptr, *adv = nullptr, *target = nullptr, *noise = nullptr,
+        *adv_stats = nullptr, *losses = nullptr, *stats = nullptr;
+  unsigned char* done = nullptr;
+  int* perm = nullptr;
+  double* adv_sums = nullptr;
+  float *fwd_ws = nullptr, *grad_ws = nullptr, *adam_ws = nullptr;
+  float* stat_ret_in = nullptr;
+  int* stat_len_in = nullptr;
+  unsigned* jax_rng = nullptr;  // [2] carried key | [T][2] action keys | [E][rounds][2] sort keys (rng_impl = 1)
+  int jax_rounds = 0;
+  void* perm_ws = nullptr;
+  size_t perm_ws_bytes = 0;
+  mppo::Comm* comm = nullptr;
+  mppo::PeerComm* peer = nullptr;  // the ranks' peer-to-peer exchange (peer.h); takes precedence over `comm` once connected
+  mppo::GraphExec* graph = nullptr;
+  bool graph_failed = false, was_reset = false, graph_agreed = false;
+  float* flag_ws = nullptr;        // one float of the arena: the ranks' agreement on the graph capture (RCCL path)
+  bool prepared = false;           // an update has been prepared (captured or not): the launch sequence is fixed
+  // The environments: state records, reset record, metrics and scratch (regions of the arena), the counter word of the draws (count[1], the update index, times
+  // T), and every option of the rollout's step sequence as its mppo_engine_set_* call left it - all off after mppo_engine_create: the step launches are the plain
+  // ones, not one launch is added.  What the shared sequences read (env_sequence.h); the ring, the applied actions, the latency table and the noise's sigma are
+  // regions of the arena too.  The domain randomisation's table [N][4] is the engine's own allocation, not a region: it is a function of (seed, rank) alone, so a
+  // checkpoint does not carry it and the arena's layout is what it always was
+  mppo::EnvRun env;
+  unsigned* reset_rng = nullptr;    // [T][2] this update's step keys (train.py:163) | [2] the reset key (train.py:142): the reset noise's threefry keys (rng_impl = 1)
+  unsigned char* truncated = nullptr;  // [T][N] the samples the episode time limit cut
+  // observation normalisation (mppo_engine_set_obs_norm; off: nothing below is used and no launch is added; on: env.norm_table is obs_norm_table)
+  bool obs_norm = false;
+  float obs_norm_eps = 0.f;
+  double* obs_norm_stats = nullptr;     // [1 + 2 O] count | mean | M2
+  float* obs_norm_table = nullptr;      // [2][OP] mean32 | inv_std32: what this update's rollout applies
+  double* obs_norm_partials = nullptr;  // [T][G][2][O] the apply launches' sums of this update
   // reward scaling (mppo_engine_set_reward_norm; off: nothing below is used and no launch is added)
-  bool reward_norm;
-  float reward_norm_clip, reward_norm_eps;
-  double* reward_norm_stats;     // [3] count | mean | M2 of the discounted return
-  float* reward_norm_table;      // [2] mean32 | inv_std32: the scale this update's rollout applies
-  float* reward_norm_carry;      // [N] the discounted return carried from one update to the next
-  double* reward_norm_partials;  // [G][2] the apply launch's sums of this update
-  float* reward_scaled;          // [T][N] what GAE reads; "reward" stays raw
+  bool reward_norm = false;
+  float reward_norm_clip = 0.f, reward_norm_eps = 0.f;
+  double* reward_norm_stats = nullptr;     // [3] count | mean | M2 of the discounted return
+  float* reward_norm_table = nullptr;      // [2] mean32 | inv_std32: the scale this update's rollout applies
+  float* reward_norm_carry = nullptr;      // [N] the discounted return carried from one update to the next
+  double* reward_norm_partials = nullptr;  // [G][2] the apply launch's sums of this update
+  float* reward_scaled = nullptr;          // [T][N] what GAE reads; "reward" stays raw
   // both of them on several ranks: the ranks' sums of this update, gathered - [world][2][O] for the observations, behind them [world][2] for the returns
-  double* norm_slots;
-  // random pushes (mppo_engine_set_push; body 0: off - the rollout's step launches are the unpushed ones)
-  mppo::EnvPush push;
-  // episode time limit (mppo_engine_set_time_limit; length 0: off - no launch is added, GAE and the statistics are the plain ones)
-  mppo::LimitCfg limit;
-  unsigned char* truncated;  // [T][N] the samples the limit cut
-  // domain randomisation (mppo_engine_set_domain; table null: off - every launch and every argument is what it was).  The table [N][4] is the engine's own
-  // allocation, not a region of the arena: it is a function of (seed, rank) alone, so a checkpoint does not carry it and the arena's layout is what it always was
-  mppo::EnvDomain domain;
-  // sensor noise and actuation latency (mppo_engine_set_obs_noise / _set_action_delay; off: nothing below is used, no launch is added and the step reads action[t])
-  bool obs_noise;
-  mppo::ObsNoiseDraw noise_draw;
-  float* obs_noise_scale;  // [OP] the per-column half-widths, pad columns 0
-  mppo::DelayDraw delay;   // dmax 0: off
-  float* action_hist;      // [kMaxActionDelay][N][A] the ring of the policy's past actions (the first dmax slots are used)
-  float* action_applied;   // [N][A] what the step launch is given
-  int* action_delay;       // [N] the latency table
+  double* norm_slots = nullptr;
 };
 
 namespace mppo {
@@ -213,8 +187,8 @@ static size_t layout(mppo_engine* e, bool assign) {
   e->adam_v = (float*)take("adam_v", P * 4);
   e->grad = (float*)take("grad", P * 4);
   e->count = (int*)take("count", 4 * 4);
-  e->state = (float*)take("state", N * e->mv.rec_dim * 4);
-  e->reset_rec = (float*)take("reset_rec", (size_t)e->mv.rec_dim * 4);
+  e->env.state = (float*)take("state", N * e->mv.rec_dim * 4);
+  e->env.reset_rec = (float*)take("reset_rec", (size_t)e->mv.rec_dim * 4);
   e->obs = (float*)take("obs", (T + 1) * N * OP * 4);
   e->action = (float*)take("action", T * N * A * 4);
   e->value = (float*)take("value", (B + N) * 4);  // [T][N] + the bootstrap values behind them (region "last_val" below): one critic launch can write both
@@ -233,12 +207,13 @@ static size_t layout(mppo_engine* e, bool assign) {
   e->stats = (float*)take("rollout_stats", 8 * 4);
   e->stat_ret_in = (float*)take("stats_carry_returns", N * 4);
   e->stat_len_in = (int*)take("stats_carry_lengths", N * 4);
-  e->met.episode_returns = (float*)take("episode_returns", N * 4);
-  e->met.episode_lengths = (int32_t*)take("episode_lengths", N * 4);
-  e->met.returned_episode_returns = (float*)take("returned_episode_returns", N * 4);
-  e->met.returned_episode_lengths = (int32_t*)take("returned_episode_lengths", N * 4);
-  e->met.timestep = (int32_t*)take("timestep", N * 4);
-  e->met.returned_episode = (uint8_t*)take("returned_episode", N);
+  mppo_env_metrics_t& met = e->env.met;
+  met.episode_returns = (float*)take("episode_returns", N * 4);
+  met.episode_lengths = (int32_t*)take("episode_lengths", N * 4);
+  met.returned_episode_returns = (float*)take("returned_episode_returns", N * 4);
+  met.returned_episode_lengths = (int32_t*)take("returned_episode_lengths", N * 4);
+  met.timestep = (int32_t*)take("timestep", N * 4);
+  met.returned_episode = (uint8_t*)take("returned_episode", N);
   e->fwd_ws = (float*)take("fwd_ws", fwd_bufs_floats(net, (int)N) * 4);
   e->grad_ws = (float*)take("grad_ws", grad_bufs_floats(net, e->mb) * 4);
   e->adam_ws = (float*)take("adam_ws", mppo_adam_ws_bytes(P));
@@ -249,8 +224,8 @@ static size_t layout(mppo_engine* e, bool assign) {
   if (permutation_batch_ws_bytes((int)B, e->E) > e->perm_ws_bytes) e->perm_ws_bytes = permutation_batch_ws_bytes((int)B, e->E);  // all epochs in one sort
   e->perm_ws = take("perm_ws", e->perm_ws_bytes);
   // a large robot's mass matrices and contact Jacobians, one record per environment (k_physics.hip; nothing for the robots whose working set fits LDS)
-  e->env_ws_bytes = model_scratch_bytes(e->model, (int)N);
-  e->env_ws = e->env_ws_bytes ? (float*)take("env_scratch", e->env_ws_bytes) : nullptr;
+  e->env.ws_bytes = model_scratch_bytes(e->model, (int)N);
+  e->env.ws = e->env.ws_bytes ? (float*)take("env_scratch", e->env.ws_bytes) : nullptr;
   // the keys of the reset noise's threefry stream: behind everything else, so that every other region is where it was ("jax_rng" keeps its size and meaning)
   e->reset_rng = (unsigned*)take("reset_rng", (2 * T + 2) * 4);
   // observation normalisation: behind those again, present whether or not the option is on
@@ -266,13 +241,25 @@ static size_t layout(mppo_engine* e, bool assign) {
   // the episode time limit's flags: behind those again, present whether or not a limit is set
   e->truncated = (unsigned char*)take("truncated", B);
   // actuation latency and sensor noise: behind those again, present whether or not the options are on
-  e->action_hist = (float*)take("action_hist", (size_t)kMaxActionDelay * N * A * 4);
-  e->action_applied = (float*)take("action_applied", N * A * 4);
-  e->action_delay = (int*)take("action_delay", N * 4);
-  e->obs_noise_scale = (float*)take("obs_noise_scale", OP * 4);
+  e->env.action_hist = (float*)take("action_hist", (size_t)kMaxActionDelay * N * A * 4);
+  e->env.action_applied = (float*)take("action_applied", N * A * 4);
+  e->env.action_delay = (int*)take("action_delay", N * 4);
+  e->env.obs_noise_scale = (float*)take("obs_noise_scale", OP * 4);
   // the normalisations across ranks: behind those again, present whatever the options and the rank count are (one rank never touches it)
   e->norm_slots = (double*)take("norm_slots", (size_t)e->cfg.world_size * 2 * ((size_t)e->O + 1) * 8);
   return align_up(off, 256);
+}
+
+// what the engine and the evaluator ask of a network beside a model (ppo_layout.h); `layers_name` / `bf16_needs`: the caller's words for the field and for the refusal
+int32_t check_net(const char* who, const mppo_net_t& net, const ModelView& mv, const char* layers_name, const char* bf16_needs) {
+  MPPO_REQUIRE(net.O == mv.obs_dim && net.OP == mv.obs_pad, "%s: net O/OP (%d/%d) do not match the model's observation (%d/%d)", who, net.O, net.OP, mv.obs_dim, mv.obs_pad);
+  MPPO_REQUIRE(net.A == mv.nu, "%s: net A = %d but the model has %d actuators", who, net.A, mv.nu);
+  // (up to 32 action dimensions take the fused kernels, 33 .. 63 the layer-wise path: fused_supported, k_fused.hip)
+  MPPO_REQUIRE(net.A >= 1 && net.A <= 63 && net.H >= 4 && net.H % 4 == 0, "%s: unsupported A / H (1 <= A <= 63, H a multiple of 4)", who);
+  MPPO_REQUIRE(net.num_layers >= 0 && net.num_layers <= kMaxHidden, "%s: %s = %d (1 .. %d hidden layers, 0 = 2)", who, layers_name, net.num_layers, kMaxHidden);
+  // bf16-in / f32-accumulate products exist in the fused kernels (two hidden layers, H a multiple of 32 up to 256); the layer-wise path is float only
+  MPPO_REQUIRE(!net.bf16 || (net_layers(net) == 2 && net.H % 32 == 0 && net.H <= 256 && net.A <= 32), "%s: %s", who, bf16_needs);
+  return MPPO_OK;
 }
 
 static int32_t validate_cfg(const mppo_model* m, const mppo_engine_cfg_t* c) {
@@ -285,15 +272,8 @@ static int32_t validate_cfg(const mppo_model* m, const mppo_engine_cfg_t* c) {
   MPPO_REQUIRE(B <= permutation_max_samples(), "engine: %ld samples per rank and update (num_envs x num_steps); the minibatch permutations take at most %d", B, permutation_max_samples());
   MPPO_REQUIRE(B % c->num_minibatches == 0, "`batch_size` must be equal to `num_steps * num_envs` (num_envs*num_steps = %ld is not divisible by num_minibatches = %d)", B,
                c->num_minibatches);
-  MPPO_REQUIRE(c->net.O == mv.obs_dim && c->net.OP == mv.obs_pad, "engine: net O/OP (%d/%d) do not match the model's observation (%d/%d)", c->net.O, c->net.OP,
-               mv.obs_dim, mv.obs_pad);
-  MPPO_REQUIRE(c->net.A == mv.nu, "engine: net A = %d but the model has %d actuators", c->net.A, mv.nu);
-  // (up to 32 action dimensions take the fused kernels, 33 .. 63 the layer-wise path: fused_supported, k_fused.hip)
-  MPPO_REQUIRE(c->net.A >= 1 && c->net.A <= 63 && c->net.H >= 4 && c->net.H % 4 == 0, "engine: unsupported A / H (1 <= A <= 63, H a multiple of 4)");
-  MPPO_REQUIRE(c->net.num_layers >= 0 && c->net.num_layers <= kMaxHidden, "engine: model.num_layers = %d (1 .. %d hidden layers)", c->net.num_layers, kMaxHidden);
-  // bf16-in / f32-accumulate products exist in the fused kernels (two hidden layers, H a multiple of 32 up to 256); the layer-wise path is float only
-  MPPO_REQUIRE(!c->net.bf16 || (net_layers(c->net) == 2 && c->net.H % 32 == 0 && c->net.H <= 256 && c->net.A <= 32),
-               "engine: training.mlp_dtype=bf16 needs the fused kernels (model.num_layers = 2, hidden_size a multiple of 32 up to 256, at most 32 actuators)");
+  MPPO_TRY(check_net("engine", c->net, mv, "model.num_layers",
+                     "training.mlp_dtype=bf16 needs the fused kernels (model.num_layers = 2, hidden_size a multiple of 32 up to 256, at most 32 actuators)"));
   MPPO_REQUIRE(c->num_updates >= 1, "engine: num_updates must be >= 1 (total_timesteps too small)");
   MPPO_REQUIRE(c->rng_impl == 0 || c->rng_impl == 1, "engine: rng_impl %d (0 philox, 1 threefry)", c->rng_impl);
   MPPO_REQUIRE(c->rng_impl == 0 || c->world_size == 1, "engine: the threefry streams follow the reference's single-device key plumbing (world_size must be 1)");
@@ -338,13 +318,13 @@ static int32_t do_rollout(mppo_engine* e, hipStream_t s) {
   const mppo_engine_cfg_t& c = e->cfg;
   const size_t N = e->N, OP = e->OP, A = e->A;
   // episode bookkeeping as it stands before the rollout: carry-in of the statistics kernel at the end
-  MPPO_CHECK_HIP(hipMemcpyAsync(e->stat_ret_in, e->met.episode_returns, N * 4, hipMemcpyDeviceToDevice, s));
-  MPPO_CHECK_HIP(hipMemcpyAsync(e->stat_len_in, e->met.episode_lengths, N * 4, hipMemcpyDeviceToDevice, s));
+  MPPO_CHECK_HIP(hipMemcpyAsync(e->stat_ret_in, e->env.met.episode_returns, N * 4, hipMemcpyDeviceToDevice, s));
+  MPPO_CHECK_HIP(hipMemcpyAsync(e->stat_len_in, e->env.met.episode_lengths, N * 4, hipMemcpyDeviceToDevice, s));
   if (!c.external_random) {
     if (c.rng_impl == 1) {
       // the reference's key plumbing (train.py:158,163,252): this update's action keys and sort keys from the carried key,
       // then one jax.random.normal(action_rng, (N, A)) per env step (what `pi.sample(seed=action_rng)` draws)
-      MPPO_TRY(threefry_chain(e->jax_rng, e->T, e->E, e->jax_rounds, e->jax_rng + 2, e->jax_rng + 2 + 2 * e->T, e->reset_noise > 0.f ? e->reset_rng : nullptr, s));
+      MPPO_TRY(threefry_chain(e->jax_rng, e->T, e->E, e->jax_rounds, e->jax_rng + 2, e->jax_rng + 2 + 2 * e->T, e->env.reset_noise > 0.f ? e->reset_rng : nullptr, s));
       for (int t = 0; t < e->T; ++t) MPPO_TRY(threefry_normal(e->jax_rng + 2 + 2 * t, N * A, e->noise + (size_t)t * N * A, s));
     } else {
       MPPO_TRY(normal_fill_ctr(c.seed, kStreamNoise + ((unsigned long long)c.rank << 16), e->count + 1, (size_t)e->T * N * A, e->noise, s));
@@ -365,40 +345,16 @@ static int32_t do_rollout(mppo_engine* e, hipStream_t s) {
     const float* obs_t = e->obs + (size_t)t * N * OP;
     MPPO_TRY(policy_forward(c.net, e->params, e->N, obs_t, e->OP, fb, e->noise + t * N * A, e->action + t * N * A, e->log_prob + t * N,
                             defer_critic ? nullptr : e->value + (size_t)t * N, nullptr, s));                          // train.py:157-160
-    // (random pushes: the wrench of step u * T + t, u the device's update index, is drawn inside this launch - a replayed graph draws fresh ones; off: the plain step)
-    EnvPush push = e->push;
-    push.add = t;
-    // actuation latency: the policy's action goes into the ring, the step is given the one its environment's latency ago (zeros at an episode's start); the
-    // trajectory keeps the policy's own action and log_prob - what PPO's ratio refers to.  Off: the step reads action[t] as it always did
-    const float* act_t = e->action + t * N * A;
-    if (e->delay.dmax > 0) {
-      MPPO_TRY(action_delay_launch(e->N, e->A, e->delay.dmax, e->action_delay, e->met.timestep, e->met.episode_lengths, act_t, e->A, e->action_hist, e->action_applied,
-                                   e->A, s));
-      act_t = e->action_applied;
-    }
-    MPPO_TRY(env_step_push_ws(e->model, e->N, c.n_frames, &c.reward, e->state, e->reset_rec, act_t, e->A, e->obs + (size_t)(t + 1) * N * OP,
-                              e->OP, e->reward + t * N, e->done + t * N, &e->met, push, e->env_ws, e->env_ws_bytes, static_cast<hipStream_t>(s), e->domain));            // :165
-    // episode time limit: the environments that have reached it are truncated - flags, metrics, the reset record - as the step's epilogue ends an episode;
-    // done[t] then includes them, so the masked reinit below restarts them too and the reward scaling's carry restarts behind them
-    if (e->limit.length > 0)
-      MPPO_TRY(time_limit_launch(e->limit, e->N, e->mv.rec_dim, e->OP, e->state, e->reset_rec, e->obs + (size_t)(t + 1) * N * OP, e->OP, e->done + t * N,
-                                 e->truncated + t * N, e->met, s));
-    // reset noise: the environments whose episode ended at this step restart from a randomised state instead of the constant record the step kernel
-    // gave them (env.py:166,179-180) - one masked launch of the reset kernel over done[t]; a workgroup without an ended episode leaves at once
-    // (domain randomisation: the one shared reset record is another robot's - every restart goes through the reset kernel with the environment's own row,
-    // at scale 0 when reset noise is off)
-    if (e->reset_noise > 0.f || e->domain.table)
-      MPPO_TRY(env_reinit_ws(e->model, e->N, e->state, e->obs + (size_t)(t + 1) * N * OP, e->OP, e->done + t * N, e->reset_noise, c.rng_impl, c.seed, c.rank,
-                             e->reset_rng + 2 * t, e->count + 1, e->T, 1 + t, e->env_ws, e->env_ws_bytes, s, e->domain));
-    // sensor noise: the new rows - restarted environments' included - get the noise of step u * T + t + 1, u the device's update index; what is stored is what
-    // the next forward, the critic's bootstrap, the learn phase and the normalisation's statistics read
-    if (e->obs_noise)
-      MPPO_TRY(obs_noise_launch(e->noise_draw, e->N, e->O, e->obs + (size_t)(t + 1) * N * OP, e->OP, e->obs_noise_scale, e->count + 1, e->T, t + 1, s));
-    // observation normalisation: the new rows are stored normalised with this update's table (the next forward and the learn phase read them so);
-    // their raw values go into this step's partial sums first
-    if (e->obs_norm)
-      MPPO_TRY(obs_norm_apply_launch(e->N, e->O, e->obs + (size_t)(t + 1) * N * OP, e->OP, e->obs_norm_table, e->OP, e->obs_norm_clip,
-                                     e->obs_norm_partials + (size_t)t * obs_norm_partial_doubles(e->N, e->O), s));
+    // the step and its optional stages (env_sequence.hip, shared with the evaluator): action[t] in, row t + 1 out, the draws at u * T + t, u the device's update
+    // index (done[t] includes the time limit's truncations, so the reward scaling's carry restarts behind them too)
+    EnvStep st;
+    st.action = e->action + t * N * A;
+    st.obs = e->obs + (size_t)(t + 1) * N * OP; st.obs_ld = e->OP;
+    st.reward = e->reward + t * N; st.done = e->done + t * N; st.truncated = e->truncated + t * N;
+    st.norm_partials = e->obs_norm_partials + (size_t)t * obs_norm_partial_doubles(e->N, e->O);
+    st.reset_key = e->reset_rng + 2 * t;
+    st.t = t;
+    MPPO_TRY(env_sequence_step(e->env, st, s));                                                                        // train.py:165
   }
   if (defer_critic)  // value[t] of all T steps and the bootstrap value in ONE critic launch over the [T + 1][N] observation rows (nothing before GAE reads them)
     MPPO_TRY(policy_forward(c.net, e->params, (e->T + 1) * e->N, e->obs, e->OP, fb, nullptr, nullptr, nullptr, e->value, nullptr, s));
@@ -411,8 +367,8 @@ static int32_t do_rollout(mppo_engine* e, hipStream_t s) {
                                       e->reward_norm_partials, s));
   // (under a time limit the scan is cut at the truncated samples and the statistics count them; without one: the plain launches)
   MPPO_TRY(gae_truncated_launch(e->T, e->N, c.gamma, c.gae_lambda, e->reward_norm ? e->reward_scaled : e->reward, e->value, e->done,
-                                e->limit.length > 0 ? e->truncated : nullptr, e->last_val, e->adv, e->target, s));
-  if (e->limit.length > 0)
+                                e->env.limit.length > 0 ? e->truncated : nullptr, e->last_val, e->adv, e->target, s));
+  if (e->env.limit.length > 0)
     hipLaunchKernelGGL(rollout_stats_limit_kernel, dim3(1), dim3(kStatsThreads), 0, s, e->T, e->N, e->reward, e->done, e->truncated, e->stat_ret_in, e->stat_len_in, e->stats);
   else
     hipLaunchKernelGGL(rollout_stats_kernel, dim3(1), dim3(kStatsThreads), 0, s, e->T, e->N, e->reward, e->done, e->stat_ret_in, e->stat_len_in, e->stats);
@@ -559,14 +515,11 @@ extern "C" int32_t mppo_engine_create(const mppo_model_t* m, const mppo_engine_c
   fill_dims(e);
   const size_t need = layout(e, true);
   if (arena_bytes < need) { delete e; return fail(MPPO_ENOMEM, "mppo_engine_create: arena %zu < %zu bytes", arena_bytes, need); }
-  e->comm = nullptr; e->peer = nullptr; e->graph = nullptr; e->graph_failed = false; e->was_reset = false; e->graph_agreed = false;
-  e->reset_noise = 0.f; e->prepared = false;
-  e->obs_norm = false; e->obs_norm_clip = 0.f; e->obs_norm_eps = 0.f;
-  e->reward_norm = false; e->reward_norm_clip = 0.f; e->reward_norm_eps = 0.f;
-  e->push = EnvPush{};
-  e->limit = LimitCfg{};
-  e->domain = EnvDomain{};
-  e->obs_noise = false; e->noise_draw = ObsNoiseDraw{}; e->delay = DelayDraw{};
+  // the environments' run: every draw is the engine configuration's (seed, rank) at step u * T + ..., u the device's update index - the word that
+  // advance_counters_kernel moves on at the end of every update, so a replayed graph draws fresh values at every step
+  e->env.model = m; e->env.N = e->N; e->env.n_frames = cfg->n_frames; e->env.rc = cfg->reward;
+  e->env.counter = e->count + 1; e->env.counter_mul = e->T;
+  e->env.rng_impl = cfg->rng_impl; e->env.seed = cfg->seed; e->env.rank = cfg->rank;
   *out = e;
   return MPPO_OK;
 }
@@ -576,7 +529,7 @@ extern "C" int32_t mppo_engine_destroy(mppo_engine_t* e) {
   if (e->graph) graph_destroy(e->graph);
   if (e->comm) comm_destroy(e->comm);
   if (e->peer) peer_destroy(e->peer);
-  if (e->domain.table) (void)hipFree(const_cast<float*>(e->domain.table));
+  if (e->env.domain.table) (void)hipFree(const_cast<float*>(e->env.domain.table));
   delete e;
   return MPPO_OK;
 }
@@ -615,19 +568,12 @@ extern "C" int32_t mppo_engine_reset(mppo_engine_t* e, void* stream) {
   MPPO_CHECK_HIP(hipMemsetAsync(e->adam_v, 0, (size_t)e->P * 4, s));
   MPPO_CHECK_HIP(hipMemsetAsync(e->obs, 0, (size_t)(e->T + 1) * e->N * e->OP * 4, s));
   MPPO_TRY(permutation_batch_prepare(e->B, e->E, e->perm_ws, e->perm_ws_bytes, s));
-  MPPO_TRY(env_reset_ws(e->model, e->N, e->state, e->reset_rec, e->obs, e->OP, nullptr, nullptr, &e->met, e->env_ws, e->env_ws_bytes, static_cast<hipStream_t>(s), e->domain));  // train.py:142-144
-  // reset noise: the plain reset above made the noise-free reset record and the zeroed metrics; every environment then starts from a state of its own
-  // (event 0 of the Philox stream; the reset key behind the step keys of region "reset_rng" for threefry: the caller writes it before this call)
-  if (e->reset_noise > 0.f)
-    MPPO_TRY(env_reinit_ws(e->model, e->N, e->state, e->obs, e->OP, nullptr, e->reset_noise, e->cfg.rng_impl, e->cfg.seed, e->cfg.rank, e->reset_rng + 2 * e->T, nullptr, 0, 0,
-                           e->env_ws, e->env_ws_bytes, s, e->domain));
-  // sensor noise: the row the reset wrote is step 0 of the noise's stream (the state records stay exact)
-  if (e->obs_noise) MPPO_TRY(obs_noise_launch(e->noise_draw, e->N, e->O, e->obs, e->OP, e->obs_noise_scale, nullptr, 0, 0, s));
-  // actuation latency: an empty ring, and the table of every environment's latency (a function of seed and rank: a resumed run has the same robots)
-  if (e->delay.dmax > 0) {
-    MPPO_CHECK_HIP(hipMemsetAsync(e->action_hist, 0, (size_t)kMaxActionDelay * e->N * e->A * 4, s));
-    MPPO_TRY(action_delay_fill_launch(e->delay, e->N, e->action_delay, s));
-  }
+  // the reset and what the options put behind it (env_sequence.hip, shared with the evaluator): row 0 of "obs", no reward / done; under threefry the reset
+  // noise's key lies behind the step keys of region "reset_rng" - the caller writes it before this call
+  EnvStep first;
+  first.obs = e->obs; first.obs_ld = e->OP;
+  first.reset_key = e->reset_rng + 2 * e->T;
+  MPPO_TRY(env_sequence_reset(e->env, first, s));
   if (e->obs_norm) {  // nothing counted, the identity table (pad columns included); obs[0] above stays raw
     MPPO_CHECK_HIP(hipMemsetAsync(e->obs_norm_stats, 0, (1 + 2 * (size_t)e->O) * 8, s));
     MPPO_TRY(obs_norm_update_launch(e->O, 0, 0, nullptr, e->obs_norm_stats, e->obs_norm_eps, e->obs_norm_table, e->OP, s));
@@ -641,19 +587,29 @@ extern "C" int32_t mppo_engine_reset(mppo_engine_t* e, void* stream) {
   return MPPO_OK;
 }
 
+// What every mppo_engine_set_* refuses: an option changes the update's launch sequence, which is fixed once an update has been prepared, and what mppo_engine_reset
+// wrote.  `before`: the setter's words for when to call it instead; `after_reset`: its clause behind "mppo_engine_reset has run already" (null: the setter has a
+// rule of its own for that)
+static int32_t require_unprepared(const mppo_engine_t* e, const char* fn, const char* before, const char* after_reset) {
+  if (e->graph || e->prepared)
+    return fail(MPPO_ESTATE, "%s: the update has been prepared already (its launch sequence is fixed, a captured graph holds it): %s", fn, before);
+  if (after_reset && e->was_reset) return fail(MPPO_ESTATE, "%s: mppo_engine_reset has run already%s", fn, after_reset);
+  return MPPO_OK;
+}
+
 extern "C" int32_t mppo_engine_set_obs_norm(mppo_engine_t* e, int32_t enabled, float clip, float eps) {
   MPPO_REQUIRE(e, "mppo_engine_set_obs_norm: null engine");
   MPPO_REQUIRE(clip >= 0.f && eps >= 0.f, "mppo_engine_set_obs_norm: clip %g / eps %g is negative (or not a number)", (double)clip, (double)eps);
   MPPO_REQUIRE(!enabled || e->cfg.world_size == 1 || e->comm || peer_connected(e->peer), "mppo_engine_set_obs_norm: world_size = %d ranks - the running statistics are "
                "gathered over the ranks' transport once per update: connect it first (mppo_engine_peer_connect or mppo_engine_comm_init), then enable the option", e->cfg.world_size);
-  if (e->graph || e->prepared)
-    return fail(MPPO_ESTATE, "mppo_engine_set_obs_norm: the update has been prepared already (its launch sequence is fixed, a captured graph holds it): "
-                             "call it before mppo_engine_reset, mppo_engine_prepare and the first mppo_engine_update");
-  if (e->was_reset)
-    return fail(MPPO_ESTATE, "mppo_engine_set_obs_norm: mppo_engine_reset has run already (it zeroes the statistics and writes the identity table): call it before the reset");
+  MPPO_TRY(require_unprepared(e, "mppo_engine_set_obs_norm", "call it before mppo_engine_reset, mppo_engine_prepare and the first mppo_engine_update",
+                              " (it zeroes the statistics and writes the identity table): call it before the reset"));
   e->obs_norm = enabled != 0;
-  e->obs_norm_clip = clip;
   e->obs_norm_eps = eps;
+  // what the rollout's step sequence applies: this update's table, collected through the previous one
+  e->env.norm_table = e->obs_norm ? e->obs_norm_table : nullptr;
+  e->env.norm_ld = e->OP;
+  e->env.norm_clip = clip;
   return MPPO_OK;
 }
 
@@ -662,12 +618,8 @@ extern "C" int32_t mppo_engine_set_reward_norm(mppo_engine_t* e, int32_t enabled
   MPPO_REQUIRE(clip >= 0.f && eps >= 0.f, "mppo_engine_set_reward_norm: clip %g / eps %g is negative (or not a number)", (double)clip, (double)eps);
   MPPO_REQUIRE(!enabled || e->cfg.world_size == 1 || e->comm || peer_connected(e->peer), "mppo_engine_set_reward_norm: world_size = %d ranks - the running statistics are "
                "gathered over the ranks' transport once per update: connect it first (mppo_engine_peer_connect or mppo_engine_comm_init), then enable the option", e->cfg.world_size);
-  if (e->graph || e->prepared)
-    return fail(MPPO_ESTATE, "mppo_engine_set_reward_norm: the update has been prepared already (its launch sequence is fixed, a captured graph holds it): "
-                             "call it before mppo_engine_reset, mppo_engine_prepare and the first mppo_engine_update");
-  if (e->was_reset)
-    return fail(MPPO_ESTATE, "mppo_engine_set_reward_norm: mppo_engine_reset has run already (it zeroes the statistics and the carry and writes the identity table): "
-                             "call it before the reset");
+  MPPO_TRY(require_unprepared(e, "mppo_engine_set_reward_norm", "call it before mppo_engine_reset, mppo_engine_prepare and the first mppo_engine_update",
+                              " (it zeroes the statistics and the carry and writes the identity table): call it before the reset"));
   e->reward_norm = enabled != 0;
   e->reward_norm_clip = clip;
   e->reward_norm_eps = eps;
@@ -677,13 +629,11 @@ extern "C" int32_t mppo_engine_set_reward_norm(mppo_engine_t* e, int32_t enabled
 extern "C" int32_t mppo_engine_set_reset_noise(mppo_engine_t* e, float scale) {
   MPPO_REQUIRE(e, "mppo_engine_set_reset_noise: null engine");
   MPPO_REQUIRE(scale >= 0.f, "mppo_engine_set_reset_noise: scale %g is negative (or not a number)", (double)scale);
-  if (e->graph || e->prepared)
-    return fail(MPPO_ESTATE, "mppo_engine_set_reset_noise: the update has been prepared already (its launch sequence is fixed, a captured graph holds it): "
-                             "set the scale before mppo_engine_prepare and the first mppo_engine_update");
-  if (e->was_reset && scale != e->reset_noise)
+  MPPO_TRY(require_unprepared(e, "mppo_engine_set_reset_noise", "set the scale before mppo_engine_prepare and the first mppo_engine_update", nullptr));
+  if (e->was_reset && scale != e->env.reset_noise)  // (the same scale again changes nothing: allowed)
     return fail(MPPO_ESTATE, "mppo_engine_set_reset_noise: mppo_engine_reset has run already (the environments hold the initial states of scale %g): set the scale before it",
-                (double)e->reset_noise);
-  e->reset_noise = scale;
+                (double)e->env.reset_noise);
+  e->env.reset_noise = scale;
   return MPPO_OK;
 }
 
@@ -692,17 +642,13 @@ extern "C" int32_t mppo_engine_set_push(mppo_engine_t* e, const mppo_push_cfg_t*
   if (push) MPPO_TRY(check_push_cfg("mppo_engine_set_push", push));
   const bool on = push && push->force > 0.f;
   if (on) MPPO_TRY(check_push_body("mppo_engine_set_push", e->model, push->body));
-  if (e->graph || e->prepared)
-    return fail(MPPO_ESTATE, "mppo_engine_set_push: the update has been prepared already (its launch sequence is fixed, a captured graph holds it): "
-                             "set the pushes before mppo_engine_prepare and the first mppo_engine_update");
-  if (e->was_reset)
-    return fail(MPPO_ESTATE, "mppo_engine_set_push: mppo_engine_reset has run already: set the pushes before it");
-  e->push = EnvPush{};
+  MPPO_TRY(require_unprepared(e, "mppo_engine_set_push", "set the pushes before mppo_engine_prepare and the first mppo_engine_update", ": set the pushes before it"));
+  e->env.push = EnvPush{};
   if (on) {
     mppo_push_cfg_t pc = *push;
     pc.seed = e->cfg.seed; pc.rank = e->cfg.rank;  // (the engine's own: one stream per rank, as the action noise and the reset noise have)
     MPPO_TRY(check_push_cfg("mppo_engine_set_push", &pc));  // (the rank that is used - the engine configuration's - fits the stream id's eight bits)
-    e->push.body = pc.body; e->push.draw = push_draw_of(pc); e->push.ctr = e->count + 1; e->push.mul = e->T;
+    e->env.push.body = pc.body; e->env.push.draw = push_draw_of(pc);
   }
   return MPPO_OK;
 }
@@ -717,11 +663,8 @@ extern "C" int32_t mppo_engine_set_domain(mppo_engine_t* e, const mppo_domain_cf
     on = domain_cfg_on(dc);
     MPPO_TRY(check_domain_cfg("mppo_engine_set_domain", on ? e->model : nullptr, &dc));
   }
-  if (e->graph || e->prepared)
-    return fail(MPPO_ESTATE, "mppo_engine_set_domain: the update has been prepared already (its launch sequence is fixed, a captured graph holds it): "
-                             "set the randomisation before mppo_engine_prepare and the first mppo_engine_update");
-  if (e->was_reset)
-    return fail(MPPO_ESTATE, "mppo_engine_set_domain: mppo_engine_reset has run already (the environments hold the initial states of the robots they were): set the randomisation before it");
+  MPPO_TRY(require_unprepared(e, "mppo_engine_set_domain", "set the randomisation before mppo_engine_prepare and the first mppo_engine_update",
+                              " (the environments hold the initial states of the robots they were): set the randomisation before it"));
   // the table lives on the device the arena is on, whatever the calling thread's current device is (restored on the way out)
   int cur = -1, dev = -1;
 #ifndef MPPO_EMU
@@ -739,18 +682,18 @@ extern "C" int32_t mppo_engine_set_domain(mppo_engine_t* e, const mppo_domain_cf
 #endif
     return rc;
   };
-  if (e->domain.table) {
+  if (e->env.domain.table) {
     if (hipDeviceSynchronize() != hipSuccess) return back(fail(MPPO_EHIP, "mppo_engine_set_domain: the device does not synchronise"));
-    (void)hipFree(const_cast<float*>(e->domain.table));
+    (void)hipFree(const_cast<float*>(e->env.domain.table));
   }
-  e->domain = EnvDomain{};
+  e->env.domain = EnvDomain{};
   if (on) {
     float* table = nullptr;
     if (hipMalloc(reinterpret_cast<void**>(&table), (size_t)e->N * 16) != hipSuccess) return back(fail(MPPO_EHIP, "mppo_engine_set_domain: no device memory for the table of %d environments", e->N));
     int32_t rc = domain_fill_launch(dc, e->N, table, nullptr);
     if (rc == MPPO_OK && hipStreamSynchronize(nullptr) != hipSuccess) rc = fail(MPPO_EHIP, "mppo_engine_set_domain: the fill launch failed");
     if (rc != MPPO_OK) { (void)hipFree(table); return back(rc); }
-    e->domain = EnvDomain{table, dc.mass_body};
+    e->env.domain = EnvDomain{table, dc.mass_body};
   }
   return back(MPPO_OK);
 }
@@ -761,13 +704,8 @@ extern "C" int32_t mppo_engine_set_time_limit(mppo_engine_t* e, int32_t length, 
   lc.length = length; lc.stagger = stagger != 0 ? 1 : 0; lc.seed = e->cfg.seed;
   lc.rank = length > 0 ? e->cfg.rank : 0;  // (the engine's own: one stream per rank, as the pushes have; it fits the stream id's eight bits or the limit is refused)
   MPPO_TRY(check_limit_cfg("mppo_engine_set_time_limit", &lc));
-  if (e->graph || e->prepared)
-    return fail(MPPO_ESTATE, "mppo_engine_set_time_limit: the update has been prepared already (its launch sequence is fixed, a captured graph holds it): "
-                             "set the limit before mppo_engine_prepare and the first mppo_engine_update");
-  if (e->was_reset)
-    return fail(MPPO_ESTATE, "mppo_engine_set_time_limit: mppo_engine_reset has run already: set the limit before it");
-  e->limit = LimitCfg{};
-  if (length > 0) e->limit = limit_cfg_of(lc);
+  MPPO_TRY(require_unprepared(e, "mppo_engine_set_time_limit", "set the limit before mppo_engine_prepare and the first mppo_engine_update", ": set the limit before it"));
+  e->env.limit = length > 0 ? limit_cfg_of(lc) : LimitCfg{};
   return MPPO_OK;
 }
 
@@ -779,18 +717,15 @@ extern "C" int32_t mppo_engine_set_obs_noise(mppo_engine_t* e, const float* scal
   mppo_obs_noise_cfg_t nc{};
   nc.seed = e->cfg.seed; nc.rank = on ? e->cfg.rank : 0;  // (the engine's own: one stream per rank, as the pushes have; it fits the stream id's eight bits or the noise is refused)
   MPPO_TRY(check_obs_noise_cfg("mppo_engine_set_obs_noise", &nc));
-  if (e->graph || e->prepared)
-    return fail(MPPO_ESTATE, "mppo_engine_set_obs_noise: the update has been prepared already (its launch sequence is fixed, a captured graph holds it): "
-                             "set the noise before mppo_engine_prepare and the first mppo_engine_update");
-  if (e->was_reset)
-    return fail(MPPO_ESTATE, "mppo_engine_set_obs_noise: mppo_engine_reset has run already (the observation it wrote has its noise or has none): set the noise before it");
-  e->obs_noise = false;
+  MPPO_TRY(require_unprepared(e, "mppo_engine_set_obs_noise", "set the noise before mppo_engine_prepare and the first mppo_engine_update",
+                              " (the observation it wrote has its noise or has none): set the noise before it"));
+  e->env.obs_noise = false;
   if (on) {  // the table into its region (pad columns 0), before anything is enqueued
     std::vector<float> table((size_t)e->OP, 0.f);
     for (int j = 0; j < e->O; ++j) table[j] = scale[j];
-    MPPO_CHECK_HIP(hipMemcpy(e->obs_noise_scale, table.data(), (size_t)e->OP * 4, hipMemcpyHostToDevice));
-    e->obs_noise = true;
-    e->noise_draw = obs_noise_draw_of(nc);
+    MPPO_CHECK_HIP(hipMemcpy(e->env.obs_noise_scale, table.data(), (size_t)e->OP * 4, hipMemcpyHostToDevice));
+    e->env.obs_noise = true;
+    e->env.noise_draw = obs_noise_draw_of(nc);
   }
   return MPPO_OK;
 }
@@ -801,13 +736,9 @@ extern "C" int32_t mppo_engine_set_action_delay(mppo_engine_t* e, int32_t dmin, 
   dc.min = dmin; dc.max = dmax; dc.seed = e->cfg.seed;
   dc.rank = dmax > 0 ? e->cfg.rank : 0;  // (the engine's own, as above)
   MPPO_TRY(check_action_delay_cfg("mppo_engine_set_action_delay", &dc));
-  if (e->graph || e->prepared)
-    return fail(MPPO_ESTATE, "mppo_engine_set_action_delay: the update has been prepared already (its launch sequence is fixed, a captured graph holds it): "
-                             "set the latency before mppo_engine_prepare and the first mppo_engine_update");
-  if (e->was_reset)
-    return fail(MPPO_ESTATE, "mppo_engine_set_action_delay: mppo_engine_reset has run already (it empties the ring and writes the latency table): set the latency before it");
-  e->delay = DelayDraw{};
-  if (dmax > 0) e->delay = delay_draw_of(dc);
+  MPPO_TRY(require_unprepared(e, "mppo_engine_set_action_delay", "set the latency before mppo_engine_prepare and the first mppo_engine_update",
+                              " (it empties the ring and writes the latency table): set the latency before it"));
+  e->env.delay = dmax > 0 ? delay_draw_of(dc) : DelayDraw{};
   return MPPO_OK;
 }
 

@@ -1,5 +1,6 @@
 // env_model.hip - the model handle of the environment kernel (k_physics.hip): a validated model's (model_blob.hip) LDS layout, the on-device check of a specialised kernel, attached code objects, the C ABI
 #include "env_kernel.h"
+#include "env_launch.h"
 
 #include <algorithm>
 #include <cmath>
@@ -68,15 +69,6 @@ static int32_t launch_env(const mppo_model_t* m, EnvArgs a, hipStream_t stream, 
   }
   return launch_env_spec(m->spec, m->mv, a, m->lds, m->lds_bytes, blocks, m->waves, !m->no_split, stream);
 }
-// the engine's entry: mppo_env_step with the out-of-LDS matrices in a region of the engine's arena (hipGraph capture: nothing is allocated)
-int32_t env_step_ws(const mppo_model_t* m, int32_t N, int32_t n_frames, const mppo_reward_cfg_t* rc, float* state, const float* reset_rec, const float* action,
-                    int32_t act_ld, float* obs, int32_t obs_ld, float* reward, uint8_t* done, const mppo_env_metrics_t* metrics, float* ws, size_t ws_bytes, hipStream_t stream) {
-  EnvArgs a{};
-  a.N = N; a.mode = 1; a.n_frames = n_frames; a.state = state; a.reset_in = reset_rec; a.action = action; a.act_ld = act_ld;
-  a.obs = obs; a.obs_ld = obs_ld; a.reward = reward; a.done = done; a.rc = *rc;
-  if (metrics) a.met = *metrics;
-  return launch_env(m, a, stream, ws, ws_bytes);
-}
 // Domain randomisation.  What every entry point that takes a domain configuration refuses (with a model at hand: the payload's body and the mass it leaves)
 int32_t check_domain_body(const char* who, const mppo_model_t* m, int32_t body) {
   MPPO_REQUIRE(body >= 1 && body < m->mv.nbody, "%s: mass_body %d outside 1 .. nbody - 1 = %d (0 is the world)", who, body, m->mv.nbody - 1);
@@ -122,7 +114,8 @@ int32_t check_push_body(const char* who, const mppo_model_t* m, int32_t body) {
 PushDraw push_draw_of(const mppo_push_cfg_t& p) {
   return PushDraw{p.force, p.interval, p.duration, p.seed, kStreamPush + ((unsigned long long)p.rank << 16)};
 }
-// env_step_ws under an external wrench (push.xfrc given, or drawn in the kernel when push.draw.force > 0; neither: exactly env_step_ws)
+// the step launch, with the out-of-LDS matrices in the caller's region (the engine's arena - hipGraph capture: nothing is allocated): under an external wrench
+// (push.xfrc given, or drawn in the kernel when push.draw.force > 0; neither: the unpushed step) and a randomisation table (none: the kernels it always ran)
 int32_t env_step_push_ws(const mppo_model_t* m, int32_t N, int32_t n_frames, const mppo_reward_cfg_t* rc, float* state, const float* reset_rec, const float* action,
                          int32_t act_ld, float* obs, int32_t obs_ld, float* reward, uint8_t* done, const mppo_env_metrics_t* metrics, const EnvPush& push, float* ws,
                          size_t ws_bytes, hipStream_t stream, const EnvDomain& dom) {
@@ -265,7 +258,7 @@ static int32_t spec_self_check(mppo_model* m) {
     if (he != hipSuccess) { st = fail(MPPO_EHIP, "specialised-kernel self-check: %s", hipGetErrorString(he)); break; }
     st = env_reset_ws(mm, N, state, reset_rec, obs, v.obs_pad, rew, done, nullptr, nullptr, 0, nullptr, EnvDomain{});
     for (int t = 0; t < steps && st == MPPO_OK; ++t)
-      st = env_step_ws(mm, N, 1, &rc, state, reset_rec, actd + (size_t)t * nact, nu, obs, v.obs_pad, rew, done, nullptr, nullptr, 0, nullptr);
+      st = env_step_push_ws(mm, N, 1, &rc, state, reset_rec, actd + (size_t)t * nact, nu, obs, v.obs_pad, rew, done, nullptr, EnvPush{}, nullptr, 0, nullptr, EnvDomain{});
     if (st != MPPO_OK) break;
     got[which].resize(words);
     he = hipDeviceSynchronize();
@@ -464,7 +457,8 @@ extern "C" int32_t mppo_env_step(const mppo_model_t* m, int32_t N, int32_t n_fra
   MPPO_REQUIRE(m->mv.nq >= 3, "mppo_env_step: the environment reads qpos[2] as the height (env.py:239); nq = %d", m->mv.nq);
   MPPO_REQUIRE(act_ld >= m->mv.nu, "mppo_env_step: act_ld %d < nu %d", act_ld, m->mv.nu);
   MPPO_REQUIRE(obs_ld >= m->mv.obs_pad, "mppo_env_step: obs_ld %d < padded observation width %d", obs_ld, m->mv.obs_pad);
-  return env_step_ws(m, N, n_frames, rc, state, reset_rec, action, act_ld, obs, obs_ld, reward, done, metrics, nullptr, 0, static_cast<hipStream_t>(stream));
+  return env_step_push_ws(m, N, n_frames, rc, state, reset_rec, action, act_ld, obs, obs_ld, reward, done, metrics, EnvPush{}, nullptr, 0, static_cast<hipStream_t>(stream),
+                          EnvDomain{});
 }
 
 extern "C" int32_t mppo_physics_forward(const mppo_model_t* m, int32_t N, const float* qpos, const float* qvel, const float* ctrl,

@@ -17,12 +17,10 @@
 //   eval_limit_reduce_kernel once at the end, ONE workgroup in a fixed order: the truncations' sum and the number of environments with a termination.
 #include <wave_ops.h>
 
+#include "env_launch.h"
 #include "limit.h"
-#include "model_view.h"
 
 namespace mppo {
-
-const ModelView& model_view(const mppo_model* m);
 
 constexpr int kLimitThreads = 256, kLimitLanes = 16, kLimitEnvs = kLimitThreads / kLimitLanes;
 

@@ -22,6 +22,9 @@ namespace mppo {
 constexpr int kMaxHidden = 4;
 constexpr int kMaxPads = 4 * (kMaxHidden + 1) + 1;
 inline int net_layers(const mppo_net_t& n) { return n.num_layers > 0 ? n.num_layers : 2; }
+// engine.hip: the network geometry the engine and the evaluator accept beside a model - O / OP and A the model's, the A / H ranges, the depth, what bf16 needs
+struct ModelView;
+int32_t check_net(const char* who, const mppo_net_t& net, const ModelView& mv, const char* layers_name, const char* bf16_needs);
 struct ParamLayout {
   int a_w1, a_b1, a_w2, a_b2, a_w3, a_b3, log_std, c_w1, c_b1, c_w2, c_b2, c_w3, c_b3, total;
   int nl, a_w[kMaxHidden + 1], a_b[kMaxHidden + 1], c_w[kMaxHidden + 1], c_b[kMaxHidden + 1];

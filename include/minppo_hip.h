@@ -327,8 +327,9 @@ typedef struct mppo_net {
   int32_t use_tanh;  /* actor activation; the critic is always ReLU (train.py:82) */
   int32_t bf16;      /* 0: exact f32 MFMA; 1: bf16-in/f32-accumulate MFMA for the hidden GEMMs */
   int32_t num_layers; /* hidden layers of each MLP (`model.num_layers`, config.py:53, train.py:79,82): 1 .. 4; 0 means 2, the
-                         reference's default.  Two hidden layers take the fused kernels; 1, 3 and 4 hidden layers of a float network take the
-                         depth-generic row pass where the geometry fits it, the layer-wise path otherwise (mppo_network_path). */
+                         reference's default.  Two hidden layers take the fused kernels; 1, 3 and 4 hidden layers of a float network - and two
+                         where the fused kernels refuse the geometry, e.g. an observation wider than 736 - take the depth-generic row pass
+                         where the geometry fits it (any observation width), the layer-wise path otherwise (mppo_network_path). */
 } mppo_net_t;
 
 /* Length (floats) of the flat parameter / gradient / Adam-moment vectors: the model's parameters with every tensor starting on
@@ -386,7 +387,9 @@ typedef struct mppo_loss_cfg { float clip_eps, vf_coef, ent_coef; } mppo_loss_cf
 /* *fused = 1 if mppo_minibatch_grad takes the fused row pass + single-launch weight gradients for this geometry
  * (H a multiple of 32 up to 256, A <= 32, 16-byte aligned observation rows), 0 if it runs the layer-wise kernels. */
 int32_t mppo_minibatch_path(const mppo_net_t* net, const mppo_batch_t* batch, int32_t* fused);
-/* 0: layer-wise kernels, 1: the two-layer fused kernels (k_fused.hip), 2: the depth-generic row pass (k_deep.hip).
+/* 0: layer-wise kernels, 1: the two-layer fused kernels (k_fused.hip), 2: the depth-generic row pass (k_deep.hip): float networks of
+ * 1 to 4 hidden layers that 1 does not take, H a multiple of 32 up to 256, A <= 32, 16-byte aligned observation rows of ANY width (an
+ * observation whose row tile does not fit a CU's LDS streams through it in slabs).
  * *rowpass: the row-local half of mppo_minibatch_grad / mppo_minibatch_rowpass; *rollout: mppo_policy_forward. */
 int32_t mppo_network_path(const mppo_net_t* net, const float* obs, int32_t obs_ld, int32_t* rowpass, int32_t* rollout);
 /* *rows = minibatch rows per workgroup of the fused row pass for a minibatch of mb rows: 16, or 32 where the engine's minibatch loop

@@ -1,5 +1,6 @@
-// deep.h — the depth-generic row pass (k_deep.hip: deep_mlp_kernel) for networks of 1, 3 and 4 hidden layers: its argument block, its LDS
-// layout and the launchers that k_ppo.hip dispatches to.  Two hidden layers are fused_mlp_kernel's (k_fused.hip); nothing here touches it.
+// deep.h — the depth-generic row pass (k_deep.hip: deep_mlp_kernel) for networks of 1 to 4 hidden layers: its argument block, its LDS
+// layout and the launchers that k_ppo.hip dispatches to.  Two hidden layers are fused_mlp_kernel's (k_fused.hip) wherever that kernel takes
+// the geometry; nothing here touches it.
 #pragma once
 #include "ppo_layout.h"
 
@@ -7,6 +8,9 @@ namespace mppo {
 
 constexpr int kDeepRows = 16;             // minibatch rows per workgroup (one 16 x 16 MFMA row tile)
 constexpr size_t kDeepLdsMax = 160 * 1024;  // LDS of a CU: geometries beyond it are refused by the ..._supported predicates
+constexpr int kDeepSlab = 96;             // streamed first layer: observation columns per LDS slab = one turn of the weight ring (3 stages of 32 k)
+constexpr int kDeepSlabChunks = kDeepRows * kDeepSlab / 4;  // float4 pieces of a slab
+constexpr int kDeepSlabQ = kDeepSlabChunks / 64;            // ... per thread of the narrowest workgroup (one wave)
 
 struct DeepArgs {
   int mb, O, OP, A, AP, DP, H, nl, use_tanh;
@@ -34,17 +38,22 @@ struct DeepArgs {
 //             go over the tile the last layer READ (8 H OT <= T floats).
 //   training: R0 + (L + 1) T + 2 * 16 SD + 16.  x | h_0 .. h_{L-1} (all kept: the backward reads act'(h_l) from them) | D1 | s_do | s_red | s_l.
 //             The dZ tiles ping-pong between D0 = R0 (x is dead after layer 0) and D1: dZ_l lives in D(l & 1); s_hp shares D1.
+//   streamed (stream = true: the resident layout is beyond a CU's LDS): the x tile is never resident.  The first region holds a ring of two
+//             slabs of 16 x kDeepSlab observation columns, row stride XS = kDeepSlab + 4, slab s in half s & 1: R0 = 16 max(2 XS, HS) - for
+//             H >= 196 no more than a hidden tile, whatever O.  Everything behind the first region is as above.
 // The host sizes the launch (bytes()) and the device carves its pointers from the same members.
 struct DeepLds {
   int KP, XS, HS, SD, T, R0, L;
   bool rollout;
-  __host__ __device__ DeepLds(int O, int H, int OT, int L_, bool rollout_)
-      : KP((O + 31) & ~31), XS(KP + 4), HS(H + 4), SD(16 * OT), T(kDeepRows * HS), R0(kDeepRows * (XS > HS ? XS : HS)), L(L_), rollout(rollout_) {}
+  __host__ __device__ DeepLds(int O, int H, int OT, int L_, bool rollout_, bool stream)
+      : KP((O + 31) & ~31), XS(stream ? kDeepSlab + 4 : KP + 4), HS(H + 4), SD(16 * OT), T(kDeepRows * HS),
+        R0(kDeepRows * ((stream ? 2 * XS : XS) > HS ? (stream ? 2 * XS : XS) : HS)), L(L_), rollout(rollout_) {}
   __host__ __device__ size_t floats() const {
     return rollout ? (size_t)R0 + T : (size_t)R0 + (size_t)(L + 1) * T + 2 * (size_t)kDeepRows * SD + kDeepRows;
   }
   __host__ __device__ size_t bytes() const { return sizeof(float) * floats(); }
   __host__ __device__ float* xt(float* sm) const { return sm; }
+  __host__ __device__ float* slab(float* sm, int s) const { return (s & 1) ? sm + kDeepRows * XS : sm; }        // streamed: slab s of the ring
   __host__ __device__ float* tile(float* sm, int k) const { return (k & 1) ? sm + R0 : sm; }                  // rollout ping-pong
   __host__ __device__ float* h(float* sm, int l) const { return sm + R0 + (size_t)l * T; }                     // training: hidden layer l
   __host__ __device__ float* dz(float* sm, int l) const { return (l & 1) ? sm + R0 + (size_t)L * T : sm; }     // training: dZ_l
@@ -54,8 +63,9 @@ struct DeepLds {
   __host__ __device__ float* s_l(float* sm) const { return s_red(sm) + kDeepRows * SD; }
 };
 
-// k_deep.hip.  The predicates decide the dispatch in k_ppo.hip (policy_forward, minibatch_rowpass): depth 1, 3 or 4, float network,
-// H a multiple of 32 in [32, 256], A <= 32, observation rows of stride OP (a multiple of 4) on a 16-byte boundary, LDS within kDeepLdsMax.
+// k_deep.hip.  The predicates decide the dispatch in k_ppo.hip (policy_forward, minibatch_rowpass), which asks the two-layer kernels first: depth 1 to 4,
+// float network, H a multiple of 32 in [32, 256], A <= 32, observation rows of stride OP (a multiple of 4) on a 16-byte boundary.  Any O: the resident layout
+// where it is within kDeepLdsMax, the streamed one otherwise.
 bool deep_supported(const mppo_net_t& net, const mppo_batch_t& b);
 bool deep_rollout_supported(const mppo_net_t& net, const float* obs, int obs_ld);
 int32_t deep_forward_backward(const mppo_net_t& net, const float* params, const mppo_batch_t& batch, const int* idx, int mb, const float* adv_stat,

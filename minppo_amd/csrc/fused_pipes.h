@@ -94,29 +94,37 @@ struct GemmPipe {
   // (a redundant, harmless load) instead of being skipped: straight-line code, exact vmcnt bookkeeping.
   template <bool BF16>
   __device__ __forceinline__ void run(const float* At, int AS, int K, const float* W, int H, int n0, int lane, f32x4& acc0, f32x4& acc1) {
+    run_part<BF16>(At, AS, 0, K / 32, K, W, H, n0, lane, acc0, acc1);
+  }
+  // Stages S0 .. S0 + ns - 1 of a K-deep product whose A columns arrive piecewise (k_deep.hip: the streamed first layer): `At` holds columns
+  // 32 S0 .. 32 (S0 + ns) - 1 only, the weight ring keeps walking the whole K.  The invariant holds again on return when ns is a multiple of 3
+  // (one turn of the ring); any other count is the LAST part of the product.  Parts run in order into the same accumulators: the sums of run().
+  template <bool BF16>
+  __device__ __forceinline__ void run_part(const float* At, int AS, int S0, int ns, int K, const float* W, int H, int n0, int lane, f32x4& acc0, f32x4& acc1) {
     const int j = lane & 15, kq = lane >> 4;
     const float* arow = At + j * AS + 4 * kq;
-    const int nst = K / 32, last = nst - 1;
+    const int last = K / 32 - 1;
     BStage<NT> b2;
-    int S = 0;
+    int i = 0;
     // MPPO_SCHED_FENCE: the machine scheduler otherwise sinks a stage's loads down to their first use (it minimises
     // register pressure), which is exactly the latency exposure the ring exists to avoid
-    for (; S + 2 < nst; S += 3) {
+    for (; i + 2 < ns; i += 3) {
+      const int S = S0 + i;
       b2.load(W, wb, H, K, S + 2, n0, j, kq);
       MPPO_SCHED_FENCE();
-      stage_mfma<BF16>(arow, S, b0.x0, b0.x1, acc0, acc1);
+      stage_mfma<BF16>(arow, i, b0.x0, b0.x1, acc0, acc1);
       MPPO_SCHED_FENCE();
       b0.load(W, wb, H, K, S + 3 < last ? S + 3 : last, n0, j, kq);
       MPPO_SCHED_FENCE();
-      stage_mfma<BF16>(arow, S + 1, b1.x0, b1.x1, acc0, acc1);
+      stage_mfma<BF16>(arow, i + 1, b1.x0, b1.x1, acc0, acc1);
       MPPO_SCHED_FENCE();
       b1.load(W, wb, H, K, S + 4 < last ? S + 4 : last, n0, j, kq);
       MPPO_SCHED_FENCE();
-      stage_mfma<BF16>(arow, S + 2, b2.x0, b2.x1, acc0, acc1);
+      stage_mfma<BF16>(arow, i + 2, b2.x0, b2.x1, acc0, acc1);
       MPPO_SCHED_FENCE();
     }
-    if (S < nst) stage_mfma<BF16>(arow, S, b0.x0, b0.x1, acc0, acc1);
-    if (S + 1 < nst) stage_mfma<BF16>(arow, S + 1, b1.x0, b1.x1, acc0, acc1);
+    if (i < ns) stage_mfma<BF16>(arow, i, b0.x0, b0.x1, acc0, acc1);
+    if (i + 1 < ns) stage_mfma<BF16>(arow, i + 1, b1.x0, b1.x1, acc0, acc1);
   }
   // Two 16-row tiles per workgroup (RT = 2: rows j and j + 16 of a 32-row activation tile): every weight stage is fetched ONCE and
   // multiplied into both tiles - twice the MFMAs per byte streamed, the same ring otherwise.

@@ -1,8 +1,9 @@
-// k_deep.hip — the row-local half of a minibatch step, and the rollout policy step, for networks of 1, 3 and 4 hidden layers in ONE launch:
+// k_deep.hip — the row-local half of a minibatch step, and the rollout policy step, for networks of 1 to 4 hidden layers in ONE launch:
 //   x -> h_0 -> ... -> h_{L-1} -> output layer -> clipped-PPO loss terms -> d(loss)/d(outputs) -> dZ_{L-1} -> ... -> dZ_0
 // (reference minppo/train.py:56-68 `MLP([hidden_size] * num_layers + [out])`, :222-243 the loss, :157-160,182 the rollout).  Two hidden layers are
-// fused_mlp_kernel's (k_fused.hip, tried first by the dispatch in k_ppo.hip); the other depths used to take 2L layer-wise launches per optimizer
-// step and L + 1 per rollout step, every activation going to HBM and back between them.
+// fused_mlp_kernel's (k_fused.hip, tried first by the dispatch in k_ppo.hip) and come here only where that kernel refuses them (an observation
+// wider than its weight-gradient tile table, a weight offset off a 16-byte boundary); without this kernel a depth takes 2L layer-wise launches
+// per optimizer step and L + 1 per rollout step, every activation going to HBM and back between them.
 //
 // Work split: one workgroup = 16 rows (training: gathered by permutation index) of ONE network (blockIdx.y: 0 actor, 1 critic), H/32 waves; wave w
 // owns hidden columns [32w, 32w + 32) of every layer as two interleaved 16 x 16 tiles of v_mfma_f32_16x16x4_f32 - exact f32 products.
@@ -15,20 +16,28 @@
 // Outputs (training): the layer-wise path's buffers in plain row-major layout - h_l and dZ_l [mb][H], dOut [mb][AP + 4], the gathered rows
 // [mb][OP], one row of loss partials per 16-row tile - consumed unchanged by the layer-wise weight-gradient GEMMs and grad_reduce_kernel.
 // Only rows below mb are stored: a last partial tile stays inside the workspace.
+// XSTREAM (the resident x tile would not fit a CU's LDS: wide robots): the x tile is never resident.  Layer 0 consumes the observation in slabs of
+// kDeepSlab = 96 columns through a ring of two LDS slabs.  A thread resolves the rows of its float4 pieces once; per slab it requests the pieces of
+// slab s + 1 from memory, multiplies slab s (one turn of the weight ring: GemmPipe::run_part, the ring walks on across the slab boundaries), stores
+// the pieces into the other half of the ring (and, the actor workgroup, into xmb) and meets ONE barrier: the half it stores to was last read before the
+// previous slab's barrier, and is read after this one.  Same stages, same order, one accumulation: the bits of the resident form.  Behind layer 0
+// the two forms are the same code.
 #include "deep.h"
 #include "fused_common.h"
 #include "fused_pipes.h"
 
 namespace mppo {
 
-template <bool ROLLOUT, int OT>
+template <bool ROLLOUT, int OT, int XQ>  // XQ: 0 = resident x tile; streamed: float4 pieces of a slab per thread (kDeepSlabChunks <= XQ blockDim.x)
 __global__ void __launch_bounds__(512, ROLLOUT ? MPPO_ROLLOUT_WAVES : MPPO_TRAIN_WAVES) deep_mlp_kernel(DeepArgs a) {
+  constexpr bool XSTREAM = XQ > 0;
+  constexpr int NQ = XSTREAM ? XQ : 1;
   constexpr int SD = 16 * OT;  // row stride of the per-row output-space tiles
   MPPO_DYN_SMEM(smem_raw);
   float* sm = reinterpret_cast<float*>(smem_raw);
   const int H = a.H, O = a.O, OP = a.OP, A = a.A, AP = a.AP, L = a.nl;
   const int net = blockIdx.y + (ROLLOUT ? a.net0 : 0);  // 0 actor, 1 critic
-  const DeepLds lds(O, H, OT, L, ROLLOUT);               // the layout the host sized the launch from
+  const DeepLds lds(O, H, OT, L, ROLLOUT, XSTREAM);      // the layout the host sized the launch from
   const int KP = lds.KP, XS = lds.XS, HS = lds.HS;
   float* xt = lds.xt(sm);
   const int t = threadIdx.x, nthr = blockDim.x, lane = t & 63, wave = t >> 6;
@@ -77,7 +86,18 @@ __global__ void __launch_bounds__(512, ROLLOUT ? MPPO_ROLLOUT_WAVES : MPPO_TRAIN
     return gather ? (long)a.idx[gi] : (long)gi;
   };
   const int e0 = t, e1 = t + nthr < nx ? t + nthr : t;  // (this thread's first two chunks; a wide workgroup on a narrow observation has threads without one)
-  const long xrow0 = chunk_row(e0), xrow1 = chunk_row(e1);
+  const long xrow0 = XSTREAM ? 0 : chunk_row(e0), xrow1 = XSTREAM ? 0 : chunk_row(e1);
+  // streamed: piece q of this thread is float4 e = t + q nthr of EVERY slab - row e / 24 of the tile, columns 4 (e % 24) .. + 3 of the slab - so
+  // its row is resolved here, once (xsrc: that row at the piece's column of slab 0)
+  const float* xsrc[NQ];
+  if (XSTREAM) {
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) {
+      const int e = t + q * nthr, r = e / (kDeepSlab / 4);
+      const int gi = row0 + r < a.mb ? row0 + r : a.mb - 1;  // (e past the slab: a clamped row, never loaded)
+      xsrc[q] = a.bt.obs + (gather ? (long)a.idx[gi] : (long)gi) * a.bt.obs_ld + 4 * (e % (kDeepSlab / 4));
+    }
+  }
   long prow[4];
   bool pon[4];
 #pragma unroll
@@ -98,7 +118,30 @@ __global__ void __launch_bounds__(512, ROLLOUT ? MPPO_ROLLOUT_WAVES : MPPO_TRAIN
     // the gathered rows, [mb][OP], for the first layer's weight gradient (the actor workgroup writes them)
     if (!ROLLOUT && net == 0 && row0 + r < a.mb && c < OP) stream_store(a.xmb + (size_t)(row0 + r) * OP + c, q);
   };
-  const float4 xq0 = load_chunk(e0, xrow0), xq1 = load_chunk(e1, xrow1);
+  // streamed: the pieces of slab s -> registers (zeros from column OP on: the K tail, and every piece of a slab past the last) ...
+  float4 xq[NQ];
+  auto load_slab = [&](int s) {
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) {
+      const int e = t + q * nthr, c = s * kDeepSlab + 4 * (e % (kDeepSlab / 4));
+      xq[q] = (e < kDeepSlabChunks && c < OP) ? *reinterpret_cast<const float4*>(xsrc[q] + s * kDeepSlab) : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+  };
+  // ... and from there into its half of the ring, and the gathered rows [mb][OP]
+  auto put_slab = [&](int s) {
+    float* sl = lds.slab(sm, s);
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) {
+      const int e = t + q * nthr, r = e / (kDeepSlab / 4), cs = 4 * (e % (kDeepSlab / 4)), c = s * kDeepSlab + cs;
+      if (e < kDeepSlabChunks) {
+        *reinterpret_cast<float4*>(sl + r * XS + cs) = xq[q];
+        if (!ROLLOUT && net == 0 && row0 + r < a.mb && c < OP) stream_store(a.xmb + (size_t)(row0 + r) * OP + c, xq[q]);
+      }
+    }
+  };
+  float4 xq0, xq1;
+  if (XSTREAM) load_slab(0);
+  else { xq0 = load_chunk(e0, xrow0); xq1 = load_chunk(e1, xrow1); }
   // actor: action[o], old log_prob, advantage | critic: old value, target | rollout: noise[o].  Raw loads on clamped addresses; every use is masked.
   float pf0[OT][4], pf1[4], pf2[4];
 #pragma unroll
@@ -136,10 +179,13 @@ __global__ void __launch_bounds__(512, ROLLOUT ? MPPO_ROLLOUT_WAVES : MPPO_TRAIN
       pf1[r] = a.bt.target[prow[r]];
     }
   }
-  // ---- P0: observation rows -> LDS ----
-  if (e0 < nx) put_chunk(e0, xq0);
-  if (t + nthr < nx) put_chunk(e1, xq1);
-  for (int e = t + 2 * nthr; e < nx; e += nthr) put_chunk(e, load_chunk(e, chunk_row(e)));  // (narrow networks: more than two chunks per thread)
+  // ---- P0: observation rows -> LDS (streamed: the first slab) ----
+  if (XSTREAM) put_slab(0);
+  else {
+    if (e0 < nx) put_chunk(e0, xq0);
+    if (t + nthr < nx) put_chunk(e1, xq1);
+    for (int e = t + 2 * nthr; e < nx; e += nthr) put_chunk(e, load_chunk(e, chunk_row(e)));  // (narrow networks: more than two chunks per thread)
+  }
   __syncthreads();
 
   // ---- forward: layer l multiplies tile `in` by W_l into the wave's 16 x 32 slab, bias + activation -> tile `out` (and, training, h_l in memory) ----
@@ -152,7 +198,19 @@ __global__ void __launch_bounds__(512, ROLLOUT ? MPPO_ROLLOUT_WAVES : MPPO_TRAIN
     for (int r = 0; r < 4; ++r) { acc0[r] = 0.f; acc1[r] = 0.f; }
     // rollout: four waves per SIMD hide the fill latency, and the 128-VGPR budget has no room for a ring that lives across the epilogue
     if (ROLLOUT && l > 0) fwd.prefetch(H, H, a.params + a.w[net][l], H, n0, lane);
-    fwd.template run<false>(in, in_stride, K, a.params + a.w[net][l], H, n0, lane, acc0, acc1);
+    if (XSTREAM && l == 0) {
+      const int nst = KP / 32, nslab = (nst + 2) / 3;
+      for (int s = 0; s < nslab; ++s) {
+        load_slab(s + 1);  // (past the last slab: no piece is below OP, nothing is loaded)
+        fwd.template run_part<false>(lds.slab(sm, s), XS, 3 * s, nst - 3 * s < 3 ? nst - 3 * s : 3, KP, a.params + a.w[net][0], H, n0, lane, acc0, acc1);
+        if (s + 1 < nslab) {  // (uniform)
+          put_slab(s + 1);
+          __syncthreads();
+        }
+      }
+    } else {
+      fwd.template run<false>(in, in_stride, K, a.params + a.w[net][l], H, n0, lane, acc0, acc1);
+    }
     if (!ROLLOUT) {  // the next GEMM's first two stages arrive under this layer's epilogue and barrier (the last layer: under heads and loss)
       if (l + 1 < L) fwd.prefetch(H, H, a.params + a.w[net][l + 1], H, n0, lane);
       else if (L > 1) bwd.prefetch(H, H, a.params + a.w[net][L - 1], H, n0, lane);
@@ -364,15 +422,25 @@ __global__ void __launch_bounds__(512, ROLLOUT ? MPPO_ROLLOUT_WAVES : MPPO_TRAIN
 
 // ---- every instantiation the library launches; the dynamic-LDS attribute is set on exactly these ----
 using DeepKernelFn = void (*)(DeepArgs);
-struct DeepKernel { bool rollout; int ot; DeepKernelFn fn; };
-static const DeepKernel kDeepKernels[] = {
-    {false, 1, deep_mlp_kernel<false, 1>}, {false, 2, deep_mlp_kernel<false, 2>}, {true, 1, deep_mlp_kernel<true, 1>}, {true, 2, deep_mlp_kernel<true, 2>}};
+struct DeepKernel { bool rollout; int ot, xq; DeepKernelFn fn; };
+#define MPPO_DEEP_FORMS(XQ) {false, 1, XQ, deep_mlp_kernel<false, 1, XQ>}, {false, 2, XQ, deep_mlp_kernel<false, 2, XQ>}, \
+                            {true, 1, XQ, deep_mlp_kernel<true, 1, XQ>}, {true, 2, XQ, deep_mlp_kernel<true, 2, XQ>}
+// (streamed: as many pieces per thread as the workgroup needs for the 384 of a slab and no more - 1 from six waves on (H >= 192, the wide robots'
+// networks), 2 from three, 3 at two waves, kDeepSlabQ = 6 at one: a form sized for one wave would carry staging registers that a wider workgroup never fills)
+static const DeepKernel kDeepKernels[] = {MPPO_DEEP_FORMS(0), MPPO_DEEP_FORMS(1), MPPO_DEEP_FORMS(2), MPPO_DEEP_FORMS(3), MPPO_DEEP_FORMS(kDeepSlabQ)};
 
-static DeepLds deep_lds(const mppo_net_t& net, bool rollout) { return DeepLds(net.O, net.H, net.A > 16 ? 2 : 1, net_layers(net), rollout); }
+// The resident layout wherever it fits a CU's LDS (every geometry keeps the form it has had), the streamed one beyond
+static bool deep_streamed(const mppo_net_t& net, bool rollout) {
+  return DeepLds(net.O, net.H, net.A > 16 ? 2 : 1, net_layers(net), rollout, false).bytes() > kDeepLdsMax;
+}
+static int deep_pieces(const mppo_net_t& net, bool rollout) { return !deep_streamed(net, rollout) ? 0 : cdiv(kDeepSlabChunks, 2 * net.H) <= 3 ? cdiv(kDeepSlabChunks, 2 * net.H) : kDeepSlabQ; }
+static DeepLds deep_lds(const mppo_net_t& net, bool rollout) {
+  return DeepLds(net.O, net.H, net.A > 16 ? 2 : 1, net_layers(net), rollout, deep_streamed(net, rollout));
+}
 
 static bool deep_geometry(const mppo_net_t& net, const float* obs, int obs_ld, bool rollout) {
   const int L = net_layers(net);
-  return (L == 1 || L == 3 || L == 4) && !net.bf16 && net.H % 32 == 0 && net.H >= 32 && net.H <= 256 && net.A <= 32 && obs_ld == net.OP && (net.OP % 4) == 0 &&
+  return L >= 1 && L <= 4 && !net.bf16 && net.H % 32 == 0 && net.H >= 32 && net.H <= 256 && net.A <= 32 && obs_ld == net.OP && (net.OP % 4) == 0 &&
          (reinterpret_cast<uintptr_t>(obs) & 15) == 0 && deep_lds(net, rollout).bytes() <= kDeepLdsMax;
 }
 bool deep_supported(const mppo_net_t& net, const mppo_batch_t& b) { return deep_geometry(net, b.obs, b.obs_ld, false); }
@@ -388,7 +456,7 @@ static int32_t deep_launch(bool rollout, const mppo_net_t& net, const DeepArgs& 
   }
   DeepKernelFn fn = nullptr;
   for (const DeepKernel& k : kDeepKernels)
-    if (k.rollout == rollout && k.ot == (net.A > 16 ? 2 : 1)) fn = k.fn;
+    if (k.rollout == rollout && k.ot == (net.A > 16 ? 2 : 1) && k.xq == deep_pieces(net, rollout)) fn = k.fn;
   MPPO_REQUIRE(fn, "deep_mlp_kernel: no instantiation for this launch");
   hipLaunchKernelGGL(fn, dim3(cdiv(a.mb, kDeepRows), ny), dim3(2 * net.H), smem, stream, a);
   MPPO_CHECK_LAUNCH(rollout ? "deep_mlp_kernel<rollout>" : "deep_mlp_kernel");

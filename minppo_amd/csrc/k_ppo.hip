@@ -262,7 +262,7 @@ static_assert(kSqSlots == 2 * kNormBlocks, "adam_kernel adds kSqSlots partials; 
 // and loss4 from the head kernel's per-workgroup partials, and the per-workgroup sums of squares of the result in
 // `sq_partial[kNormBlocks]` (consumed by the clip when no all-reduce sits between this kernel and Adam).
 // Launched with exactly kNormBlocks workgroups of 256 threads; requires P <= kNormBlocks * 256 * 4 * kReduceIter.
-constexpr int kReduceIter = 4;
+constexpr int kReduceIter = 8;  // (2^21 parameters: a 93-body robot's O = 1575 at H = 256 is 1.08 M at three hidden layers, 1.21 M at four)
 struct PadList { int n, off[kMaxPads], cnt[kMaxPads]; };  // alignment words of the flat layout: no GEMM writes them into the slabs
 __device__ __forceinline__ bool is_pad(const PadList& pl, size_t e) {
   bool r = false;
@@ -634,7 +634,7 @@ int32_t policy_forward(const mppo_net_t& net, const float* params, int n, const 
   static const char* nofuse = MPPO_EXPERIMENT_ENV("MPPO_NO_FUSED");  // A/B switch for measurements
   if (fused_rollout_supported(net, obs, obs_ld) && !(nofuse && nofuse[0] == '1'))
     return fused_policy_forward(net, params, n, obs, obs_ld, noise, action, log_prob, value, noise ? mean_out : nullptr, fb.AP, stream, fb.frag, fb.frag_net_stride);  // one launch
-  if (deep_rollout_supported(net, obs, obs_ld) && !(nofuse && nofuse[0] == '1'))  // 1, 3 or 4 hidden layers: one launch as well (k_deep.hip)
+  if (deep_rollout_supported(net, obs, obs_ld) && !(nofuse && nofuse[0] == '1'))  // 1, 3 or 4 hidden layers, or two that the fused kernel refuses: one launch as well (k_deep.hip)
     return deep_policy_forward(net, params, n, obs, obs_ld, noise, action, log_prob, value, noise ? mean_out : nullptr, fb.AP, stream);
   MPPO_TRY(mlp_hidden_forward(net, params, n, obs, obs_ld, nullptr, fb, nullptr, stream));
   HeadArgs a = head_args(net, params, n, fb);
@@ -646,7 +646,7 @@ int32_t policy_forward(const mppo_net_t& net, const float* params, int n, const 
 }
 
 // Everything of a minibatch step that is local to a row: forward of both networks, loss terms, d(loss)/d(outputs), dZ2, dZ1
-// (one fused launch where supported - k_fused.hip at two hidden layers, k_deep.hip at 1, 3 and 4; otherwise layer-wise GEMMs + the head kernel).  Leaves h1, h2, dZ2, dZ1,
+// (one fused launch where supported - k_fused.hip at two hidden layers, k_deep.hip at 1, 3 and 4 and at two where k_fused.hip refuses; otherwise layer-wise GEMMs + the head kernel).  Leaves h1, h2, dZ2, dZ1,
 // dOut, xmb and the loss partials in the GradBufs; *nblk_out = number of partial rows written.
 int32_t minibatch_rowpass(const mppo_net_t& net, const float* params, const mppo_batch_t& batch, const int* idx, int mb, const float* adv_stat,
                           float inv_count, const mppo_loss_cfg_t& lc, const GradBufs& gbuf, int* nblk_out, bool* fused_out, hipStream_t stream, const XPre* pre = nullptr) {
@@ -662,7 +662,8 @@ int32_t minibatch_rowpass(const mppo_net_t& net, const float* params, const mppo
     *nblk_out = cdiv(mb, fused_rows_per_workgroup(net, mb, pre != nullptr));  // one row of loss partials per row-pass workgroup
     return MPPO_OK;
   }
-  // 1, 3 or 4 hidden layers: the depth-generic row pass (k_deep.hip), one launch.  *fused_out stays false: it means "k-quad operands for
+  // 1, 3 or 4 hidden layers, or two with an observation beyond the weight-gradient tile table: the depth-generic row pass (k_deep.hip), one launch,
+  // whatever the observation's width.  *fused_out stays false: it means "k-quad operands for
   // wgrad_kernel", and this kernel writes the layer-wise path's plain buffers for the layer-wise weight-gradient GEMMs.
   if (deep_supported(net, batch) && !(nofuse && nofuse[0] == '1')) {
     MPPO_TRY(deep_forward_backward(net, params, batch, idx, mb, adv_stat, inv_count, lc, gbuf, stream));

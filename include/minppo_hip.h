@@ -325,7 +325,9 @@ int32_t mppo_action_delay_apply(const mppo_action_delay_cfg_t* cfg, int32_t N, i
 typedef struct mppo_net {
   int32_t O, OP, A, H;
   int32_t use_tanh;  /* actor activation; the critic is always ReLU (train.py:82) */
-  int32_t bf16;      /* 0: exact f32 MFMA; 1: bf16-in/f32-accumulate MFMA for the hidden GEMMs */
+  int32_t bf16;      /* 0: exact f32 MFMA; 1: bf16-in/f32-accumulate MFMA for the hidden GEMMs: two hidden layers, H a multiple of 32 up to
+                        256, A <= 32 - the fused kernels, and behind them (an observation wider than 736) the bf16 row pass with a resident
+                        observation tile (k_deep_bf16.hip: O up to 3392 at H = 256) */
   int32_t num_layers; /* hidden layers of each MLP (`model.num_layers`, config.py:53, train.py:79,82): 1 .. 4; 0 means 2, the
                          reference's default.  Two hidden layers take the fused kernels; 1, 3 and 4 hidden layers of a float network - and two
                          where the fused kernels refuse the geometry, e.g. an observation wider than 736 - take the depth-generic row pass
@@ -389,7 +391,9 @@ typedef struct mppo_loss_cfg { float clip_eps, vf_coef, ent_coef; } mppo_loss_cf
 int32_t mppo_minibatch_path(const mppo_net_t* net, const mppo_batch_t* batch, int32_t* fused);
 /* 0: layer-wise kernels, 1: the two-layer fused kernels (k_fused.hip), 2: the depth-generic row pass (k_deep.hip): float networks of
  * 1 to 4 hidden layers that 1 does not take, H a multiple of 32 up to 256, A <= 32, 16-byte aligned observation rows of ANY width (an
- * observation whose row tile does not fit a CU's LDS streams through it in slabs).
+ * observation whose row tile does not fit a CU's LDS streams through it in slabs) - or, for a bf16 network (two hidden layers) that 1
+ * does not take, the bf16 row pass (k_deep_bf16.hip): the same H, A and alignment, the observation tile resident in LDS as bf16 (160 KB:
+ * O up to 3392 at H = 256; beyond that 0, which a bf16 network's mppo_minibatch_grad refuses).
  * *rowpass: the row-local half of mppo_minibatch_grad / mppo_minibatch_rowpass; *rollout: mppo_policy_forward. */
 int32_t mppo_network_path(const mppo_net_t* net, const float* obs, int32_t obs_ld, int32_t* rowpass, int32_t* rollout);
 /* *rows = minibatch rows per workgroup of the fused row pass for a minibatch of mb rows: 16, or 32 where the engine's minibatch loop

@@ -11,6 +11,7 @@
 #include "mppo_common.h"
 #include "ppo_layout.h"
 #include "deep.h"
+#include "deep_bf16.h"
 #include "wgrad.h"
 #include "peer.h"
 #include "limit.h"
@@ -636,6 +637,8 @@ int32_t policy_forward(const mppo_net_t& net, const float* params, int n, const 
     return fused_policy_forward(net, params, n, obs, obs_ld, noise, action, log_prob, value, noise ? mean_out : nullptr, fb.AP, stream, fb.frag, fb.frag_net_stride);  // one launch
   if (deep_rollout_supported(net, obs, obs_ld) && !(nofuse && nofuse[0] == '1'))  // 1, 3 or 4 hidden layers, or two that the fused kernel refuses: one launch as well (k_deep.hip)
     return deep_policy_forward(net, params, n, obs, obs_ld, noise, action, log_prob, value, noise ? mean_out : nullptr, fb.AP, stream);
+  if (wide_bf16_rollout_supported(net, obs, obs_ld) && !(nofuse && nofuse[0] == '1'))  // a bf16 network whose observation the fused kernel refuses: its own row pass (k_deep_bf16.hip)
+    return wide_bf16_policy_forward(net, params, n, obs, obs_ld, noise, action, log_prob, value, noise ? mean_out : nullptr, fb.AP, stream);
   MPPO_TRY(mlp_hidden_forward(net, params, n, obs, obs_ld, nullptr, fb, nullptr, stream));
   HeadArgs a = head_args(net, params, n, fb);
   a.noise = noise; a.action = action; a.log_prob = log_prob; a.value = value; a.mean_out = mean_out;
@@ -670,8 +673,15 @@ int32_t minibatch_rowpass(const mppo_net_t& net, const float* params, const mppo
     *nblk_out = cdiv(mb, kDeepRows);  // one row of loss partials per 16-row tile
     return MPPO_OK;
   }
-  MPPO_REQUIRE(!net.bf16, "minibatch_grad: bf16 products need the fused kernels and this geometry (O=%d A=%d H=%d: e.g. an observation too wide for the weight-gradient "
-               "tile table) runs the layer-wise path, which is float only", net.O, net.A, net.H);
+  // a bf16 network with two hidden layers and an observation beyond the fused kernels: the bf16 row pass with a resident x tile (k_deep_bf16.hip), same
+  // plain buffers - dZ and dOut rounded, the B operands of the layer-wise weight-gradient products gemm_tn_kernel<bf16> and the terms of their bias sums
+  if (wide_bf16_supported(net, batch) && !(nofuse && nofuse[0] == '1')) {
+    MPPO_TRY(wide_bf16_forward_backward(net, params, batch, idx, mb, adv_stat, inv_count, lc, gbuf, stream));
+    *nblk_out = cdiv(mb, kDeepRows);
+    return MPPO_OK;
+  }
+  MPPO_REQUIRE(!net.bf16, "minibatch_grad: bf16 products need the fused kernels and this geometry (O=%d A=%d H=%d: an observation too wide for the weight-gradient "
+               "tile table AND for the bf16 row pass's resident tile, or rows off a 16-byte boundary) runs the layer-wise path, which is float only", net.O, net.A, net.H);
   MPPO_TRY(mlp_hidden_forward(net, params, mb, batch.obs, batch.obs_ld, idx, gbuf.f, gbuf.xmb, stream));
   HeadArgs ha = head_args(net, params, mb, gbuf.f);
   ha.idx = idx; ha.b = batch; ha.adv_stat = adv_stat; ha.inv_count = inv_count; ha.lc = lc;
@@ -936,8 +946,8 @@ extern "C" int32_t mppo_network_path(const mppo_net_t* net, const float* obs, in
   const bool off = nofuse && nofuse[0] == '1';
   mppo_batch_t b{};
   b.obs = obs; b.obs_ld = obs_ld;
-  *rowpass = off ? 0 : fused_supported(*net, b) ? 1 : deep_supported(*net, b) ? 2 : 0;
-  *rollout = off ? 0 : fused_rollout_supported(*net, obs, obs_ld) ? 1 : deep_rollout_supported(*net, obs, obs_ld) ? 2 : 0;
+  *rowpass = off ? 0 : fused_supported(*net, b) ? 1 : (deep_supported(*net, b) || wide_bf16_supported(*net, b)) ? 2 : 0;
+  *rollout = off ? 0 : fused_rollout_supported(*net, obs, obs_ld) ? 1 : (deep_rollout_supported(*net, obs, obs_ld) || wide_bf16_rollout_supported(*net, obs, obs_ld)) ? 2 : 0;
   return MPPO_OK;
 }
 
